@@ -12,6 +12,7 @@ list) over one synthetic batch.  Workloads (`--workload`, numbered like BASELINE
 config2-4 are fixed-size jobs sharded by contig ("strong" scaling); every rank generates and holds only its own contigs.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload configX]      (N > 1: re-launches itself under torch.distributed.run)
+    python bench.py --dump-outputs DIR ...       (N = 1: the loci list of the last timed step as DIR/*.npy, see dump_outputs)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Multi-GPU: one process per GPU; host objects and the timing barrier go over a CPU-side `gloo` group, the data path's one exchange step (the
@@ -134,7 +135,14 @@ def parse_args():
                     "gloo and still print a line (marked in config.exchange); without this flag the run exits non-zero instead")
     ap.add_argument("--fold-model", default="vienna-2.1.2", choices=["vienna-2.1.2", "vienna-1.8.5"],
                     help="RNALfold flavour to reproduce (the headline metric is quoted on the default, Turner-2004)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the loci list the last one returned as DIR/<name>.npy "
+                    "(float64 / float32, see dump_outputs) so that two builds can be compared output for output; --gpus 1 only")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and a.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
+    return a
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -476,6 +484,42 @@ def fold_microbench(ctx, n_windows):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: the result of the last timed step as its caller receives it (ctx.predict_raw), written as DIR/<name>.npy:
+      locus_<field>.npy    float64 [n]     one file per field of records.MIRNA_DTYPE (window, tid, fold_s, ..., total_depth_star)
+      locus_ss.npy         float32 [n, w]  each locus' structure string as byte codes, zero past its ss_len, w = the longest ss_len
+      window_n_passed.npy  float64 [m]     loci passing the filter, per window
+      window_status.npy    float64 [m]     capacity status, per window
+      locus_rows.npy / window_rows.npy     float64  the row numbers written
+    All rows are written while the arrays fit into 64 MB; above that, a seeded sample of rows of the same share on each side (the same rows for the same
+    sizes).  The workload is generated from fixed seeds, so two runs with the same arguments fold the same inputs."""
+    import numpy as np
+    res, text = out["result"], out["text"]
+    n, m = len(res), len(out["n_passed"])
+    width = int(res["ss_len"].max()) if n else 0
+    locus_bytes = 8 * (len(res.dtype.names) + 1) + 4 * width
+    window_bytes = 8 * 3
+    share = min(1.0, (DUMP_BUDGET_BYTES - (64 << 10)) / float(max(n * locus_bytes + m * window_bytes, 1)))          # 64 KB: the files' headers
+
+    def rows(count, seed):
+        k = int(count * share)
+        return np.arange(count) if k >= count else np.sort(np.random.default_rng(seed).choice(count, k, replace=False))
+    lr, wr = rows(n, 1), rows(m, 2)
+    os.makedirs(path, exist_ok=True)
+    arrays = {"locus_rows": lr.astype(np.float64), "window_rows": wr.astype(np.float64),
+              "window_n_passed": out["n_passed"][wr].astype(np.float64), "window_status": out["status"][wr].astype(np.float64)}
+    for f in res.dtype.names:
+        arrays["locus_" + f] = res[f][lr].astype(np.float64)
+    ss = text[lr, :width].astype(np.float32)
+    ss[np.arange(width)[None, :] >= res["ss_len"][lr][:, None]] = 0
+    arrays["locus_ss"] = ss
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+
+
 def main():
     a = parse_args()
     a.workload = a.workload.replace("cfg", "config")
@@ -609,7 +653,7 @@ def main():
             total = sum(len(x) for x in parts) if rank == 0 else 0
         else:
             total = len(out["result"])
-        return nwin, total, tm_own, km_own
+        return nwin, total, tm_own, km_own, out
 
     def sync():
         # every C-ABI call above returns after its stream has drained; across ranks: a RCCL reduction on the library's communicator and the
@@ -626,12 +670,14 @@ def main():
     fold_ms, cov_ms, rest_ms, pred_ms, fill_ms, epi_ms = [], [], [], [], [], []
     nwin = nres = 0
     for _ in range(a.steps):
-        nwin, nres, tm, km = step()
+        nwin, nres, tm, km, last = step()
         fold_ms.append(tm["fold_ms"]); cov_ms.append(tm["coverage_ms"]); rest_ms.append(tm["candidate_rest_ms"]); pred_ms.append(tm["predict_ms"])
         fill_ms.append(km[0]); epi_ms.append(km[1])
     t_own = time.time() - t0          # this rank's own K steps (before waiting for the others)
     sync()
     elapsed = time.time() - t0
+    if a.dump_outputs:
+        dump_outputs(last, a.dump_outputs)
     ranks = None
     if world > 1:
         box = [None] * world
