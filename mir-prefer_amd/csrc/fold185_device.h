@@ -10,7 +10,7 @@
 namespace mirp {
 namespace v185 {
 
-#if defined(MIRP_EPI_CLOCKS) && defined(EPI_T)      // phase clocks of the LDS-path epilogue (dev build; fold_epilogue.h defines the macros)
+#if defined(MIRP_DIAG) && defined(EPI_T)      // phase clocks of the LDS-path epilogue (diagnostics build; fold_epilogue.h defines the macros)
 #define V185_T0() EPI_T0()
 #define V185_T(k) EPI_T(k)
 #else

@@ -189,11 +189,7 @@ __global__ void __launch_bounds__(V_NT, PHASE == 1 ? V_FILL_WAVES : V_EPI_WAVES)
             }
             __syncthreads();
             const int n1max = (d - 2 - (V_TURN + 1) < V_MAXLOOP) ? d - 2 - (V_TURN + 1) : V_MAXLOOP;
-#ifdef MIRP_X_GEN_NOA               // timing experiment: no interior loops (tables wrong by construction)
-            if (false) {
-#else
             if (n1max >= 0 && np > 0) {
-#endif
                 // Task = (block of 64 paired cells, group of loop sizes s = n1 + n2), as fold_generic_kernel: a size's inner pairs are consecutive cells of
                 // ONE diagonal's row (d - 2 - s); the block's segment of that row is loaded once by the wave (aligned 16 bytes per lane, three sizes in
                 // flight), staged in LDS, and each lane reads its s + 1 words from there.  A generic candidate -- every shape of this model but stack, bulge,
@@ -446,12 +442,8 @@ __global__ void __launch_bounds__(V_NT, PHASE == 1 ? V_FILL_WAVES : V_EPI_WAVES)
         }
 
         } else {
-#ifdef MIRP_X_GEN_NOEPI             // timing experiment: fill only (results are empty)
-        if (tid == 0) { out_nlines[win] = 0; out_mfe[win] = 0; out_status[win] = 0; }
-#else
         epilogue<FoldParams185, GTab185, V_NT>(X, T, f3, starts, lens, btstk, red, btbuf, nc, win, max_lines, ss_stride, out_lines, out_ss, out_nlines,
                                                 out_mfe, out_status);
-#endif
         }
     }
 }

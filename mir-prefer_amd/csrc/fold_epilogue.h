@@ -168,7 +168,7 @@ __device__ __forceinline__ int wave_min(int v) {
 // first set lane of a 64-bit ballot, or -1
 __device__ __forceinline__ int first_lane(unsigned long long mask) { return mask ? (__ffsll((long long)mask) - 1) : -1; }
 
-#ifdef MIRP_EPI_CLOCKS     // diagnostics build: phase clocks of wave 0 (lane 0) of every epilogue workgroup, summed in LDS, flushed once per workgroup
+#ifdef MIRP_DIAG     // diagnostics build: phase clocks of wave 0 (lane 0) of every epilogue workgroup, summed in LDS, flushed once per workgroup
 static __device__ unsigned long long g_epi_clk[32];
 __device__ inline long long* epi_acc() { __shared__ long long acc[32]; return acc; }
 #define EPI_CNT(k) do { if ((threadIdx.x & 63) == 0) atomicAdd((unsigned long long*)&epi_acc()[k], 1ull); } while (0)
@@ -680,7 +680,7 @@ __device__ void f3_sweep_tiled(const WinCtx& X, const Tab& T, int* f3, int* scra
         for (int x = tid; x < RBK * RBK / 2; x += NT) reinterpret_cast<int*>(innerT)[x] = 0x7fff7fff;
         __syncthreads();
         EPI_T(8);
-#ifdef MIRP_EPI_CLOCKS
+#ifdef MIRP_DIAG
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         EPI_T(9);
 #endif
@@ -783,13 +783,8 @@ __device__ void fold_epilogue(const WinCtx& X, const Tab& T, int span, int* f3 /
     for (int x = tid; x < n + 3; x += NT) f3[x] = 0;
     __syncthreads();
     EPI_T0();
-#ifdef MIRP_X_EPI_NOSWEEP          // timing experiment: no exterior sweep (f3 stays 0: no structures follow)
-    if constexpr (Tab::kTiled) {}
-    else {
-#else
     if constexpr (Tab::kTiled) f3_sweep_tiled<Tab, NT>(X, T, f3, btstk);
     else {
-#endif
     constexpr int NW = NT / 64;
     constexpr int RB = 32;   // rows per block: 32 consecutive i share their cache lines of every archived diagonal
     static_assert(RB == 32, "step 1 maps a half-wave onto the rows of a block");
@@ -904,16 +899,8 @@ __device__ void fold_epilogue(const WinCtx& X, const Tab& T, int span, int* f3 /
         int L = -10;
         EPI_T(2);
         if (pp >= 0) {
-#ifdef MIRP_X_EPI_NOBT             // timing experiment: sweep and enumeration only
-            if constexpr (Tab::kTiled) L = -10;
-#else
             if constexpr (Tab::kTiled) L = backtrack_wave_tiled(X, T, lind, (pp + 2 < n ? pp + 2 : n), span, mybuf, mystk);
-#endif
-#ifdef MIRP_X_GEN_NOBT              // timing experiment (generic path): sweep and enumeration only
-            else L = -10;
-#else
             else L = backtrack_wave(X, T, lind, (pp + 2 < n ? pp + 2 : n), span, mybuf, mystk);
-#endif
         }
         EPI_T(3);
         if (L < 0) {

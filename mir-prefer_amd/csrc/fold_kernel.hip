@@ -239,13 +239,6 @@ __global__ void __launch_bounds__(GEN_NT, GEN_MIN_WAVES(PHASE)) fold_generic_ker
         //     c(p, q) are neighbours on ONE diagonal (d - n1 - n2 - 2); the minimum per cell is merged with an LDS atomic;
         //  B  a thread per cell: hairpin, multiloop closing from the DML ring, DML(i,j) from DML(i,j-1) and the column's split candidates, fML.
         const int lane = tid & 63, wave = tid >> 6;
-#ifdef MIRP_X_GEN_CLOCKS              // dev: where a wave's time goes (printed by wave 0 of block 0 for its first window)
-        long long ck_0 = 0, ck_small = 0, ck_large = 0, ck_b = 0, ck_wait = 0, ck_t = clock64();
-        int ck_nsmall = 0, ck_nlarge = 0;
-#define CK(acc) do { const long long now_ = clock64(); acc += now_ - ck_t; ck_t = now_; } while (0)
-#else
-#define CK(acc) do { } while (0)
-#endif
         // A turn of the loop: pair types and the paired-cell list of diagonal d, then -- no barrier between them: they touch different diagonals -- the interior
         // loops of d (interval A: reads rows <= d - 2 of the packed table) and hairpin / multiloop / fML of d - 1 (interval B: writes row d - 1).  Each wave runs
         // its share of both, so the turn takes the slowest wave's SUM, not the slowest of A plus the slowest of B, and a diagonal costs two barriers, not three.
@@ -283,16 +276,10 @@ __global__ void __launch_bounds__(GEN_NT, GEN_MIN_WAVES(PHASE)) fold_generic_ker
                 np_run += total;
                 if (base + 2 * GEN_NT < ncell) __syncthreads();          // (the counts are rewritten by the next pass)
             }
-            CK(ck_0);
             __syncthreads();
-            CK(ck_wait);
             const int np = np_run;
             const int n1max = (d - 2 - (TURN + 1) < MAXLOOP) ? d - 2 - (TURN + 1) : MAXLOOP;      // q - p = d - n1 - n2 - 2 >= TURN + 1
-#ifdef MIRP_X_GEN_NOA               // timing experiment: no interior loops (tables wrong by construction)
-            if (false) {
-#else
             if (n1max >= 0) {
-#endif
                 // Task = (block of 64 paired cells, group of loop sizes s = n1 + n2).  All candidates of one size have their inner pair on ONE diagonal,
                 // dd = d - 2 - s, and a lane's candidates n1 = 0 .. s are the CONSECUTIVE cells p = i + 1 + n1 of that diagonal's row: four of them per 16-byte
                 // load, and every load of a size is issued before the first is used (the earlier order -- n1 outer, n2 inner, one 4-byte gather per
@@ -485,15 +472,11 @@ __global__ void __launch_bounds__(GEN_NT, GEN_MIN_WAVES(PHASE)) fold_generic_ker
                             else if (span_w + s_hi + 1 > 256) sizes_staged(std::true_type{}, s_lo, s_hi);
                             else sizes_staged(std::false_type{}, s_lo, s_hi);
                         }
-#ifdef MIRP_X_GEN_CLOCKS
-                        if (grp == 0) { CK(ck_small); ck_nsmall++; } else { CK(ck_large); ck_nlarge++; }
-#endif
                         const int best = kmin >> 10;
                         if (active && best < GEN_EMAX) atomicMin(&cbA[cell], kmin);
                     }
                 }
             }
-            CK(ck_large);
             }          // (d <= D)
             if (d - 1 >= TURN + 1) {
             const int d_turn = d;
@@ -577,22 +560,12 @@ __global__ void __launch_bounds__(GEN_NT, GEN_MIN_WAVES(PHASE)) fold_generic_ker
                 T.m[(size_t)d * T.ld + i] = mm;
                 dml[(size_t)(d & 3) * T.ld + i] = mdec;
             }
-            CK(ck_b);
             }          // (interval B of d - 1)
             __syncthreads();
-            CK(ck_wait);
         }
-#ifdef MIRP_X_GEN_CLOCKS
-        if (blockIdx.x == 0 && w == 0 && lane == 0)
-            printf("[gen clocks] wave %d n %d: phase0 %lld small %lld (%d tasks) large %lld (%d tasks) B %lld barrier-wait %lld\n", wave, n, ck_0, ck_small, ck_nsmall, ck_large, ck_nlarge, ck_b, ck_wait);
-#endif
         } else {
-#ifdef MIRP_X_GEN_NOEPI             // timing experiment: fill only (results are empty)
-        if (tid == 0) { out_nlines[win] = 0; out_mfe[win] = 0; out_status[win] = 0; }
-#else
         fold_epilogue<GTab, GEN_NT>(X, T, span, f3, starts, lens, btbuf, nc, btstk, sh_misc, win, max_lines, ss_stride,
                                    out_lines, out_ss, out_nlines, out_mfe, out_status);
-#endif
         }
     }
 }

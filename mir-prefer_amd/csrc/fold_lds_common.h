@@ -1,6 +1,5 @@
-// Shared definitions of the LDS-resident fill kernels (fold_lds_kernel.hip: one diagonal per barrier interval, vienna-1.8.5 model;
-// fold_lds2_kernel.hip: two diagonals per barrier interval, default model): LDS table copies, triangle / archive layouts and the
-// phase-A1 candidate jobs (lane = paired cell, wave = candidate group).  Reference work unit: RNALfold -L, /root/reference/miR_PREFeR.py:3053.
+// Definitions of the LDS-resident fill kernel (fold_lds_kernel.hip: one diagonal per barrier interval, both models): LDS table copies,
+// triangle / archive layouts and the phase-A1 candidate jobs (lane = paired cell, wave = candidate group).  Reference work unit: RNALfold -L, /root/reference/miR_PREFeR.py:3053.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -32,7 +31,7 @@ struct LdsTables {          // int16 copies of the hot parameter tables
     short mismatchI[200], mismatchH[200], mismatchM[200], mismatch1nI[200], mismatch23I[200];
     // inner-pair terms relative to G0, as bytes (term + FoldParams::xb_bias / x1_bias), at index xt_pcode(p) + xt_qcode(q) (below): 175 bytes = 44
     // dwords per table, fewer than the LDS has banks -- a wave's gather never has two lanes on different dwords of one bank.  (Before: 625
-    // shorts at PA(p) * 25 + QB(q); the 3- to 4-way conflicts of those gathers cost 3.3 ms of the kernel: timing build -DMIRP_X_XBBCAST.)
+    // shorts at PA(p) * 25 + QB(q); the 3- to 4-way conflicts of those gathers cost 3.3 ms of the kernel: timing build with a broadcast gather.)
     unsigned char XB[176];  // TerminalAU(inner) - mismatchI(inner)           (bulges of size >= 2)
     unsigned char X1[176];  // mismatch1nI(inner) - mismatchI(inner)          (1 x n loops, n >= 3)
     short dangle5[40], dangle3[40];   // [type*5 + base], clamped <= 0 (vienna-1.8.5 model)
@@ -158,9 +157,6 @@ __host__ __device__ inline int arch_rowblk_off(int b, int n, int dcap) {
 struct LdsLayout {
     unsigned fml, aux, S, seq, pax, qb2, list, tabs, misc, total, fml_bytes, code4;
 };
-#ifndef MIRP_A1_CODES4
-#define MIRP_A1_CODES4 0      // fold_lds_kernel.hip sets it: the bulge / 1xn jobs read their pair codes four per ds_read_b32 (see a1_codes4)
-#endif
 #define CODE_STR 368          // bytes per shifted copy of a pair-code array (LCAP + 8 codes + the last job's over-read of 3), a multiple of 16
 __host__ __device__ constexpr unsigned lds_al(unsigned x) { return (x + 15u) & ~15u; }
 // SPARSE: the multiloop splits run over a pool of split candidates (see "sparse splits" in fold_lds_kernel.hip): a third mdec buffer, and the pool
@@ -175,14 +171,11 @@ __host__ __device__ constexpr LdsLayout lds_layout() {
     L.aux = o; o += lds_al(CRING_ROWS * CSTR * 2 + (MODEL ? 5 : 3) * LCAP * 2 + (SPARSE ? 6 : 5) * LCAP * 4);   // c ring (32 diagonals + mirror row), DML ring (3; 5 in the vienna-1.8.5 model), 3 x ckey, 2 (sparse: 3) x mdec
     L.S = o; o += lds_al(LCAP + 8);
     L.seq = o; o += lds_al(LCAP + 8);
-    if (MIRP_A1_CODES4 && SPARSE) {      // 4 byte-shifted copies of the q codes, then 4 of the p codes (bytes); copy 0 of each IS the array
+    if (SPARSE) {      // 4 byte-shifted copies of the q codes, then 4 of the p codes (bytes); copy 0 of each IS the array (a1_codes4)
         L.code4 = o; L.qb2 = o; L.pax = o + 4 * CODE_STR; o += 8 * CODE_STR;
-    } else if (MIRP_A1_CODES4) {         // the dense instantiations (overflow pass) have no room for the copies: byte arrays, codes read one by one
+    } else {           // the dense instantiations (overflow pass) have no room for the copies: byte arrays, codes read one by one
         L.pax = o; o += CODE_STR;
         L.qb2 = o; o += CODE_STR;
-    } else {
-        L.pax = o; o += lds_al((LCAP + 8) * 2);
-        L.qb2 = o; o += lds_al(LCAP + 8);
     }
     L.list = o; o += lds_al(3 * LSEG * 4);      // 32-bit entries (see `list` in the kernel)
     L.tabs = o; o += lds_al((unsigned)sizeof(LdsTables));
@@ -201,17 +194,9 @@ typedef const volatile __attribute__((address_space(3))) unsigned* lds_vu32;
 #ifndef MIRP_A1_SMALLPACK
 #define MIRP_A1_SMALLPACK 10     // short generic rows (U < 13) from this size on through realigned dwords as well (8: no gain, 10: -0.3 %)
 #endif
-#ifndef MIRP_A1_WPACK
-#define MIRP_A1_WPACK 2      // 0: 16-bit reads of the generic rows (rounds 3-5), 1: the wings as aligned dwords, 2: whole rows as aligned dwords (round 6)
-#endif
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-#if MIRP_A1_CODES4
 typedef unsigned char pax_t;          // the p codes (xt_pcode < 256) as bytes: copy 0 of their four shifted copies
 typedef lds_vu8 lds_vpax;
-#else
-typedef unsigned short pax_t;
-typedef lds_vu16 lds_vpax;
-#endif
 struct A1 {
     const FoldParams* __restrict__ P;
     const LdsTables* T;
@@ -219,19 +204,27 @@ struct A1 {
     const unsigned short* cring;
     const pax_t* pax;              // xt_pcode(S[x], S[x-1])
     const unsigned char* qbr;      // xt_qcode(S[x], S[x+1]) at n + 1 - x: the q side is walked downwards, so it is stored reversed (ascending immediates)
-    const unsigned char* code4 = nullptr;      // MIRP_A1_CODES4: [4][CODE_STR] copy c of qbr shifted by c bytes, then the same of the p codes as bytes
+    const unsigned char* code4 = nullptr;      // sparse instantiations: [4][CODE_STR] copy c of qbr shifted by c bytes, then the same of the p codes as bytes
     int r0, um, n;
     const int* __restrict__ rowtab;    // FoldParams::ring_rowoff[r0 & 31]: ring-row offset (shorts) of loop size u, i.e. ((r0 - u) & 31) * CSTR
     const unsigned short* rba = nullptr;       // a1_gen_row_w: cring + i + 1 rounded down to a dword, and the end masks of the lane's parity
     unsigned w_lo = 0, w_hie = 0, w_hio = 0, w_sh = 0;
 };
 
+// Aligned-dword ring reads (the steady-state generic rows below, round 6): a run is read from the aligned dword at or below its first entry, so
+// every ring-row offset (rowtab[U] = k * CSTR shorts) must be a whole dword.
+static_assert(CSTR % 2 == 0, "the aligned-dword ring reads need dword-aligned ring rows");
+// Those reads cover ring entries up to U + 1 of a lane's run, at most 3 past its last candidate (U - 2).  A run starts at column i + 1 <= LCAP - 2
+// of ring row <= 32 (the mirror row, CRING_ROWS), so the farthest read lands at most a few entries into the DML ring that follows the c ring in
+// the aux region (lds_layout: at least 3 DML rows of LCAP shorts) -- never outside the aux allocation.
+static_assert((CRING_ROWS - 1) * CSTR + (LCAP - 2) + 1 + MAXLOOP + 1 < CRING_ROWS * CSTR + 3 * LCAP, "the ring over-read stays inside the aux region");
+
 // generic loops (n1, n2 >= 2) of size U: one contiguous run of ring row r0 - U.  The reads stay 16-bit on purpose (volatile keeps the
 // compiler from fusing neighbours into b64/b128 reads): a lane's run starts at an arbitrary 2-byte boundary, and a wide DS read off its
 // natural alignment is replayed at 64 cycles per wave-instruction on gfx950, against 2 cycles for a 16-bit read.
 template <bool CHECK, int U>
 __device__ __forceinline__ void a1_gen_row(const A1& a, const unsigned short* rb, unsigned& bg) {
-    if constexpr (MIRP_A1_WPACK == 2 && !CHECK && U >= 8) {
+    if constexpr (!CHECK && U >= 8) {
         // (round 6) the row as aligned dwords, every entry out of a realigned register (see a1_gen_row_w): half the LDS passes of 16-bit reads
         lds_vu32 rq = (lds_vu32)(a.rba + a.rowtab[U]);
         constexpr int m1 = (U - 2) >> 1;
@@ -280,7 +273,7 @@ __device__ __forceinline__ unsigned a1_key(unsigned b, int adj) {
 template <bool CHECK, int WD, int U>
 __device__ __forceinline__ void a1_gen_row_w(const A1& a, const unsigned short* rb, unsigned& bg) {
     constexpr int nL = (U - WD) / 2, nR = (U + WD + 1) / 2;      // last entry of the left wing, first of the right one
-    if constexpr (MIRP_A1_WPACK == 2 && !CHECK && nL < 4 && U >= MIRP_A1_SMALLPACK) {
+    if constexpr (!CHECK && nL < 4 && U >= MIRP_A1_SMALLPACK) {
         // short rows (wings of at most two entries): every entry out of a realigned register, the wing entries with the wing's key term
         lds_vu32 rq = (lds_vu32)(a.rba + a.rowtab[U]);
         constexpr int m1 = (U - 2) >> 1;
@@ -304,7 +297,7 @@ __device__ __forceinline__ void a1_gen_row_w(const A1& a, const unsigned short* 
             }
         }
     } else
-    if constexpr (MIRP_A1_WPACK == 2 && !CHECK && nL >= 4) {
+    if constexpr (!CHECK && nL >= 4) {
         // the whole row as contiguous aligned dwords; the centre's entries come out of the same registers: v_alignbit by the lane's parity puts entries
         // (2 m, 2 m + 1) into one register, v_mad_u32_u16 takes either half (op_sel) times 1024 plus the candidate's scalar key term
         lds_vu32 rq = (lds_vu32)(a.rba + a.rowtab[U]);
@@ -335,47 +328,11 @@ __device__ __forceinline__ void a1_gen_row_w(const A1& a, const unsigned short* 
             bg = e < bg ? e : bg;
         }
     } else
-    if constexpr (MIRP_A1_WPACK && !CHECK && nL >= 4) {
-        lds_vu16 rp = (lds_vu16)(rb + a.rowtab[U]);
-        lds_vu32 rq = (lds_vu32)(a.rba + a.rowtab[U]);           // the aligned dword at or below entry 0 (row offsets are whole dwords)
-        constexpr int kL0 = 1, kL1 = (1 + nL) >> 1, kR0 = nR >> 1, kR1 = (U - 1) >> 1;
-        static_assert(kL1 < kR0 && nR - nL - 1 >= 2, "the wings' dwords stay apart and over-cover centre candidates only");
-        unsigned wl[kL1 - kL0 + 1], wr[kR1 - kR0 + 1], c[nR - nL - 1];
-#pragma unroll
-        for (int k = kL0; k <= kL1; k++) wl[k - kL0] = rq[k];
-#pragma unroll
-        for (int n1 = nL + 1; n1 < nR; n1++) c[n1 - nL - 1] = rp[n1];
-#pragma unroll
-        for (int k = kR0; k <= kR1; k++) wr[k - kR0] = rq[k];
-        wl[0] |= a.w_lo;
-        wr[kR1 - kR0] |= (U & 1) ? a.w_hio : a.w_hie;
-        us2 m, t;
-        __builtin_memcpy(&m, &wl[0], 4);
-#pragma unroll
-        for (int k = 1; k <= kL1 - kL0; k++) { __builtin_memcpy(&t, &wl[k], 4); m = __builtin_elementwise_min(m, t); }
-#pragma unroll
-        for (int k = 0; k <= kR1 - kR0; k++) { __builtin_memcpy(&t, &wr[k], 4); m = __builtin_elementwise_min(m, t); }
-        const unsigned w0 = m[0], w1 = m[1], w = w0 < w1 ? w0 : w1;
-        { const unsigned k = (w << 10) + a.P->gen_wing_key[U - 6]; bg = k < bg ? k : bg; }
-#pragma unroll
-        for (int n1 = nL + 1; n1 < nR; n1++) { const unsigned e = (c[n1 - nL - 1] << 10) + a.P->gen_key[U - 6][n1]; bg = e < bg ? e : bg; }
-    } else
     if (!CHECK || U <= a.um) {
         lds_vu16 rp = (lds_vu16)(rb + a.rowtab[U]);
         unsigned v[U - 3];      // all reads of the run in flight before the first use
-#ifdef MIRP_X_NOGENLDS          // timing experiment: the row's values without touching LDS
-#pragma unroll
-        for (int n1 = 2; n1 <= U - 2; n1++) v[n1 - 2] = 50000u + (((unsigned)(size_t)rp + (unsigned)n1) & 1023u);
-#else
 #pragma unroll
         for (int n1 = 2; n1 <= U - 2; n1++) v[n1 - 2] = rp[n1];
-#endif
-#ifdef MIRP_X_NOGENVALU         // timing experiment: the reads, folded with the fewest instructions that keep them alive
-        { unsigned x = 0;
-#pragma unroll
-          for (int n1 = 2; n1 <= U - 2; n1++) x |= v[n1 - 2];
-          bg = (x << 10) < bg ? (x << 10) : bg; return; }
-#endif
         unsigned w = 65535u;    // wing minimum, ring units
         unsigned e[2 * WD];     // keys of the centre candidates
         int ne = 0;
@@ -395,7 +352,7 @@ __device__ __forceinline__ unsigned a1_generic(const A1& a0, int i, int j, int m
     unsigned bg = KEY_INF;
     const unsigned short* rb = a0.cring + i + 1;
     A1 a = a0;
-    if constexpr (MIRP_A1_WPACK == 2 && !CHECK) {
+    if constexpr (!CHECK) {
         const unsigned par = ((unsigned)(size_t)(lds_vu16)rb >> 1) & 1u;
         a.rba = rb - par; a.w_sh = par * 16u;
     }
@@ -405,13 +362,9 @@ __device__ __forceinline__ unsigned a1_generic(const A1& a0, int i, int j, int m
 template <bool CHECK, int WD, int... Us>
 __device__ __forceinline__ unsigned a1_generic_w(const A1& a0, int i, int j, int mm_outer) {
     unsigned bg = KEY_INF;
-#ifdef MIRP_X_GENBCAST          // timing experiment: every lane reads the same ring columns (no bank conflicts in the generic rows)
-    const unsigned short* rb = a0.cring + 40 + (i & 1);
-#else
     const unsigned short* rb = a0.cring + i + 1;
-#endif
     A1 a = a0;
-    if constexpr (MIRP_A1_WPACK && !CHECK) {
+    if constexpr (!CHECK) {
         // entry n1 of a row sits at halfword (par + n1) of the aligned base: the dword below the left wing holds entry 1 (1 x n) when par is set, the dword
         // at the right wing's end entry U - 1 (U even, par clear), entries U - 1 and U (U odd, par clear) or entry U - 1 (U odd, par set)
         const unsigned par = ((unsigned)(size_t)(lds_vu16)rb >> 1) & 1u;
@@ -533,14 +486,6 @@ __device__ __forceinline__ void a1_small_g(const A1& a, int i, int j, int type, 
 // the table reads that depend on it as a second one, then the arithmetic.  The straightforward versions interleave a volatile read (kept
 // narrow on purpose, see a1_gen_row) with the reads that depend on it, and a volatile access is an ordering point for the scheduler: they
 // compile to one LDS round trip per candidate.
-#ifdef MIRP_X_XBBCAST          // timing experiment: every lane gathers the same table entry (no bank conflicts in the XB / X1 reads)
-#define MIRP_XIDX(e) (((e) & 0u))
-#elif defined(MIRP_X_NOCODE)      // timing experiment: the table gather without the dependent code read in front of it
-#define MIRP_XIDX(e) ((e) & 127u)
-#define MIRP_NOCODE_READ 1
-#else
-#define MIRP_XIDX(e) (e)
-#endif
 #define A1_CHUNK 10
 // N consecutive pair codes starting at byte A of a code array, four per read.  A lane's A has any alignment (consecutive cells have consecutive
 // columns) and a ds_read_b32 off its alignment costs several aligned ones (profiles/tools/lds_unaligned.hip), so the array exists four times, copy c
@@ -588,22 +533,13 @@ __device__ __forceinline__ void a1_b0f(const A1& a, int i, int j, unsigned& best
         int x[N];
 #pragma unroll
         for (int k = 0; k < N; k++) g[k] = rb[a.rowtab[LO + k]];
-#ifdef MIRP_X_RINGONLY          // timing experiment: what a ring of c + bulge / 1xn term would leave of these jobs (no code read, no table gather)
 #pragma unroll
-        for (int k = 0; k < N; k++) { code[k] = 0; x[k] = (int)idxp; }
-#else
-#pragma unroll
-#ifdef MIRP_NOCODE_READ
-        for (int k = 0; k < N; k++) code[k] = 3 * (LO + k);
-#else
-        for (int k = 0; k < N; k++) if (!(MIRP_A1_CODES4 && a.code4)) code[k] = ql[LO + k];
-#endif
-        if (MIRP_A1_CODES4 && a.code4) a1_codes4<N>(a, 0, a.n + 2 - j + LO, xb, idxp, x);
+        for (int k = 0; k < N; k++) if (!a.code4) code[k] = ql[LO + k];
+        if (a.code4) a1_codes4<N>(a, 0, a.n + 2 - j + LO, xb, idxp, x);
         else {
 #pragma unroll
-            for (int k = 0; k < N; k++) x[k] = xb[MIRP_XIDX(idxp + code[k])];
+            for (int k = 0; k < N; k++) x[k] = xb[idxp + code[k]];
         }
-#endif
 #pragma unroll
         for (int k = 0; k < N; k++) { const unsigned e = ((g[k] + (unsigned)x[k]) << 10) + a.P->kb0_key[LO + k]; best = e < best ? e : best; }
     }
@@ -621,22 +557,13 @@ __device__ __forceinline__ void a1_b1f(const A1& a, int i, int j, unsigned& best
         int x[N];
 #pragma unroll
         for (int k = 0; k < N; k++) g[k] = rb[a.rowtab[LO + k] + (LO + k)];
-#ifdef MIRP_X_RINGONLY
 #pragma unroll
-        for (int k = 0; k < N; k++) { code[k] = 0; x[k] = (int)idxq; }
-#else
-#pragma unroll
-#ifdef MIRP_NOCODE_READ
-        for (int k = 0; k < N; k++) code[k] = 3 * (LO + k);
-#else
-        for (int k = 0; k < N; k++) if (!(MIRP_A1_CODES4 && a.code4)) code[k] = pl[LO + k];
-#endif
-        if (MIRP_A1_CODES4 && a.code4) a1_codes4<N>(a, 1, i + 1 + LO, xb, idxq, x);
+        for (int k = 0; k < N; k++) if (!a.code4) code[k] = pl[LO + k];
+        if (a.code4) a1_codes4<N>(a, 1, i + 1 + LO, xb, idxq, x);
         else {
 #pragma unroll
-            for (int k = 0; k < N; k++) x[k] = xb[MIRP_XIDX(idxq + code[k])];
+            for (int k = 0; k < N; k++) x[k] = xb[idxq + code[k]];
         }
-#endif
 #pragma unroll
         for (int k = 0; k < N; k++) { const unsigned e = ((g[k] + (unsigned)x[k]) << 10) + a.P->kb1_key[LO + k]; best = e < best ? e : best; }
     }
@@ -654,22 +581,13 @@ __device__ __forceinline__ void a1_i0f(const A1& a, int i, int j, unsigned& best
         int x[N];
 #pragma unroll
         for (int k = 0; k < N; k++) g[k] = rb[a.rowtab[LO + k + 1]];
-#ifdef MIRP_X_RINGONLY          // timing experiment: what a ring of c + bulge / 1xn term would leave of these jobs (no code read, no table gather)
 #pragma unroll
-        for (int k = 0; k < N; k++) { code[k] = 0; x[k] = (int)idxp; }
-#else
-#pragma unroll
-#ifdef MIRP_NOCODE_READ
-        for (int k = 0; k < N; k++) code[k] = 3 * (LO + k);
-#else
-        for (int k = 0; k < N; k++) if (!(MIRP_A1_CODES4 && a.code4)) code[k] = ql[LO + k];
-#endif
-        if (MIRP_A1_CODES4 && a.code4) a1_codes4<N>(a, 0, a.n + 2 - j + LO, xb, idxp, x);
+        for (int k = 0; k < N; k++) if (!a.code4) code[k] = ql[LO + k];
+        if (a.code4) a1_codes4<N>(a, 0, a.n + 2 - j + LO, xb, idxp, x);
         else {
 #pragma unroll
-            for (int k = 0; k < N; k++) x[k] = xb[MIRP_XIDX(idxp + code[k])];
+            for (int k = 0; k < N; k++) x[k] = xb[idxp + code[k]];
         }
-#endif
 #pragma unroll
         for (int k = 0; k < N; k++) { const unsigned e = ((g[k] + (unsigned)x[k]) << 10) + a.P->k1n0_key[LO + k]; best = e < best ? e : best; }
     }
@@ -687,22 +605,13 @@ __device__ __forceinline__ void a1_i1f(const A1& a, int i, int j, unsigned& best
         int x[N];
 #pragma unroll
         for (int k = 0; k < N; k++) g[k] = rb[a.rowtab[LO + k + 1] + (LO + k)];
-#ifdef MIRP_X_RINGONLY
 #pragma unroll
-        for (int k = 0; k < N; k++) { code[k] = 0; x[k] = (int)idxq; }
-#else
-#pragma unroll
-#ifdef MIRP_NOCODE_READ
-        for (int k = 0; k < N; k++) code[k] = 3 * (LO + k);
-#else
-        for (int k = 0; k < N; k++) if (!(MIRP_A1_CODES4 && a.code4)) code[k] = pl[LO + k];
-#endif
-        if (MIRP_A1_CODES4 && a.code4) a1_codes4<N>(a, 1, i + 1 + LO, xb, idxq, x);
+        for (int k = 0; k < N; k++) if (!a.code4) code[k] = pl[LO + k];
+        if (a.code4) a1_codes4<N>(a, 1, i + 1 + LO, xb, idxq, x);
         else {
 #pragma unroll
-            for (int k = 0; k < N; k++) x[k] = xb[MIRP_XIDX(idxq + code[k])];
+            for (int k = 0; k < N; k++) x[k] = xb[idxq + code[k]];
         }
-#endif
 #pragma unroll
         for (int k = 0; k < N; k++) { const unsigned e = ((g[k] + (unsigned)x[k]) << 10) + a.P->k1n1_key[LO + k]; best = e < best ? e : best; }
     }
@@ -714,7 +623,7 @@ __device__ __forceinline__ unsigned a1_small_key(unsigned g, int mm_inner, int e
     return g == 65535u ? KEY_NONE : ((unsigned)(e + KEY_BIAS) << 10) | code;
 }
 // stack, the two 1-bulges, 1x1, 1x2 of the lane's cell (i, j): the seven bases and five ring entries first, pair types by arithmetic, then the table reads
-__device__ __forceinline__ unsigned a1_small14f(const A1& a, int i, int j, int type, bool ahead, bool noglobal = false) {
+__device__ __forceinline__ unsigned a1_small14f(const A1& a, int i, int j, int type, bool ahead) {
     lds_vu8 Sv = (lds_vu8)a.S;
     const int s_i = Sv[i], s_i1 = Sv[i + 1], s_i2 = Sv[i + 2], s_j3 = Sv[j - 3], s_j2 = Sv[j - 2], s_j1 = Sv[j - 1], s_j = Sv[j];
     const unsigned short* rb = a.cring;
@@ -726,8 +635,8 @@ __device__ __forceinline__ unsigned a1_small14f(const A1& a, int i, int j, int t
     const int m00 = T.mismatchI[t00 * 25 + s_j * 5 + s_i], m01 = T.mismatchI[t01 * 25 + s_j1 * 5 + s_i], m10 = T.mismatchI[t10 * 25 + s_j * 5 + s_i1];
     const int m11 = T.mismatchI[t11 * 25 + s_j1 * 5 + s_i1], m12 = T.mismatchI[t12 * 25 + s_j2 * 5 + s_i1];
     const int st00 = T.stack[type * 8 + t00], st01 = T.stack[type * 8 + t01], st10 = T.stack[type * 8 + t10], b1 = T.bulge[1];
-    const int r11 = noglobal ? 0 : a.P->int11[type][t11][s_i1][s_j1];
-    const int r12 = noglobal ? 0 : a.P->int21[type][t12][s_i1][s_j2][s_j1];
+    const int r11 = a.P->int11[type][t11][s_i1][s_j1];
+    const int r12 = a.P->int21[type][t12][s_i1][s_j2][s_j1];
     unsigned res = a1_small_key(g01, m01, b1 + st01, 0u << 5 | 1u);
     unsigned k = a1_small_key(g10, m10, b1 + st10, 1u << 5 | 0u); res = k < res ? k : res;
     k = a1_small_key(g00, m00, st00, 0u); if (!ahead) res = k < res ? k : res;     // the stacked pair of a lane of diagonal d+1 is not final yet
@@ -736,7 +645,7 @@ __device__ __forceinline__ unsigned a1_small14f(const A1& a, int i, int j, int t
     return res;
 }
 // 2x1, 2x2, 2x3, 3x2
-__device__ __forceinline__ unsigned a1_small15f(const A1& a, int i, int j, int type, bool noglobal = false) {
+__device__ __forceinline__ unsigned a1_small15f(const A1& a, int i, int j, int type) {
     lds_vu8 Sv = (lds_vu8)a.S;
     const int s_i1 = Sv[i + 1], s_i2 = Sv[i + 2], s_i3 = Sv[i + 3], s_i4 = Sv[i + 4], s_j4 = Sv[j - 4], s_j3 = Sv[j - 3], s_j2 = Sv[j - 2], s_j1 = Sv[j - 1];
     const unsigned short* rb = a.cring;
@@ -749,8 +658,8 @@ __device__ __forceinline__ unsigned a1_small15f(const A1& a, int i, int j, int t
     const int m32 = T.mismatchI[t32 * 25 + s_j2 * 5 + s_i3];
     const int o23 = T.mismatch23I[type * 25 + s_i1 * 5 + s_j1], i23 = T.mismatch23I[t23 * 25 + s_j3 * 5 + s_i2], i32 = T.mismatch23I[t32 * 25 + s_j2 * 5 + s_i3];
     const int base23 = T.internal_loop[5] + T.ninio;
-    const int r21 = noglobal ? 0 : a.P->int21[t21][type][s_j1][s_i1][s_i2];
-    const int r22 = noglobal ? 0 : a.P->int22[type][t22][s_i1][s_i2][s_j2][s_j1];
+    const int r21 = a.P->int21[t21][type][s_j1][s_i1][s_i2];
+    const int r22 = a.P->int22[type][t22][s_i1][s_i2][s_j2][s_j1];
     unsigned res = a1_small_key(g23, m23, base23 + o23 + i23, 2u << 5 | 3u);
     unsigned k = a1_small_key(g32, m32, base23 + o23 + i32, 3u << 5 | 2u); res = k < res ? k : res;
     k = a1_small_key(g21, m21, r21, 2u << 5 | 1u); res = k < res ? k : res;

@@ -21,7 +21,6 @@
 //     INF is >= 65535 and can never beat the 65535 start value of a running minimum;
 //   * windows whose energies leave the 16-bit ranges are flagged and re-run by the generic kernel.
 // No MFMA: integer min-plus DP with irregular table lookups.
-#define MIRP_A1_CODES4 1
 #include "fold_lds_common.h"
 // In-place compaction of the split-candidate pool, period in diagonals per model (0 = never) and the number of 64-entry rounds a wave holds in registers.
 #ifndef MIRP_CPERIOD0
@@ -46,36 +45,25 @@ namespace mirp {
 // {s-1, j, fML(s,j)} behind the window's fML triangle; phase A2 maps LANE = POOL ENTRY: the entry's column j holds exactly one cell of the
 // diagonal at hand, (j-d, j), which it relaxes with one gather + one LDS atomic minimum.  A row's thread carries DML(i,j-1) in a register.
 // A window whose pool overflows (tandem repeats) or whose length leaves no room for one is handed to the dense instantiation (second launch).
-// MIRP_FILL_ATTR (dev builds): extra attributes of the fill kernel, e.g. -DMIRP_FILL_ATTR='__attribute__((amdgpu_num_vgpr(52)))' -- gfx950 doubles the
-// request (unified register file), 52 caps the kernel at 104 VGPRs
-#ifndef MIRP_FILL_ATTR
-#define MIRP_FILL_ATTR
-#endif
 template <int MODEL, bool SPARSE>
-__global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
+__global__ void __launch_bounds__(LNT) fold_lds_kernel(
     const FoldParams* __restrict__ P, const unsigned char* __restrict__ seqs, const long long* __restrict__ offs, const int* __restrict__ win_lens,
     int n_work, int win_base, int span, short* __restrict__ slabs, size_t slab_shorts, int* __restrict__ win_state,
     unsigned int* __restrict__ work_counter, int* __restrict__ fallback_list,
     unsigned int* __restrict__ fallback_count, int max_lines, int ss_stride, MirpFoldLine* __restrict__ out_lines, char* __restrict__ out_ss,
-    int* __restrict__ out_nlines, int* __restrict__ out_mfe, int* __restrict__ out_status, int dbg_flags_arg, long long* __restrict__ dbg_cycles_arg,
+    int* __restrict__ out_nlines, int* __restrict__ out_mfe, int* __restrict__ out_status, int light_clocks_arg, long long* __restrict__ dbg_cycles_arg,
     const int* __restrict__ todo_list, const unsigned int* __restrict__ todo_count, int* __restrict__ dense_list, unsigned int* __restrict__ dense_count) {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr LdsLayout LY = lds_layout<MODEL, SPARSE>();
-    // phase ablation flags and phase clocks exist in the diagnostics build only (make DIAG=1); the product kernel carries none of that code
+    // phase clocks exist in the diagnostics build only (make DIAG=1); the product kernel carries none of that code.  Light mode: per wave only the
+    // busy time and the barrier wait (two clock reads per wave and interval)
 #ifdef MIRP_DIAG
-    const int dbg_flags = dbg_flags_arg;
+    const bool light = light_clocks_arg != 0;
     long long* const dbg_cycles = dbg_cycles_arg;
-#elif defined(MIRP_LITE_CLOCKS)      // dev build: product code + per-wave busy / barrier-wait clocks only (two clock reads per wave and interval)
-    constexpr int dbg_flags = 1 << 20;
-    long long* const dbg_cycles = dbg_cycles_arg;
-    (void)dbg_flags_arg;
 #else
-#ifndef MIRP_ABLATE
-#define MIRP_ABLATE 0      // dev builds only (make ABLATE=<flags>): phases removed at compile time, to time product-like code without them
-#endif
-    constexpr int dbg_flags = MIRP_ABLATE;
+    constexpr bool light = false;
     constexpr long long* dbg_cycles = nullptr;
-    (void)dbg_flags_arg; (void)dbg_cycles_arg;
+    (void)light_clocks_arg; (void)dbg_cycles_arg;
 #endif
     constexpr int DMLR = MODEL ? 5 : 3;      // depth of the DML ring
     // outer-pair terms of a list entry (default model): two 10-bit signed fields above the 12 bits of i and type; the host checks that the tables fit
@@ -101,7 +89,7 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
     // [3][LSEG]: paired cells of diagonal d in buffer d % 3 (compact, unordered).  Default model: i | type << 9 | mmo << 12 | mm1 << 22, mmo / mm1 = the cell's
     // outer-pair terms mismatchI / mismatch1nI [type][S[i+1]][S[j-1]] as 10-bit signed values (ENT_OUTER below): phase B, which has the time, looks them up
     // when it builds the entry, and a block's prologue in phase A1 goes from the entry straight to arithmetic -- no dependent table read in front
-    // of every block of every wave (timing build -DMIRP_X_NOOUTER: worth 2 ms).  (Before: oi = type * 25 + S[i+1] * 5 + S[j-1]
+    // of every block of every wave (worth 2 ms in a timing build without the lookup).  (Before: oi = type * 25 + S[i+1] * 5 + S[j-1]
     // indexes the outer pair's mismatch tables: it rides in the entry so that phase A1 goes from the entry straight to the tables (reading the two
     // bases first was one more LDS round trip in front of every block of every wave)
     using list_t = unsigned;
@@ -249,10 +237,7 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
         int sp_ncpad = 0, sp_nsub = 0, sp_pair = 0, sp_sub = 0, sp_so1 = 0, sp_si1 = 0, sp_so2 = 0, sp_si2 = 0;
         int sp_snap = 0;          // sparse splits: pool size as read one interval ago (wave-uniform)
         int dml_carry = INF;      // sparse splits: DML(i, j-1) of this thread's row i = tid + 1 (phase B carries it from diagonal to diagonal)
-#ifndef MIRP_PB_BASES
-#define MIRP_PB_BASES 1
-#endif
-        // (MIRP_PB_BASES, round 6) phase B of the default model takes its bases out of two registers: the row's own three once per window, the far side's five as a window that slides by one
+        // (round 6) phase B of the default model takes its bases out of two registers: the row's own three once per window, the far side's five as a window that slides by one
         // base per diagonal (a row's thread owns cell (i, i + d) in interval d) -- one byte read per cell and interval instead of eight
         int pb_si = 0;            // S[i-1] | S[i] << 3 | S[i+1] << 6
         int pb_sj = 0;            // S[j-1] | S[j] << 3 | S[j+1] << 6 | S[j+2] << 9 | S[j+3] << 12 of the cell of the coming phase B
@@ -284,7 +269,6 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
                     const unsigned pa = (unsigned)(size_t)(__attribute__((address_space(3))) int*)&misc[3];
                     asm volatile("ds_read_b32 %0, %1" : "=v"(pnv) : "v"(pa) : "memory");
                 }
-                if (!(dbg_flags & 2))
                 for (int k = (LNW - 1 - wave) * 64 + lane; k < lim; k += LNT) {
                     const unsigned ea = poolA[k];
                     const unsigned vb = poolB[k];
@@ -310,7 +294,6 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
                     const unsigned pa = (unsigned)(size_t)(__attribute__((address_space(3))) int*)&misc[3];
                     asm volatile("ds_read_b32 %0, %1" : "=v"(pnv) : "v"(pa) : "memory");
                 }
-                if (!(dbg_flags & 2))
                 for (int k = (LNW - 1 - wave) * 64 + lane; k < lim; k += LNT) {
                     const unsigned lo = poolA[k], hi = poolB32[k];
                     const int p = (int)(lo & 511u), q = (int)((lo >> 9) & 511u);
@@ -359,7 +342,7 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
                     sp_si2 += 2 * sp_nsub;
                 }
                 const int nsub = sp_nsub, pair = sp_pair, sub = sp_sub;
-                if (sub < nsub && !(dbg_flags & 2)) {
+                if (sub < nsub) {
                     const int i = 2 * pair + 1;
                     // every split t in [4, d-5] is relaxed unconditionally: with the biased uint16 encoding a sum that involves an INF entry
                     // saturates at 65535 and any sum of two finite entries is <= 65534, so no per-lane range bookkeeping is needed.
@@ -377,13 +360,8 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
                     const unsigned fb0 = (unsigned)(size_t)(lds_cu32)reinterpret_cast<const unsigned*>(fml + i);
                     unsigned va = fb0 + (unsigned)so1, vb = fb0 + (unsigned)so2;
 #define MIRP_SSTEP() do { va += (unsigned)si1; vb += (unsigned)si2; asm volatile("s_sub_i32 %0, %0, %2\n\ts_sub_i32 %1, %1, %2" : "+s"(si1), "+s"(si2) : "s"(sss) : "scc"); } while (0)
-#ifdef MIRP_X_NOSPLITLDS          // timing experiment: the split loop's address arithmetic and packed min-plus without its LDS reads
-#define MIRP_LDA() (va | 0x40004000u)
-#define MIRP_LDB(o) ((vb + (o)) | 0x40004000u)
-#else
 #define MIRP_LDA() (*(lds_cu32)(va))
 #define MIRP_LDB(o) (*(lds_cu32)(vb + (o)))
-#endif
                     // K splits with all their reads in flight before the first use.  The tail of a wave's split range (up to 7 splits) goes through
                     // the 4-, 2- and 1-deep groups: at most three LDS round trips instead of one per split.
                     auto group = [&](auto ODD, auto KK) {
@@ -417,38 +395,29 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
                         if (t + s1 <= d - 5) group(ODD, std::integral_constant<int, 2>{});
                         if (t <= d - 5) group(ODD, std::integral_constant<int, 1>{});
                     };
-#ifdef MIRP_X_SPLITODD          // timing experiment: every wave takes the aligned (odd t) path: no third read, no v_alignbit
-                    relax(std::true_type{});
-#else
                     if (odd) relax(std::true_type{}); else relax(std::false_type{});
-#endif
 #undef MIRP_SSTEP
 #undef MIRP_LDA
 #undef MIRP_LDB
                     const unsigned r0 = bu[0], r1 = bu[1];
-#ifdef MIRP_X_NOSPLITATOM      // timing experiment: plain stores instead of the split loop's two atomic minima
-                    if (i <= ncell && r0 < 65535u) mdec[i] = (int)r0 - 2 * FML_BIAS;
-                    if (i + 1 <= ncell && r1 < 65535u) mdec[i + 1] = (int)r1 - 2 * FML_BIAS;
-#else
                     if (i <= ncell && r0 < 65535u) atomicMin(&mdec[i], (int)r0 - 2 * FML_BIAS);
                     if (i + 1 <= ncell && r1 < 65535u) atomicMin(&mdec[i + 1], (int)r1 - 2 * FML_BIAS);
-#endif
                 }
             };
             // Half of the waves run the splits before the interior loops: the split loop loads the LDS pipe much more than the interior loops do,
             // so the two halves even out the LDS load of the interval (the phases are independent: both only feed phase B of this diagonal).
-            const bool swap_order = !SPARSE && (wave & 1) && !(dbg_flags & 2048);      // (the sparse splits are too short to matter: measured 0.5 ms better behind the interior loops)
+            const bool swap_order = !SPARSE && (wave & 1);      // (the sparse splits are too short to matter: measured 0.5 ms better behind the interior loops)
             auto splits = [&]() { if constexpr (SPARSE && MODEL != 0) splits_sparse185(); else if constexpr (SPARSE) splits_sparse(); else splits_dense(); };
             if (swap_order) splits();
-            if (dbg_cycles && lane == 0 && !(dbg_flags & (1 << 20))) wt = clock64();
+            if (dbg_cycles && lane == 0 && !light) wt = clock64();
             // phase A1: interior-loop candidates.  The c ring holds G0(p,q) = c(p,q) + mismatchI[rtype(pq)][S[q+1]][S[p-1]] (+ 32768).
-            if (!(dbg_flags & (1 | 64)) && d >= 6 && d <= D) {
+            if (d >= 6 && d <= D) {
                 const list_t* clist = list + (d % 3) * LSEG;
                 // Lane fill: the blocks of 64 paired cells of diagonal d are topped up with the first cells of diagonal d+1.  All candidates of
                 // a cell of d+1 except the stacked pair have their inner pair on diagonals <= d-2, which are final in this interval; the stacked
                 // pair follows one interval later (`done` cells below).  Such a lane differs only in j = i + d + 1 and in its ring rows, which
                 // are the rows after those of diagonal d (CRING_ROWS).  Only once every loop size is admissible (um = MAXLOOP for both).
-                const bool mix = d - 2 - (TURN + 1) >= MAXLOOP && d + 1 <= D && !(dbg_flags & 256);
+                const bool mix = d - 2 - (TURN + 1) >= MAXLOOP && d + 1 <= D;
                 // the length of this list is known since the previous interval (a1_ncp); the first block's entries are fetched before anything
                 // else: every dependent LDS access in front of the shape code costs hundreds of cycles when the pipe is loaded
                 const int ncp = a1_ncp;                    // = lcnt[d % 6], read one interval ago as ncp2: no LDS round trip in front of the first block
@@ -468,9 +437,6 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
                     const int ka = lane - (64 - room);
                     if (ka >= 0 && ka < take2) aent = list[((d + 1) % 3) * LSEG + ka];
                 }
-#ifndef MIRP_ROLEMAP
-#define MIRP_ROLEMAP 1
-#endif
 #define MIRP_XROWS15 9, 7
 #define MIRP_XROWS8 8
 #define MIRP_XROWS9 10
@@ -480,8 +446,6 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
                 const int role = wave < 4 ? wave : wave < 6 ? wave + 10 : wave < 12 ? wave + 2 : wave - 8;
                 A1 a;
                 a.P = P; a.T = &T; a.S = S; a.cring = cring; a.pax = pax; a.qbr = qbr; a.code4 = code4; a.n = n;
-                const bool slow = (dbg_flags & 8192) != 0;     // diagnostics build: the one-round-trip-per-candidate versions of the jobs
-                {
                 for (int blk = 0; blk < nblk; blk++) {
                     {   // re-materialise the wave-uniform loop parameters per block: keeps the admissibility tests and row offsets as plain
                         // scalar compares inside the block instead of dozens of hoisted masks (SGPR spills)
@@ -493,11 +457,7 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
                     const int k = blk * 64 + lane;
                     const bool own = k < rem, ahead = !own && aent != 0;       // k >= rem only happens in the last block
                     const bool act = own || ahead;
-#ifdef MIRP_X_NOENT           // timing experiment: no list-entry read in front of a block
-                    const unsigned ent = own ? (unsigned)(((done + k) * 3 + 1) % 300 + 1) | (1u << 9) : ahead ? aent : (1u | (1u << 9));
-#else
                     const unsigned ent = own ? clist[done + k] : ahead ? aent : (1u | (1u << 9));   // idle lanes: harmless dummy cell
-#endif
                     const int i = ent & 511, type = (ent >> 9) & 7, j = i + d + (ahead ? 1 : 0);
                     a.cring = cring + (ahead ? CSTR : 0);
                     unsigned* ck = ahead ? ckey2 : ckey;
@@ -505,24 +465,23 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
                     // the terms of the outer pair that turn a job's running minimum into the cell's key: fetched before the shape code, so that
                     // their two round trips (bases, then tables) overlap the job's own reads instead of following them
                     int au1 = 0, mmo = 0, mm1 = 0;
-                    if (role < 14 || (MIRP_ROLEMAP && MODEL == 0)) {
+                    if (role < 14 || MODEL == 0) {
                         au1 = type > 2 ? tau_s : 0;
                         mmo = ((int)(ent << 10)) >> 22; mm1 = ((int)ent) >> 22;          // the 10-bit signed fields of the entry
                     }
                     if (role < 8) {
-                        if (!(dbg_flags & 4)) {
 #define MIRP_GEN(CK)                                                                      \
     switch (role) {                                                                       \
-    case 0: res = MIRP_A1G<CK MIRP_A1WD, 30, 23>(a, i, j, mmo); if (CK || slow) a1_i1<CK, 28, 29>(a, i, j, xi); else a1_i1f<28, 29>(a, i, j, xi); break;      \
-    case 1: res = MIRP_A1G<CK MIRP_A1WD, 29, 24>(a, i, j, mmo); if (CK || slow) a1_i1<CK, 25, 27>(a, i, j, xi); else a1_i1f<25, 27>(a, i, j, xi); break;      \
-    case 2: res = MIRP_A1G<CK MIRP_A1WD, 28, 25>(a, i, j, mmo); if (CK || slow) a1_i0<CK, 26, 29>(a, i, j, xi); else a1_i0f<26, 29>(a, i, j, xi); break;      \
-    case 3: res = MIRP_A1G<CK MIRP_A1WD, 27, 26>(a, i, j, mmo); if (CK || slow) a1_b1<CK, 26, 30>(a, i, j, xb); else a1_b1f<26, 30>(a, i, j, xb); break;      \
+    case 0: res = MIRP_A1G<CK MIRP_A1WD, 30, 23>(a, i, j, mmo); if (CK) a1_i1<CK, 28, 29>(a, i, j, xi); else a1_i1f<28, 29>(a, i, j, xi); break;      \
+    case 1: res = MIRP_A1G<CK MIRP_A1WD, 29, 24>(a, i, j, mmo); if (CK) a1_i1<CK, 25, 27>(a, i, j, xi); else a1_i1f<25, 27>(a, i, j, xi); break;      \
+    case 2: res = MIRP_A1G<CK MIRP_A1WD, 28, 25>(a, i, j, mmo); if (CK) a1_i0<CK, 26, 29>(a, i, j, xi); else a1_i0f<26, 29>(a, i, j, xi); break;      \
+    case 3: res = MIRP_A1G<CK MIRP_A1WD, 27, 26>(a, i, j, mmo); if (CK) a1_b1<CK, 26, 30>(a, i, j, xb); else a1_b1f<26, 30>(a, i, j, xb); break;      \
     case 4: res = MIRP_A1G<CK MIRP_A1WD, MIRP_ROWS4>(a, i, j, mmo); break;                    \
     case 5: res = MIRP_A1G<CK MIRP_A1WD, MIRP_ROWS5>(a, i, j, mmo); break;                    \
     case 6: res = MIRP_A1G<CK MIRP_A1WD, MIRP_ROWS6>(a, i, j, mmo); break;                    \
     default: res = MIRP_A1G<CK MIRP_A1WD, MIRP_ROWS7>(a, i, j, mmo); break;               \
     }
-// generic rows that ride on the waves of other jobs (MIRP_ROLEMAP 1): with the split loop sparse, the 4-5-row generic groups were the busiest waves of an
+// generic rows that ride on the waves of other jobs (default model): with the split loop sparse, the 4-5-row generic groups were the busiest waves of an
 // interval (90 % busy against 56-65 % on the small-shape and bulge waves, profiles/tools/wave_busy.sh); a row can run anywhere -- the key carries the shape
 #define MIRP_XGEN(CK)                                                                     \
     switch (role) {                                                                       \
@@ -531,89 +490,73 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
     case 9: rx = MIRP_A1G<CK MIRP_A1WD, MIRP_XROWS9>(a, i, j, mmo); break;                           \
     default: break;                                                                       \
     }
-                            // the 2-row generic groups run on the phase-B waves, which have slack left: they also take a few bulge / 1xn shapes
-                            unsigned xb = KEY_INF, xi = KEY_INF;
-                            // default model: the saturated-asymmetry candidates of a row go through one minimum (a1_gen_row_w)
-                            if constexpr (MODEL == 0) {
+                        // the 2-row generic groups run on the phase-B waves, which have slack left: they also take a few bulge / 1xn shapes
+                        unsigned xb = KEY_INF, xi = KEY_INF;
+                        // default model: the saturated-asymmetry candidates of a row go through one minimum (a1_gen_row_w)
+                        if constexpr (MODEL == 0) {
 #define MIRP_A1G a1_generic_w
 #define MIRP_A1WD , GEN_WD
-#if MIRP_ROLEMAP              // rows 7 - 10 ride on the small-shape and bulge waves (MIRP_XGEN below)
+// rows 7 - 10 ride on the small-shape and bulge waves (MIRP_XGEN below)
 #define MIRP_ROWS4 22, 17, 12
 #define MIRP_ROWS5 21, 18, 11
 #define MIRP_ROWS6 20, 16, 13
 #define MIRP_ROWS7 19, 15, 14, 6
-#else
-#define MIRP_ROWS4 22, 17, 12, 7
-#define MIRP_ROWS5 21, 18, 11, 8
-#define MIRP_ROWS6 20, 16, 13, 9
-#define MIRP_ROWS7 19, 15, 14, 10, 6
-#endif
-                                if (a.um >= MAXLOOP) { MIRP_GEN(false) } else { MIRP_GEN(true) }
+                            if (a.um >= MAXLOOP) { MIRP_GEN(false) } else { MIRP_GEN(true) }
 #undef MIRP_A1G
 #undef MIRP_A1WD
 #undef MIRP_ROWS4
 #undef MIRP_ROWS5
 #undef MIRP_ROWS6
 #undef MIRP_ROWS7
-                            } else {          // vienna-1.8.5 keeps all generic rows on roles 4 - 7 (the other map measured +0.6 ms there)
+                        } else {          // vienna-1.8.5 keeps all generic rows on roles 4 - 7 (the other map measured +0.6 ms there)
 #define MIRP_A1G a1_generic
 #define MIRP_A1WD
 #define MIRP_ROWS4 22, 17, 12, 7
 #define MIRP_ROWS5 21, 18, 11, 8
 #define MIRP_ROWS6 20, 16, 13, 9
 #define MIRP_ROWS7 19, 15, 14, 10, 6
-                                if (a.um >= MAXLOOP) { MIRP_GEN(false) } else { MIRP_GEN(true) }
+                            if (a.um >= MAXLOOP) { MIRP_GEN(false) } else { MIRP_GEN(true) }
 #undef MIRP_A1G
 #undef MIRP_A1WD
 #undef MIRP_ROWS4
 #undef MIRP_ROWS5
 #undef MIRP_ROWS6
 #undef MIRP_ROWS7
-                            }
-                            if (role < 4) {
-                                const unsigned rb = a1_key(xb, -32768 - OTH_BIAS + au1);
-                                const unsigned ri = a1_key(xi, -32768 - OTH_BIAS + mm1);
-                                res = rb < res ? rb : res;
-                                res = ri < res ? ri : res;
-                            }
+                        }
+                        if (role < 4) {
+                            const unsigned rb = a1_key(xb, -32768 - OTH_BIAS + au1);
+                            const unsigned ri = a1_key(xi, -32768 - OTH_BIAS + mm1);
+                            res = rb < res ? rb : res;
+                            res = ri < res ? ri : res;
+                        }
 #undef MIRP_GEN
-                        }
                     } else if (role < 14) {
-                        if (!(dbg_flags & 8)) {
-                            unsigned bb = KEY_INF, bi = KEY_INF;
-#define MIRP_OTH(CK)                                                                      \
-    switch (role) {                                                                       \
-    case 8: a1_b0<CK, 2, 18>(a, i, j, bb); break;                                         \
-    case 9: a1_b0<CK, 19, 30>(a, i, j, bb); a1_b1<CK, 2, 6>(a, i, j, bb); break;          \
-    case 10: a1_b1<CK, 7, 22>(a, i, j, bb); break;                                        \
-    case 11: a1_b1<CK, 23, 25>(a, i, j, bb); a1_i0<CK, 3, 15>(a, i, j, bi); break;        \
-    case 12: a1_i0<CK, 16, 25>(a, i, j, bi); a1_i1<CK, 3, 8>(a, i, j, bi); break;         \
-    default: a1_i1<CK, 9, 24>(a, i, j, bi); break;                                        \
-    }
-                            if (a.um >= MAXLOOP && !slow) {
-                                switch (role) {
-                                case 8: a1_b0f<2, 18>(a, i, j, bb); break;
-                                case 9: a1_b0f<19, 30>(a, i, j, bb); a1_b1f<2, 6>(a, i, j, bb); break;
-                                case 10: a1_b1f<7, 22>(a, i, j, bb); break;
-                                case 11: a1_b1f<23, 25>(a, i, j, bb); a1_i0f<3, 15>(a, i, j, bi); break;
-                                case 12: a1_i0f<16, 25>(a, i, j, bi); a1_i1f<3, 8>(a, i, j, bi); break;
-                                default: a1_i1f<9, 24>(a, i, j, bi); break;
-                                }
-                            } else if (a.um >= MAXLOOP) { MIRP_OTH(false) } else { MIRP_OTH(true) }
-#undef MIRP_OTH
-                            const unsigned rb = a1_key(bb, -32768 - OTH_BIAS + au1);
-                            const unsigned ri = a1_key(bi, -32768 - OTH_BIAS + mm1);
-                            res = rb < ri ? rb : ri;
+                        unsigned bb = KEY_INF, bi = KEY_INF;
+                        if (a.um >= MAXLOOP) {
+                            switch (role) {
+                            case 8: a1_b0f<2, 18>(a, i, j, bb); break;
+                            case 9: a1_b0f<19, 30>(a, i, j, bb); a1_b1f<2, 6>(a, i, j, bb); break;
+                            case 10: a1_b1f<7, 22>(a, i, j, bb); break;
+                            case 11: a1_b1f<23, 25>(a, i, j, bb); a1_i0f<3, 15>(a, i, j, bi); break;
+                            case 12: a1_i0f<16, 25>(a, i, j, bi); a1_i1f<3, 8>(a, i, j, bi); break;
+                            default: a1_i1f<9, 24>(a, i, j, bi); break;
+                            }
+                        } else {
+                            switch (role) {
+                            case 8: a1_b0<true, 2, 18>(a, i, j, bb); break;
+                            case 9: a1_b0<true, 19, 30>(a, i, j, bb); a1_b1<true, 2, 6>(a, i, j, bb); break;
+                            case 10: a1_b1<true, 7, 22>(a, i, j, bb); break;
+                            case 11: a1_b1<true, 23, 25>(a, i, j, bb); a1_i0<true, 3, 15>(a, i, j, bi); break;
+                            case 12: a1_i0<true, 16, 25>(a, i, j, bi); a1_i1<true, 3, 8>(a, i, j, bi); break;
+                            default: a1_i1<true, 9, 24>(a, i, j, bi); break;
+                            }
                         }
-                    } else if (!(dbg_flags & 32) && a.um >= MAXLOOP && !slow) {
-#ifdef MIRP_X_NOSMALLGLOBAL     // timing experiment: the small-shape jobs without their global table loads
-                        res = role == 14 ? a1_small14f(a, i, j, type, ahead, true) : a1_small15f(a, i, j, type, true);
-#elif defined(MIRP_X_NOSMALL)        // timing experiment: no small-shape jobs at all
-                        res = KEY_NONE;
-#else
-                        res = role == 14 ? a1_small14f(a, i, j, type, ahead, (dbg_flags & 16384) != 0) : a1_small15f(a, i, j, type, (dbg_flags & 16384) != 0);
-#endif
-                    } else if (!(dbg_flags & 32)) {
+                        const unsigned rb = a1_key(bb, -32768 - OTH_BIAS + au1);
+                        const unsigned ri = a1_key(bi, -32768 - OTH_BIAS + mm1);
+                        res = rb < ri ? rb : ri;
+                    } else if (a.um >= MAXLOOP) {
+                        res = role == 14 ? a1_small14f(a, i, j, type, ahead) : a1_small15f(a, i, j, type);
+                    } else {
                         const int si1 = S[i + 1], sj1 = S[j - 1];
                         int ra, ca, rb2, cb2;
                         unsigned ka, kb2;
@@ -631,9 +574,8 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
                         if (ca < INF) { const unsigned k = ((unsigned)(ra + ca + KEY_BIAS) << 10) | ka; res = k < res ? k : res; }
                         if (cb2 < INF) { const unsigned k = ((unsigned)(rb2 + cb2 + KEY_BIAS) << 10) | kb2; res = k < res ? k : res; }
                     }
-#if MIRP_ROLEMAP
                     if constexpr (MODEL == 0) {
-                        if (role >= 8 && !(dbg_flags & 4)) {
+                        if (role >= 8) {
                             unsigned rx = KEY_NONE;
 #define MIRP_A1G a1_generic_w
 #define MIRP_A1WD , GEN_WD
@@ -643,14 +585,9 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
                             res = rx < res ? rx : res;
                         }
                     }
-#endif
-#ifdef MIRP_X_NOATOM            // timing experiment: a plain store instead of the block's atomic minimum
-                    if (act && res != KEY_NONE) ck[i] = res;
-#else
                     if (act && res != KEY_NONE) atomicMin(&ck[i], res);
-#endif
                 }
-                if (role == 14 && done > 0 && !(dbg_flags & 32)) {   // stacked pairs of the cells that went ahead in the previous interval (done <= 63)
+                if (role == 14 && done > 0) {   // stacked pairs of the cells that went ahead in the previous interval (done <= 63)
                     const bool act = lane < done;
                     const unsigned ent = act ? clist[lane] : (1u | (1u << 9));
                     const int i = ent & 511, type = (ent >> 9) & 7, j = i + d;
@@ -661,162 +598,19 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
                     a1_small<0, 0>(a, i, j, type, S[i + 1], S[j - 1], res);
                     if (act && res != KEY_NONE) atomicMin(&ckey[i], res);
                 }
-                }
-                if (dbg_cycles && lane == 0 && wave == 9 && !(dbg_flags & (1 << 20))) {   // diagnostics: interior-loop time of one wave by number of blocks
+                if (dbg_cycles && lane == 0 && wave == 9 && !light) {   // diagnostics: interior-loop time of one wave by number of blocks
                     const int b = nblk < 3 ? nblk : 3;
                     atomicAdd((unsigned long long*)&dbg_cycles[68 + b], (unsigned long long)(clock64() - wt));
                     atomicAdd((unsigned long long*)&dbg_cycles[72 + b], 1ull);
                 }
             }
-            if (dbg_cycles && lane == 0 && !(dbg_flags & (1 << 20))) { const long long t = clock64(); wA1 += t - wt; wt = t; }
+            if (dbg_cycles && lane == 0 && !light) { const long long t = clock64(); wA1 += t - wt; wt = t; }
             if (!swap_order) splits();
-        };
-        auto phaseB = [&](const int d) {
-            const int ncell = n - d;
-            unsigned* ckey = reinterpret_cast<unsigned*>(acc + MIRP_CK(d) * LCAP);
-            int* mdec = mdec_of(d);
-            int cand = 0; unsigned cent = 0, cval = 0;      // sparse splits: this cell as a split candidate
-            int rp = 0, rq = 0, rval = 0, rtp = 0;          // vienna-1.8.5 candidate pass: the pair whose term realises fML of this cell, its plain term and type
-            if constexpr (SPARSE && MODEL != 0) { if (tid < 11) pbits[((d + 1) & 3) * 11 + tid] = 0; }      // the row of diagonal d-3 serves diagonal d+1 from the next interval on
-            const int hp_u = P->hairpinE[d - 1 < MIRP_HP_MAX ? d - 1 : MIRP_HP_MAX - 1];
-            const int od = tri_off(d, n), od1 = tri_off(d - 1, n);     // scalar arithmetic instead of a table read on the cell's dependency chain
-            const int x = tid;
-            // paired-cell list of diagonal d+3 (phase A1 of this interval reads those of d+1 and d+2): the range is claimed first, the entry is
-            // written at the end, so that the atomic's latency is covered by the cell work in between
-            int lt = 0, lbase = 0, loi = 0;
-            unsigned long long lbal = 0;
-            if (d + 3 <= D && wave < 6) {
-                if (x + 1 + d + 3 <= n) { lt = pair_type(S[x + 1], S[x + 1 + d + 3]); loi = lt * 25 + S[x + 2] * 5 + S[x + d + 3]; }
-                lbal = __ballot(lt != 0);
-                if (lbal && lane == 0) lbase = atomicAdd(&lcnt[(d + 3) % 6], (int)__popcll(lbal));
-            }
-            if (tid == 0) lcnt[(d + 4) % 6] = 0;   // the list of diagonal d-2 is dead: its counter serves diagonal d+4 in the next interval
-            if (x < ncell) {
-                const int i = x + 1, j = i + d;
-                const int type = (MODEL && d > D) ? 0 : pair_type(S[i], S[j]);
-                int cv = INF;
-                int md = mdec[i];
-                if constexpr (SPARSE) { md = dml_carry < md ? dml_carry : md; dml_carry = md; }      // DML(i,j) = min(DML(i,j-1), candidate splits)
-                int tb = 0;          // trace-back code: 0 = hairpin / multiloop / unpaired, else 1 + (n1 << 5 | n2) of the interior loop the backtrack takes
-                if (type) {
-                    const unsigned kk = ckey[i];
-                    const int cint = kk == KEY_NONE ? INF : (int)(kk >> 10) - KEY_BIAS;
-                    cv = cint;
-                    int h;
-                    const int u = d - 1;
-                    if (MODEL) {
-                        h = hp_u + (u == 3 ? (type > 2 ? (int)T.TerminalAU : 0) : (int)T.mismatchH[type * 25 + S[i + 1] * 5 + S[j - 1]]);
-                        if (u == 4) h += spec[nc + i];
-                    } else {
-                        int sv = -32768;
-                        if (u == 4) sv = spec[nc + i]; else if (u == 6) sv = spec[2 * nc + i]; else if (u == 3) sv = spec[i];
-                        if (sv != -32768) h = sv;
-                        else if (u == 3) h = hp_u + (type > 2 ? T.TerminalAU : 0);
-                        else h = hp_u + T.mismatchH[type * 25 + S[i + 1] * 5 + S[j - 1]];
-                    }
-                    cv = h < cv ? h : cv;
-                    if (MODEL) {
-                        // multiloop closed by (i,j), dangles 1: min over { DML(i+1,j-1), DML(i+2,j-1)+d3, DML(i+1,j-2)+d5, DML(i+2,j-2)+d3+d5 }
-                        const int tt = rtype_of(type);
-                        const int e3 = T.dangle3[tt * 5 + S[i + 1]], e5 = T.dangle5[tt * 5 + S[j - 1]];
-                        int X = INF, v;
-                        v = dmlring[((d + DMLR - 2) % DMLR) * LCAP + i + 1]; if (v != I16_INF) X = v;
-                        v = dmlring[((d + DMLR - 3) % DMLR) * LCAP + i + 2]; if (v != I16_INF && v + e3 < X) X = v + e3;
-                        v = dmlring[((d + DMLR - 3) % DMLR) * LCAP + i + 1]; if (v != I16_INF && v + e5 < X) X = v + e5;
-                        v = dmlring[((d + DMLR - 4) % DMLR) * LCAP + i + 2]; if (v != I16_INF && v + e3 + e5 < X) X = v + e3 + e5;
-                        if (X < INF) {
-                            const int e = X + T.ML_closing + T.ML_intern + (type > 2 ? (int)T.TerminalAU : 0);
-                            cv = e < cv ? e : cv;
-                        }
-                    } else {
-                        int dml = dmlring[((d + DMLR - 2) % DMLR) * LCAP + i + 1];
-                        if (dml != I16_INF) {
-                            int e = dml + T.ML_closing + lds_mlstem(T, P, rtype_of(type), S[j - 1], S[i + 1]);
-                            cv = e < cv ? e : cv;
-                        }
-                    }
-                    // the backtrack tests the hairpin first, then the interior loops in key order, then the multiloop
-                    if (cint < INF && cint == cv && h != cv) tb = (int)(kk & 1023u) + 1;
-                }
-                int m = INF;
-                if (d > 4) {
-                    int a = fml[od1 + i], b = fml[od1 + i + 1];
-                    a = a == 65535 ? INF : a - FML_BIAS; b = b == 65535 ? INF : b - FML_BIAS;
-                    m = a < b ? a : b;
-                }
-                const int mab = m;
-                if (MODEL) {
-                    // fML pair terms, dangles 1: (i,j) plain, (i+1,j) with a 5' dangle, (i,j-1) with a 3' dangle, (i+1,j-1) with both.  Plain c of the
-                    // neighbouring cells comes out of the G0 ring (G0 = c + mismatchI of the pair seen as an inner pair).
-                    const int mli = T.ML_intern, tau = T.TerminalAU;
-                    if (type) { const int e = cv + mli + (type > 2 ? tau : 0); if (e < m) { m = e; rp = i; rq = j; rval = e; rtp = type; } }
-                    auto plain = [&](int dd, int ii, int& tp) -> int {
-                        tp = 0;
-                        if (dd < 4) return INF;
-                        const unsigned g = cring[(dd & 31) * CSTR + ii];
-                        if (g == 65535u) return INF;
-                        tp = pair_type(S[ii], S[ii + dd]);
-                        return (int)g - 32768 - (int)T.mismatchI[rtype_of(tp) * 25 + S[ii + dd + 1] * 5 + S[ii - 1]];
-                    };
-                    int tp;
-                    int cc = plain(d - 1, i + 1, tp);
-                    if (cc < INF) { const int pl = cc + mli + (tp > 2 ? tau : 0), e = pl + T.dangle5[tp * 5 + S[i]]; if (e < m) { m = e; rp = i + 1; rq = j; rval = pl; rtp = tp; } }
-                    cc = plain(d - 1, i, tp);
-                    if (cc < INF) { const int pl = cc + mli + (tp > 2 ? tau : 0), e = pl + T.dangle3[tp * 5 + S[j]]; if (e < m) { m = e; rp = i; rq = j - 1; rval = pl; rtp = tp; } }
-                    cc = plain(d - 2, i + 1, tp);
-                    if (cc < INF) { const int pl = cc + mli + (tp > 2 ? tau : 0), e = pl + T.dangle5[tp * 5 + S[i]] + T.dangle3[tp * 5 + S[j]]; if (e < m) { m = e; rp = i + 1; rq = j - 1; rval = pl; rtp = tp; } }
-                } else if (type) {
-                    int e = cv + lds_mlstem(T, P, type, i > 1 ? (int)S[i - 1] : -1, j < n ? (int)S[j + 1] : -1); m = e < m ? e : m;
-                }
-                if constexpr (SPARSE) cand = m < mab && m < md;      // fML(i,j) strictly realised by a pair term: a split candidate of column j
-                m = md < m ? md : m;
-                if ((cv < INF && (cv > FIN_LIMIT || cv < -FIN_LIMIT)) || (m < INF && (m > FML_MAX || m < -FML_BIAS)) ||
-                    (md < INF && (md > FIN_LIMIT || md < -FIN_LIMIT))) misc[1] = 1;
-                const short c16 = cv >= INF ? (short)I16_INF : (short)cv;
-                const unsigned short m16 = m >= INF ? (unsigned short)65535 : (unsigned short)(m + FML_BIAS);
-                {   // G0 = c + mismatchI of (i,j) seen as the inner pair of a generic interior loop
-                    unsigned short g16 = 65535;
-                    if (cv < INF) g16 = (unsigned short)(cv + T.mismatchI[rtype_of(type) * 25 + S[j + 1] * 5 + S[i - 1]] + 32768);
-                    cring[(d & 31) * CSTR + i] = g16;
-                    if ((d & 31) == 0) cring[32 * CSTR + i] = g16;
-                }
-                carch[abase + 8 * d] = c16;
-                tb_out[abase + 8 * d] = (unsigned short)tb;
-                fml[od + i] = m16;
-                dmlring[(d % DMLR) * LCAP + i] = md >= INF ? (short)I16_INF : (short)md;
-                ckey[i] = KEY_NONE;
-                if constexpr (SPARSE) { mdec_of(d + 2)[i] = INF; cval = m16; cent = (unsigned)(i - 1) | ((unsigned)j << 9); }
-                else mdec[i] = INF;
-                if constexpr (SPARSE && MODEL != 0) {
-                    if (cand) {      // the realising pair goes to the pool once: the first of its (up to four) candidate cells claims its bit
-                        const unsigned bit = 1u << (rp & 31);
-                        const unsigned old = atomicOr(&pbits[((rq - rp) & 3) * 11 + (rp >> 5)], bit);
-                        cand = (old & bit) ? 0 : 1;
-                        cent = (unsigned)rp | ((unsigned)rq << 9);
-                        cval = (unsigned)(rval + FML_BIAS) | ((unsigned)(-(int)T.dangle5[rtp * 5 + S[rp - 1]]) << 16) | ((unsigned)(-(int)T.dangle3[rtp * 5 + S[rq + 1]]) << 24);
-                        if (rval + FML_BIAS < 0 || rval + FML_BIAS > 65534) misc[1] = 1;      // (cannot happen inside the fML range check above; kept as a guard)
-                    }
-                }
-            }
-            if constexpr (SPARSE) {
-                const unsigned long long cbal = __ballot(cand != 0);
-                if (cbal) {      // wave-uniform
-                    int cbase = 0;
-                    if (lane == (int)__builtin_ctzll(cbal)) cbase = atomicAdd(&misc[3], (int)__popcll(cbal));
-                    const int at = __builtin_amdgcn_readlane(cbase, (int)__builtin_ctzll(cbal)) + (int)__popcll(cbal & ((1ull << lane) - 1ull));
-                    if (cand) {
-                        if (at < pool_cap) { poolA[at] = cent; if constexpr (MODEL != 0) poolB32[at] = cval; else poolB[at] = (unsigned short)cval; }
-                        else misc[2] = 1;
-                    }
-                }
-            }
-            const int lb = __builtin_amdgcn_readfirstlane(lbase);      // lane 0 holds the claimed range
-            if (lt) list[(d % 3) * LSEG + lb + __popcll(lbal & ((1ull << lane) - 1ull))] = (list_t)((unsigned)(x + 1) | ((unsigned)lt << 9) | (ENT_OUTER((int)T.mismatchI[loi], (int)T.mismatch1nI[loi]) << 12));
         };
         // Phase B of the default model, written as two rounds of loads and then arithmetic: every LDS read whose address depends on (i, j, d)
         // only is issued first (round 1), the parameter-table reads that need the pair type and the neighbouring bases follow together
-        // (round 2), and nothing is read inside a branch.  The straightforward version (phaseB above, still the vienna-1.8.5 path) compiles
-        // to a chain of a dozen read-wait pairs, which is what the waves that own cells spend their interval on.
+        // (round 2), and nothing is read inside a branch.  The straightforward version (one thread per cell, reads where the arithmetic needs
+        // them) compiled to a chain of a dozen read-wait pairs, which is what the waves that own cells spend their interval on.
         auto phaseB0 = [&](const int d) {
             const int ncell = n - d;
             unsigned* ckey = reinterpret_cast<unsigned*>(acc + MIRP_CK(d) * LCAP);
@@ -828,21 +622,15 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
             const int x = tid;
             int lt = 0, lbase = 0, loi = 0, ent_terms = 0;
             unsigned long long lbal = 0;
-            const bool do_list = d + 3 <= D && !(dbg_flags & 32768);
+            const bool do_list = d + 3 <= D;
             if (tid == 0) lcnt[(d + 4) % 6] = 0;
-            if (x < ncell && !(dbg_flags & 131072)) {
+            if (x < ncell) {
                 const int i = x + 1, j = i + d, u = d - 1;
                 // ---- round 1
                 lds_vu8 Sv = (lds_vu8)S;
-#if MIRP_PB_BASES
                 const int s_im1 = pb_si & 7, s_i = (pb_si >> 3) & 7, s_ip1 = (pb_si >> 6) & 7, s_jm1 = pb_sj & 7, s_j = (pb_sj >> 3) & 7, s_jp1 = (pb_sj >> 6) & 7;
-                const int s_j2 = (pb_sj >> 9) & 7, s_j3 = (pb_sj >> 12) & 7;
+                const int s_j2 = (pb_sj >> 9) & 7, s_j3 = (pb_sj >> 12) & 7;      // s_j3: far end of cell (i, j+3), the paired-cell list of diagonal d+3
                 pb_sj = (pb_sj >> 3) | ((int)Sv[j + 4] << 12);      // (S holds LCAP + 8 bytes: in range for every j <= n)
-#else
-                const int s_im1 = Sv[i - 1], s_i = Sv[i], s_ip1 = Sv[i + 1], s_jm1 = Sv[j - 1], s_j = Sv[j], s_jp1 = Sv[j + 1];
-                const int s_j3 = Sv[j + 3 <= n ? j + 3 : n];          // far end of cell (i, j+3): the paired-cell list of diagonal d+3
-                const int s_j2 = Sv[j + 2 <= n ? j + 2 : n];          // its 5' neighbour, for the entry's outer-pair table index
-#endif
                 int md = mdec[i];
                 if constexpr (SPARSE) { md = dml_carry < md ? dml_carry : md; dml_carry = md; }      // DML(i,j) = min(DML(i,j-1), candidate splits)
                 const unsigned kk = ckey[i];
@@ -866,15 +654,11 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
                 const int type = pair_type(s_i, s_j);
                 const int rt = rtype_of(type);
                 const int tau = T.TerminalAU, mli = T.ML_intern, mlc = T.ML_closing;
-#ifdef MIRP_X_NOPBTAB          // timing experiment: phase B without its second round of LDS reads (what precomputing the sequence-only terms would remove)
-                const int mmH = -(type * 7 + s_ip1), mmMc = -(rt * 3 + s_jm1), mmMs = -(type + s_im1 * 5), dg5 = -s_im1, dg3 = -s_jp1, mmI = rt * 10 - s_jp1;
-#else
                 const int mmH = T.mismatchH[type * 25 + s_ip1 * 5 + s_jm1];
                 const int mmMc = T.mismatchM[rt * 25 + s_jm1 * 5 + s_ip1];
                 const int mmMs = T.mismatchM[type * 25 + s_im1 * 5 + s_jp1];
                 const int dg5 = T.dangle5[type * 5 + s_im1], dg3 = T.dangle3[type * 5 + s_jp1];
                 const int mmI = T.mismatchI[rt * 25 + s_jp1 * 5 + s_im1];
-#endif
                 ent_terms = ENT_OUTER((int)T.mismatchI[loi], (int)T.mismatch1nI[loi]);          // (a type-0 row is valid memory, the value is not used)
                 // ---- arithmetic
                 const int au = type > 2 ? tau : 0;
@@ -913,18 +697,15 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
                     }
                     cent = (unsigned)(i - 1) | ((unsigned)j << 9);
                 }
-#ifndef MIRP_TIMING_ONLY          // (timing experiments compute garbage on purpose: no hand-over to the generic kernel)
                 if ((cv < INF && (cv > FIN_LIMIT || cv < -FIN_LIMIT)) || (m < INF && (m > FML_MAX || m < -FML_BIAS)) ||
                     (md < INF && (md > FIN_LIMIT || md < -FIN_LIMIT))) misc[1] = 1;
-#endif
                 const short c16 = cv >= INF ? (short)I16_INF : (short)cv;
                 const unsigned short m16 = m >= INF ? (unsigned short)65535 : (unsigned short)(m + FML_BIAS);
                 const unsigned short g16 = cv < INF ? (unsigned short)(cv + mmI + 32768) : (unsigned short)65535;
                 cring[(d & 31) * CSTR + i] = g16;
                 if ((d & 31) == 0) cring[32 * CSTR + i] = g16;
-#ifndef MIRP_X_NOHBM           // (timing experiment: no archive stores)
-                if (!(dbg_flags & 65536)) { carch[abase + 8 * d] = c16; tb_out[abase + 8 * d] = (unsigned short)tb; }
-#endif
+                carch[abase + 8 * d] = c16;
+                tb_out[abase + 8 * d] = (unsigned short)tb;
                 fml[od + i] = m16;
                 dmlring[(d % DMLR) * LCAP + i] = md >= INF ? (short)I16_INF : (short)md;
                 ckey[i] = KEY_NONE;
@@ -945,7 +726,7 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
             const int lb = __builtin_amdgcn_readfirstlane(lbase);
             if (lt) list[(d % 3) * LSEG + lb + __popcll(lbal & ((1ull << lane) - 1ull))] = (list_t)((unsigned)(x + 1) | ((unsigned)lt << 9) | ((unsigned)ent_terms << 12));
         };
-        // Phase B of the vienna-1.8.5 model in the same two-round form (round 4): the straightforward phaseB above reads inside branches and lambdas --
+        // Phase B of the vienna-1.8.5 model in the same two-round form (round 4): the straightforward version read inside branches and lambdas --
         // a dozen read-wait pairs per cell -- and cost the model 22 ms against the default model's phase B.  Same arithmetic, same order of the
         // minima (the first of equal terms wins wherever the order matters: the realising pair of the candidate pass).
         auto phaseB1 = [&](const int d) {
@@ -966,14 +747,9 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
                 const int i = x + 1, j = i + d, u = d - 1;
                 // ---- round 1: everything addressed by (i, j, d) alone
                 lds_vu8 Sv = (lds_vu8)S;
-#if MIRP_PB_BASES
                 const int s_im1 = pb_si & 7, s_i = (pb_si >> 3) & 7, s_ip1 = (pb_si >> 6) & 7, s_jm1 = pb_sj & 7, s_j = (pb_sj >> 3) & 7, s_jp1 = (pb_sj >> 6) & 7;
                 const int s_j2 = (pb_sj >> 9) & 7, s_j3 = (pb_sj >> 12) & 7;
                 pb_sj = (pb_sj >> 3) | ((int)Sv[j + 4] << 12);
-#else
-                const int s_im1 = Sv[i - 1], s_i = Sv[i], s_ip1 = Sv[i + 1], s_jm1 = Sv[j - 1], s_j = Sv[j], s_jp1 = Sv[j + 1];
-                const int s_j3 = Sv[j + 3 <= n ? j + 3 : n], s_j2 = Sv[j + 2 <= n ? j + 2 : n];
-#endif
                 int md = mdec[i];
                 if constexpr (SPARSE) { md = dml_carry < md ? dml_carry : md; dml_carry = md; }
                 const unsigned kk = ckey[i];
@@ -1118,13 +894,11 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
             sp_snap = __builtin_amdgcn_readfirstlane(tot);
             __syncthreads();
         };
-        if constexpr (MIRP_PB_BASES != 0) {
-            if (tid < n - 4) {
-                const int i = tid + 1, j = i + 4;
-                lds_vu8 Sv = (lds_vu8)S;
-                pb_si = (int)Sv[i - 1] | ((int)Sv[i] << 3) | ((int)Sv[i + 1] << 6);
-                pb_sj = (int)Sv[j - 1] | ((int)Sv[j] << 3) | ((int)Sv[j + 1] << 6) | ((int)Sv[j + 2] << 9) | ((int)Sv[j + 3] << 12);
-            }
+        if (tid < n - 4) {
+            const int i = tid + 1, j = i + 4;
+            lds_vu8 Sv = (lds_vu8)S;
+            pb_si = (int)Sv[i - 1] | ((int)Sv[i] << 3) | ((int)Sv[i + 1] << 6);
+            pb_sj = (int)Sv[j - 1] | ((int)Sv[j] << 3) | ((int)Sv[j + 1] << 6) | ((int)Sv[j + 2] << 9) | ((int)Sv[j + 3] << 12);
         }
         if (Dm >= 4) phaseA(4);
         __syncthreads();
@@ -1139,13 +913,13 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
                 asm volatile("ds_read_b32 %0, %1" : "=v"(lc_pre) : "v"(la) : "memory");
                 lc_have = true;
             }
-            if constexpr (MODEL == 0) { if (!SPARSE && (dbg_flags & 4096)) phaseB(d); else phaseB0(d); } else { if (dbg_flags & 4096) phaseB(d); else phaseB1(d); }
-            if (dbg_cycles && lane == 0 && !(dbg_flags & (1 << 20))) { const long long t = clock64(); wB += t - wt; wt = t; }   // bit 20: light mode, busy / barrier only
+            if constexpr (MODEL == 0) phaseB0(d); else phaseB1(d);
+            if (dbg_cycles && lane == 0 && !light) { const long long t = clock64(); wB += t - wt; wt = t; }   // light mode: busy / barrier only
             if (d + 1 <= Dm) phaseA(d + 1);
             if (dbg_cycles && lane == 0) { const long long t = clock64(); wA2 += t - wt; wt = t; }
             __syncthreads();
             if (dbg_cycles && lane == 0) { const long long t = clock64(); wW += t - wt; wt = t; }
-            if (dbg_cycles && tid == 0 && !(dbg_flags & (1 << 20))) { long long t = clock64(); tB += t - t0; t0 = t; }
+            if (dbg_cycles && tid == 0 && !light) { long long t = clock64(); tB += t - t0; t0 = t; }
         }
         const int overflow = misc[1];
         __syncthreads();
@@ -1159,7 +933,7 @@ __global__ void __launch_bounds__(LNT) MIRP_FILL_ATTR fold_lds_kernel(
             // hand the tables to the epilogue kernel: c and the trace-back codes were archived on the fly, fML is copied out now into the same tiled
             // layout.  A wave takes whole row blocks; lane = diagonal, so the 8 rows of a row block on one diagonal are one 16-byte store and a
             // wave stores contiguous kilobytes; all of a row block's LDS reads are issued before the first store.
-            if (Dm >= 4 && !(dbg_flags & 262144)) {
+            if (Dm >= 4) {
                 constexpr int NGD = (LDMAX + 1 - 4) / 64 + 1;
                 for (int rb = wave; 8 * rb + 1 + 4 <= n; rb += LNW) {
                     const int dmax_rb = Dm < n - 1 - 8 * rb ? Dm : n - 1 - 8 * rb;      // the block's first row reaches furthest
@@ -1397,7 +1171,7 @@ int fold_lds_max_span() { return LSPAN; }
 hipError_t launch_fold_lds(hipStream_t stream, int model, int grid, int grid_epi, const FoldParams* P, const unsigned char* seqs, const long long* offs, const int* lens,
                            int n_work, int win_base, int span, short* slabs, size_t slab_shorts, int* win_state, unsigned int* work_counter, int* fallback_list,
                            unsigned int* fallback_count, int max_lines, int ss_stride, MirpFoldLine* out_lines, char* out_ss, int* out_nlines, int* out_mfe,
-                           int* out_status, int dbg_flags, long long* dbg_cycles, hipEvent_t ev_between, int* dense_list, int force_dense) {
+                           int* out_status, int light_clocks, long long* dbg_cycles, hipEvent_t ev_between, int* dense_list, int force_dense) {
     const size_t lds = model ? lds_layout<1>().total : lds_layout<0>().total;
     const size_t lds_sp = lds_layout<0, true>().total, lds_sp1 = lds_layout<1, true>().total;
     hipError_t e = hipFuncSetAttribute((const void*)fold_lds_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_layout<1>().total);
@@ -1413,66 +1187,57 @@ hipError_t launch_fold_lds(hipStream_t stream, int model, int grid, int grid_epi
         const bool sparse185 = !force_dense;
         if (sparse185) {      // as the default model below: candidate-pool pass, then the dense instantiation over what it handed over
             hipLaunchKernelGGL((fold_lds_kernel<1, true>), dim3(grid), dim3(LNT), lds_sp1, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter,
-                               fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, dbg_flags, dbg_cycles,
+                               fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, light_clocks, dbg_cycles,
                                no_list, no_count, dense_list, work_counter + 3);
             e = hipGetLastError();
             if (e != hipSuccess) return e;
             hipLaunchKernelGGL((fold_lds_kernel<1, false>), dim3(grid), dim3(LNT), lds, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter + 2,
-                               fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, dbg_flags, dbg_cycles,
+                               fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, light_clocks, dbg_cycles,
                                (const int*)dense_list, (const unsigned int*)(work_counter + 3), dense_list, work_counter + 3);
         } else
             hipLaunchKernelGGL((fold_lds_kernel<1, false>), dim3(grid), dim3(LNT), lds, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter,
-                               fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, dbg_flags, dbg_cycles,
+                               fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, light_clocks, dbg_cycles,
                                no_list, no_count, dense_list, work_counter + 3);
     } else {
-#if !defined(MIRP_FILL2)
         // product: first pass with sparse multiloop splits (candidate pool), then the dense instantiation over the windows the first pass handed over
         // (pool overflow, no room for a pool: zero on the benchmark inputs; the launch then finds an empty list).  force_dense (tests, A/B timing): the
-        // dense instantiation folds everything.  -DMIRP_FILL2 (dev builds, make VARIANT=...) selects the two-diagonal schedule of
-        // fold_lds2_kernel.hip, which is parity-green but measured no faster
+        // dense instantiation folds everything.
         if (!force_dense) {
             hipLaunchKernelGGL((fold_lds_kernel<0, true>), dim3(grid), dim3(LNT), lds_sp, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter,
-                               fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, dbg_flags, dbg_cycles,
+                               fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, light_clocks, dbg_cycles,
                                no_list, no_count, dense_list, work_counter + 3);
             e = hipGetLastError();
             if (e != hipSuccess) return e;
             hipLaunchKernelGGL((fold_lds_kernel<0, false>), dim3(grid), dim3(LNT), lds, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter + 2,
-                               fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, dbg_flags, dbg_cycles,
+                               fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, light_clocks, dbg_cycles,
                                (const int*)dense_list, (const unsigned int*)(work_counter + 3), dense_list, work_counter + 3);
         } else
             hipLaunchKernelGGL((fold_lds_kernel<0, false>), dim3(grid), dim3(LNT), lds, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter,
-                               fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, dbg_flags, dbg_cycles,
+                               fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, light_clocks, dbg_cycles,
                                no_list, no_count, dense_list, work_counter + 3);
-#else
-        e = launch_fold_lds2_fill(stream, grid, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter, fallback_list, fallback_count,
-                                  out_nlines, out_mfe, out_status);
-        if (e != hipSuccess) return e;
-#endif
     }
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (ev_between) { e = hipEventRecord(ev_between, stream); if (e != hipSuccess) return e; }   // fill | epilogue boundary (mirp_last_fold_kernel_ms)
-    if (!(dbg_flags & 16)) {
-        if (model) {
-            const size_t el = fold185_lds_epilogue_bytes(max_lines);
-            if (el > 64 * 1024) {
-                e = hipFuncSetAttribute((const void*)fold185_lds_epilogue_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)el);
-                if (e != hipSuccess) return e;
-            }
-            hipLaunchKernelGGL(fold185_lds_epilogue_kernel, dim3(grid_epi), dim3(ENT), el, stream, P, seqs, offs, lens, n_work, span, slabs, slab_shorts, win_state,
-                               work_counter + 1, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status);
-        } else {
-            hipLaunchKernelGGL(fold_lds_epilogue_kernel, dim3(grid_epi), dim3(ENT), fold_lds_epilogue_bytes(max_lines), stream, P, seqs, offs, lens, n_work, span,
-                               slabs, slab_shorts, win_state, work_counter + 1, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status);
+    if (model) {
+        const size_t el = fold185_lds_epilogue_bytes(max_lines);
+        if (el > 64 * 1024) {
+            e = hipFuncSetAttribute((const void*)fold185_lds_epilogue_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)el);
+            if (e != hipSuccess) return e;
         }
+        hipLaunchKernelGGL(fold185_lds_epilogue_kernel, dim3(grid_epi), dim3(ENT), el, stream, P, seqs, offs, lens, n_work, span, slabs, slab_shorts, win_state,
+                           work_counter + 1, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status);
+    } else {
+        hipLaunchKernelGGL(fold_lds_epilogue_kernel, dim3(grid_epi), dim3(ENT), fold_lds_epilogue_bytes(max_lines), stream, P, seqs, offs, lens, n_work, span,
+                           slabs, slab_shorts, win_state, work_counter + 1, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status);
     }
     return hipGetLastError();
 }
 
-#ifdef MIRP_EPI_CLOCKS
+#ifdef MIRP_DIAG
 void fold_lds_epi_clocks_print() {
     unsigned long long h[32];
-    hipMemcpyFromSymbol(h, HIP_SYMBOL(g_epi_clk), sizeof(h));
+    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_epi_clk), sizeof(h));
     const char* nm[14] = {"f3 sweep", "enumeration", "partner scan", "backtrack", "output", "loop tail", "barrier", "containment",
                           "sweep: issue+init+barrier", "sweep: load wait", "sweep: step 1", "sweep: barrier 2", "sweep: step 2", "sweep: barrier 3"};
     for (int k = 0; k < 14; k++) std::fprintf(stderr, "[mirp epi clocks] %-14s %llu\n", nm[k], h[k]);
@@ -1480,7 +1245,7 @@ void fold_lds_epi_clocks_print() {
                           "line-end code fetches", "ml split rounds (closing)", "short-backtrack scan rounds", "structures"};
     for (int k = 0; k < 10; k++) std::fprintf(stderr, "[mirp epi counts] %-28s %llu\n", cn[k], h[16 + k]);
     unsigned long long z[32] = {0};
-    hipMemcpyToSymbol(HIP_SYMBOL(g_epi_clk), z, sizeof(z));
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_epi_clk), z, sizeof(z));
 }
 #endif
 

@@ -317,9 +317,8 @@ int mirp_run_fold(mirp_ctx* c, const unsigned char* d_seqs, const long long* d_o
             return 0;
         }
         const size_t slot_ints = mirp::fold_generic_ws_slot_ints(n_cap, span);          // c, fML, DML ring, split-candidate pool of one window
-        int wg_per_cu = 96;         // windows per CU and batch (the hardware keeps as many resident as registers and LDS allow: 6 of the fill, 8 of the epilogue): one batch for
-                                    // 20,000 windows -- every batch ends with a tail of idle CUs (three batches of 8,192: 0.075 s at L = 301, one: 0.069), and 288 GB hold the 45 - 75 GB
-        if (const char* e = std::getenv("MIRP_GENERIC_WG_PER_CU")) wg_per_cu = std::max(1, std::atoi(e));      // dev: occupancy experiments (profiles/tools/l400_time.py)
+        constexpr int wg_per_cu = 96;   // windows per CU and batch (the hardware keeps as many resident as registers and LDS allow: 6 of the fill, 8 of the epilogue): one batch for
+                                        // 20,000 windows -- every batch ends with a tail of idle CUs (three batches of 8,192: 0.075 s at L = 301, one: 0.069), and 288 GB hold the 45 - 75 GB
         int slots = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->n_cu * wg_per_cu, ((size_t)128 << 30) / (slot_ints * 4)));      // PRECURSOR_LEN = 3000: 160 MB a slot
         slots = std::min(slots, n_generic);
         while (c->ws.ensure((size_t)slots * slot_ints * 4)) {          // (the device may be shared: take fewer windows per batch before giving up)
@@ -346,19 +345,15 @@ int mirp_run_fold(mirp_ctx* c, const unsigned char* d_seqs, const long long* d_o
             return fail(c, -6, "device allocation failed (fold LDS kernel)");
         HIPCHK(c, hipMemsetAsync(c->fctl.p, 0, 1024, c->stream));
         unsigned int* ctl = (unsigned int*)c->fctl.p;
-        // diagnostics exist only in a -DMIRP_DIAG build (`make DIAG=1`, profiles/tools/): MIRP_FOLD_DEBUG=<flags> ablates phases (results then
-        // wrong), MIRP_FOLD_CLOCKS=1 prints phase clocks, MIRP_FOLD_DUMP=<path> dumps slabs.  The shipped library reads no environment.
-#if defined(MIRP_DIAG) || defined(MIRP_LITE_CLOCKS)
-        const char* dbg_env = std::getenv("MIRP_FOLD_DEBUG");
-        int dbg_flags = dbg_env ? std::atoi(dbg_env) : 0;
+        // diagnostics exist only in a -DMIRP_DIAG build (`make DIAG=1`, profiles/tools/): MIRP_FOLD_CLOCKS=1 prints phase clocks (=2: light mode, per
+        // wave only busy time, reported as splits, and barrier wait), MIRP_FOLD_DUMP=<path> dumps slabs; the epilogue's clocks print with the fill's.  The shipped
+        // library reads no environment.
+#ifdef MIRP_DIAG
         const char* clk_env = std::getenv("MIRP_FOLD_CLOCKS");
         long long* dbg_cycles = clk_env ? (long long*)(ctl + 8) : nullptr;
-        if (clk_env && std::atoi(clk_env) == 2) dbg_flags |= 1 << 20;      // light mode: per wave only busy (reported as splits) and barrier wait
-#elif defined(MIRP_ABLATE) || defined(MIRP_TIMING_ONLY)
-        const int dbg_flags = 16;          // timing experiments whose fill results are wrong by construction: no epilogue (it could walk garbage forever)
-        long long* dbg_cycles = nullptr;
+        const int light_clocks = clk_env && std::atoi(clk_env) == 2;
 #else
-        const int dbg_flags = 0;
+        const int light_clocks = 0;
         long long* dbg_cycles = nullptr;
 #endif
         int n_sub = 0;
@@ -373,7 +368,7 @@ int mirp_run_fold(mirp_ctx* c, const unsigned char* d_seqs, const long long* d_o
             hipError_t e = mirp::launch_fold_lds(c->stream, m185 ? 1 : 0, grid, grid_epi, m185 ? c->d_params185l : c->d_params, d_seqs, d_offs + b0, d_lens ? d_lens + b0 : nullptr, nb, b0, span,
                                                  (short*)c->carch.p, slab, (int*)c->wstate.p, ctl, (int*)c->flist.p, ctl + 4, max_lines, stride,
                                                  d_lines + (size_t)b0 * max_lines, d_ss + (size_t)b0 * max_lines * stride, d_nlines + b0, d_mfe + b0,
-                                                 d_status + b0, dbg_flags, dbg_cycles, ev3[1], (int*)c->dlist.p, c->fold_dense);
+                                                 d_status + b0, light_clocks, dbg_cycles, ev3[1], (int*)c->dlist.p, c->fold_dense);
             if (e != hipSuccess) return fail(c, -2, std::string("fold LDS kernel launch failed: ") + hipGetErrorString(e));
             HIPCHK(c, hipEventRecord(ev3[2], c->stream));
             n_sub++;
@@ -391,7 +386,7 @@ int mirp_run_fold(mirp_ctx* c, const unsigned char* d_seqs, const long long* d_o
             (void)hipEventElapsedTime(&b, c->fold_ev[3 * k + 1], c->fold_ev[3 * k + 2]);
             c->fold_kernel_ms[0] += a; c->fold_kernel_ms[1] += b;
         }
-#if defined(MIRP_DIAG) || defined(MIRP_LITE_CLOCKS)
+#ifdef MIRP_DIAG
         if (const char* dump = std::getenv("MIRP_FOLD_DUMP")) {   // diagnostics: c / fML slabs of the first window of the last sub-batch
             std::vector<short> h(3 * slab);
             HIPCHK(c, hipMemcpy(h.data(), c->carch.p, 6 * slab, hipMemcpyDeviceToHost));
@@ -407,13 +402,8 @@ int mirp_run_fold(mirp_ctx* c, const unsigned char* d_seqs, const long long* d_o
                              cyc[7 + 4 * w]);
             for (int b = 0; b < 4; b++)
                 std::fprintf(stderr, "[mirp fold clocks] wave 9, diagonals with %d%s blocks: %lld, interior ticks %lld\n", b, b == 3 ? "+" : "", cyc[72 + b], cyc[68 + b]);
+            mirp::fold_lds_epi_clocks_print();
         }
-#endif
-#ifdef MIRP_EPI_CLOCKS
-        mirp::fold_lds_epi_clocks_print();
-#endif
-#ifdef MIRP_L2_CLOCKS
-        if (!m185) mirp::fold_lds2_clocks_print();
 #endif
         if (nfb == 0) return 0;
         work_list = (const int*)c->flist.p;

@@ -1,5 +1,5 @@
-"""Dev tool: fill / epilogue kernel times of the bench workload with the library given by MIRP_LIB (product or a compile-time ablation build,
-make -C mir-prefer_amd/csrc ABLATE=<flags>).  Prints one line; run several libraries back to back on one box to compare."""
+"""Dev tool: fill / epilogue kernel times of the bench workload with the library given by MIRP_LIB (product or a build with extra compile flags,
+make -C mir-prefer_amd/csrc VARIANT=<name> VFLAGS=...).  Prints one line; run several libraries back to back on one box to compare."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np

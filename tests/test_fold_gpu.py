@@ -52,47 +52,20 @@ def test_fold_maximal_asymmetric_interior_loop_tie(gpu_ctx, oracle):
     _compare(gpu_ctx, oracle, [s], 300)
 
 
-_FILL2_WORKER = r"""
-import json, sys
-sys.path.insert(0, sys.argv[1])
-from mir_prefer_amd import capi
-seqs = json.load(open(sys.argv[2]))
-ctx = capi.Context(0)
-out = ctx.fold_batch(seqs, 300)
-json.dump([[g["status"], g["mfe"], g["lines"]] for g in out], open(sys.argv[3], "w"))
-"""
-
-
-def test_two_diagonal_fill_schedule_equals_the_product_kernel(gpu_ctx, oracle, tmp_path):
-    """fold_lds2_kernel.hip (two anti-diagonals per barrier interval: stacked pairs / 1-bulges finished in phase B, multiloop closings pushed two
-    diagonals ahead, fML handed over by DPP) is a second, independently scheduled implementation of the fill.  Its build
-    (libmirprefer_vfill2.so, make VARIANT=fill2 VFLAGS="-DMIRP_FILL2 -DMIRP_E1", built by __graft_entry__.build) runs in a child process through MIRP_LIB and must
-    produce the product kernel's lines and the oracle's: GU-rich windows put hundreds of paired cells on a diagonal, short windows end on an odd
-    number of diagonals, n = 350 fills the LDS layout."""
-    import json
-    import os
+def test_fold_gu_rich_repeat_and_layout_edge_windows(gpu_ctx, oracle):
+    """Windows that load the fill kernel's schedule and LDS layout hardest, against the oracle: GU-rich windows put hundreds of paired cells on a
+    diagonal, GGGUUC repeats pair densely, short windows (5-120) end on an odd number of diagonals, n = 348-350 fills the LDS layout and
+    n = 299-301 straddle the span."""
     import random
-    import subprocess
-    import sys
-    from mir_prefer_amd import capi
-    lib = os.path.join(os.path.dirname(capi.LIB_PATH), "libmirprefer_vfill2.so")
-    if not os.path.exists(lib):
-        pytest.fail("libmirprefer_vfill2.so is not built: run __graft_entry__.build()")
     r = random.Random(5)
     seqs = seqgen.windows(14, 24, 280, 350) + ["".join(r.choice("GU") for _ in range(330)), "".join(r.choice("GGGUUC") for _ in range(300))]
     seqs += seqgen.windows(15, 30, 5, 120) + ["".join(r.choice("ACGU") for _ in range(n)) for n in (348, 349, 350, 301, 300, 299)]
     product = gpu_ctx.fold_batch(seqs, 300)
-    (tmp_path / "w.py").write_text(_FILL2_WORKER)
-    (tmp_path / "in.json").write_text(json.dumps(seqs))
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, str(tmp_path / "w.py"), root, str(tmp_path / "in.json"), str(tmp_path / "out.json")], env=dict(os.environ, MIRP_LIB=lib),
-                       capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stdout + p.stderr
-    other = json.load(open(tmp_path / "out.json"))
-    for s, g, h in zip(seqs, product, other):
+    assert len(product) == len(seqs)
+    for s, g in zip(seqs, product):
         want = oracle.lfold(s, 300)
-        assert g["status"] == 0 and h[0] == 0
-        assert g["lines"] == want["lines"] and [tuple(x) for x in h[2]] == want["lines"] and g["mfe"] == h[1] == want["mfe"], s
+        assert g["status"] == 0, (s, g["status"])
+        assert g["lines"] == want["lines"] and g["mfe"] == want["mfe"], s
 
 
 def test_fold_edge_cases(gpu_ctx, oracle):
