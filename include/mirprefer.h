@@ -403,6 +403,18 @@ int mirp_fold_predict_report_stream(mirp_ctx* ctx, int32_t span, int32_t max_lin
                                     const char* sample_names, int32_t n_samples, const char* mirbase_form, const char* outdir, const char* prefix,
                                     int64_t* n_loci, int32_t* n_chunks_used, double device_ms[2]);
 
+/* Read collapse of scripts/process-reads-fasta.py:60-80 (the step before the pipeline: the reads' ids carry their depth, `sample_rA_xN`, parsed
+ * at MP:242-253) for one uncollapsed FASTA file: every line that does not start with '>' is a read, taken after str.strip(); lines end at \n, \r\n
+ * or a lone \r (universal newlines); a blank line is the read "".  out_path receives ">" + prefix + "_r" + A + "_x" + B + "\n" + read + "\n" per
+ * distinct read, A = 0, 1, ... in order of first occurrence (Python 3 dict order), B = its count.  Bytes >= 0x80 are refused (-9, the message
+ * names the file and the byte's offset); more than 2^31 - 1 lines are refused.  hash_bits: width of the grouping hash, 64 on the product path
+ * (smaller widths force collisions, which are resolved exactly).  Out: n_reads, n_unique, seconds = {read + upload, split, hash + sort,
+ * verify + rank, emit + download, write}.  Nothing is written on error. */
+int mirp_collapse_reads(mirp_ctx* ctx, const char* path, const char* prefix, const char* out_path, int32_t hash_bits, int64_t* n_reads,
+                        int64_t* n_unique, double seconds[6]);
+/* Reads of the last mirp_collapse_reads that lay in hash runs whose bytes differ (resolved on the host). */
+int64_t mirp_last_collapse_collisions(const mirp_ctx* ctx);
+
 #ifdef __cplusplus
 }
 #endif

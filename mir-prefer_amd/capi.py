@@ -8,7 +8,7 @@ import numpy as np
 
 from . import early
 from .early import LIB_PATH, FastaData, SamData
-ABI_VERSION = 7      # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
+ABI_VERSION = 8      # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
 
 
 class MirpError(RuntimeError):
@@ -336,6 +336,10 @@ def load_library():
     lib.mirp_read_fasta.restype = C.c_int
     lib.mirp_free_fasta_data.argtypes = [C.POINTER(FastaData)]
     lib.mirp_free_fasta_data.restype = None
+    lib.mirp_collapse_reads.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, i64p, i64p, C.POINTER(C.c_double)]
+    lib.mirp_collapse_reads.restype = C.c_int
+    lib.mirp_last_collapse_collisions.argtypes = [vp]
+    lib.mirp_last_collapse_collisions.restype = C.c_int64
     lib.mirp_dist_unique_id.argtypes = [vp]
     lib.mirp_dist_unique_id.restype = C.c_int
     lib.mirp_dist_init.argtypes = [vp, vp, C.c_int32, C.c_int32]
@@ -394,6 +398,15 @@ class Context:
     def _check(self, rc, what):
         if rc != 0:
             raise MirpError("%s failed (%d): %s" % (what, rc, self.lib.mirp_last_error(self.h).decode()))
+
+    def collapse_reads(self, path, prefix, out_path, hash_bits=64):
+        """process-reads-fasta.py on one file (mirp_collapse_reads): writes out_path, returns {n_reads, n_unique, collisions, seconds}; seconds =
+        {read + upload, split, hash + sort, verify + rank, emit + download, write}.  hash_bits < 64 only to force hash collisions in tests."""
+        nr, nu = C.c_int64(), C.c_int64()
+        sec = (C.c_double * 6)()
+        self._check(self.lib.mirp_collapse_reads(self.h, os.fsencode(path), prefix.encode(), os.fsencode(out_path), int(hash_bits), C.byref(nr), C.byref(nu), sec),
+                    "mirp_collapse_reads")
+        return {"n_reads": nr.value, "n_unique": nu.value, "collisions": int(self.lib.mirp_last_collapse_collisions(self.h)), "seconds": list(sec)}
 
     def fold_batch(self, seqs, span, max_lines=96):
         """RNALfold -L replacement. seqs: list of str/bytes. Returns a list (per sequence) of

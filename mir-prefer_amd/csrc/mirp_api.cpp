@@ -3,6 +3,7 @@
 // if no gfx950 device / HIP runtime is usable.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -10,7 +11,7 @@
 #include <vector>
 #include "mirp_internal.h"
 
-#define MIRP_ABI_VERSION 7   // 7: mirp_write_result_reports, mirp_fold_predict_report_stream, mirp_select_windows, mirp_dist_comm_info, MIRP_MAX_SAMPLES 255; 6: mirp_last_coverage_fused, mirp_fold_batch_summary, mirp_predict_batch_reasons, text writers; 5: mirp_dist_*, mirp_gather_loci / mirp_gather_records, mirp_read_fasta, mirp_ingest_sams_shard; 4: MirpSamData.segs, mirp_ingest_sams_gpu, mirp_load_coverage_segments; 2: mirp_set_fold_model, mirp_ingest_sams; 3: mirp_predict returns the per-window capacity status, mirp_get_fold_overflow
+#define MIRP_ABI_VERSION 8   // 8: mirp_collapse_reads, mirp_last_collapse_collisions; 7: mirp_write_result_reports, mirp_fold_predict_report_stream, mirp_select_windows, mirp_dist_comm_info, MIRP_MAX_SAMPLES 255; 6: mirp_last_coverage_fused, mirp_fold_batch_summary, mirp_predict_batch_reasons, text writers; 5: mirp_dist_*, mirp_gather_loci / mirp_gather_records, mirp_read_fasta, mirp_ingest_sams_shard; 4: MirpSamData.segs, mirp_ingest_sams_gpu, mirp_load_coverage_segments; 2: mirp_set_fold_model, mirp_ingest_sams; 3: mirp_predict returns the per-window capacity status, mirp_get_fold_overflow
 #define MIRP_NMAX 3096
 
 #include "mirp_ctx.h"
@@ -100,7 +101,9 @@ extern "C" void mirp_destroy(mirp_ctx* c) {
                       &c->keep, &c->kscan, &c->csq, &c->cdest, &c->peaks_sq, &c->peaks_sorted, &c->head, &c->hscan, &c->rfirst, &c->nent,
                       &c->isloc, &c->nslots, &c->escan, &c->lscan, &c->sscan, &c->windows, &c->roles, &c->loci, &c->wpeaks, &c->matures,
                       &c->wseqs, &c->woffs, &c->wlens, &c->segs, &c->sort_tmp, &c->sort_counts, &c->side_cnt, &c->side_idx, &c->side_list, &c->side_offs, &c->side_lens, &c->lines2, &c->ss2,
-                      &c->nlines2, &c->mfe2, &c->status2, &c->p_out, &c->p_nout, &c->p_status, &c->p_keep, &c->p_kscan, &c->p_res, &c->p_text})
+                      &c->nlines2, &c->mfe2, &c->status2, &c->p_out, &c->p_nout, &c->p_status, &c->p_keep, &c->p_kscan, &c->p_res, &c->p_text,
+                      &c->r_text, &c->r_bcnt, &c->r_bscan, &c->r_starts, &c->r_flag, &c->r_fscan, &c->r_span, &c->r_rec, &c->r_rectmp, &c->r_rscan,
+                      &c->r_first, &c->r_bad, &c->r_cnt, &c->r_isfirst, &c->r_inbad, &c->r_rank, &c->r_out, &c->r_small})
         b->release();
     for (int i = 0; i < 6; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     for (hipEvent_t ev : c->fold_ev) (void)hipEventDestroy(ev);
@@ -411,3 +414,48 @@ int mirp_run_fold(mirp_ctx* c, const unsigned char* d_seqs, const long long* d_o
     }
     return run_generic(work_list, n_generic);
 }
+
+// Read collapse of scripts/process-reads-fasta.py:60-80 for one file (reads_kernels.hip does the device part).
+extern "C" int mirp_collapse_reads(mirp_ctx* c, const char* path, const char* prefix, const char* out_path, int32_t hash_bits, int64_t* n_reads,
+                                   int64_t* n_unique, double seconds[6]) {
+    if (!c) return -1;
+    if (!path || !prefix || !out_path || hash_bits < 1 || hash_bits > 64) return fail(c, -1, "mirp_collapse_reads: bad argument");
+    double sec[6] = {0, 0, 0, 0, 0, 0};
+    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    HIPCHK(c, hipSetDevice(c->device));
+    double t = now();
+    FILE* f = std::fopen(path, "rb");
+    if (!f) return fail(c, -8, std::string("cannot open ") + path);
+    fseeko(f, 0, SEEK_END);
+    const long long n = (long long)ftello(f);
+    fseeko(f, 0, SEEK_SET);
+    char* text = (char*)std::malloc((size_t)n + 1);
+    if (!text) { std::fclose(f); return fail(c, -7, "host allocation failed (collapse: text)"); }
+    const size_t got = n > 0 ? std::fread(text, 1, (size_t)n, f) : 0;
+    std::fclose(f);
+    if ((long long)got != n) { std::free(text); return fail(c, -8, std::string("cannot read ") + path); }
+    sec[0] = now() - t;
+    char* out = nullptr;
+    long long out_len = 0, nr = 0, nu = 0, bad = -1;
+    const int rc = mirp_device_collapse_reads(c, text, n, prefix, hash_bits, &out, &out_len, &nr, &nu, &bad, sec);
+    if (rc == -9) {
+        char msg[160];
+        std::snprintf(msg, sizeof msg, ": byte 0x%02x at offset %lld is not ASCII (bytes >= 0x80 are not supported)", (unsigned)(unsigned char)text[bad], bad);
+        c->err = std::string(path) + msg;
+    }
+    std::free(text);
+    if (rc) return rc;
+    t = now();
+    FILE* o = std::fopen(out_path, "wb");
+    bool ok = o && (out_len == 0 || std::fwrite(out, 1, (size_t)out_len, o) == (size_t)out_len);
+    if (o && std::fclose(o) != 0) ok = false;
+    std::free(out);
+    if (!ok) return fail(c, -8, std::string("cannot write ") + out_path);
+    sec[5] = now() - t;
+    if (n_reads) *n_reads = nr;
+    if (n_unique) *n_unique = nu;
+    if (seconds) std::memcpy(seconds, sec, sizeof sec);
+    return 0;
+}
+
+extern "C" int64_t mirp_last_collapse_collisions(const mirp_ctx* c) { return c ? c->last_collapse_collisions : -1; }

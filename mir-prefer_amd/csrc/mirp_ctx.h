@@ -95,6 +95,9 @@ struct mirp_ctx {
     const int* v_roles() const { return (const int*)roles.p + win_first; }
     const long long* v_woffs() const { return (const long long*)woffs.p + win_first; }
     const int* v_wlens() const { return (const int*)wlens.p + win_first; }
+    // ---- read collapse (reads_kernels.hip): the file text and the per-line / per-read arrays, reused from file to file
+    DevBuf r_text, r_bcnt, r_bscan, r_starts, r_flag, r_fscan, r_span, r_rec, r_rectmp, r_rscan, r_first, r_bad, r_cnt, r_isfirst, r_inbad, r_rank, r_out, r_small;
+    long long last_collapse_collisions = 0;   // reads in hash runs that failed the byte compare (resolved on the host)
     long long n_result = 0;           // records of the last mirp_predict (p_res / p_text), what mirp_gather_loci sends
     bool have_result = false;
 };
@@ -114,6 +117,10 @@ static inline int fail(mirp_ctx* c, int code, const std::string& msg) {
 // Uses the LDS-resident kernel when span allows and re-runs flagged windows (length / int16 range) with the generic kernel.
 // sort_kernels.hip: stable device sort by (tid, pos) / keep-region filter of the resident record array
 int mirp_device_sort_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long n, int posbits, int tidbits);
+int mirp_device_sort_hashes(mirp_ctx* c, MirpHashRec* d, MirpHashRec* d_tmp, long long n, int bits);
+// reads_kernels.hip: the read collapse of process-reads-fasta.py on a file held in host memory (out: the .processed text, malloc'ed)
+int mirp_device_collapse_reads(mirp_ctx* c, const char* text, long long n, const char* prefix, int hash_bits, char** out, long long* out_len,
+                               long long* n_reads, long long* n_unique, long long* bad_offset, double seconds[6]);
 int mirp_device_mask_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long* n_io, MirpAln* d_segs, MirpAln* d_segtmp, const int* d_owner, const int* d_seg_span,
                           long long* nseg_io,
                           const long long* d_rfirst, const int* d_rstart, const int* d_remax);

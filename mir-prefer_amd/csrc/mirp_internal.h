@@ -7,6 +7,9 @@
 #include "../../include/mirprefer.h"
 #include "fold_params.h"
 
+// One read of the read collapse (reads_kernels.hip): 64-bit content hash and the read's index in file order, sorted by the hash (sort_kernels.hip).
+struct MirpHashRec { unsigned long long hash; unsigned idx, pad; };
+
 namespace mirp {
 
 size_t fold_generic_lds_bytes(int n_cap, int max_lines);

@@ -15,13 +15,22 @@ namespace mirp {
 #define SORT_WAVES 4                 // waves per workgroup
 #define SORT_WTILE 2048              // records per wave tile
 
-__device__ __forceinline__ unsigned sort_digit(const MirpAln& r, int posbits, int shift) {
-    const unsigned long long key = ((unsigned long long)(unsigned)r.tid << posbits) | (unsigned long long)(unsigned)r.pos;
-    return (unsigned)(key >> shift) & 255u;
-}
+// The sort is templated on the record and on its digit function (digit(record, shift) -> 8 bits): MirpAln by (tid, pos) here, the (hash, read
+// index) records of the read collapse by hash (reads_kernels.hip).
+struct AlnDigit {
+    int posbits;
+    __device__ __forceinline__ unsigned operator()(const MirpAln& r, int shift) const {
+        const unsigned long long key = ((unsigned long long)(unsigned)r.tid << posbits) | (unsigned long long)(unsigned)r.pos;
+        return (unsigned)(key >> shift) & 255u;
+    }
+};
+struct HashDigit {
+    __device__ __forceinline__ unsigned operator()(const MirpHashRec& r, int shift) const { return (unsigned)(r.hash >> shift) & 255u; }
+};
 
 // counts[digit * n_tiles + tile]
-__global__ void __launch_bounds__(64 * SORT_WAVES) sort_hist_kernel(const MirpAln* __restrict__ in, long long n, int posbits, int shift, long long n_tiles,
+template <class Rec, class Digit>
+__global__ void __launch_bounds__(64 * SORT_WAVES) sort_hist_kernel(const Rec* __restrict__ in, long long n, Digit digit, int shift, long long n_tiles,
                                                                     unsigned* __restrict__ counts) {
     __shared__ unsigned hist[SORT_WAVES][256];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -30,41 +39,21 @@ __global__ void __launch_bounds__(64 * SORT_WAVES) sort_hist_kernel(const MirpAl
     __syncthreads();
     if (tile < n_tiles) {
         const long long b = tile * SORT_WTILE, e = b + SORT_WTILE < n ? b + SORT_WTILE : n;
-        for (long long k = b + lane; k < e; k += 64) atomicAdd(&hist[wave][sort_digit(in[k], posbits, shift)], 1u);
+        for (long long k = b + lane; k < e; k += 64) atomicAdd(&hist[wave][digit(in[k], shift)], 1u);
     }
     __syncthreads();
     if (tile < n_tiles)
         for (int x = lane; x < 256; x += 64) counts[(long long)x * n_tiles + tile] = hist[wave][x];
 }
 
-// exclusive scan of a 32-bit array in place (one workgroup: thread-sequential segments + one block scan); returns the total in *total
-__global__ void __launch_bounds__(1024) sort_scan_kernel(unsigned* __restrict__ a, long long n, unsigned long long* __restrict__ total) {
-    __shared__ unsigned long long part[1024];
-    const int t = threadIdx.x;
-    const long long per = (n + 1023) / 1024;
-    const long long b = (long long)t * per, e = b + per < n ? b + per : n;
-    unsigned long long s = 0;
-    for (long long k = b; k < e; k++) s += a[k];
-    part[t] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        unsigned long long v = t >= o ? part[t - o] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    unsigned long long run = part[t] - s;
-    for (long long k = b; k < e; k++) { const unsigned v = a[k]; a[k] = (unsigned)run; run += v; }
-    if (t == 1023 && total) *total = part[1023];
-}
-
-__global__ void __launch_bounds__(64 * SORT_WAVES) sort_scatter_kernel(const MirpAln* __restrict__ in, MirpAln* __restrict__ out, long long n, int posbits,
-                                                                       int shift, long long n_tiles, const unsigned* __restrict__ offsets) {
+template <class Rec, class Digit>
+__global__ void __launch_bounds__(64 * SORT_WAVES) sort_scatter_kernel(const Rec* __restrict__ in, Rec* __restrict__ out, long long n, Digit digit,
+                                                                       int shift, long long n_tiles, const long long* __restrict__ offsets) {
     __shared__ unsigned run[SORT_WAVES][256];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long tile = (long long)blockIdx.x * SORT_WAVES + wave;
     if (tile < n_tiles)
-        for (int x = lane; x < 256; x += 64) run[wave][x] = offsets[(long long)x * n_tiles + tile];
+        for (int x = lane; x < 256; x += 64) run[wave][x] = (unsigned)offsets[(long long)x * n_tiles + tile];
     __syncthreads();
     if (tile >= n_tiles) return;
     const long long b = tile * SORT_WTILE, e = b + SORT_WTILE < n ? b + SORT_WTILE : n;
@@ -72,9 +61,9 @@ __global__ void __launch_bounds__(64 * SORT_WAVES) sort_scatter_kernel(const Mir
     for (long long c = b; c < e; c += 64) {
         const long long k = c + lane;
         const bool act = k < e;
-        MirpAln r;
+        Rec r;
         unsigned dg = 0;
-        if (act) { r = in[k]; dg = sort_digit(r, posbits, shift); }
+        if (act) { r = in[k]; dg = digit(r, shift); }
         // lanes with the same digit (in lane order = input order)
         unsigned long long peers = __ballot(act);
 #pragma unroll
@@ -130,26 +119,41 @@ static inline int grid_for(long long n, int block, int cap) {
     return (int)(g < 1 ? 1 : g > cap ? cap : g);
 }
 
-// Stable sort of d_alns[0, n) by (tid, pos) into place; d_tmp: a second record buffer of the same size; d_counts: 256 * n_tiles + 8 unsigned.
-int mirp_device_sort_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long n, int posbits, int tidbits) {
+// Stable LSD sort of d[0, n) over the low `bits` bits of the digit function's key into place; d_tmp: a second record buffer of the same size.
+template <class Rec, class Digit>
+static int device_radix_sort(mirp_ctx* c, Rec* d, Rec* d_tmp, long long n, int bits, Digit digit) {
     if (n <= 1) return 0;
     const long long n_tiles = (n + SORT_WTILE - 1) / SORT_WTILE;
     if (n_tiles * SORT_WTILE > 0xffffffffll) return fail(c, -5, "device sort: more than 2^32 records in one call");
-    if (c->sort_counts.ensure(4 * (size_t)(256 * n_tiles + 8))) return fail(c, -6, "device allocation failed (sort)");
-    unsigned* counts = (unsigned*)c->sort_counts.p;
+    // per-pass digit counts, then their exclusive scan (the many-workgroup scan of the candidate stage): the scatter offsets
+    const long long n_counts = 256 * n_tiles;
+    if (c->sort_counts.ensure(4 * (size_t)(n_counts + 2) + 8 * (size_t)(n_counts + 1))) return fail(c, -6, "device allocation failed (sort)");
+    int* counts = (int*)c->sort_counts.p;
+    long long* offsets = (long long*)c->sort_counts.p + (n_counts + 2) / 2;
     const int blocks = (int)((n_tiles + SORT_WAVES - 1) / SORT_WAVES);
-    MirpAln* src = d_alns;
-    MirpAln* dst = d_tmp;
-    for (int shift = 0; shift < posbits + tidbits; shift += 8) {
-        hipLaunchKernelGGL(mirp::sort_hist_kernel, dim3(blocks), dim3(64 * SORT_WAVES), 0, c->stream, (const MirpAln*)src, n, posbits, shift, n_tiles, counts);
-        hipLaunchKernelGGL(mirp::sort_scan_kernel, dim3(1), dim3(1024), 0, c->stream, counts, 256 * n_tiles, (unsigned long long*)nullptr);
-        hipLaunchKernelGGL(mirp::sort_scatter_kernel, dim3(blocks), dim3(64 * SORT_WAVES), 0, c->stream, (const MirpAln*)src, dst, n, posbits, shift, n_tiles,
-                           (const unsigned*)counts);
-        MirpAln* t = src; src = dst; dst = t;
+    Rec* src = d;
+    Rec* dst = d_tmp;
+    for (int shift = 0; shift < bits; shift += 8) {
+        hipLaunchKernelGGL((mirp::sort_hist_kernel<Rec, Digit>), dim3(blocks), dim3(64 * SORT_WAVES), 0, c->stream, (const Rec*)src, n, digit, shift, n_tiles,
+                           (unsigned*)counts);
+        mirp::launch_excl_scan(c->stream, counts, offsets, n_counts);
+        hipLaunchKernelGGL((mirp::sort_scatter_kernel<Rec, Digit>), dim3(blocks), dim3(64 * SORT_WAVES), 0, c->stream, (const Rec*)src, dst, n, digit, shift, n_tiles,
+                           (const long long*)offsets);
+        Rec* t = src; src = dst; dst = t;
     }
-    if (src != d_alns) HIPCHK(c, hipMemcpyAsync(d_alns, src, sizeof(MirpAln) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+    if (src != d) HIPCHK(c, hipMemcpyAsync(d, src, sizeof(Rec) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipGetLastError());
     return 0;
+}
+
+// Stable sort of d_alns[0, n) by (tid, pos) into place; d_tmp: a second record buffer of the same size.
+int mirp_device_sort_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long n, int posbits, int tidbits) {
+    return device_radix_sort(c, d_alns, d_tmp, n, posbits + tidbits, mirp::AlnDigit{posbits});
+}
+
+// Stable sort of (hash, read index) records by the low `bits` bits of the hash (the read collapse, reads_kernels.hip).
+int mirp_device_sort_hashes(mirp_ctx* c, MirpHashRec* d, MirpHashRec* d_tmp, long long n, int bits) {
+    return device_radix_sort(c, d, d_tmp, n, bits, mirp::HashDigit{});
 }
 
 // keep[] + stable compaction of records (and of the coverage segments through their owners).  Regions arrive per contig, sorted by start.
