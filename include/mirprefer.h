@@ -415,6 +415,21 @@ int mirp_collapse_reads(mirp_ctx* ctx, const char* path, const char* prefix, con
 /* Reads of the last mirp_collapse_reads that lay in hash runs whose bytes differ (resolved on the host). */
 int64_t mirp_last_collapse_collisions(const mirp_ctx* ctx);
 
+/* Read alignment of scripts/bowtie-align-reads.py (`bowtie-build`, then `bowtie -v V --best --strata -k K -S`), with the semantics of DESIGN.md §12.
+ * mirp_align_index parses the reference FASTA files paths[0 .. n_paths) in order (contig name = first word of the header; A C G T in either case are
+ * bases, every other character is ambiguous and never aligned over), packs them 2-bit and builds the device-resident index, which every later
+ * mirp_align_reads of this context uses until the next mirp_align_index.  Contigs of length 0 are dropped with a warning on stderr; duplicate or
+ * empty names and 2^32 bases or more are refused (-10).  Out: n_contigs, total bases, seconds = {read + parse + pack, upload, keys, sort,
+ * positions + buckets}. */
+int mirp_align_index(mirp_ctx* ctx, const char* const* paths, int32_t n_paths, int32_t* n_contigs, int64_t* total, double seconds[5]);
+/* Aligns the reads of one FASTA file (QNAME = first word of the header, multi-line sequences concatenated) with at most v (0..3) mismatches: only
+ * the best stratum, and a read with more than m (> 0) hits there is reported unaligned with XM:i:<m+1> (m = 0: off); the first k hits in (contig,
+ * offset, + before -) order.  Writes out_path: @HD, one @SQ per contig, @PG with CL:"<pg_cl>", one record per hit or unaligned read (filter_unmapped:
+ * no unaligned records).  A read longer than 1,024 nt or more than 2^31 - 1 reads are refused (-10) before out_path is opened.  Out: stats =
+ * {reads, aligned, unaligned, suppressed, records}, seconds = {read + parse, upload, seeds, verify, sort, emit + download + write}. */
+int mirp_align_reads(mirp_ctx* ctx, const char* reads_path, const char* out_path, const char* pg_cl, int32_t v, int32_t k, int32_t m, int32_t filter_unmapped,
+                     int64_t stats[5], double seconds[6]);
+
 #ifdef __cplusplus
 }
 #endif

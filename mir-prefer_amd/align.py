@@ -1,0 +1,171 @@
+"""Read alignment before the pipeline: the reference's scripts/bowtie-align-reads.py, with the alignment on the GPU instead of bowtie.
+
+    python -m mir_prefer_amd.align [options] <read fasta1> ... <read fastaN>
+
+Every read file X (collapsed reads, ids `sample_rA_xN`) gives X.sam next to it.  The options are the script's (-r, -i, -t, -v, -k, -p, -f) plus -m
+(the README's direct `bowtie -m`) and --device.  The reference FASTA files (-r) are indexed once per invocation on the device (mirp_align_index) and
+every read file is aligned against that index in the same device context (mirp_align_reads); there is no CPU path.  What is reported is defined in
+DESIGN.md §12: only the best stratum of hits with at most -v mismatches, the first -k of them in (contig, offset, + before -) order.
+
+-i cannot be served (a bowtie index cannot be read): it passes the script's checks and is then refused.  -p is accepted and ignored.  -t is
+accepted and the folder created, as the script does; no index files are written there.  Argument errors exit before a device is opened: option
+errors with status 2 (optparse), read ids that fail the script's check with status 255."""
+import os
+import re
+import sys
+from optparse import OptionParser
+
+HELP = """python -m mir_prefer_amd.align [options] <read fasta1> ... <read fastaN>
+
+    Align fasta format reads to genome on the GPU.
+
+    The input fasta format should follow the output of
+    'python -m mir_prefer_amd.reads collapse'. That is, the read should be collapsed; the read ID
+    must be in format of 'samplename_rA_xN'. Here samplename is the name of the
+    sample from with small RNASeq library came from, 'A' is an unique number to
+    identify the read, 'N' is the depth of the read.
+
+    The output are SAM format alignment files, which can be then used
+    in the pipeline to do miRNA prediction. The output are in the same folder as
+    the input files, with suffix ".sam".
+
+    Example:
+    python -m mir_prefer_amd.align -k 20 -f -r TAIR10.fa SAMPLE1.fa.processed
+"""
+
+READID_ERROR = ("The ID for each read in the output files has the following format: SampleName_rA_xN. Here A is an number uniquely identifies the "
+                "read, N is the total count of the read (depth of the read). 'SampleName' is the name of the sample/tissue/library that the input "
+                "fasta file represents. For example, if the sample name is 'root', and the read occurred 120 times in the library, then it's "
+                "identifier could be root_r23_x120. Here '23' is just a number that donates the order of the reads when processing it, it has no "
+                "use otherwise.\n")
+READID_HINT = ("Please use the provided scripts(process-reads-fasta.py, convert-mirdeep2-fasta.py, convert-readcount-file.py) to preprocess the "
+               "read fasta files. Refer to the README file for more information.\n\n")
+
+
+def make_parser():
+    parser = OptionParser(HELP, prog="mir_prefer_amd.align")
+    parser.add_option("-r", "--reference", action="append",
+                      help="Reference genome in fasta format. If you have multiple reference files, please use multipe -r options.")
+    parser.add_option("-i", "--index", help="A bowtie index (checked as the script does, then refused: pass the reference FASTA with -r).")
+    parser.add_option("-t", "--temp", help="Temporary folder (created if missing; the index lives on the device, nothing is written there). Only used with -r.")
+    parser.add_option("-v", "--allowedmismatch", type=int, default=0, help="Number of mismatches allowed, 0..3. Default is 0.")
+    parser.add_option("-k", "--multialignment", type=int, default=20, help="Report up to <int> valid alignments. Default is 20.")
+    parser.add_option("-m", "--maxmultialignment", type=int, default=None,
+                      help="Report reads with more than <int> alignments in their best stratum as unaligned (XM:i:<int+1>). Default: off.")
+    parser.add_option("-p", "--processor", type=int, default=1, help="Accepted for compatibility and ignored.")
+    parser.add_option("-f", "--filterunmapped", action="store_true", help="Filter out unmapped alignments in the output.")
+    parser.add_option("--device", type=int, default=0, help="GPU device index. Default is 0.")
+    return parser
+
+
+def parse_args(argv):
+    """The script's parse_option_optparse, plus the range checks of -v, -k, -m and --device; parser.error exits with status 2."""
+    parser = make_parser()
+    options, args = parser.parse_args(argv)
+    if len(args) < 1:
+        parser.error("incorrect number of arguments. Run the script with -h option to see help.")
+    if options.reference and options.index:
+        parser.error("Options -r and -i are mutually exclusive. Please use only one of them.")
+    if not options.reference and not options.index:
+        parser.error("Either option -r or -i should be provided.")
+    if options.index and options.temp:
+        parser.error("Option -t is not needed for option '-r'")
+    if not 0 <= options.allowedmismatch <= 3:
+        parser.error("Option -v must be between 0 and 3.")
+    if options.multialignment < 1:
+        parser.error("Option -k must be at least 1.")
+    if options.maxmultialignment is not None and options.maxmultialignment < 1:
+        parser.error("Option -m must be at least 1.")
+    if options.device < 0:
+        parser.error("Option --device must be at least 0.")
+    if options.reference:
+        for name in options.reference:
+            if not os.path.exists(os.path.abspath(os.path.expanduser(name))):
+                parser.error("File " + name + " in option -r does not exist!!")
+    if options.index:
+        for s in ["1.ebwt", "2.ebwt", "3.ebwt", "4.ebwt", "rev.1.ebwt", "rev.2.ebwt"]:
+            name = options.index + "." + s
+            if not os.path.exists(os.path.abspath(os.path.expanduser(name))):
+                parser.error("Index file " + name + " does not exist!! Please use the -r option instead.")
+    for name in args:
+        if not os.path.exists(os.path.abspath(os.path.expanduser(name))):
+            parser.error("File " + name + " does not exist!!")
+    return options, args
+
+
+def check_readid(readname):
+    """The script's check: the headers before the 2,000th must match ^>\\S+_r[0-9]+_x[0-9]+$."""
+    count = 0
+    pattern = r"^>\S+_r[0-9]+_x[0-9]+$"
+    with open(readname, encoding="utf-8", errors="surrogateescape") as f:
+        for line in f:
+            if line.startswith(">"):
+                count += 1
+                if count >= 2000:
+                    break
+                if not re.match(pattern, line.strip()):
+                    return False
+    return True
+
+
+def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    options, args = parse_args(argv)
+    allgood = True
+    for name in args:
+        if not check_readid(name):
+            sys.stderr.write("ERROR: The format of the read IDs in file " + name + " is not right.\n\n")
+            sys.stderr.write(READID_ERROR)
+            sys.stderr.write(READID_HINT)
+            allgood = False
+    if not allgood:
+        return 255
+    if options.index:
+        sys.stderr.write("Error: option -i cannot be used: a bowtie index cannot be read here. Pass the reference FASTA file(s) with -r instead; "
+                         "the index is built on the GPU.\n")
+        return 255
+    if options.temp:
+        tempfolder = os.path.expanduser(options.temp)
+        if not os.path.exists(tempfolder):
+            os.makedirs(tempfolder)
+    m = options.maxmultialignment or 0
+    cl = " ".join(["python", "-m", "mir_prefer_amd.align"] + argv).replace("\t", " ").replace('"', "'")
+
+    from . import capi
+    try:
+        ctx = capi.Context(options.device)
+    except capi.MirpError as e:
+        sys.stderr.write("Error: alignment runs on the GPU and none is usable (%s); there is no CPU path.\n" % e)
+        return 255
+    outnames = []
+    try:
+        sys.stdout.write("\nIndexing reference genomes: " + " ".join(options.reference) + "\n")
+        sys.stdout.flush()
+        try:
+            ctx.align_index(options.reference)
+        except capi.MirpError as e:
+            sys.stderr.write("Error occurred when indexing reference sequences: %s\n" % e)
+            return 255
+        for name in args:
+            outname = name + ".sam"
+            print("SAM file: " + outname)
+            sys.stdout.write("\nMapping file " + name + "\n")
+            sys.stdout.flush()
+            try:
+                ctx.align_reads(name, outname, cl, options.allowedmismatch, options.multialignment, m, bool(options.filterunmapped))
+            except capi.MirpError as e:
+                sys.stderr.write("Error occurred when mapping reads: %s\n" % e)
+                return 255
+            outnames.append(outname)
+    finally:
+        ctx.close()
+    sys.stdout.write("===============================================\nDONE\n")
+    sys.stdout.write("Output SAM files can be found at:\n")
+    for name in outnames:
+        sys.stdout.write(name + "\n")
+    sys.stdout.flush()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

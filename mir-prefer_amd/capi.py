@@ -8,7 +8,7 @@ import numpy as np
 
 from . import early
 from .early import LIB_PATH, FastaData, SamData
-ABI_VERSION = 8      # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
+ABI_VERSION = 9      # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
 
 
 class MirpError(RuntimeError):
@@ -340,6 +340,10 @@ def load_library():
     lib.mirp_collapse_reads.restype = C.c_int
     lib.mirp_last_collapse_collisions.argtypes = [vp]
     lib.mirp_last_collapse_collisions.restype = C.c_int64
+    lib.mirp_align_index.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int32, i32p, i64p, C.POINTER(C.c_double)]
+    lib.mirp_align_index.restype = C.c_int
+    lib.mirp_align_reads.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i64p, C.POINTER(C.c_double)]
+    lib.mirp_align_reads.restype = C.c_int
     lib.mirp_dist_unique_id.argtypes = [vp]
     lib.mirp_dist_unique_id.restype = C.c_int
     lib.mirp_dist_init.argtypes = [vp, vp, C.c_int32, C.c_int32]
@@ -407,6 +411,25 @@ class Context:
         self._check(self.lib.mirp_collapse_reads(self.h, os.fsencode(path), prefix.encode(), os.fsencode(out_path), int(hash_bits), C.byref(nr), C.byref(nu), sec),
                     "mirp_collapse_reads")
         return {"n_reads": nr.value, "n_unique": nu.value, "collisions": int(self.lib.mirp_last_collapse_collisions(self.h)), "seconds": list(sec)}
+
+    def align_index(self, paths):
+        """bowtie-build on the reference FASTA files, in order (mirp_align_index): the index stays on the device for later align_reads calls.
+        -> {n_contigs, total, seconds}; seconds = {read + parse + pack, upload, keys, sort, positions + buckets}."""
+        arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
+        nc, tot = C.c_int32(), C.c_int64()
+        sec = (C.c_double * 5)()
+        self._check(self.lib.mirp_align_index(self.h, arr, len(paths), C.byref(nc), C.byref(tot), sec), "mirp_align_index")
+        return {"n_contigs": nc.value, "total": tot.value, "seconds": list(sec)}
+
+    def align_reads(self, reads_path, out_path, pg_cl="", v=0, k=20, m=0, filter_unmapped=False):
+        """bowtie -v v --best --strata -k k [-m m] -S on one read FASTA file against the index of align_index (mirp_align_reads): writes out_path.
+        m = 0: no -m.  -> {reads, aligned, unaligned, suppressed, records, seconds}; seconds = {read + parse, upload, seeds, verify, sort,
+        emit + download + write}."""
+        st = (C.c_int64 * 5)()
+        sec = (C.c_double * 6)()
+        self._check(self.lib.mirp_align_reads(self.h, os.fsencode(reads_path), os.fsencode(out_path), pg_cl.encode(), int(v), int(k), int(m),
+                                              int(bool(filter_unmapped)), st, sec), "mirp_align_reads")
+        return dict(zip(("reads", "aligned", "unaligned", "suppressed", "records"), list(st)), seconds=list(sec))
 
     def fold_batch(self, seqs, span, max_lines=96):
         """RNALfold -L replacement. seqs: list of str/bytes. Returns a list (per sequence) of

@@ -11,7 +11,7 @@
 #include <vector>
 #include "mirp_internal.h"
 
-#define MIRP_ABI_VERSION 8   // 8: mirp_collapse_reads, mirp_last_collapse_collisions; 7: mirp_write_result_reports, mirp_fold_predict_report_stream, mirp_select_windows, mirp_dist_comm_info, MIRP_MAX_SAMPLES 255; 6: mirp_last_coverage_fused, mirp_fold_batch_summary, mirp_predict_batch_reasons, text writers; 5: mirp_dist_*, mirp_gather_loci / mirp_gather_records, mirp_read_fasta, mirp_ingest_sams_shard; 4: MirpSamData.segs, mirp_ingest_sams_gpu, mirp_load_coverage_segments; 2: mirp_set_fold_model, mirp_ingest_sams; 3: mirp_predict returns the per-window capacity status, mirp_get_fold_overflow
+#define MIRP_ABI_VERSION 9   // 9: mirp_align_index, mirp_align_reads; 8: mirp_collapse_reads, mirp_last_collapse_collisions; 7: mirp_write_result_reports, mirp_fold_predict_report_stream, mirp_select_windows, mirp_dist_comm_info, MIRP_MAX_SAMPLES 255; 6: mirp_last_coverage_fused, mirp_fold_batch_summary, mirp_predict_batch_reasons, text writers; 5: mirp_dist_*, mirp_gather_loci / mirp_gather_records, mirp_read_fasta, mirp_ingest_sams_shard; 4: MirpSamData.segs, mirp_ingest_sams_gpu, mirp_load_coverage_segments; 2: mirp_set_fold_model, mirp_ingest_sams; 3: mirp_predict returns the per-window capacity status, mirp_get_fold_overflow
 #define MIRP_NMAX 3096
 
 #include "mirp_ctx.h"
@@ -103,7 +103,10 @@ extern "C" void mirp_destroy(mirp_ctx* c) {
                       &c->wseqs, &c->woffs, &c->wlens, &c->segs, &c->sort_tmp, &c->sort_counts, &c->side_cnt, &c->side_idx, &c->side_list, &c->side_offs, &c->side_lens, &c->lines2, &c->ss2,
                       &c->nlines2, &c->mfe2, &c->status2, &c->p_out, &c->p_nout, &c->p_status, &c->p_keep, &c->p_kscan, &c->p_res, &c->p_text,
                       &c->r_text, &c->r_bcnt, &c->r_bscan, &c->r_starts, &c->r_flag, &c->r_fscan, &c->r_span, &c->r_rec, &c->r_rectmp, &c->r_rscan,
-                      &c->r_first, &c->r_bad, &c->r_cnt, &c->r_isfirst, &c->r_inbad, &c->r_rank, &c->r_out, &c->r_small})
+                      &c->r_first, &c->r_bad, &c->r_cnt, &c->r_isfirst, &c->r_inbad, &c->r_rank, &c->r_out, &c->r_small, &c->a_pk, &c->a_amb, &c->a_cst,
+                      &c->a_cstart, &c->a_names, &c->a_noff, &c->a_sa, &c->a_bkt, &c->a_codes, &c->a_roff, &c->a_qn, &c->a_qoff, &c->a_small, &c->a_rcnt,
+                      &c->a_rscan, &c->a_seeds, &c->a_ccnt, &c->a_cscan, &c->a_lvl, &c->a_best, &c->a_supp, &c->a_slots, &c->a_off, &c->a_cursor,
+                      &c->a_items, &c->a_itmp, &c->a_size, &c->a_toff, &c->a_text})
         b->release();
     for (int i = 0; i < 6; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     for (hipEvent_t ev : c->fold_ev) (void)hipEventDestroy(ev);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdlib>
+#include <functional>
 #include <memory>
 #include <string>
 #include <thread>
@@ -98,6 +99,16 @@ struct mirp_ctx {
     // ---- read collapse (reads_kernels.hip): the file text and the per-line / per-read arrays, reused from file to file
     DevBuf r_text, r_bcnt, r_bscan, r_starts, r_flag, r_fscan, r_span, r_rec, r_rectmp, r_rscan, r_first, r_bad, r_cnt, r_isfirst, r_inbad, r_rank, r_out, r_small;
     long long last_collapse_collisions = 0;   // reads in hash runs that failed the byte compare (resolved on the host)
+    // ---- read alignment (align_kernels.hip, mirp_align.cpp): the packed reference and its index stay resident between mirp_align_reads calls
+    DevBuf a_pk, a_amb, a_cst, a_cstart, a_names, a_noff, a_sa, a_bkt;
+    long long a_total = 0, a_nsa = 0;
+    int a_n_contigs = 0;
+    bool a_ready = false;
+    std::vector<std::string> a_contig_names;
+    std::vector<long long> a_contig_lens;
+    DevBuf a_codes, a_roff, a_qn, a_qoff, a_small, a_rcnt, a_rscan, a_seeds, a_ccnt, a_cscan, a_lvl, a_best, a_supp, a_slots, a_off, a_cursor, a_items, a_itmp,
+        a_size, a_toff, a_text;
+    std::vector<char> h_text;         // one piece (<= 1 GiB) of the SAM text on its way to the file
     long long n_result = 0;           // records of the last mirp_predict (p_res / p_text), what mirp_gather_loci sends
     bool have_result = false;
 };
@@ -117,10 +128,16 @@ static inline int fail(mirp_ctx* c, int code, const std::string& msg) {
 // Uses the LDS-resident kernel when span allows and re-runs flagged windows (length / int16 range) with the generic kernel.
 // sort_kernels.hip: stable device sort by (tid, pos) / keep-region filter of the resident record array
 int mirp_device_sort_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long n, int posbits, int tidbits);
+int mirp_device_sort_u64(mirp_ctx* c, unsigned long long* d, unsigned long long* d_tmp, long long n, int base, int bits);
 int mirp_device_sort_hashes(mirp_ctx* c, MirpHashRec* d, MirpHashRec* d_tmp, long long n, int bits);
 // reads_kernels.hip: the read collapse of process-reads-fasta.py on a file held in host memory (out: the .processed text, malloc'ed)
 int mirp_device_collapse_reads(mirp_ctx* c, const char* text, long long n, const char* prefix, int hash_bits, char** out, long long* out_len,
                                long long* n_reads, long long* n_unique, long long* bad_offset, double seconds[6]);
+// align_kernels.hip: the alignment index and one batch of reads (mirp_align.cpp parses the files)
+int mirp_device_align_index(mirp_ctx* c, const unsigned* pk, const unsigned* amb, const unsigned* cst, long long total,
+                            const std::vector<unsigned long long>& cstart, const std::string& names, const std::vector<long long>& noff, double seconds[4]);
+int mirp_device_align_batch(mirp_ctx* c, const unsigned char* codes, const long long* roff, const char* qn, const long long* qoff, long long n, int v, int k,
+                            int m, int filter, const std::function<int(const char*, size_t)>& sink, long long stats[4], double seconds[5]);
 int mirp_device_mask_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long* n_io, MirpAln* d_segs, MirpAln* d_segtmp, const int* d_owner, const int* d_seg_span,
                           long long* nseg_io,
                           const long long* d_rfirst, const int* d_rstart, const int* d_remax);

@@ -24,6 +24,11 @@ struct AlnDigit {
         return (unsigned)(key >> shift) & 255u;
     }
 };
+// 64-bit records by bits [base, base + bits): the alignment index (key32 << 32 | pos, by key) and its hits (read << 33 | gpos << 1 | strand)
+struct U64Digit {
+    int base;
+    __device__ __forceinline__ unsigned operator()(const unsigned long long& r, int shift) const { return (unsigned)(r >> (shift + base)) & 255u; }
+};
 struct HashDigit {
     __device__ __forceinline__ unsigned operator()(const MirpHashRec& r, int shift) const { return (unsigned)(r.hash >> shift) & 255u; }
 };
@@ -154,6 +159,11 @@ int mirp_device_sort_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long lon
 // Stable sort of (hash, read index) records by the low `bits` bits of the hash (the read collapse, reads_kernels.hip).
 int mirp_device_sort_hashes(mirp_ctx* c, MirpHashRec* d, MirpHashRec* d_tmp, long long n, int bits) {
     return device_radix_sort(c, d, d_tmp, n, bits, mirp::HashDigit{});
+}
+
+// Stable sort of 64-bit records by bits [base, base + bits) (the read alignment, align_kernels.hip).
+int mirp_device_sort_u64(mirp_ctx* c, unsigned long long* d, unsigned long long* d_tmp, long long n, int base, int bits) {
+    return device_radix_sort(c, d, d_tmp, n, bits, mirp::U64Digit{base});
 }
 
 // keep[] + stable compaction of records (and of the coverage segments through their owners).  Regions arrive per contig, sorted by start.
