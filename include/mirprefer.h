@@ -430,6 +430,24 @@ int mirp_align_index(mirp_ctx* ctx, const char* const* paths, int32_t n_paths, i
 int mirp_align_reads(mirp_ctx* ctx, const char* reads_path, const char* out_path, const char* pg_cl, int32_t v, int32_t k, int32_t m, int32_t filter_unmapped,
                      int64_t stats[5], double seconds[6]);
 
+/* 3' adapter and quality trimming of raw reads, the step before mirp_collapse_reads.  adapter[0 .. adapter_len) = A C G T in either
+ * case (adapter_len 0..64; 0 = no adapter search); error_permille 0..999 = E in per-mille (an overlap of length l allows floor(E * l / 1000)
+ * mismatches); min_overlap 1..adapter_len; quality_cutoff 0..93 (0 = off; Phred+33, FASTQ only); reads shorter than min_length or, when max_length
+ * > 0, longer than max_length after trimming are dropped, and with discard_untrimmed so are reads without an adapter match. */
+typedef struct {
+    char adapter[64];
+    int32_t adapter_len, error_permille, min_overlap, quality_cutoff, min_length, max_length, discard_untrimmed, reserved;
+} MirpTrimOpts;
+/* Trims the reads of one FASTQ or FASTA text held in host memory (data[0 .. n), decompressed by the caller; name = what messages call the file) and
+ * writes one FASTA record `>name\n<trimmed read>\n` per kept read to out_path, in input order.  The format is told by the first byte (@ or >).
+ * Refusals, each before out_path is opened: a byte >= 0x80 (-9, the offset in mirp_last_error); a malformed FASTQ record, a read longer than
+ * 1,024 nt or a name longer than 1,048,576 bytes (-10, the 1-based record in mirp_last_error); an unknown first byte, more than 2^31 - 1 reads
+ * and quality_cutoff > 0 on FASTA (-10, whole-file refusals without a record).  On a refusal or a later error a file at out_path (also one left
+ * by an earlier call) is removed.  Out: stats = {reads, quality-trimmed, with adapter, untrimmed discarded, too short, too long, written} (reads = the last four
+ * summed), seconds = {upload, split, records, trim, emit + download, write}. */
+int mirp_trim_reads(mirp_ctx* ctx, const char* data, int64_t n, const char* name, const MirpTrimOpts* opts, const char* out_path, int64_t stats[7],
+                    double seconds[6]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import early
 from .early import LIB_PATH, FastaData, SamData
-ABI_VERSION = 9      # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
+ABI_VERSION = 10     # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
 
 
 class MirpError(RuntimeError):
@@ -21,6 +21,15 @@ class FoldLine(C.Structure):
 
 class Region(C.Structure):
     _fields_ = [("tid", C.c_int32), ("start", C.c_int32), ("end", C.c_int32)]
+
+
+class TrimOpts(C.Structure):
+    """MirpTrimOpts of include/mirprefer.h."""
+    _fields_ = [("adapter", C.c_char * 64)] + [(f, C.c_int32) for f in ("adapter_len", "error_permille", "min_overlap", "quality_cutoff", "min_length",
+                                                                       "max_length", "discard_untrimmed", "reserved")]
+
+
+TRIM_STATS = ("reads", "quality_trimmed", "adapter", "untrimmed", "too_short", "too_long", "written")
 
 
 def report_readmapping(loci, ss_list, alns, contig_arrays, sample_names, counts0):
@@ -344,6 +353,8 @@ def load_library():
     lib.mirp_align_index.restype = C.c_int
     lib.mirp_align_reads.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i64p, C.POINTER(C.c_double)]
     lib.mirp_align_reads.restype = C.c_int
+    lib.mirp_trim_reads.argtypes = [vp, C.c_char_p, C.c_int64, C.c_char_p, C.POINTER(TrimOpts), C.c_char_p, i64p, C.POINTER(C.c_double)]
+    lib.mirp_trim_reads.restype = C.c_int
     lib.mirp_dist_unique_id.argtypes = [vp]
     lib.mirp_dist_unique_id.restype = C.c_int
     lib.mirp_dist_init.argtypes = [vp, vp, C.c_int32, C.c_int32]
@@ -430,6 +441,20 @@ class Context:
         self._check(self.lib.mirp_align_reads(self.h, os.fsencode(reads_path), os.fsencode(out_path), pg_cl.encode(), int(v), int(k), int(m),
                                               int(bool(filter_unmapped)), st, sec), "mirp_align_reads")
         return dict(zip(("reads", "aligned", "unaligned", "suppressed", "records"), list(st)), seconds=list(sec))
+
+    def trim_reads(self, data, name, out_path, adapter="", error_permille=100, overlap=3, quality=0, min_length=18, max_length=0, discard_untrimmed=False):
+        """3' adapter and quality trimming of one FASTQ / FASTA text (bytes, already decompressed) (mirp_trim_reads): writes out_path,
+        the FASTA of the kept reads; name is what messages call the file.  -> {reads, quality_trimmed, adapter, untrimmed, too_short, too_long,
+        written, seconds}; seconds = {upload, split, records, trim, emit + download, write}."""
+        o = TrimOpts()
+        ad = adapter.encode() if isinstance(adapter, str) else bytes(adapter)
+        o.adapter = ad
+        o.adapter_len, o.error_permille, o.min_overlap, o.quality_cutoff = len(ad), int(error_permille), int(overlap), int(quality)
+        o.min_length, o.max_length, o.discard_untrimmed = int(min_length), int(max_length), int(bool(discard_untrimmed))
+        st = (C.c_int64 * 7)()
+        sec = (C.c_double * 6)()
+        self._check(self.lib.mirp_trim_reads(self.h, data, len(data), os.fsencode(name), C.byref(o), os.fsencode(out_path), st, sec), "mirp_trim_reads")
+        return dict(zip(TRIM_STATS, list(st)), seconds=list(sec))
 
     def fold_batch(self, seqs, span, max_lines=96):
         """RNALfold -L replacement. seqs: list of str/bytes. Returns a list (per sequence) of

@@ -23,6 +23,10 @@ struct DevBuf {
         return 0;
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;              // owns its allocation: never copied, freed when its owner goes (a buffer left out of mirp_destroy's list)
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
 };
 
 struct TmpDevice {   // scoped device allocations
@@ -109,6 +113,9 @@ struct mirp_ctx {
     DevBuf a_codes, a_roff, a_qn, a_qoff, a_small, a_rcnt, a_rscan, a_seeds, a_ccnt, a_cscan, a_lvl, a_best, a_supp, a_slots, a_off, a_cursor, a_items, a_itmp,
         a_size, a_toff, a_text;
     std::vector<char> h_text;         // one piece (<= 1 GiB) of the SAM text on its way to the file
+    // ---- read trimming (trim_kernels.hip, mirp_trim.cpp): the file text, its lines and the per-read arrays, reused from file to file
+    DevBuf t_text, t_bcnt, t_bscan, t_starts, t_small, t_hdr, t_llen, t_lb, t_hscan, t_goff, t_first, t_gbuf, t_src, t_len, t_qual, t_nameb, t_namel,
+        t_flen, t_off, t_out;
     long long n_result = 0;           // records of the last mirp_predict (p_res / p_text), what mirp_gather_loci sends
     bool have_result = false;
 };
@@ -138,6 +145,11 @@ int mirp_device_align_index(mirp_ctx* c, const unsigned* pk, const unsigned* amb
                             const std::vector<unsigned long long>& cstart, const std::string& names, const std::vector<long long>& noff, double seconds[4]);
 int mirp_device_align_batch(mirp_ctx* c, const unsigned char* codes, const long long* roff, const char* qn, const long long* qoff, long long n, int v, int k,
                             int m, int filter, const std::function<int(const char*, size_t)>& sink, long long stats[4], double seconds[5]);
+// reads_kernels.hip: the line split of an uploaded text shared by the collapse and the trim (starts[0 .. n_lines]); trim_kernels.hip: the trim of one FASTQ / FASTA text
+int mirp_device_split_lines(mirp_ctx* c, const unsigned char* d_text, long long n, long long max_lines, DevBuf& tile_cnt, DevBuf& tile_scan, DevBuf& starts,
+                            unsigned long long* d_first_bad, long long* n_lines, long long* bad_offset);
+int mirp_device_trim_reads(mirp_ctx* c, const char* text, long long n, const char* name, const MirpTrimOpts& o,
+                           const std::function<int(const char*, size_t)>& sink, long long stats[7], double seconds[6]);
 int mirp_device_mask_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long* n_io, MirpAln* d_segs, MirpAln* d_segtmp, const int* d_owner, const int* d_seg_span,
                           long long* nseg_io,
                           const long long* d_rfirst, const int* d_rstart, const int* d_remax);

@@ -282,25 +282,9 @@ int mirp_device_collapse_reads(mirp_ctx* c, const char* text, long long n, const
     t = rd_now();
     long long n_lines = 0, R = 0;
     if (n > 0) {
-        const long long tiles = (n + RD_TILE - 1) / RD_TILE;
-        if (c->r_bcnt.ensure(4 * (size_t)tiles) || c->r_bscan.ensure(8 * (size_t)(tiles + 1))) return fail(c, -6, "device allocation failed (collapse: tiles)");
-        hipLaunchKernelGGL(reads_count_kernel, dim3((unsigned)tiles), dim3(RD_NT), 0, st, (const unsigned char*)d_text, n, (int*)c->r_bcnt.p, d_small);
-        launch_excl_scan(st, (const int*)c->r_bcnt.p, (long long*)c->r_bscan.p, tiles);
-        unsigned long long first_bad = 0;
-        long long ends = 0;
-        HIPCHK(c, hipMemcpyAsync(&first_bad, d_small, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(&ends, (long long*)c->r_bscan.p + tiles, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        if (first_bad != ~0ull) { *bad_offset = (long long)first_bad; return fail(c, -9, "byte outside ASCII"); }
-        n_lines = ends + 1;
-        if (n_lines > 0x7fffffffll) return fail(c, -5, "more than 2^31 - 1 lines in one file");
-        if (c->r_starts.ensure(8 * (size_t)(n_lines + 1)) || c->r_flag.ensure(4 * (size_t)n_lines) || c->r_fscan.ensure(8 * (size_t)(n_lines + 1)))
-            return fail(c, -6, "device allocation failed (collapse: lines)");
-        long long* d_starts = (long long*)c->r_starts.p;
-        const long long edge[2] = {0, n};
-        HIPCHK(c, hipMemcpyAsync(d_starts, &edge[0], 8, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(d_starts + n_lines, &edge[1], 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(reads_starts_kernel, dim3((unsigned)tiles), dim3(RD_NT), 0, st, (const unsigned char*)d_text, n, (const long long*)c->r_bscan.p, d_starts);
+        if (int rc = mirp_device_split_lines(c, d_text, n, 0x7fffffffll, c->r_bcnt, c->r_bscan, c->r_starts, d_small, &n_lines, bad_offset)) return rc;
+        if (c->r_flag.ensure(4 * (size_t)n_lines) || c->r_fscan.ensure(8 * (size_t)(n_lines + 1))) return fail(c, -6, "device allocation failed (collapse: lines)");
+        const long long* d_starts = (const long long*)c->r_starts.p;
         hipLaunchKernelGGL(reads_flag_kernel, dim3(rd_grid(n_lines)), dim3(256), 0, st, (const unsigned char*)d_text, (const long long*)d_starts, n_lines, (int*)c->r_flag.p);
         launch_excl_scan(st, (const int*)c->r_flag.p, (long long*)c->r_fscan.p, n_lines);
         HIPCHK(c, hipMemcpyAsync(&R, (long long*)c->r_fscan.p + n_lines, 8, hipMemcpyDeviceToHost, st));
@@ -421,5 +405,37 @@ int mirp_device_collapse_reads(mirp_ctx* c, const char* text, long long n, const
     *out = h_out;
     *out_len = total;
     *n_unique = U;
+    return 0;
+}
+
+// The split phase of the collapse and the trim (trim_kernels.hip) on an uploaded text: d_text holds n bytes plus RD_PAD zero bytes.
+// starts[0 .. n_lines] as reads_starts_kernel leaves them (starts[n_lines] = n).  -9 with *bad_offset set: a byte >= 0x80; -5: more than
+// max_lines lines.  n > 0.
+int mirp_device_split_lines(mirp_ctx* c, const unsigned char* d_text, long long n, long long max_lines, DevBuf& tile_cnt, DevBuf& tile_scan, DevBuf& starts,
+                            unsigned long long* d_first_bad, long long* n_lines, long long* bad_offset) {
+    using namespace mirp;
+    hipStream_t st = c->stream;
+    const long long tiles = (n + RD_TILE - 1) / RD_TILE;
+    if (tile_cnt.ensure(4 * (size_t)tiles) || tile_scan.ensure(8 * (size_t)(tiles + 1))) return fail(c, -6, "device allocation failed (split: tiles)");
+    const unsigned long long none = ~0ull;
+    HIPCHK(c, hipMemcpyAsync(d_first_bad, &none, 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(reads_count_kernel, dim3((unsigned)tiles), dim3(RD_NT), 0, st, d_text, n, (int*)tile_cnt.p, d_first_bad);
+    launch_excl_scan(st, (const int*)tile_cnt.p, (long long*)tile_scan.p, tiles);
+    unsigned long long first_bad = 0;
+    long long ends = 0;
+    HIPCHK(c, hipMemcpyAsync(&first_bad, d_first_bad, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(&ends, (long long*)tile_scan.p + tiles, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (first_bad != ~0ull) { *bad_offset = (long long)first_bad; return fail(c, -9, "byte outside ASCII"); }
+    *n_lines = ends + 1;
+    if (*n_lines > max_lines) return fail(c, -5, "more than 2^31 - 1 lines in one file");
+    if (starts.ensure(8 * (size_t)(*n_lines + 1))) return fail(c, -6, "device allocation failed (split: lines)");
+    long long* d_starts = (long long*)starts.p;
+    const long long edge[2] = {0, n};
+    HIPCHK(c, hipMemcpyAsync(d_starts, &edge[0], 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_starts + *n_lines, &edge[1], 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(reads_starts_kernel, dim3((unsigned)tiles), dim3(RD_NT), 0, st, d_text, n, (const long long*)tile_scan.p, d_starts);
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
     return 0;
 }
