@@ -8,7 +8,7 @@ import numpy as np
 
 from . import early
 from .early import LIB_PATH, FastaData, SamData
-ABI_VERSION = 10     # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
+ABI_VERSION = 11     # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
 
 
 class MirpError(RuntimeError):
@@ -30,6 +30,14 @@ class TrimOpts(C.Structure):
 
 
 TRIM_STATS = ("reads", "quality_trimmed", "adapter", "untrimmed", "too_short", "too_long", "written")
+
+
+class TargetOpts(C.Structure):
+    """MirpTargetOpts of include/mirprefer.h."""
+    _fields_ = [("max_half_score", C.c_int32), ("both_strands", C.c_int32), ("cleavage_site", C.c_int32), ("reserved", C.c_int32), ("max_sites", C.c_int64)]
+
+
+TARGET_STATS = ("mirnas", "targets", "bases", "evaluations", "sites", "passes")
 
 
 def report_readmapping(loci, ss_list, alns, contig_arrays, sample_names, counts0):
@@ -355,6 +363,10 @@ def load_library():
     lib.mirp_align_reads.restype = C.c_int
     lib.mirp_trim_reads.argtypes = [vp, C.c_char_p, C.c_int64, C.c_char_p, C.POINTER(TrimOpts), C.c_char_p, i64p, C.POINTER(C.c_double)]
     lib.mirp_trim_reads.restype = C.c_int
+    lib.mirp_target_scan.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(TargetOpts), C.c_char_p, i64p, C.POINTER(C.c_double)]
+    lib.mirp_target_scan.restype = C.c_int
+    lib.mirp_set_target_capacity.argtypes = [vp, C.c_int64]
+    lib.mirp_set_target_capacity.restype = C.c_int
     lib.mirp_dist_unique_id.argtypes = [vp]
     lib.mirp_dist_unique_id.restype = C.c_int
     lib.mirp_dist_init.argtypes = [vp, vp, C.c_int32, C.c_int32]
@@ -455,6 +467,23 @@ class Context:
         sec = (C.c_double * 6)()
         self._check(self.lib.mirp_trim_reads(self.h, data, len(data), os.fsencode(name), C.byref(o), os.fsencode(out_path), st, sec), "mirp_trim_reads")
         return dict(zip(TRIM_STATS, list(st)), seconds=list(sec))
+
+    def target_scan(self, mirna_path, target_paths, out_path, max_half_score=8, both_strands=False, cleavage_site=False, max_sites=0):
+        """Plant miRNA target sites (mirp_target_scan): every miRNA of mirna_path against the target FASTA files, in order; writes
+        the TSV to out_path.  max_half_score = 2 x the -s score.  -> {mirnas, targets, bases, evaluations, sites, passes, seconds}; seconds =
+        {parse, upload, scan, sort + cut, emit + download + write}."""
+        o = TargetOpts()
+        o.max_half_score, o.both_strands, o.cleavage_site, o.max_sites = int(max_half_score), int(bool(both_strands)), int(bool(cleavage_site)), int(max_sites)
+        arr = (C.c_char_p * len(target_paths))(*[os.fsencode(p) for p in target_paths])
+        st = (C.c_int64 * 6)()
+        sec = (C.c_double * 5)()
+        self._check(self.lib.mirp_target_scan(self.h, os.fsencode(mirna_path), arr, len(target_paths), C.byref(o), os.fsencode(out_path), st, sec),
+                    "mirp_target_scan")
+        return dict(zip(TARGET_STATS, list(st)), seconds=list(sec))
+
+    def set_target_capacity(self, keys):
+        """Sites one target_scan pass holds on the device (0 = the default, 2^26; at least 2): lowered only to test the overflow path."""
+        self._check(self.lib.mirp_set_target_capacity(self.h, int(keys)), "mirp_set_target_capacity")
 
     def fold_batch(self, seqs, span, max_lines=96):
         """RNALfold -L replacement. seqs: list of str/bytes. Returns a list (per sequence) of

@@ -28,6 +28,7 @@
 #include <string>
 #include <vector>
 #include "mirp_ctx.h"
+#include "text_out.h"
 
 namespace mirp {
 
@@ -290,26 +291,10 @@ struct AlText {
     const unsigned long long* cstart; int n_contigs;
 };
 
-__device__ __forceinline__ int al_digits(unsigned long long v) { int d = 1; while (v >= 10) { v /= 10; d++; } return d; }
-
-template <bool WRITE>
-struct AlOut {
-    char* p;
-    long long n = 0;
-    __device__ void ch(char c) { if (WRITE) p[n] = c; n++; }
-    __device__ void num(unsigned long long v) {
-        const int d = al_digits(v);
-        if (WRITE) for (int k = d - 1; k >= 0; k--) { p[n + k] = (char)('0' + v % 10); v /= 10; }
-        n += d;
-    }
-    __device__ void str(const char* s, long long len) { if (WRITE) for (long long k = 0; k < len; k++) p[n + k] = s[k]; n += len; }
-    __device__ void lit(const char* s) { while (*s) ch(*s++); }
-};
-
 // one SAM record: item = read << 33 | gpos << 1 | strand; best < 0: unaligned (XM:i:0, or XM:i:<M+1> when suppressed)
 template <bool WRITE>
 __device__ long long al_record(const AlRef& R, const AlText& T, const AlParams& P, unsigned long long item, int best, int supp, char* out) {
-    AlOut<WRITE> o{out};
+    TextOut<WRITE> o{out};
     const long long r = (long long)(item >> 33);
     const long long rb = T.roff[r];
     const int L = (int)(T.roff[r + 1] - rb);

@@ -8,13 +8,11 @@
 #include <string>
 #include <unordered_set>
 #include <vector>
-#include "mirp_ctx.h"
+#include "mirp_fasta.h"
 
 namespace {
 
 double al_clock() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-bool al_ws(unsigned char ch) { return ch == 32 || (ch >= 9 && ch <= 13) || (ch >= 0x1c && ch <= 0x1f); }   // str.strip() / str.split(), ASCII
 
 // base codes: A C G T in either case 0..3, anything else 4
 struct Codes {
@@ -26,7 +24,9 @@ struct Codes {
 };
 const Codes kCodes;
 
-int read_whole(mirp_ctx* c, const char* path, std::string& buf) {
+}  // namespace
+
+int mirp::read_whole(mirp_ctx* c, const char* path, std::string& buf) {
     FILE* f = std::fopen(path, "rb");
     if (!f) return fail(c, -8, std::string("cannot open ") + path);
     fseeko(f, 0, SEEK_END);
@@ -39,48 +39,13 @@ int read_whole(mirp_ctx* c, const char* path, std::string& buf) {
     return 0;
 }
 
-// Calls fn(begin, end) for every line of buf (ends at \n, \r\n or a lone \r: Python's universal newlines; an empty line between \r and \n is harmless
-// to both parsers below).  The line is given stripped of surrounding whitespace.  fn returns nonzero to stop.
-template <class F>
-int for_lines(const std::string& buf, F fn) {
-    const char* p = buf.data();
-    const char* end = p + buf.size();
-    while (p < end) {
-        const char* q = p;
-        while (q < end && *q != '\n' && *q != '\r') q++;
-        const char* a = p;
-        const char* b = q;
-        while (a < b && al_ws((unsigned char)*a)) a++;
-        while (b > a && al_ws((unsigned char)b[-1])) b--;
-        if (int rc = fn(p, a, b)) return rc;
-        p = q < end ? q + 1 : q;
-    }
-    return 0;
-}
-
-// first word of a header line (after '>')
-std::string first_word(const char* raw, const char* b) {
-    const char* a = raw + 1;
-    while (a < b && al_ws((unsigned char)*a)) a++;
-    const char* z = a;
-    while (z < b && !al_ws((unsigned char)*z)) z++;
-    return std::string(a, z);
-}
-
-}  // namespace
-
-// Parses the reference FASTA files (in order), packs them and builds the device-resident index.  seconds = {read + parse + pack, upload, keys, sort,
-// positions + buckets}.  Contigs of length 0 are dropped with a warning on stderr; duplicate names, empty names and 2^32 bases or more are refused.
-extern "C" int mirp_align_index(mirp_ctx* c, const char* const* paths, int32_t n_paths, int32_t* n_contigs, int64_t* total_out, double seconds[5]) {
-    if (!c) return -1;
-    if (!paths || n_paths < 1) return fail(c, -1, "mirp_align_index: bad argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    c->a_ready = false;
-    double sec[5] = {0, 0, 0, 0, 0};
-    double t = al_clock();
-    std::vector<unsigned> pk, amb, cst;
-    std::vector<std::string> names;
-    std::vector<long long> lens;
+int mirp::pack_fasta(mirp_ctx* c, const char* const* paths, int n_paths, PackedFasta& out) {
+    std::vector<unsigned>& pk = out.pk;
+    std::vector<unsigned>& amb = out.amb;
+    std::vector<unsigned>& cst = out.cst;
+    std::vector<std::string>& names = out.names;
+    std::vector<long long>& lens = out.lens;
+    pk.clear(); amb.clear(); cst.clear(); names.clear(); lens.clear();
     std::unordered_set<std::string> seen;
     unsigned long long pos = 0;           // bases so far
     const unsigned long long limit = 1ull << 32;
@@ -136,23 +101,38 @@ extern "C" int mirp_align_index(mirp_ctx* c, const char* const* paths, int32_t n
         const long long lo = (long long)w * 32;
         amb[w] |= lo >= total ? 0xffffffffu : ~((1u << (total - lo)) - 1u);
     }
-    std::string blob;
-    std::vector<long long> noff(1, 0);
-    std::vector<unsigned long long> cstart(1, 0);
+    out.blob.clear();
+    out.noff.assign(1, 0);
+    out.cstart.assign(1, 0);
     for (size_t i = 0; i < names.size(); i++) {
-        blob += names[i];
-        noff.push_back((long long)blob.size());
-        cstart.push_back(cstart.back() + (unsigned long long)lens[i]);
+        out.blob += names[i];
+        out.noff.push_back((long long)out.blob.size());
+        out.cstart.push_back(out.cstart.back() + (unsigned long long)lens[i]);
     }
+    out.total = total;
+    return 0;
+}
+
+// Parses the reference FASTA files (in order), packs them and builds the device-resident index.  seconds = {read + parse + pack, upload, keys, sort,
+// positions + buckets}.  Contigs of length 0 are dropped with a warning on stderr; duplicate names, empty names and 2^32 bases or more are refused.
+extern "C" int mirp_align_index(mirp_ctx* c, const char* const* paths, int32_t n_paths, int32_t* n_contigs, int64_t* total_out, double seconds[5]) {
+    if (!c) return -1;
+    if (!paths || n_paths < 1) return fail(c, -1, "mirp_align_index: bad argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->a_ready = false;
+    double sec[5] = {0, 0, 0, 0, 0};
+    double t = al_clock();
+    mirp::PackedFasta ref;
+    if (int rc = mirp::pack_fasta(c, paths, n_paths, ref)) return rc;
     std::vector<std::string>().swap(c->a_contig_names);
     sec[0] = al_clock() - t;
     double dsec[4] = {0, 0, 0, 0};
-    if (int rc = mirp_device_align_index(c, pk.data(), amb.data(), cst.data(), total, cstart, blob, noff, dsec)) return rc;
+    if (int rc = mirp_device_align_index(c, ref.pk.data(), ref.amb.data(), ref.cst.data(), ref.total, ref.cstart, ref.blob, ref.noff, dsec)) return rc;
     for (int i = 0; i < 4; i++) sec[1 + i] = dsec[i];
-    c->a_contig_names = names;
-    c->a_contig_lens = lens;
-    if (n_contigs) *n_contigs = (int32_t)names.size();
-    if (total_out) *total_out = total;
+    c->a_contig_names = ref.names;
+    c->a_contig_lens = ref.lens;
+    if (n_contigs) *n_contigs = (int32_t)ref.names.size();
+    if (total_out) *total_out = ref.total;
     if (seconds) std::memcpy(seconds, sec, sizeof sec);
     return 0;
 }
@@ -169,18 +149,18 @@ extern "C" int mirp_align_reads(mirp_ctx* c, const char* reads_path, const char*
     double sec[6] = {0, 0, 0, 0, 0, 0};
     double t = al_clock();
     std::string buf;
-    if (int rc = read_whole(c, reads_path, buf)) return rc;
+    if (int rc = mirp::read_whole(c, reads_path, buf)) return rc;
     std::vector<unsigned char> codes;
     std::vector<long long> roff(1, 0), qoff(1, 0);
     std::string qn;
     codes.reserve(buf.size() / 2);
     bool open = false;
     const long long max_reads = 0x7fffffffll;
-    int rc = for_lines(buf, [&](const char* raw, const char* a, const char* b) -> int {
+    int rc = mirp::for_lines(buf, [&](const char* raw, const char* a, const char* b) -> int {
         if (*raw == '>') {
             if (open) roff.push_back((long long)codes.size());
             if ((long long)qoff.size() > max_reads) return fail(c, -10, std::string(reads_path) + ": more than 2^31 - 1 reads in one file");
-            const std::string name = first_word(raw, b);
+            const std::string name = mirp::first_word(raw, b);
             if (name.empty()) return fail(c, -10, std::string(reads_path) + ": a read header without a name");
             qn += name;
             qoff.push_back((long long)qn.size());

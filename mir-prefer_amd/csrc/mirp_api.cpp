@@ -11,7 +11,7 @@
 #include <vector>
 #include "mirp_internal.h"
 
-#define MIRP_ABI_VERSION 10  // 10: mirp_trim_reads; 9: mirp_align_index, mirp_align_reads; 8: mirp_collapse_reads, mirp_last_collapse_collisions; 7: mirp_write_result_reports, mirp_fold_predict_report_stream, mirp_select_windows, mirp_dist_comm_info, MIRP_MAX_SAMPLES 255; 6: mirp_last_coverage_fused, mirp_fold_batch_summary, mirp_predict_batch_reasons, text writers; 5: mirp_dist_*, mirp_gather_loci / mirp_gather_records, mirp_read_fasta, mirp_ingest_sams_shard; 4: MirpSamData.segs, mirp_ingest_sams_gpu, mirp_load_coverage_segments; 2: mirp_set_fold_model, mirp_ingest_sams; 3: mirp_predict returns the per-window capacity status, mirp_get_fold_overflow
+#define MIRP_ABI_VERSION 11  // 11: mirp_target_scan, mirp_set_target_capacity; 10: mirp_trim_reads; 9: mirp_align_index, mirp_align_reads; 8: mirp_collapse_reads, mirp_last_collapse_collisions; 7: mirp_write_result_reports, mirp_fold_predict_report_stream, mirp_select_windows, mirp_dist_comm_info, MIRP_MAX_SAMPLES 255; 6: mirp_last_coverage_fused, mirp_fold_batch_summary, mirp_predict_batch_reasons, text writers; 5: mirp_dist_*, mirp_gather_loci / mirp_gather_records, mirp_read_fasta, mirp_ingest_sams_shard; 4: MirpSamData.segs, mirp_ingest_sams_gpu, mirp_load_coverage_segments; 2: mirp_set_fold_model, mirp_ingest_sams; 3: mirp_predict returns the per-window capacity status, mirp_get_fold_overflow
 #define MIRP_NMAX 3096
 
 #include "mirp_ctx.h"
@@ -108,7 +108,9 @@ extern "C" void mirp_destroy(mirp_ctx* c) {
                       &c->a_rscan, &c->a_seeds, &c->a_ccnt, &c->a_cscan, &c->a_lvl, &c->a_best, &c->a_supp, &c->a_slots, &c->a_off, &c->a_cursor,
                       &c->a_items, &c->a_itmp, &c->a_size, &c->a_toff, &c->a_text, &c->t_text, &c->t_bcnt, &c->t_bscan, &c->t_starts, &c->t_small,
                       &c->t_hdr, &c->t_llen, &c->t_lb, &c->t_hscan, &c->t_goff, &c->t_first, &c->t_gbuf, &c->t_src, &c->t_len, &c->t_qual, &c->t_nameb,
-                      &c->t_namel, &c->t_flen, &c->t_off, &c->t_out})
+                      &c->t_namel, &c->t_flen, &c->t_off, &c->t_out, &c->tg_pk, &c->tg_amb, &c->tg_cst, &c->tg_cstart, &c->tg_names, &c->tg_noff, &c->tg_mcodes,
+                      &c->tg_mnames, &c->tg_mnoff, &c->tg_mi, &c->tg_emitted, &c->tg_hist, &c->tg_small, &c->tg_keys, &c->tg_ktmp, &c->tg_size, &c->tg_toff,
+                      &c->tg_text})
         b->release();
     for (int i = 0; i < 6; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     for (hipEvent_t ev : c->fold_ev) (void)hipEventDestroy(ev);

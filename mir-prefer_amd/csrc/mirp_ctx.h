@@ -116,6 +116,10 @@ struct mirp_ctx {
     // ---- read trimming (trim_kernels.hip, mirp_trim.cpp): the file text, its lines and the per-read arrays, reused from file to file
     DevBuf t_text, t_bcnt, t_bscan, t_starts, t_small, t_hdr, t_llen, t_lb, t_hscan, t_goff, t_first, t_gbuf, t_src, t_len, t_qual, t_nameb, t_namel,
         t_flen, t_off, t_out;
+    // ---- target-site search (targets_kernels.hip, mirp_targets.cpp): the packed targets, the miRNAs and the key / text buffers of one call
+    DevBuf tg_pk, tg_amb, tg_cst, tg_cstart, tg_names, tg_noff, tg_mcodes, tg_mnames, tg_mnoff, tg_mi, tg_emitted, tg_hist, tg_small, tg_keys, tg_ktmp,
+        tg_size, tg_toff, tg_text;
+    long long tg_cap = 0;             // keys held per pass; 0 = the default, 2^26 (mirp_set_target_capacity)
     long long n_result = 0;           // records of the last mirp_predict (p_res / p_text), what mirp_gather_loci sends
     bool have_result = false;
 };
@@ -150,6 +154,11 @@ int mirp_device_split_lines(mirp_ctx* c, const unsigned char* d_text, long long 
                             unsigned long long* d_first_bad, long long* n_lines, long long* bad_offset);
 int mirp_device_trim_reads(mirp_ctx* c, const char* text, long long n, const char* name, const MirpTrimOpts& o,
                            const std::function<int(const char*, size_t)>& sink, long long stats[7], double seconds[6]);
+// targets_kernels.hip: the target-site search over packed targets (mirp_targets.cpp parses the files)
+int mirp_device_target_scan(mirp_ctx* c, const unsigned long long* pk, const unsigned* amb, const unsigned* cst, long long total,
+                            const std::vector<unsigned long long>& cstart, const std::string& tnames, const std::vector<long long>& tnoff,
+                            std::vector<TgMirna>& mi, const std::vector<unsigned char>& mcodes, const std::string& mnames, const std::vector<long long>& mnoff,
+                            const MirpTargetOpts& o, const std::function<int(const char*, size_t)>& sink, long long stats[2], double seconds[4]);
 int mirp_device_mask_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long* n_io, MirpAln* d_segs, MirpAln* d_segtmp, const int* d_owner, const int* d_seg_span,
                           long long* nseg_io,
                           const long long* d_rfirst, const int* d_rstart, const int* d_remax);

@@ -10,6 +10,13 @@
 // One read of the read collapse (reads_kernels.hip): 64-bit content hash and the read's index in file order, sorted by the hash (sort_kernels.hip).
 struct MirpHashRec { unsigned long long hash; unsigned idx, pad; };
 
+// One strand of one miRNA in the target-site search (targets_kernels.hip): 32-bit masks over the window positions j = 0 .. L - 1.
+// pl / ph: low / high bit of the 2-bit code of the Watson-Crick target base; unk: unknown miRNA letters; g1 / g2: miRNA G / U (G:U with target U /
+// G); seed: miRNA positions 2..13; cleave: positions 10 and 11 under -c, else 0.
+struct TgStrand { unsigned pl, ph, unk, g1, g2, seed, cleave, pad; };
+// One miRNA, plus (s[0]) and minus (s[1]) strand; lmask = positions 0 .. L - 1; half-scores smin .. smax are reported in the current pass.
+struct TgMirna { TgStrand s[2]; unsigned lmask; int L, smin, smax; };
+
 namespace mirp {
 
 size_t fold_generic_lds_bytes(int n_cap, int max_lines);

@@ -1,0 +1,456 @@
+// Device side of the plant miRNA target-site search (mirp_target_scan, mirp_targets.cpp), with the semantics of DESIGN.md §14.
+//
+// Targets (uploaded once per call): pk as 64-bit words of 32 2-bit bases (base i at bits 2 (i % 32)), amb / cst bitmaps as in align_kernels.hip
+// (amb also set on every position past the end), the contigs' first positions and names.  Positions are global over the targets in file order.
+//
+// miRNAs: one TgMirna per miRNA, built on the host (mirp_targets.cpp).  Window position j of a lane at offset o is the forward base t[o + j];
+// miRNA position i pairs with j = L - i on the plus strand and j = i - 1 on the minus strand.  Every mask is a 32-bit mask over j, and the
+// Watson-Crick target bases are held as two bit planes (low and high bit of the 2-bit code), so one (position, miRNA, strand) evaluation is
+//     nonwc = ((wl ^ pl) | (wh ^ ph) | unk) & lmask            bases that are not Watson-Crick pairs (an unknown miRNA letter never is)
+//     gu    = (isX & g1) | (isY & g2)                          G:U pairs: X = T, Y = G on the plus strand, X = A, Y = C on the minus strand
+//     mm    = nonwc & ~gu
+//     half  = popc(nonwc) + popc(mm) + popc(nonwc & seed) + popc(mm & seed)      the score in half-units: mismatch 2, G:U 1, doubled in the seed
+// and the site is a hit when smin <= half <= smax, mm & cleave == 0 and L <= stop, stop = the distance to the first ambiguous base or to the next
+// contig start (per lane, computed once).
+//
+//   scan   tg_scan_kernel<0>: one lane per target offset, miRNAs of the pass in wave-uniform (scalar) loads; every hit appends the key
+//          mloc << 38 | half << 33 | o << 1 | strand (mloc = the miRNA's index in its group of <= 2^16) to a buffer of `cap` keys and counts it.
+//          tg_scan_kernel<1>: the same scan counting hits per (miRNA, half-score) only, run when a pass's hits overflow the buffer: the host then
+//          plans passes of at most cap keys each, by ranges of (miRNA, half-score) and, for one (miRNA, half-score) over cap, by ranges of offsets.
+//   order  mirp_device_sort_u64 by the whole key: per miRNA, (score, target, start, + before -) = the output order.
+//   cut    tg_size_kernel: -k from the rank inside the miRNA's run plus what earlier passes emitted; the line's length; launch_excl_scan.
+//   emit   tg_emit_kernel writes the lines; the text goes to the sink in pieces of at most 1 GiB.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <functional>
+#include <string>
+#include <vector>
+#include "mirp_ctx.h"
+#include "text_out.h"
+
+namespace mirp {
+
+#define TG_GROUP (1 << 16)           // miRNAs per group (the key holds 16 bits of miRNA index)
+#define TG_NHALF 17                  // half-scores 0 .. 16
+#define TG_LAUNCH_POS (1ll << 30)    // offsets per scan launch (the grid's work-items stay below 2^32)
+
+struct TgRef {
+    const unsigned long long* pk;
+    const unsigned* amb;
+    const unsigned* cst;
+    unsigned long long total;
+};
+
+__device__ __forceinline__ unsigned tg_base(const unsigned long long* __restrict__ pk, unsigned long long q) { return (unsigned)(pk[q >> 5] >> (2 * (q & 31))) & 3u; }
+
+// the even bits of x, packed into 32 bits
+__device__ __forceinline__ unsigned tg_even(unsigned long long x) {
+    x &= 0x5555555555555555ull;
+    x = (x | (x >> 1)) & 0x3333333333333333ull;
+    x = (x | (x >> 2)) & 0x0f0f0f0f0f0f0f0full;
+    x = (x | (x >> 4)) & 0x00ff00ff00ff00ffull;
+    x = (x | (x >> 8)) & 0x0000ffff0000ffffull;
+    x = (x | (x >> 16)) & 0x00000000ffffffffull;
+    return (unsigned)x;
+}
+
+__device__ __forceinline__ unsigned tg_bits32(const unsigned* __restrict__ bm, unsigned long long p) {
+    const unsigned long long w = bm[p >> 5] | ((unsigned long long)bm[(p >> 5) + 1] << 32);
+    return (unsigned)(w >> (p & 31));
+}
+
+// one strand of one miRNA: a hit when (half - smin) <= span (unsigned) and no mismatch under the cleavage mask
+__device__ __forceinline__ bool tg_eval(const TgStrand& S, unsigned lmask, unsigned wl, unsigned wh, unsigned x1, unsigned x2, unsigned smin, unsigned span,
+                                        unsigned* half) {
+    const unsigned nonwc = ((wl ^ S.pl) | (wh ^ S.ph) | S.unk) & lmask;
+    const unsigned gu = (x1 & S.g1) | (x2 & S.g2);
+    const unsigned mm = nonwc & ~gu;
+    const unsigned h = __popc(nonwc) + __popc(mm) + __popc(nonwc & S.seed) + __popc(mm & S.seed);
+    *half = h;
+    return h - smin <= span && (mm & S.cleave) == 0;
+}
+
+// MODE 0: keys (keys[0 .. cap), counter[0] = hits, also past cap); MODE 1: hist[mloc * 17 + half] += hits.  miRNAs [m0, m1) of the group's
+// array, offsets [p0, p1).
+template <int MODE, bool BOTH>
+__global__ __launch_bounds__(256) void tg_scan_kernel(TgRef R, const TgMirna* __restrict__ mi, int m0, int m1, unsigned long long p0, unsigned long long p1,
+                                                      unsigned long long* __restrict__ keys, unsigned long long cap, unsigned long long* __restrict__ counter,
+                                                      unsigned long long* __restrict__ hist) {
+    const unsigned long long o = p0 + (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    unsigned wl = 0, wh = 0, stop = 0;                         // a lane past p1 has stop 0: no miRNA (L >= 12) fits
+    if (o < p1) {
+        const unsigned long long q = o >> 5;
+        const unsigned sh = 2 * (unsigned)(o & 31);
+        unsigned long long w = R.pk[q];
+        if (sh) w = (w >> sh) | (R.pk[q + 1] << (64 - sh));
+        wl = tg_even(w);
+        wh = tg_even(w >> 1);
+        const unsigned sm = tg_bits32(R.amb, o) | (tg_bits32(R.cst, o) & ~1u);
+        stop = sm ? (unsigned)(__ffs(sm) - 1) : 32u;
+    }
+    const unsigned tA = ~(wl | wh), tC = wl & ~wh, tG = ~wl & wh, tT = wl & wh;
+    for (int m = m0; m < m1; m++) {
+        const TgMirna& M = mi[m];
+        if ((unsigned)M.L > stop) continue;
+        const unsigned span = (unsigned)(M.smax - M.smin);
+        unsigned h;
+        #pragma unroll
+        for (int s = 0; s < (BOTH ? 2 : 1); s++) {
+            if (tg_eval(M.s[s], M.lmask, wl, wh, s ? tA : tT, s ? tC : tG, (unsigned)M.smin, span, &h)) {
+                if (MODE == 0) {
+                    const unsigned long long i = atomicAdd(counter, 1ull);
+                    if (i < cap) keys[i] = ((unsigned long long)m << 38) | ((unsigned long long)h << 33) | (o << 1) | (unsigned long long)s;
+                } else {
+                    atomicAdd(&hist[(long long)m * TG_NHALF + h], 1ull);
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------- text
+struct TgText {
+    const unsigned long long* pk;
+    const unsigned char* mcodes;            // 32 per miRNA: 0..3 = A C G U, 4 = unknown
+    const TgMirna* mi;                      // the group's miRNAs (L)
+    const char* mnames; const long long* mnoff;
+    const char* tnames; const long long* tnoff;
+    const unsigned long long* cstart; int n_contigs;
+    int mbase;                              // the group's first miRNA
+};
+
+// pair class of miRNA code mc (0..3 A C G U, 4 unknown) with target-strand base y (0..3 A C G U): 0 Watson-Crick, 1 G:U, 2 mismatch
+__device__ __forceinline__ int tg_class(unsigned mc, unsigned y) {
+    if (mc > 3) return 2;
+    if (mc + y == 3) return 0;
+    return (mc == 2 && y == 3) || (mc == 3 && y == 2) ? 1 : 2;
+}
+
+// one line: miRNA target start end strand score mismatches gu mirna_5to3 pairs target_3to5
+template <bool WRITE>
+__device__ long long tg_line(const TgText& T, unsigned long long key, char* out) {
+    TextOut<WRITE> o{out};
+    const int mloc = (int)(key >> 38);
+    const unsigned half = (unsigned)(key >> 33) & 31u;
+    const unsigned long long g = (key >> 1) & 0xffffffffull;
+    const int strand = (int)(key & 1);
+    const long long m = (long long)T.mbase + mloc;
+    const int L = T.mi[mloc].L;
+    const unsigned char* mc = T.mcodes + 32 * m;
+    int a = 0, z = T.n_contigs;                 // target: last cstart <= g
+    while (z - a > 1) { const int md = (a + z) >> 1; if (T.cstart[md] <= g) a = md; else z = md; }
+    int nmm = 0, ngu = 0;
+    for (int i = 1; i <= L; i++) {
+        const unsigned b = tg_base(T.pk, strand ? g + i - 1 : g + L - i);
+        const int k = tg_class(mc[i - 1], strand ? 3u - b : b);
+        nmm += k == 2;
+        ngu += k == 1;
+    }
+    o.str(T.mnames + T.mnoff[m], T.mnoff[m + 1] - T.mnoff[m]);
+    o.ch('\t');
+    o.str(T.tnames + T.tnoff[a], T.tnoff[a + 1] - T.tnoff[a]);
+    o.ch('\t');
+    o.num(g - T.cstart[a] + 1);
+    o.ch('\t');
+    o.num(g - T.cstart[a] + L);
+    o.ch('\t');
+    o.ch(strand ? '-' : '+');
+    o.ch('\t');
+    o.num(half >> 1);
+    o.ch('.');
+    o.ch(half & 1 ? '5' : '0');
+    o.ch('\t');
+    o.num((unsigned long long)nmm);
+    o.ch('\t');
+    o.num((unsigned long long)ngu);
+    o.ch('\t');
+    const char* RNA = "ACGUN";
+    for (int i = 0; i < L; i++) o.ch(RNA[mc[i]]);
+    o.ch('\t');
+    for (int i = 1; i <= L; i++) {
+        const unsigned b = tg_base(T.pk, strand ? g + i - 1 : g + L - i);
+        const int k = tg_class(mc[i - 1], strand ? 3u - b : b);
+        o.ch(k == 0 ? '|' : k == 1 ? 'o' : 'x');
+    }
+    o.ch('\t');
+    for (int i = 1; i <= L; i++) {
+        const unsigned b = tg_base(T.pk, strand ? g + i - 1 : g + L - i);
+        o.ch(RNA[strand ? 3u - b : b]);
+    }
+    o.ch('\n');
+    return o.n;
+}
+
+// first index of the miRNA run that holds keys[i] (the keys are sorted)
+__device__ __forceinline__ long long tg_run_first(const unsigned long long* __restrict__ keys, long long i) {
+    const unsigned long long lo = keys[i] >> 38 << 38;
+    long long a = 0, z = i;
+    while (a < z) { const long long md = (a + z) >> 1; if (keys[md] < lo) a = md + 1; else z = md; }
+    return a;
+}
+
+// size[i] of sorted key i, 0 when -k cuts it (emitted[mloc] = lines of the miRNA written by earlier passes); kept[0] += lines kept
+__global__ void tg_size_kernel(TgText T, const unsigned long long* __restrict__ keys, long long n, long long k, const unsigned long long* __restrict__ emitted,
+                               int* __restrict__ size, unsigned long long* __restrict__ kept) {
+    unsigned long long cnt = 0;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const unsigned long long key = keys[i];
+        const bool keep = k == 0 || emitted[key >> 38] + (unsigned long long)(i - tg_run_first(keys, i)) < (unsigned long long)k;
+        size[i] = keep ? (int)tg_line<false>(T, key, nullptr) : 0;
+        cnt += keep;
+    }
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(kept, cnt);
+}
+// emitted[mloc] += the miRNA's keys in this pass (after tg_size_kernel)
+__global__ void tg_emitted_kernel(const unsigned long long* __restrict__ keys, long long n, unsigned long long* __restrict__ emitted) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        if (i == n - 1 || (keys[i + 1] >> 38) != (keys[i] >> 38)) emitted[keys[i] >> 38] += (unsigned long long)(i + 1 - tg_run_first(keys, i));
+}
+__global__ void tg_emit_kernel(TgText T, const unsigned long long* __restrict__ keys, long long i0, long long i1, const long long* __restrict__ toff,
+                               char* __restrict__ text) {
+    const long long base = toff[i0];
+    for (long long i = i0 + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < i1; i += (long long)gridDim.x * blockDim.x)
+        if (toff[i + 1] != toff[i]) (void)tg_line<true>(T, keys[i], text + (toff[i] - base));
+}
+
+}  // namespace mirp
+
+static inline int tg_grid(long long n) {
+    const long long g = (n + 255) / 256;
+    return (int)(g < 1 ? 1 : g > 16384 ? 16384 : g);
+}
+static inline double tg_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+namespace {
+
+struct TgRun {
+    mirp_ctx* c;
+    mirp::TgRef R;
+    mirp::TgText T;
+    const MirpTargetOpts* o;
+    std::vector<TgMirna>* mi;                  // all miRNAs (host); smin / smax rewritten per pass
+    const std::function<int(const char*, size_t)>* sink;
+    long long cap;
+    int group_n = 0;                           // miRNAs in the current group
+    long long stats[2];                        // sites written, passes
+    double sec[3];                             // scan, sort + cut, emit + download + write
+
+    // scan miRNAs [a, b) of the group at mbase (their smin / smax as set in *mi) over offsets [p0, p1): keys in tg_keys; -> hits (maybe > cap)
+    int scan(int mode, int mbase, int a, int b, unsigned long long p0, unsigned long long p1, long long* hits) {
+        using namespace mirp;
+        const double t = tg_now();
+        hipStream_t st = c->stream;
+        const int n = b - a;
+        HIPCHK(c, hipMemcpyAsync((TgMirna*)c->tg_mi.p + a, mi->data() + mbase + a, sizeof(TgMirna) * (size_t)n, hipMemcpyHostToDevice, st));
+        unsigned long long* d_small = (unsigned long long*)c->tg_small.p;
+        HIPCHK(c, hipMemsetAsync(d_small, 0, 8, st));
+        for (unsigned long long q = p0; q < p1; q += (unsigned long long)TG_LAUNCH_POS) {
+            const unsigned long long q1 = std::min(p1, q + (unsigned long long)TG_LAUNCH_POS);
+            const dim3 grid((unsigned)((q1 - q + 255) / 256));
+            const TgMirna* d_mi = (const TgMirna*)c->tg_mi.p;
+            unsigned long long* d_keys = (unsigned long long*)c->tg_keys.p;
+            unsigned long long* d_hist = (unsigned long long*)c->tg_hist.p;
+            if (mode == 0 && o->both_strands) hipLaunchKernelGGL((tg_scan_kernel<0, true>), grid, dim3(256), 0, st, R, d_mi, a, b, q, q1, d_keys, (unsigned long long)cap, d_small, d_hist);
+            else if (mode == 0) hipLaunchKernelGGL((tg_scan_kernel<0, false>), grid, dim3(256), 0, st, R, d_mi, a, b, q, q1, d_keys, (unsigned long long)cap, d_small, d_hist);
+            else if (o->both_strands) hipLaunchKernelGGL((tg_scan_kernel<1, true>), grid, dim3(256), 0, st, R, d_mi, a, b, q, q1, d_keys, (unsigned long long)cap, d_small, d_hist);
+            else hipLaunchKernelGGL((tg_scan_kernel<1, false>), grid, dim3(256), 0, st, R, d_mi, a, b, q, q1, d_keys, (unsigned long long)cap, d_small, d_hist);
+        }
+        unsigned long long h = 0;
+        HIPCHK(c, hipMemcpyAsync(&h, d_small, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        HIPCHK(c, hipGetLastError());
+        *hits = (long long)h;
+        sec[0] += tg_now() - t;
+        return 0;
+    }
+
+    // sort, cut and write the n <= cap keys of the last scan
+    int finish(int mbase, long long n) {
+        using namespace mirp;
+        hipStream_t st = c->stream;
+        stats[1]++;
+        if (n == 0) return 0;
+        double t = tg_now();
+        unsigned long long* d_keys = (unsigned long long*)c->tg_keys.p;
+        int mbits = 0;                                         // the key's bits above the miRNA index are 0
+        while ((1 << mbits) < group_n) mbits++;
+        if (int rc = mirp_device_sort_u64(c, d_keys, (unsigned long long*)c->tg_ktmp.p, n, 0, (38 + mbits + 7) / 8 * 8)) return rc;
+        T.mbase = mbase;
+        unsigned long long* d_small = (unsigned long long*)c->tg_small.p;
+        long long* d_toff = (long long*)c->tg_toff.p;
+        HIPCHK(c, hipMemsetAsync(d_small + 1, 0, 8, st));
+        hipLaunchKernelGGL(tg_size_kernel, dim3(tg_grid(n)), dim3(256), 0, st, T, (const unsigned long long*)d_keys, n, (long long)o->max_sites,
+                           (const unsigned long long*)c->tg_emitted.p, (int*)c->tg_size.p, d_small + 1);
+        hipLaunchKernelGGL(tg_emitted_kernel, dim3(tg_grid(n)), dim3(256), 0, st, (const unsigned long long*)d_keys, n, (unsigned long long*)c->tg_emitted.p);
+        launch_excl_scan(st, (const int*)c->tg_size.p, d_toff, n);
+        long long bytes = 0;
+        unsigned long long kept = 0;
+        HIPCHK(c, hipMemcpyAsync(&bytes, d_toff + n, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(&kept, d_small + 1, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        HIPCHK(c, hipGetLastError());
+        stats[0] += (long long)kept;
+        sec[1] += tg_now() - t;
+        t = tg_now();
+        // pieces of at most 1 GiB of text (at least one line each)
+        const long long piece = 1ll << 30;
+        for (long long i0 = 0; i0 < n;) {
+            long long base = 0;
+            HIPCHK(c, hipMemcpy(&base, d_toff + i0, 8, hipMemcpyDeviceToHost));
+            long long i1 = n, end = bytes;
+            if (bytes - base > piece) {                        // the last i1 in [i0 + 1, n) with toff[i1] - base <= piece
+                long long a = i0 + 1, z = n - 1;
+                while (a < z) {
+                    const long long md = (a + z + 1) >> 1;
+                    long long v = 0;
+                    HIPCHK(c, hipMemcpy(&v, d_toff + md, 8, hipMemcpyDeviceToHost));
+                    if (v - base <= piece) a = md; else z = md - 1;
+                }
+                i1 = a;
+                HIPCHK(c, hipMemcpy(&end, d_toff + i1, 8, hipMemcpyDeviceToHost));
+            }
+            const long long len = end - base;
+            if (len > 0) {
+                if (c->tg_text.ensure((size_t)len + 16)) return fail(c, -6, "device allocation failed (targets: text)");
+                hipLaunchKernelGGL(tg_emit_kernel, dim3(tg_grid(i1 - i0)), dim3(256), 0, st, T, (const unsigned long long*)d_keys, i0, i1, (const long long*)d_toff,
+                                   (char*)c->tg_text.p);
+                HIPCHK(c, hipStreamSynchronize(st));
+                HIPCHK(c, hipGetLastError());
+                if (c->h_text.size() < (size_t)len) c->h_text.resize((size_t)len);
+                HIPCHK(c, hipMemcpy(c->h_text.data(), c->tg_text.p, (size_t)len, hipMemcpyDeviceToHost));
+                if (int rc = (*sink)(c->h_text.data(), (size_t)len)) return rc;
+            }
+            i0 = i1;
+        }
+        sec[2] += tg_now() - t;
+        return 0;
+    }
+
+    void set_range(int mbase, int m, int smin, int smax) {
+        TgMirna& x = (*mi)[(size_t)(mbase + m)];
+        x.smin = smin;
+        x.smax = smax;
+    }
+
+    // one group of miRNAs [mbase, mbase + n)
+    int group(int mbase, int n) {
+        using namespace mirp;
+        hipStream_t st = c->stream;
+        const int smax = o->max_half_score;
+        const unsigned long long total = R.total;
+        group_n = n;
+        HIPCHK(c, hipMemsetAsync(c->tg_emitted.p, 0, 8 * (size_t)n, st));
+        for (int m = 0; m < n; m++) set_range(mbase, m, 0, smax);
+        long long hits = 0;
+        if (int rc = scan(0, mbase, 0, n, 0, total, &hits)) return rc;
+        if (hits <= cap) return finish(mbase, hits);
+        // overflow: hits per (miRNA, half-score), then passes of at most cap keys in output order
+        HIPCHK(c, hipMemsetAsync(c->tg_hist.p, 0, 8 * (size_t)n * TG_NHALF, st));
+        if (int rc = scan(1, mbase, 0, n, 0, total, &hits)) return rc;
+        std::vector<unsigned long long> hist((size_t)n * TG_NHALF);
+        HIPCHK(c, hipMemcpy(hist.data(), c->tg_hist.p, 8 * hist.size(), hipMemcpyDeviceToHost));
+        std::vector<int> lim(n, smax);               // -k: no line of a miRNA past the half-score at which its first k lines are reached
+        if (o->max_sites > 0)
+            for (int m = 0; m < n; m++) {
+                unsigned long long cum = 0;
+                for (int h = 0; h <= smax; h++) {
+                    cum += hist[(size_t)m * TG_NHALF + h];
+                    if (cum >= (unsigned long long)o->max_sites) { lim[m] = h; break; }
+                }
+            }
+        int ma = -1, ha = 0, mb = -1, hb = 0;        // the pending pass: (ma, ha) .. (mb, hb) in (miRNA, half-score) order
+        long long pend = 0;
+        auto flush = [&]() -> int {
+            if (ma < 0) return 0;
+            for (int m = ma; m <= mb; m++) set_range(mbase, m, m == ma ? ha : 0, m == mb ? hb : lim[m]);
+            long long got = 0;
+            if (int rc = scan(0, mbase, ma, mb + 1, 0, total, &got)) return rc;
+            if (got != pend) return fail(c, -5, "targets: a pass found a different number of sites than counted");
+            ma = -1;
+            pend = 0;
+            return finish(mbase, got);
+        };
+        for (int m = 0; m < n; m++)
+            for (int h = 0; h <= lim[m]; h++) {
+                const long long cnt = (long long)hist[(size_t)m * TG_NHALF + h];
+                if (cnt == 0) continue;
+                if (pend + cnt > cap)
+                    if (int rc = flush()) return rc;
+                if (cnt <= cap) {
+                    if (ma < 0) { ma = m; ha = h; }
+                    mb = m; hb = h;
+                    pend += cnt;
+                    continue;
+                }
+                // one (miRNA, half-score) over cap: ranges of offsets, halved until a range fits
+                set_range(mbase, m, h, h);
+                unsigned long long len = total;
+                for (unsigned long long p = 0; p < total;) {
+                    const unsigned long long p1 = std::min(total, p + len);
+                    long long got = 0;
+                    if (int rc = scan(0, mbase, m, m + 1, p, p1, &got)) return rc;
+                    if (got > cap) { len = std::max<unsigned long long>(1, len / 2); continue; }
+                    if (int rc = finish(mbase, got)) return rc;
+                    p = p1;
+                }
+            }
+        return flush();
+    }
+};
+
+}  // namespace
+
+// Uploads the packed targets and runs the search for every miRNA; the TSV lines (no header) go to `sink`.  pk: (total + 31) / 32 + 2 u64 words;
+// amb / cst: (total + 31) / 32 + 2 words; mcodes: 32 per miRNA.  stats = {sites written, passes}; seconds = {upload, scan, sort + cut,
+// emit + download + write}.
+int mirp_device_target_scan(mirp_ctx* c, const unsigned long long* pk, const unsigned* amb, const unsigned* cst, long long total,
+                            const std::vector<unsigned long long>& cstart, const std::string& tnames, const std::vector<long long>& tnoff,
+                            std::vector<TgMirna>& mi, const std::vector<unsigned char>& mcodes, const std::string& mnames, const std::vector<long long>& mnoff,
+                            const MirpTargetOpts& o, const std::function<int(const char*, size_t)>& sink, long long stats[2], double seconds[4]) {
+    using namespace mirp;
+    hipStream_t st = c->stream;
+    const long long n_pk = (total + 31) / 32 + 2, n_bm = (total + 31) / 32 + 2;
+    const long long n_mi = (long long)mi.size();
+    const long long cap = c->tg_cap > 0 ? c->tg_cap : (1ll << 26);
+    double t = tg_now();
+    if (c->tg_pk.ensure(8 * (size_t)n_pk) || c->tg_amb.ensure(4 * (size_t)n_bm) || c->tg_cst.ensure(4 * (size_t)n_bm) || c->tg_cstart.ensure(8 * cstart.size()) ||
+        c->tg_names.ensure(tnames.size() + 1) || c->tg_noff.ensure(8 * tnoff.size()) || c->tg_mcodes.ensure(mcodes.size() + 32) ||
+        c->tg_mnames.ensure(mnames.size() + 1) || c->tg_mnoff.ensure(8 * mnoff.size()) || c->tg_mi.ensure(sizeof(TgMirna) * TG_GROUP) ||
+        c->tg_emitted.ensure(8 * (size_t)TG_GROUP) || c->tg_hist.ensure(8 * (size_t)TG_GROUP * TG_NHALF) || c->tg_small.ensure(64) ||
+        c->tg_keys.ensure(8 * (size_t)cap) || c->tg_ktmp.ensure(8 * (size_t)cap) || c->tg_size.ensure(4 * (size_t)cap) || c->tg_toff.ensure(8 * (size_t)(cap + 1)))
+        return fail(c, -6, "device allocation failed (targets)");
+    HIPCHK(c, hipMemcpyAsync(c->tg_pk.p, pk, 8 * (size_t)n_pk, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->tg_amb.p, amb, 4 * (size_t)n_bm, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->tg_cst.p, cst, 4 * (size_t)n_bm, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->tg_cstart.p, cstart.data(), 8 * cstart.size(), hipMemcpyHostToDevice, st));
+    if (!tnames.empty()) HIPCHK(c, hipMemcpyAsync(c->tg_names.p, tnames.data(), tnames.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->tg_noff.p, tnoff.data(), 8 * tnoff.size(), hipMemcpyHostToDevice, st));
+    if (!mcodes.empty()) HIPCHK(c, hipMemcpyAsync(c->tg_mcodes.p, mcodes.data(), mcodes.size(), hipMemcpyHostToDevice, st));
+    if (!mnames.empty()) HIPCHK(c, hipMemcpyAsync(c->tg_mnames.p, mnames.data(), mnames.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->tg_mnoff.p, mnoff.data(), 8 * mnoff.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    seconds[0] = tg_now() - t;
+
+    TgRun run;
+    run.c = c;
+    run.R = TgRef{(const unsigned long long*)c->tg_pk.p, (const unsigned*)c->tg_amb.p, (const unsigned*)c->tg_cst.p, (unsigned long long)total};
+    run.T = TgText{(const unsigned long long*)c->tg_pk.p, (const unsigned char*)c->tg_mcodes.p, (const TgMirna*)c->tg_mi.p, (const char*)c->tg_mnames.p,
+                   (const long long*)c->tg_mnoff.p, (const char*)c->tg_names.p, (const long long*)c->tg_noff.p, (const unsigned long long*)c->tg_cstart.p,
+                   (int)cstart.size() - 1, 0};
+    run.o = &o;
+    run.mi = &mi;
+    run.sink = &sink;
+    run.cap = cap;
+    std::memset(run.stats, 0, sizeof run.stats);
+    std::memset(run.sec, 0, sizeof run.sec);
+    if (total > 0)
+        for (long long m0 = 0; m0 < n_mi; m0 += TG_GROUP)
+            if (int rc = run.group((int)m0, (int)std::min<long long>(TG_GROUP, n_mi - m0))) return rc;
+    for (int i = 0; i < 2; i++) stats[i] = run.stats[i];
+    for (int i = 0; i < 3; i++) seconds[1 + i] = run.sec[i];
+    return 0;
+}
