@@ -469,6 +469,22 @@ int mirp_target_scan(mirp_ctx* ctx, const char* mirna_path, const char* const* t
  * split into passes by (miRNA, score) and by ranges of offsets; lowered only to test that path. */
 int mirp_set_target_capacity(mirp_ctx* ctx, int64_t keys);
 
+/* Phased siRNA (PHAS) windows on the context's resident alignments (after any SAM ingest, or after mirp_load_alignments).  A record
+ * with len == length is a read of the unit (tid, strand, c), c = pos on the plus strand and pos + 2 on the minus strand (the 2-nt 3' overhang of a
+ * Dicer duplex); its abundance is the sum of the records' depths, and units below min_depth are dropped first.  Every distinct (tid, c) of a unit is
+ * an anchor x; its window [x, x + cycles * length) counts, over both strands, n units and k units with (c - x) % length == 0.  The window passes when
+ * k >= max(kmin[n], min_phased).  length 1..1024, cycles 1..64, min_phased >= 1, min_depth >= 1; records with pos < 0 are ignored. */
+typedef struct { int32_t length, cycles, min_phased, min_depth; } MirpPhaseOpts;
+/* One passing window: contig, anchor x (1-based), n, k, and the abundance of its phased units and of all its units. */
+typedef struct {
+    int32_t tid, n, k, reserved;
+    int64_t start, phased_reads, window_reads;
+} MirpPhaseWindow;
+/* kmin[0 .. 2 * cycles * length] is the caller's table (phasing.py computes it exactly from the hypergeometric p-value and alpha) and is only read.
+ * Out: *windows (release with mirp_free) holds the *n_windows passing windows in (tid, start) order; stats (optional) = {records of length `length`,
+ * units kept, anchors}.  Nothing resident changes. */
+int mirp_phase_scan(mirp_ctx* ctx, const MirpPhaseOpts* opts, const int32_t* kmin, MirpPhaseWindow** windows, int64_t* n_windows, int64_t stats[3]);
+
 #ifdef __cplusplus
 }
 #endif

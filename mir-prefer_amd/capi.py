@@ -8,7 +8,7 @@ import numpy as np
 
 from . import early
 from .early import LIB_PATH, FastaData, SamData
-ABI_VERSION = 11     # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
+ABI_VERSION = 12     # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
 
 
 class MirpError(RuntimeError):
@@ -38,6 +38,16 @@ class TargetOpts(C.Structure):
 
 
 TARGET_STATS = ("mirnas", "targets", "bases", "evaluations", "sites", "passes")
+
+
+class PhaseOpts(C.Structure):
+    """MirpPhaseOpts of include/mirprefer.h."""
+    _fields_ = [(f, C.c_int32) for f in ("length", "cycles", "min_phased", "min_depth")]
+
+
+# MirpPhaseWindow of include/mirprefer.h: one passing window of mirp_phase_scan
+PHASE_WINDOW_DTYPE = np.dtype([("tid", "<i4"), ("n", "<i4"), ("k", "<i4"), ("reserved", "<i4"), ("start", "<i8"), ("phased_reads", "<i8"),
+                               ("window_reads", "<i8")])
 
 
 def report_readmapping(loci, ss_list, alns, contig_arrays, sample_names, counts0):
@@ -367,6 +377,8 @@ def load_library():
     lib.mirp_target_scan.restype = C.c_int
     lib.mirp_set_target_capacity.argtypes = [vp, C.c_int64]
     lib.mirp_set_target_capacity.restype = C.c_int
+    lib.mirp_phase_scan.argtypes = [vp, C.POINTER(PhaseOpts), vp, C.POINTER(vp), i64p, i64p]
+    lib.mirp_phase_scan.restype = C.c_int
     lib.mirp_dist_unique_id.argtypes = [vp]
     lib.mirp_dist_unique_id.restype = C.c_int
     lib.mirp_dist_init.argtypes = [vp, vp, C.c_int32, C.c_int32]
@@ -484,6 +496,20 @@ class Context:
     def set_target_capacity(self, keys):
         """Sites one target_scan pass holds on the device (0 = the default, 2^26; at least 2): lowered only to test the overflow path."""
         self._check(self.lib.mirp_set_target_capacity(self.h, int(keys)), "mirp_set_target_capacity")
+
+    def phase_scan(self, length, cycles, kmin, min_phased=3, min_depth=1):
+        """Phased siRNA windows on this context's resident alignments (mirp_phase_scan).  kmin: the int32 table of the smallest
+        phased count that passes at each n = 0 .. 2 * cycles * length.  -> (PHASE_WINDOW_DTYPE array of the passing windows in (tid, start) order,
+        {records, units, anchors})."""
+        o = PhaseOpts()
+        o.length, o.cycles, o.min_phased, o.min_depth = int(length), int(cycles), int(min_phased), int(min_depth)
+        km = np.ascontiguousarray(kmin, dtype=np.int32)
+        if len(km) != 2 * int(cycles) * int(length) + 1:
+            raise ValueError("phase_scan: kmin needs 2 * cycles * length + 1 entries")
+        ptr, nw = C.c_void_p(), C.c_int64()
+        st = (C.c_int64 * 3)()
+        self._check(self.lib.mirp_phase_scan(self.h, C.byref(o), km.ctypes.data, C.byref(ptr), C.byref(nw), st), "mirp_phase_scan")
+        return _copy_out(self.lib, ptr, PHASE_WINDOW_DTYPE, nw.value), dict(zip(("records", "units", "anchors"), list(st)))
 
     def fold_batch(self, seqs, span, max_lines=96):
         """RNALfold -L replacement. seqs: list of str/bytes. Returns a list (per sequence) of
