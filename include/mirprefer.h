@@ -485,6 +485,29 @@ typedef struct {
  * units kept, anchors}.  Nothing resident changes. */
 int mirp_phase_scan(mirp_ctx* ctx, const MirpPhaseOpts* opts, const int32_t* kmin, MirpPhaseWindow** windows, int64_t* n_windows, int64_t stats[3]);
 
+/* Small-RNA clusters on the context's resident alignments (after any SAM ingest, or after mirp_load_alignments).  A record spans
+ * [pos, pos + len - 1]; coverage c(p) = the sum of the depths of the records whose span holds p, for p in 1..contig_len[tid] only (64-bit).
+ * Islands are the maximal runs of c(p) >= threshold; islands of one contig whose gap (next start - end - 1) is <= pad merge into a cluster.
+ * A record counts in the first cluster, in coordinate order, that its span overlaps, and in no other.  threshold >= 1, pad 0..10^6, n_samples
+ * 1..255 (a counted record with sample >= n_samples is refused); records of a tid >= n_contigs cover nothing. */
+typedef struct {
+    int64_t threshold, pad;
+    const int64_t* contig_len;      /* LN of contigs 0 .. n_contigs - 1 */
+    int32_t n_contigs, n_samples;
+} MirpClusterOpts;
+/* One cluster: contig, [start, end] (1-based), depth sums, distinct (pos, strand, len) placements, the major placement (largest depth sum; ties
+ * to the smallest pos, then + before -, then the shorter len; strand 0 '+', 1 '-') and the depth per size class. */
+typedef struct {
+    int32_t tid, major_strand, major_len, reserved;
+    int64_t start, end, reads, plus_reads, placements, major_pos, major_reads;
+    int64_t sizes[7];               /* len < 20, 20, 21, 22, 23, 24, > 24 */
+} MirpCluster;
+/* Out: *clusters (release with mirp_free) holds the *n_clusters clusters in (tid, start) order; *sample_counts (release with mirp_free) the depth
+ * per (cluster, sample), n_clusters x n_samples, row-major; stats (optional) = {records, total depth, islands, clusters, records counted in a
+ * cluster}.  Nothing resident changes. */
+int mirp_cluster_scan(mirp_ctx* ctx, const MirpClusterOpts* opts, MirpCluster** clusters, int64_t* n_clusters, int64_t** sample_counts,
+                      int64_t stats[5]);
+
 #ifdef __cplusplus
 }
 #endif

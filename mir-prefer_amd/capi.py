@@ -8,7 +8,7 @@ import numpy as np
 
 from . import early
 from .early import LIB_PATH, FastaData, SamData
-ABI_VERSION = 12     # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
+ABI_VERSION = 13     # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
 
 
 class MirpError(RuntimeError):
@@ -48,6 +48,18 @@ class PhaseOpts(C.Structure):
 # MirpPhaseWindow of include/mirprefer.h: one passing window of mirp_phase_scan
 PHASE_WINDOW_DTYPE = np.dtype([("tid", "<i4"), ("n", "<i4"), ("k", "<i4"), ("reserved", "<i4"), ("start", "<i8"), ("phased_reads", "<i8"),
                                ("window_reads", "<i8")])
+
+
+class ClusterOpts(C.Structure):
+    """MirpClusterOpts of include/mirprefer.h."""
+    _fields_ = [("threshold", C.c_int64), ("pad", C.c_int64), ("contig_len", C.c_void_p), ("n_contigs", C.c_int32), ("n_samples", C.c_int32)]
+
+
+# MirpCluster of include/mirprefer.h: one cluster of mirp_cluster_scan; sizes = depth of len < 20, 20, 21, 22, 23, 24, > 24
+CLUSTER_DTYPE = np.dtype([("tid", "<i4"), ("major_strand", "<i4"), ("major_len", "<i4"), ("reserved", "<i4"), ("start", "<i8"), ("end", "<i8"),
+                          ("reads", "<i8"), ("plus_reads", "<i8"), ("placements", "<i8"), ("major_pos", "<i8"), ("major_reads", "<i8"),
+                          ("sizes", "<i8", (7,))])
+CLUSTER_STATS = ("records", "total", "islands", "clusters", "assigned")
 
 
 def report_readmapping(loci, ss_list, alns, contig_arrays, sample_names, counts0):
@@ -379,6 +391,8 @@ def load_library():
     lib.mirp_set_target_capacity.restype = C.c_int
     lib.mirp_phase_scan.argtypes = [vp, C.POINTER(PhaseOpts), vp, C.POINTER(vp), i64p, i64p]
     lib.mirp_phase_scan.restype = C.c_int
+    lib.mirp_cluster_scan.argtypes = [vp, C.POINTER(ClusterOpts), C.POINTER(vp), i64p, C.POINTER(vp), i64p]
+    lib.mirp_cluster_scan.restype = C.c_int
     lib.mirp_dist_unique_id.argtypes = [vp]
     lib.mirp_dist_unique_id.restype = C.c_int
     lib.mirp_dist_init.argtypes = [vp, vp, C.c_int32, C.c_int32]
@@ -510,6 +524,20 @@ class Context:
         st = (C.c_int64 * 3)()
         self._check(self.lib.mirp_phase_scan(self.h, C.byref(o), km.ctypes.data, C.byref(ptr), C.byref(nw), st), "mirp_phase_scan")
         return _copy_out(self.lib, ptr, PHASE_WINDOW_DTYPE, nw.value), dict(zip(("records", "units", "anchors"), list(st)))
+
+    def cluster_scan(self, threshold, pad, contig_lens, n_samples):
+        """Small-RNA clusters on this context's resident alignments (mirp_cluster_scan; DESIGN.md §16).  threshold: the integer coverage T;
+        contig_lens: LN per contig.  -> (CLUSTER_DTYPE array in (tid, start) order, int64 [clusters, n_samples] depth per sample,
+        {records, total, islands, clusters, assigned})."""
+        lens = np.ascontiguousarray(contig_lens, dtype=np.int64)
+        o = ClusterOpts()
+        o.threshold, o.pad, o.contig_len, o.n_contigs, o.n_samples = int(threshold), int(pad), lens.ctypes.data, len(lens), int(n_samples)
+        ptr, cnt, nc = C.c_void_p(), C.c_void_p(), C.c_int64()
+        st = (C.c_int64 * 5)()
+        self._check(self.lib.mirp_cluster_scan(self.h, C.byref(o), C.byref(ptr), C.byref(nc), C.byref(cnt), st), "mirp_cluster_scan")
+        clusters = _copy_out(self.lib, ptr, CLUSTER_DTYPE, nc.value)
+        counts = _copy_out(self.lib, cnt, np.dtype("<i8"), nc.value * int(n_samples)).reshape(nc.value, int(n_samples))
+        return clusters, counts, dict(zip(CLUSTER_STATS, list(st)))
 
     def fold_batch(self, seqs, span, max_lines=96):
         """RNALfold -L replacement. seqs: list of str/bytes. Returns a list (per sequence) of
