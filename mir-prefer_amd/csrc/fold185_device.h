@@ -4,6 +4,7 @@
 // (int32 tables of the generic kernel, or the 16-bit slabs written by the LDS-resident fill kernel).  Behaviour: SURVEY.md Appendix B (d1).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "fold_device.h"
 #include "mirp_internal.h"
 
@@ -44,10 +45,26 @@ struct GTab185 {   // int32 tables in a global workspace (fold185_kernel)
     __device__ __forceinline__ int TB(int i, int j) const { const int d = j - i; return !tb ? -1 : (d <= V_TURN || d > M || i < 1 || j > n) ? 0 : (int)tb[(size_t)d * ld + i]; }
 };
 
+// RNALfold 1.8.5 reads `_ A C G U X K I` (any case; T as U, every other letter as _) as pair codes 0..7 (ViennaRNA 1.8.5 pair_mat.h).  Pair types:
+// those of pair_type on 0..4, and X-K = 2 (as G-C), K-X = 1, A-I = I-U = 5 (as A-U), I-A = U-I = 6 (as U-A).  Energies see alias codes instead
+// (pair_alias185: X as G, K as C, I as 0).
+__device__ __forceinline__ int pair_code185(unsigned char ch) {
+    return ch == 'A' ? 1 : ch == 'C' ? 2 : ch == 'G' ? 3 : ch == 'U' ? 4 : ch == 'X' ? 5 : ch == 'K' ? 6 : ch == 'I' ? 7 : 0;
+}
+__device__ __forceinline__ int pair_alias185(int code) { return code < 5 ? code : code == 5 ? 3 : code == 6 ? 2 : 0; }
+__device__ __forceinline__ int pair_type185(int a, int b) {
+    // the 8 x 8 matrix, 4 bits an entry (index a * 8 + b), 16 entries a word
+    const int k = a * 8 + b;
+    const unsigned long long w = k < 32 ? (k < 16 ? 0x5005000000000000ull : 0x0003020000001000ull) : (k < 48 ? 0x0200000060004060ull : 0x0005006000100000ull);
+    return (int)((w >> (4 * (k & 15))) & 15ull);
+}
+
 template <class PT>
 struct Ctx {
     const PT* __restrict__ P;
-    const unsigned char* S;     // LDS 0..n+1
+    const unsigned char* S;     // LDS 0..n+1: the codes every energy term reads (0..4; X as G, K as C, I as 0)
+    const unsigned char* Sp = nullptr;   // LDS 0..n+1: the pair codes 0..7 of pair_type185; read by the generic kernel (PT = FoldParams185) only: the
+                                         // LDS-resident path hands windows with X K I back and pairs from S
     const short* tetra;         // LDS: tetraloop bonus of the hairpin closed at i (0 = none)
     const int* f3;              // LDS
     int n, M;
@@ -62,7 +79,9 @@ template <class PT>
 __device__ __forceinline__ int ptype(const Ctx<PT>& X, int i, int j) {
     const int d = j - i;
     if (d <= V_TURN || d > X.M - 1 || i < 1 || j > X.n) return 0;
-    return pair_type(X.S[i], X.S[j]);
+    // the generic kernel (its Ctx<FoldParams185> sets Sp) pairs by the 1.8.5 codes; the LDS-resident path (Ctx<FoldParams>, Sp unset) never sees X K I
+    if constexpr (std::is_same<PT, FoldParams185>::value) return pair_type185(X.Sp[i], X.Sp[j]);
+    else return pair_type(X.S[i], X.S[j]);
 }
 template <class PT>
 __device__ __forceinline__ int AU(const Ctx<PT>& X, int t) { return t > 2 ? X.P->TerminalAU : 0; }

@@ -40,12 +40,12 @@ __host__ __device__ inline size_t fold185_table_ints(int n_cap, int span) {
 __host__ __device__ inline size_t fold185_lds_bytes_base(int n_cap, int max_lines) {
     const size_t nc = (size_t)n_cap + 8;
     size_t b = sizeof(int) * (nc + 8 + 2 * (size_t)max_lines + (V_NT / 64) * 3 * V_BT_STACK + V_NT / 64 + 8);
-    b += sizeof(short) * nc + 2 * nc + (V_NT / 64) * (nc + 8);
+    b += sizeof(short) * nc + 3 * nc + (V_NT / 64) * (nc + 8);
     return (b + 15) & ~(size_t)15;
 }
 
-// the fill kernel's share of the base carve-up: tetraloop bonuses and the sequence codes
-__host__ __device__ inline size_t fold185_lds_bytes_base_fill(int n_cap) { return ((size_t)4 * ((size_t)n_cap + 8) + 15) & ~(size_t)15; }
+// the fill kernel's share of the base carve-up: tetraloop bonuses, the sequence and its two codes
+__host__ __device__ inline size_t fold185_lds_bytes_base_fill(int n_cap) { return ((size_t)5 * ((size_t)n_cap + 8) + 15) & ~(size_t)15; }
 
 // PHASE 1 = fill, PHASE 2 = exterior sweep + backtracks, launched back to back over batches of `grid` windows (slot = blockIdx.x), as fold_generic_kernel:
 // the fill needs half the registers of the epilogue.
@@ -59,12 +59,13 @@ __global__ void __launch_bounds__(V_NT, PHASE == 1 ? V_FILL_WAVES : V_EPI_WAVES)
     // (the two kernels have their own layouts, as fold_generic_kernel: the fill needs the sequence codes and the tetraloop bonuses of the base carve-up, nothing else)
     int *f3 = nullptr, *starts = nullptr, *lens = nullptr, *btstk = nullptr, *red = nullptr;
     short* tetra;
-    unsigned char *S, *seq;
+    unsigned char *S, *seq, *Sp;
     char* btbuf = nullptr;
     if constexpr (PHASE == 1) {
         tetra = (short*)smem;                              // nc
         S = (unsigned char*)(tetra + nc);                  // nc
         seq = S + nc;                                      // nc
+        Sp = seq + nc;                                     // nc
     } else {
         f3 = (int*)smem;                                   // nc + 8
         starts = f3 + nc + 8;                              // max_lines
@@ -74,7 +75,8 @@ __global__ void __launch_bounds__(V_NT, PHASE == 1 ? V_FILL_WAVES : V_EPI_WAVES)
         tetra = (short*)(red + V_NT / 64 + 8);             // nc
         S = (unsigned char*)(tetra + nc);                  // nc
         seq = S + nc;                                      // nc
-        btbuf = (char*)(seq + nc);                         // (NT/64) * (nc + 8)
+        Sp = seq + nc;                                     // nc
+        btbuf = (char*)(Sp + nc);                          // (NT/64) * (nc + 8)
     }
     const size_t base_bytes = PHASE == 1 ? fold185_lds_bytes_base_fill(n_cap) : fold185_lds_bytes_base(n_cap, max_lines);
     int* pcnt = (int*)(smem + base_bytes);       // nc: split candidates of every column so far (| V_PL_FLAG: one of its first four does not fit the packed LDS copy)
@@ -114,7 +116,9 @@ __global__ void __launch_bounds__(V_NT, PHASE == 1 ? V_FILL_WAVES : V_EPI_WAVES)
                 if (ch == 'T') ch = 'U';
             }
             seq[x] = ch;
-            S[x] = ch == 'A' ? 1 : ch == 'C' ? 2 : ch == 'G' ? 3 : ch == 'U' ? 4 : 0;
+            const int code = pair_code185(ch);             // X K I pair by their own codes, and read as G / C / _ in every energy term
+            Sp[x] = (unsigned char)code;
+            S[x] = (unsigned char)pair_alias185(code);
         }
         if constexpr (PHASE == 2) for (int x = tid; x < nc + 8; x += V_NT) f3[x] = 0;
         __syncthreads();
@@ -146,8 +150,8 @@ __global__ void __launch_bounds__(V_NT, PHASE == 1 ? V_FILL_WAVES : V_EPI_WAVES)
         T.tb = tbtab;
         if constexpr (PHASE == 1) for (int x = tid; x <= n + 1; x += V_NT) pcnt[x] = 0;
         __syncthreads();
-        Ctx<FoldParams185> X;
-        X.P = P; X.S = S; X.tetra = tetra; X.f3 = f3; X.n = n; X.M = M;
+        Ctx<FoldParams185> X;          // (ptype of a Ctx<FoldParams185> reads Sp: every Ctx<FoldParams185> must set it)
+        X.P = P; X.S = S; X.Sp = Sp; X.tetra = tetra; X.f3 = f3; X.n = n; X.M = M;
 
         // ---- anti-diagonal wavefront fill; cells at distance M hold c = INF but a finite fML
         const int Dmax = M < n - 1 ? M : n - 1;
@@ -297,7 +301,8 @@ __global__ void __launch_bounds__(V_NT, PHASE == 1 ? V_FILL_WAVES : V_EPI_WAVES)
                         const v_int2a w5b = *reinterpret_cast<const v_int2a*>(wr[5] + 4);
                         const v_int4a w6 = *reinterpret_cast<const v_int4a*>(wr[6]), w6b = *reinterpret_cast<const v_int4a*>(wr[6] + 3);
                         // reversed type of the inner pair (p, q) = (i + 1 + n1, j - 1 - n2), 0 = no pair
-                        auto t2of = [&](const int n1, const int n2) { return pair_type(sJ[1 + n2], sI[1 + n1]); };
+                        const int pI[3] = {Sp[i + 1], Sp[i + 2], Sp[i + 3]}, pJ[3] = {Sp[j - 1], Sp[j - 2], Sp[j - 3]};      // pair codes of S[i + 1 + x], S[j - 1 - x]
+                        auto t2of = [&](const int n1, const int n2) { return pair_type185(pJ[n2], pI[n1]); };
                         const int t00 = t2of(0, 0), t01 = t2of(0, 1), t10 = t2of(1, 0), t11 = t2of(1, 1), t12 = t2of(1, 2), t21 = t2of(2, 1), t22 = t2of(2, 2);
                         // the big tables (sp1 = S[p - 1] = sI[n1], sq1 = S[q + 1] = sJ[n2]); a missing pair reads row 0 and is masked below
                         const int r11 = loopE(X, 1, 1, type, t11, si1, sj1, sI[1], sJ[1]);

@@ -95,7 +95,7 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
     using list_t = unsigned;
     list_t* list = (list_t*)(smem + LY.list);
     LdsTables& T = *(LdsTables*)(smem + LY.tabs);
-    int* misc = (int*)(smem + LY.misc);                             // 0: next window, 1: overflow flag, 2: candidate pool overflow, 3: candidates in the pool, 16..21: list lengths
+    int* misc = (int*)(smem + LY.misc);                             // 0: next window, 1: overflow flag, 2: candidate pool overflow, 3: candidates in the pool, 4: X K I in the window (vienna-1.8.5), 16..21: list lengths
     int* lcnt = misc + 16;                                          // [6]: entries in the list of diagonal d at d % 6
     int* rbt = misc + 48;                                           // [ARCH_RB]: row-block offsets of the window's archive slabs (arch_rowblk_off)
     const int tid = threadIdx.x, lane = tid & 63;
@@ -132,6 +132,7 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
     if (tid < 40) { T.dangle5[tid] = (short)P->dangle5[tid / 5][tid % 5]; T.dangle3[tid] = (short)P->dangle3[tid / 5][tid % 5]; }
     if (tid < 25) T.rt2[tid] = (unsigned char)rtype_of(pair_type(tid / 5, tid % 5));
     if (tid == 0) { T.ML_closing = (short)P->ML_closing; T.ML_intern = (short)P->ML_intern; T.TerminalAU = (short)P->TerminalAU; T.ninio = (short)P->ninio; T.MAX_NINIO = (short)P->MAX_NINIO; }
+    if constexpr (MODEL != 0) if (tid == 0) misc[4] = 0;      // the window's X K I flag (below)
     __syncthreads();
 
     const int n_todo = todo_count ? (int)*todo_count : n_work;      // second pass: the windows the sparse pass handed over
@@ -161,7 +162,19 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
         short* fml_out = carch + slab_shorts;
         unsigned short* tb_out = reinterpret_cast<unsigned short*>(carch + 2 * slab_shorts);
         if (dbg_cycles && tid == 0) t0 = clock64();
-        if (n < 1 || n > LCAP - 2) {   // wave-uniform: empty window, or too long for this kernel (-> generic kernel)
+        // vienna-1.8.5 reads X K I (any case) as bases with pair types of their own, which only the generic kernel knows (fold185_device.h,
+        // pair_type185): a window that holds one is handed back like a long one.  The flag is misc[4] (zero between windows; a workgroup
+        // reduction of the runtime would take static LDS this kernel has no room for)
+        int xki = 0;
+        if constexpr (MODEL != 0) {
+            if (n >= 1 && n <= LCAP - 2)
+                for (int x = tid; x < n; x += LNT) { const unsigned u = seqs[o0 + x] & 0xdfu; if (u == 'X' || u == 'K' || u == 'I') misc[4] = 1; }
+            __syncthreads();
+            xki = misc[4];
+            __syncthreads();
+            if (tid == 0) misc[4] = 0;      // (the next write comes after the next window's barriers)
+        }
+        if (n < 1 || n > LCAP - 2 || xki) {   // wave-uniform: empty window, too long for this kernel, or X K I under vienna-1.8.5 (-> generic kernel)
             if (tid == 0) {
                 out_nlines[win] = 0; out_mfe[win] = 0; out_status[win] = 0; win_state[win] = 0;
                 if (n >= 1) { unsigned int k = atomicAdd(fallback_count, 1u); fallback_list[k] = win_base + win; }

@@ -356,6 +356,9 @@ extern "C" int mirp_report_readmapping(const int32_t* loci, int64_t n_loci, cons
     std::vector<int> bad((size_t)nt, 0);
     std::vector<std::thread> th;
     auto up = [](uint8_t ch) -> char { char c = (char)ch; if (c >= 'a' && c <= 'z') c -= 32; return c; };
+    // a read's SEQ as `samtools view` prints it back from BAM (MP:2721, sp[9]): upper case, and every letter outside the 4-bit BAM alphabet
+    // "=ACMGRSVTWYHKDBN" (U, X, I, E, ...) as N
+    auto bam_letter = [&](uint8_t ch) -> char { const char c = up(ch); return (c && std::strchr("=ACMGRSVTWYHKDBN", c)) ? c : 'N'; };
     auto comp = [](char c) -> char { switch (c) { case 'A': return 'U'; case 'T': return 'A'; case 'G': return 'C'; case 'C': return 'G'; case 'U': return 'A'; default: return c; } };
     for (int t = 0; t < nt; t++)
         th.emplace_back([&, t] {
@@ -397,7 +400,7 @@ extern "C" int mirp_report_readmapping(const int32_t* loci, int64_t n_loci, cons
                         const int rl = r.len, sp = r.pos;
                         const char pad = (sp == ms && rl == mlen) ? 'm' : (sp == ss0 && rl == slen) ? 's' : '.';
                         line.assign((size_t)(sp - fs), pad);
-                        for (int y = 0; y < rl; y++) line.push_back(sp - 1 + y < contig_len[tid] ? up(g[sp - 1 + y]) : pad);
+                        for (int y = 0; y < rl; y++) line.push_back(sp - 1 + y < contig_len[tid] ? bam_letter(g[sp - 1 + y]) : pad);
                         if (line.size() < pre.size()) line.append(pre.size() - line.size(), pad);
                         if (minus) {      // get_reverse_complement, then U -> T (MP:2946-2947): pads are not in the table and stay
                             std::string r2(line.rbegin(), line.rend());

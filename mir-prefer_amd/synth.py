@@ -85,7 +85,9 @@ class Dataset:
         return paths
 
 
-def make_dataset(contig_lens, n_loci, n_samples=1, seed=2, contig_names=None, hairpin_frac=0.4, edge_cases=False):
+def make_dataset(contig_lens, n_loci, n_samples=1, seed=2, contig_names=None, hairpin_frac=0.4, edge_cases=False, alphabet="acgtn"):
+    """alphabet="acgtn" (the default, whose seeds never move) writes A C G T plus the edge cases' soft-masked and N stretches; alphabet="all" then
+    plants letters outside ACGTN around the loci (_plant_alphabet, from a generator of its own)."""
     rng = np.random.RandomState(seed)
     ncont = len(contig_lens)
     names = contig_names or ["Chr%d" % (i + 1) for i in range(ncont)]
@@ -167,9 +169,36 @@ def make_dataset(contig_lens, n_loci, n_samples=1, seed=2, contig_names=None, ha
                     add_read(tid, g0 + int(rng.randint(0, width)), rl, int(rng.randint(0, 2)), int(rng.randint(1, 61)))
     if edge_cases:
         _plant_edge_cases(rng, contigs, add_read)
+    if alphabet == "all":
+        _plant_alphabet(np.random.RandomState(seed + 7919), contigs, planted)
+    elif alphabet != "acgtn":
+        raise ValueError("alphabet must be 'acgtn' or 'all'")
     alns = np.array(recs, dtype=[("tid", "<i4"), ("pos", "<i4"), ("depth", "<u4"), ("len", "<u2"), ("strand", "u1"), ("sample", "u1")])
     alns = alns.astype(ALN_DTYPE)
     return Dataset(list(zip(names, contigs)), sample_names, alns, planted)
+
+
+def _plant_alphabet(rng, contigs, planted):
+    """Letters outside ACGTN inside the windows of the loci: IUPAC codes and X K I in both cases scattered around some loci, soft-masked runs
+    over others, and X-K pairs across the stem of some hairpins (they pair under RNALfold 1.8.5 only)."""
+    letters = np.frombuffer(b"RYKMSWBDHVXKIrykmswbdhvxki", dtype=np.uint8)
+    for tid, s1, e1, _strand in planted:
+        seq = contigs[tid]
+        g0, H = s1 - 1, e1 - s1
+        lo, hi = max(0, g0 - 150), min(len(seq), g0 + H + 150)
+        u = rng.rand()
+        if u < 0.35:            # a few scattered letters
+            for p in rng.randint(lo, hi, size=int(rng.randint(1, 6))):
+                seq[p] = letters[rng.randint(0, len(letters))]
+        elif u < 0.55:          # a soft-masked run
+            a = int(rng.randint(lo, hi))
+            b = min(hi, a + int(rng.randint(10, 80)))
+            seg = seq[a:b]
+            seq[a:b] = np.where((seg >= 65) & (seg <= 90), seg + 32, seg)
+        elif u < 0.8:           # X-K pairs across the stem: position g0 + i pairs with g0 + H - 1 - i
+            for i in rng.randint(2, 20, size=int(rng.randint(1, 4))):
+                x, k = (b"X", b"K") if rng.rand() < 0.5 else (b"K", b"X")
+                seq[g0 + i], seq[g0 + H - 1 - i] = x[0], k[0]
 
 
 def _plant_edge_cases(rng, contigs, add_read):

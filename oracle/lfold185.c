@@ -24,8 +24,12 @@
 #define MAXLOOP 30
 #define INF 1000000
 
-static const int PAIR[5][5] = {
-    {0, 0, 0, 0, 0}, {0, 0, 0, 0, 5}, {0, 0, 0, 1, 0}, {0, 0, 2, 0, 3}, {0, 6, 0, 4, 0}};
+/* RNALfold 1.8.5 reads `_ A C G U X K I` as codes 0 .. 7 (T as U; any other letter as 0).  The pair type comes from these codes: X-K pair as G-C,
+ * I pairs with A and U (as U and as A).  Every loop, mismatch and dangle energy sees the alias code instead: X as G, K as C, I as 0. */
+static const int PAIR[8][8] = {
+    {0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 5, 0, 0, 5}, {0, 0, 0, 1, 0, 0, 0, 0}, {0, 0, 2, 0, 3, 0, 0, 0},
+    {0, 6, 0, 4, 0, 0, 0, 6}, {0, 0, 0, 0, 0, 0, 2, 0}, {0, 0, 0, 0, 0, 1, 0, 0}, {0, 6, 0, 0, 5, 0, 0, 0}};
+static const int ALIAS[8] = {0, 1, 2, 3, 4, 3, 2, 0};
 static const int RTYPE[8] = {0, 2, 1, 4, 3, 6, 5, 7};
 
 static inline int imin(int a, int b) { return a < b ? a : b; }
@@ -296,11 +300,13 @@ int oracle_lfold185(const char *seq_in, int n, int span, OracleFoldResult *R) {
     F.n = n; F.M = span;
     F.seq = (char *)calloc(n + 16, 1);
     F.S = (int *)calloc(n + 2, sizeof(int));
+    int *code = (int *)calloc(n + 2, sizeof(int));   /* pair codes; F.S holds the alias codes the energies read */
     for (int i = 1; i <= n; i++) {
         char ch = (char)toupper((unsigned char)seq_in[i - 1]);
         if (ch == 'T') ch = 'U';
         F.seq[i] = ch;
-        F.S[i] = ch == 'A' ? 1 : ch == 'C' ? 2 : ch == 'G' ? 3 : ch == 'U' ? 4 : 0;
+        code[i] = ch == 'A' ? 1 : ch == 'C' ? 2 : ch == 'G' ? 3 : ch == 'U' ? 4 : ch == 'X' ? 5 : ch == 'K' ? 6 : ch == 'I' ? 7 : 0;
+        F.S[i] = ALIAS[code[i]];
     }
     F.S[0] = F.S[n]; F.S[n + 1] = F.S[1];
     size_t cells = (size_t)(n + 3) * (span + 2);
@@ -310,7 +316,8 @@ int oracle_lfold185(const char *seq_in, int n, int span, OracleFoldResult *R) {
     F.f3 = (int *)calloc(n + span + 8, sizeof(int));
     for (size_t x = 0; x < cells; x++) F.c[x] = F.fML[x] = INF;
     for (int i = 1; i <= n; i++)
-        for (int j = i + TURN + 1; j <= n && j - i <= span - 1; j++) F.pt[IDX(&F, i, j)] = (unsigned char)PAIR[F.S[i]][F.S[j]];
+        for (int j = i + TURN + 1; j <= n && j - i <= span - 1; j++) F.pt[IDX(&F, i, j)] = (unsigned char)PAIR[code[i]][code[j]];
+    free(code);
     fill(&F);
 
     char *prev = (char *)malloc(n + span + 16), *cur = (char *)malloc(n + span + 16);

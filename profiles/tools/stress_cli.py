@@ -1,6 +1,7 @@
 """Dev tool: differential stress of the lean `pipeline` run (early device open, no stage artefacts, streamed fold / filter / reports with a random number of chunks)
 against the stage-by-stage `-k pipeline` run of the same inputs: every output file byte for byte, on random datasets (contig counts / name orders, 1 .. 40 samples,
-both fold models, the overhang / no-star options).  usage (GPU box): python profiles/tools/stress_cli.py [n_datasets] [seed]"""
+both fold models, the overhang / no-star options).  usage (GPU box): python profiles/tools/stress_cli.py [n_datasets] [seed] [acgtn|all]
+(`all`: synth plants IUPAC letters, X K I, soft-masked runs and X-K stem pairs around the loci)"""
 import filecmp, os, random, shutil, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -14,7 +15,8 @@ for k in range(n_sets):
     lens = [r.randint(30000, 400000) for _ in range(nc)]
     ns = r.choice([1, 2, 3, 5, 17, 40])
     loci = r.randint(20, 500)
-    ds = synth.make_dataset(lens, loci, n_samples=ns, seed=r.randint(1, 10 ** 6), contig_names=names, edge_cases=True)
+    ds = synth.make_dataset(lens, loci, n_samples=ns, seed=r.randint(1, 10 ** 6), contig_names=names, edge_cases=True,
+                            alphabet=sys.argv[3] if len(sys.argv) > 3 else "acgtn")
     tmp = tempfile.mkdtemp(prefix="stresscli_")
     try:
         sams = ds.write_sams(tmp, sq_order=r.sample(range(nc), nc))

@@ -1,6 +1,8 @@
 """Dev tool: large differential stress of the HIP fold against the CPU oracle (structure lines bit-exact), with sequence families that
 provoke energy ties (repeats, low complexity, GC-only, long N runs).  Oracle runs in a process pool.
-usage: python profiles/tools/stress_fold.py [n_windows] [seed] [vienna-2.1.2|vienna-1.8.5]"""
+With `all` as the fourth argument every window comes from seqgen.alphabet_window (IUPAC codes, X K I, `_`, `-`, case, T), the letters the
+oracle is pinned on by tests/golden/fold_alphabet.json.gz.
+usage: python profiles/tools/stress_fold.py [n_windows] [seed] [vienna-2.1.2|vienna-1.8.5] [acgun|all]"""
 import os, random, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -39,8 +41,9 @@ def main():
     nw = int(sys.argv[1]) if len(sys.argv) > 1 else 4000
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     model = sys.argv[3] if len(sys.argv) > 3 else "vienna-2.1.2"
+    alphabet = sys.argv[4] if len(sys.argv) > 4 else "acgun"
     r = random.Random(seed)
-    seqs = [family(r, i % 5) for i in range(nw)]
+    seqs = [seqgen.alphabet_window(r, 40, 350) if alphabet == "all" else family(r, i % 5) for i in range(nw)]
     from tests import oracle_binding
     oracle_binding.load()
     from mir_prefer_amd import capi

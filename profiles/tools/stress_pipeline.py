@@ -1,6 +1,7 @@
 """Dev tool: end-to-end differential stress (candidate -> fold -> predict) of the device pipeline against the CPU oracle on a larger
 synthetic dataset than the test-suite uses; the oracle folds run in a process pool.
-usage: python profiles/tools/stress_pipeline.py [n_loci] [seed] [n_samples] [vienna-2.1.2|vienna-1.8.5]"""
+usage: python profiles/tools/stress_pipeline.py [n_loci] [seed] [n_samples] [vienna-2.1.2|vienna-1.8.5] [acgtn|all]
+(`all`: synth plants IUPAC letters, X K I, soft-masked runs and X-K stem pairs around the loci)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -24,7 +25,8 @@ def main():
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 31
     ns = int(sys.argv[3]) if len(sys.argv) > 3 else 2
     model = sys.argv[4] if len(sys.argv) > 4 else "vienna-2.1.2"
-    ds = synth.make_dataset([2500000, 1500000, 2000000], n_loci, n_samples=ns, seed=seed, contig_names=["c9", "c10", "c1"], edge_cases=True)
+    alphabet = sys.argv[5] if len(sys.argv) > 5 else "acgtn"
+    ds = synth.make_dataset([2500000, 1500000, 2000000], n_loci, n_samples=ns, seed=seed, contig_names=["c9", "c10", "c1"], edge_cases=True, alphabet=alphabet)
     names, alns = ds.contig_names, ds.sorted_alns()
     cut, gap, L = 10, 100, 300
     order = np.argsort(np.array(names, dtype=object), kind="stable").astype(np.int32)

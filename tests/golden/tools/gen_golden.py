@@ -89,11 +89,29 @@ def gen_fold_golden_185():
              "cases": cases}, os.path.join(GOLD, "fold_rnalfold185.json.gz"))
 
 
-def gen_pipeline_golden(name, contig_lens, names, n_loci, n_samples, seed, sq_order, config_extra, rnalfold="RNALfold212"):
+def gen_fold_golden_alphabet():
+    """Both bundled RNALfold binaries on windows with letters outside ACGUN: IUPAC codes, RNALfold 1.8.5's X K I (both cases), `_`, `-`,
+    lower case, T; planted hairpins with X/K and I/A/U arms.  Spans 300 and 120 (the LDS-resident kernels' domain, windows up to 350 nt, plus
+    some beyond) and 400 on 360 .. 480 nt (the generic kernels)."""
+    probes = ["GGGGAAAUCCCCKKKKAAAAXXXXUUUUGGGGIIIICCCC", "GGGAAAXXXXAAAACCCCAAAAKKKKAAAUCC", "ggggaaauccccKKKKaaaaxxxxuuuuggggiiiicccc",
+              "GGGGAAAUCCCCkkkkAAAAxxxxUUUUGGGGiiiiCCCC", "GGGGRYMSWBDHVNAAAACCCCRYMSWBDHVN", "GGGG____AAAACCCC----GGGGAAAACCCC", "XXXXXAAAAKKKKK",
+              "IIIIIIGGGAAAACCCIIIIII", "AAAAAUUUUUUIIIIIGGGGAAAACCCCAAAAA", "XKXKXKXKAAAAXKXKXKXK", "XXXAAAK", "K", "X" * 30, "I" * 30]
+    sets = [(301, 110, 5, 350, 300), (302, 40, 40, 300, 120), (303, 12, 360, 480, 300), (304, 14, 360, 480, 400)]
+    out = {"generator": "RNALfold 1.8.5 (reference dependency/Linux/x64/RNALfold) and RNALfold 2.1.2 (reference dependency/Mac/osx-10.9/RNALfold-2.1.2), "
+                        "-L span, default dangles; windows from tests/seqgen.py alphabet_windows()", "cases": []}
+    for seed, cnt, lo, hi, span in sets + [(0, None, None, None, 300)]:
+        seqs = probes if seed == 0 else seqgen.alphabet_windows(seed, cnt, lo, hi)
+        out["cases"].append({"seed": seed, "span": span, "seqs": seqs,
+                             "expected185": _run_rnalfold(os.path.join(ORA_BIN, "RNALfold185"), seqs, span),
+                             "expected212": _run_rnalfold(os.path.join(ORA_BIN, "RNALfold212"), seqs, span)})
+    dump_gz(out, os.path.join(GOLD, "fold_alphabet.json.gz"))
+
+
+def gen_pipeline_golden(name, contig_lens, names, n_loci, n_samples, seed, sq_order, config_extra, rnalfold="RNALfold212", alphabet="acgtn"):
     work = os.path.join("/tmp", "golden_" + name)
     shutil.rmtree(work, ignore_errors=True)
     os.makedirs(work)
-    ds = synth.make_dataset(contig_lens, n_loci, n_samples=n_samples, seed=seed, contig_names=names, edge_cases=True)
+    ds = synth.make_dataset(contig_lens, n_loci, n_samples=n_samples, seed=seed, contig_names=names, edge_cases=True, alphabet=alphabet)
     fa = os.path.join(work, "genome.fa")
     ds.write_fasta(fa)
     sams = ds.write_sams(work, sq_order=sq_order)
@@ -209,12 +227,17 @@ if __name__ == "__main__":
         gen_fold_golden()
     if "fold185" in what:
         gen_fold_golden_185()
+    if "fold_alphabet" in what:
+        gen_fold_golden_alphabet()
     if "mini" in what:
         # 3 contigs, @SQ order deliberately non-lexicographic, 2 samples, edge cases planted
         gen_pipeline_golden("mini", [120000, 60000, 90000], ["Chr2", "Chr10", "Chr1"], 130, 2, 5, None, {})
     if "mini185" in what:
         # the "mini" dataset with the RNALfold the reference bundles for Linux (1.8.5) on PATH instead of 2.1.2
         gen_pipeline_golden("mini185", [120000, 60000, 90000], ["Chr2", "Chr10", "Chr1"], 130, 2, 5, None, {}, rnalfold="RNALfold185")
+    if "mini185x" in what:
+        # the "mini185" layout on a genome with IUPAC letters, X K I (both cases), soft-masked runs and X-K stem pairs inside the windows
+        gen_pipeline_golden("mini185x", [120000, 60000, 90000], ["Chr2", "Chr10", "Chr1"], 130, 2, 23, None, {}, rnalfold="RNALfold185", alphabet="all")
     if "mini400" in what:
         # PRECURSOR_LEN = 400: window extension at another length, RNALfold -L 400 on windows of 400 / 425 nt (the generic fold kernels' domain)
         gen_pipeline_golden("mini400", [90000, 50000], ["cB", "cA"], 60, 2, 17, None, {"PRECURSOR_LEN": 400})

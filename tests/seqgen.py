@@ -29,9 +29,58 @@ def window(r, lo, hi):
     return s
 
 
-def windows(seed, count, lo, hi):
+def windows(seed, count, lo, hi, alphabet="acgun"):
+    """`alphabet="acgun"` (the default, whose seeds never move) draws window(); `alphabet="all"` draws alphabet_window()."""
     r = random.Random(seed)
-    return [window(r, lo, hi) for _ in range(count)]
+    draw = {"acgun": window, "all": alphabet_window}[alphabet]
+    return [draw(r, lo, hi) for _ in range(count)]
+
+
+# Letters outside ACGU(T)N that a window may carry (IUPAC codes, RNALfold 1.8.5's X K I, gap-like symbols)
+IUPAC = "RYKMSWBDHV"
+SPECIAL185 = "XKI"      # RNALfold 1.8.5 encodes these (any case) as bases of their own: X pairs with K, I with A and U
+OTHER = "_-"
+# partner of an arm letter in a planted hairpin that uses the 1.8.5 pair types
+_PARTNER185 = {"X": "K", "K": "X", "I": "AU", "A": "UI", "U": "AI", "G": "C", "C": "G"}
+
+
+def alphabet_window(r, lo, hi):
+    """A window() with letters of every class the fold models read: IUPAC-heavy windows, a few scattered letters, or a planted hairpin whose arms
+    pair X with K and I with A / U (so the 1.8.5 pair types are chosen); random case, T for U in some."""
+    s = list(window(r, lo, hi))
+    n = len(s)
+    mode = r.random()
+    pool = IUPAC + SPECIAL185 + OTHER + "N"
+    if mode < 0.25:                     # IUPAC-heavy
+        rate = r.choice([0.2, 0.5, 0.9])
+        for i in range(n):
+            if r.random() < rate:
+                s[i] = r.choice(pool)
+    elif mode < 0.55 or n < 16:         # a few scattered letters
+        for _ in range(r.randint(1, 6)):
+            s[r.randrange(n)] = r.choice(pool)
+    else:                               # planted hairpin with X/K or I/U arms
+        arm = r.randint(4, min(24, (n - 3) // 2))
+        letters = r.choice(["XK", "XKGC", "IAU", "IAUGC", "XKIAUGC"])
+        a = [r.choice(letters) for _ in range(arm)]
+        b = [r.choice(_PARTNER185[c]) for c in reversed(a)]
+        loop = [r.choice("ACGU") for _ in range(r.randint(3, 8))]
+        hp = a + loop + b
+        if len(hp) <= n:
+            pos = r.randint(0, n - len(hp))
+            s[pos:pos + len(hp)] = hp
+    cs = r.random()
+    if cs < 0.15:
+        s = [c.lower() for c in s]
+    elif cs < 0.35:
+        s = [c.lower() if r.random() < 0.5 else c for c in s]
+    if r.random() < 0.2:
+        s = [{"U": "T", "u": "t"}.get(c, c) for c in s]
+    return "".join(s)
+
+
+def alphabet_windows(seed, count, lo, hi):
+    return windows(seed, count, lo, hi, alphabet="all")
 
 
 def stress_family(r, k):

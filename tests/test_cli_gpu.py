@@ -32,7 +32,7 @@ def _setup(name, tmp_path):
     return exp, str(cfg), tmp_path / "out"
 
 
-@pytest.mark.parametrize("name", ["mini", "mini3", "mini185", "mini24", "mini400"])
+@pytest.mark.parametrize("name", ["mini", "mini3", "mini185", "mini185x", "mini24", "mini400"])
 def test_pipeline_verb_reproduces_reference_outputs(name, tmp_path):
     exp, cfg, out = _setup(name, tmp_path)
     assert cli.main(["-k", "-d", "--fold-model", exp.get("fold_model", "vienna-2.1.2"), "pipeline", cfg]) == 0

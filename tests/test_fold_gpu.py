@@ -130,6 +130,38 @@ def test_fold_vienna212_matches_the_bundled_binary(gpu_ctx):
     assert n >= 300 and {300, 100, 40, 20} <= spans
 
 
+@pytest.mark.parametrize("model,key", [("vienna-1.8.5", "expected185"), ("vienna-2.1.2", "expected212")])
+def test_fold_alphabet_matches_the_bundled_binaries(gpu_ctx, model, key):
+    """Letters outside ACGUN (IUPAC codes, 1.8.5's X K I in both cases, `_`, `-`, lower case, T) against both bundled binaries
+    (tests/golden/fold_alphabet.json.gz): every line, its energy and start column, and the MFE.  Spans 300 and 120 run the LDS-resident kernels on
+    windows up to 350 nt, and under vienna-1.8.5 they hand every window with X K I to the generic kernels (counted by mirp_last_fold_fallbacks);
+    span 400 runs the generic kernels alone."""
+    from tests import golden_util as gu
+    gold = gu.load_json("fold_alphabet.json.gz")
+    gpu_ctx.set_fold_model(model)
+    n = both = 0
+    try:
+        for case in gold["cases"]:
+            seqs, span = case["seqs"], case["span"]
+            got = gpu_ctx.fold_batch(seqs, span, max_lines=352 if span <= 300 else 500)
+            fallbacks = gpu_ctx.last_fold_fallbacks()
+            for g, exp, seq in zip(got, case[key], seqs):
+                assert g["status"] == 0 and g["mfe"] == exp["mfe"], (span, seq)
+                assert [list(l) for l in g["lines"]] == exp["lines"], (span, seq)
+                n += 1
+            if span <= 300:
+                handed = [s for s in seqs if len(s) > 350 or (model == "vienna-1.8.5" and any(c in s for c in "XKIxki"))]
+                assert fallbacks == len(handed), (span, fallbacks, len(handed))        # no more, no fewer: the LDS-resident kernels folded the rest
+                both += 0 < len(handed) < len(seqs)
+        assert n >= 180 and (both >= 3 or model == "vienna-2.1.2")
+        probe = gold["cases"][-1]
+        got = gpu_ctx.fold_batch(probe["seqs"][:1], 300)[0]
+        if model == "vienna-1.8.5":
+            assert got["lines"][-1] == ("((((((((((((((((....))))....))))))))))))", -2970, 1) and got["mfe"] == -2970
+    finally:
+        gpu_ctx.set_fold_model("vienna-2.1.2")
+
+
 def test_generic_kernels_match_the_real_binaries_beyond_300(gpu_ctx):
     """The generic kernels (span > 300, windows > 350 nt; fill with split candidates, lane = paired cell, trace-back codes; fill and epilogue as two kernels)
     against digests of the real RNALfold 2.1.2 / 1.8.5 output: 200 windows of 360 .. 480 nt at spans 400 and 330 (tests/golden/long_folds.json.gz)."""

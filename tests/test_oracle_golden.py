@@ -6,7 +6,7 @@ import pytest
 from mir_prefer_amd import records
 from tests import golden_util as gu
 
-CASES = ["mini", "mini3", "mini185", "mini24", "mini400"]   # mini185: the "mini" dataset run with the bundled RNALfold 1.8.5 on PATH
+CASES = ["mini", "mini3", "mini185", "mini185x", "mini24", "mini400"]   # mini185: the "mini" dataset run with the bundled RNALfold 1.8.5 on PATH; mini185x: the same under 1.8.5 on a genome with IUPAC letters, X K I and soft-masked runs in its windows
 
 
 def test_lfold_matches_rnalfold212(oracle):
@@ -32,6 +32,28 @@ def test_lfold185_matches_rnalfold185(oracle):
             assert [list(l) for l in got["lines"]] == exp["lines"], seq
             n += 1
     assert n >= 330
+
+
+@pytest.mark.parametrize("model,key", [("vienna-1.8.5", "expected185"), ("vienna-2.1.2", "expected212")])
+def test_lfold_alphabet_matches_both_binaries(oracle, model, key):
+    """Letters outside ACGUN (IUPAC codes, 1.8.5's X K I in both cases, `_`, `-`, lower case, T) against both bundled binaries: 1.8.5 pairs X with
+    K and I with A / U, 2.1.2 reads them all as N."""
+    gold = gu.load_json("fold_alphabet.json.gz")
+    n = n_special = 0
+    for case in gold["cases"]:
+        for seq, exp in zip(case["seqs"], case[key]):
+            got = oracle.lfold(seq, case["span"], model=model)
+            assert got["mfe"] == exp["mfe"], (case["span"], seq)
+            assert [list(l) for l in got["lines"]] == exp["lines"], (case["span"], seq)
+            n += 1
+            n_special += any(c in seq for c in "XKIxki")
+    assert n >= 180 and n_special >= 120
+    probe = gold["cases"][-1]
+    assert probe["seqs"][0] == "GGGGAAAUCCCCKKKKAAAAXXXXUUUUGGGGIIIICCCC"
+    # the divergence that was found first: 1.8.5 folds the X-K / I-A / I-U pairs into one helix at -29.70
+    want = (["((((((((((((((((....))))....))))))))))))", -2970, 1], -2970) if model == "vienna-1.8.5" else \
+        (["((((....((((................))))....))))", -1130, 1], -1130)
+    assert (probe[key][0]["lines"][-1], probe[key][0]["mfe"]) == want
 
 
 @pytest.fixture(scope="module", params=CASES)

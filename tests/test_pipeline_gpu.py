@@ -19,12 +19,19 @@ def _gpu_record(m, ss, names):
             records.STRAND[m["strand"]], bool(m["has_star"])]
 
 
-@pytest.mark.parametrize("name", ["mini", "mini3", "mini185", "mini24", "mini400"])
+@pytest.mark.parametrize("name", ["mini", "mini3", "mini185", "mini185x", "mini24", "mini400"])
 def test_pipeline_matches_reference_fixture(name, gpu_ctx):
+    """mini185x: vienna-1.8.5 on a genome with IUPAC letters, X K I, soft-masked runs and X-K stem pairs inside its windows -- the window payload, the
+    reverse complement of those letters and the folds against the reference run; its windows with X K I go to the generic kernels."""
     c = gu.load_pipeline_case(name)
-    gpu_ctx.set_fold_model(c["exp"].get("fold_model", "vienna-2.1.2"))
+    model = c["exp"].get("fold_model", "vienna-2.1.2")
+    gpu_ctx.set_fold_model(model)
     try:
         _check_pipeline_fixture(c, gpu_ctx)
+        if model == "vienna-1.8.5":
+            seqs = [s for p in c["exp"]["pieces"] for _h, s in p["fasta"]]
+            n_xki = sum(any(ch in s for ch in "XKIxki") for s in seqs)
+            assert gpu_ctx.last_fold_fallbacks() == n_xki and (n_xki >= 10) == (name == "mini185x")
     finally:
         gpu_ctx.set_fold_model("vienna-2.1.2")
 
