@@ -13,13 +13,17 @@ config2-4 are fixed-size jobs sharded by contig ("strong" scaling); every rank g
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload configX]      (N > 1: re-launches itself under torch.distributed.run)
     python bench.py --dump-outputs DIR ...       (N = 1: the loci list of the last timed step as DIR/*.npy, see dump_outputs)
+    python bench.py --full ...                   (every side measurement below as well; minutes instead of seconds)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Multi-GPU: one process per GPU; host objects and the timing barrier go over a CPU-side `gloo` group, the data path's one exchange step (the
 gather of the loci list, mirp_gather_loci) over RCCL on the library's own communicator.  torch never touches the GPU in this process, so it
 holds a single HIP runtime; every C-ABI call returns after its stream has drained, which is the device synchronisation of the timed region.
 
-The JSON line carries, beside the contract's keys:
+A plain run sets up, warms up, times the K steps, checks the size of the result list, writes --dump-outputs and prints the JSON line: the
+contract's keys, `config`, `stage_ms` (device time per stage of the timed steps) and, for N > 1, `ranks`.  Everything else runs only with
+--full, after the timed steps (--no-configs, --no-e2e, --no-ingest, --no-cpu-baseline, --no-cov-shard leave parts of it out); the line then
+carries as well:
   roofline       the dominant kernel (fold_lds_kernel, the dynamic program) against the roof that bounds it -- integer min-plus relaxations
                  out of LDS: `peak` is the figure of MI355X_MICROARCH.md (75 TB/s of ds_read_b32 = 9.4e12 relaxations/s at 8 B per relaxation) and
                  `frac` the fraction of it; `peak_measured` / `frac_measured` use the conflict-free ds_read_b32 / VALU rates micro-benchmarked on this
@@ -31,7 +35,8 @@ The JSON line carries, beside the contract's keys:
   configs        (N = 1, default workload) config2 on the same GPU, the vienna-1.8.5 model, and the fold micro-benchmark of SURVEY.md 8d
                  (2^16 windows, n = L = 300: uniform / 50 % planted hairpins / GC = 0.65) with generic-fallback counts per family;
   cpu_baseline   the CPU oracle (the build's own restatement of the reference, "port") timed on this box AFTER the GPU timing;
-  e2e            the CLI `pipeline` verb on files of the same workload (SAM + FASTA in -> gff3 and reports out), wall-clock and device time by stage.
+  e2e            the CLI `pipeline` verb on files of the same workload (SAM + FASTA in -> gff3 and reports out), wall-clock and device time by stage;
+  ingest         (N = 1, default workload) unsorted SAM text -> sorted packed records on the device, see ingest_leg.
 """
 import argparse
 import json
@@ -120,6 +125,8 @@ def parse_args():
     ap.add_argument("--loci", type=int, default=N_LOCI, help="config1: loci per contig")
     ap.add_argument("--genome", type=int, default=CHR1_LEN, help="config1: contig length")
     ap.add_argument("--genome-scale", type=float, default=1.0, help="tests only: config2-4 at this fraction of their size (the line says so; no expected-result check)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure everything beside the headline: roofline figures, the "
+                    "`configs` block, the end-to-end CLI runs, the ingest leg and the CPU baseline (the --no-* options below leave parts out)")
     ap.add_argument("--no-configs", action="store_true", help="skip the `configs` block (config2, vienna-1.8.5, fold micro-benchmark)")
     ap.add_argument("--micro-windows", type=int, default=1 << 16, help="windows per family of the fold micro-benchmark")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -700,44 +707,13 @@ def main():
         fill_s = float(np.mean(fill_ms)) / 1e3
         epi_s = float(np.mean(epi_ms)) / 1e3
         cov_s = float(np.mean(cov_ms)) / 1e3
-        cov_fused = ctx.last_coverage_fused()
-        wins = ctx.get_windows()
-        W = wins["windows"]
-        lens = W["seq_len"].astype(np.int64)
-        # ---- dominant kernel: the fill kernel (dynamic program).  Unit of algorithmic work = one relaxation; R is counted
-        # exactly for this rank's batch from its pair-type counts (a sample of 20,000 windows, scaled, when the batch is larger).  Roofs:
-        # LDS = 2 reads per relaxation at the ds_read_b32 rate -- measured on this GPU now, and the microarchitecture guide's figure beside it;
-        # VALU = 3 integer lane-operations per relaxation at the measured 32-bit issue rate.
-        nsmp = min(len(W), 20000)
-        R = relaxation_count(wins["seq"], W["seq_off"].astype(np.int64)[:nsmp], lens[:nsmp], L)
-        if nsmp < len(W):
-            R = {k: v * len(W) / nsmp for k, v in R.items()}
-        mb = ctx.microbench()
-        lds_roof = mb["ds_read_b32_per_s"] * 64.0 / 2.0
-        valu_roof = mb["valu_u32_per_s"] * 64.0 / 3.0
-        roof = min(lds_roof, valu_roof)
-        achieved = R["total"] / fill_s if fill_s > 0 else 0.0
-        D = np.minimum(L - 1, lens - 1)
-        cells = np.where(D > 3, (D - 3) * lens - (D * (D + 1) // 2 - 6), 0)
-        b_fold = float((lens + 64 + 10 * cells + 6000).sum())     # c, fML, trace-back triangles written once (16-bit), c + fML read once, ~6 KB of lines
-        prof = {}
-        try:
-            prof = json.load(open(os.path.join(ROOT, "profiles", "CURRENT.json")))
-        except Exception:
-            pass
         headline = a.workload == "config1" and a.genome == CHR1_LEN and a.loci == N_LOCI
         loci_expected = EXPECTED_LOCI.get((a.workload, a.fold_model)) if (world == 1 and a.genome_scale == 1.0 and (headline or a.workload != "config1")) else None
         if loci_expected is not None and int(nres) != loci_expected:
             sys.stderr.write("[bench] RESULT CHECK FAILED: %d miRNA loci, expected %d for (%s, %s) -- no line printed\n" % (nres, loci_expected, a.workload, a.fold_model))
             ctx.close()
             sys.exit(4)
-        pipe = prof.get("fold_fill_pipe_busy") if (a.workload == "config1" and a.fold_model == "vienna-2.1.2") else None
-        same_workload = headline and a.fold_model == "vienna-2.1.2"
-        traffic = prof.get("fold_fill_hbm_bytes_per_launch") if same_workload else None
-        g_tot = float(sum(len(sq) + 1 for _, sq in contigs))
-        b_cov = 16.0 * len(alns) + 16.0 * g_tot
-        b_cov_moved = 48.0 * len(alns) + 8.0 * g_tot      # what the stage moves since the clearing pass is gone: the scan reads 8 B per position; a record is
-        line = {                                           # read by the scatter and by the un-scatter (16 B each) and touches 2 x 2 x 4 B of the arrays
+        line = {
             "metric": "precursor windows folded+filtered/sec (L=300)", "value": total_windows * a.steps / elapsed, "unit": "windows/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / a.steps, "higher_is_better": True,
             "scaling": scaling, "vs_baseline": None, "dtype": "int16/int32 (energies in 0.01 kcal/mol)", "data": "synthetic",
@@ -749,39 +725,73 @@ def main():
                        "exchange": ("none (1 GPU)" if world == 1 else "mirp_gather_loci over the local transport (ranks share GPU 0: dev run)" if share_dir
                                     else "loci lists as host objects over gloo (RCCL communicator not available: %s)" % rccl_error if rccl_error
                                     else "mirp_gather_loci over RCCL (library-owned communicator), host objects over gloo")},
-            "roofline": {"kernel": "fold_lds_kernel<0, true>" if a.fold_model == "vienna-2.1.2" else "fold_lds_kernel<1, true>",
-                         "bound": "lds", "achieved": achieved / 1e12, "peak": LDS_GUIDE_RELAX_PER_S / 1e12, "unit": "T relaxations/s",
-                         "frac": achieved / LDS_GUIDE_RELAX_PER_S, "peak_measured": roof / 1e12, "frac_measured": achieved / roof if roof > 0 else None,
-                         "bound_measured": "lds" if lds_roof <= valu_roof else "valu", "avg_launch_ms": fill_s * 1e3, "pipe_busy": pipe,
-                         # `frac` prices work the kernel no longer issues.  frac_executed prices what it does issue -- interior candidates + exterior +
-                         # the split-candidate visits (2.5 % of the dense multiloop count on this workload, tests/tools/splitcand_gate.c) -- against the same roof:
-                         # the utilisation-like figure; `frac` stays the contract's algorithmic one (speed-up over a dense kernel running at the roof)
-                         "executed_relaxations_estimate": R["interior_candidates"] + R["exterior"] + 0.025 * R["multiloop_splits"],
-                         "frac_executed": ((R["interior_candidates"] + R["exterior"] + 0.025 * R["multiloop_splits"]) / fill_s / LDS_GUIDE_RELAX_PER_S) if fill_s > 0 else None,
-                         "windows_via_dense_split_pass": int(fb[2]),
-                         "relaxations_per_launch": R, "lds_roof_T": lds_roof / 1e12, "valu_roof_T": valu_roof / 1e12, "microbench_wave_insts_per_s": mb,
-                         "traffic": traffic, "traffic_source": prof.get("source") if traffic is not None else None,
-                         "note": "integer min-plus dynamic program out of LDS, SURVEY.md 8d: achieved = ALGORITHMIC relaxations of the batch (the dense count "
-                                 "R_ml + R_int + R_f3 from its pair-type counts; since round 4 the kernel relaxes the multiloop splits over split candidates only "
-                                 "and executes ~2.5 % of R_ml) / the fill kernel's time; peak = 75 TB/s of ds_read_b32 (MI355X_MICROARCH.md) / 8 B per relaxation; "
-                                 "peak_measured = min(LDS, VALU) roofs micro-benchmarked on this GPU in this run; pipe_busy = busy fractions of the LDS array, the "
-                                 "vector and the scalar issue ports from the committed rocprofv3 PMC passes (profiles/CURRENT.json); traffic = HBM bytes per launch from the same"},
-            "roofline_hbm": {"kernel": "fold_lds_kernel + fold_lds_epilogue_kernel", "bound": "hbm", "achieved": b_fold / fold_s / 1e9, "peak": HBM_PEAK_GBS,
-                             "unit": "GB/s", "frac": b_fold / fold_s / 1e9 / HBM_PEAK_GBS, "avg_launch_ms": fold_s * 1e3,
-                             "note": "HBM view of the fold (algorithmic bytes / time / 8 TB/s); << 1 is expected: the tables are LDS-resident"},
-            "roofline_coverage": {"kernel": "cov_tile_first_kernel + cov_scan_kernel<fused>" if cov_fused else "cov_scatter_kernel + cov_scan_kernel + cov_unscatter_kernel", "bound": "hbm", "achieved": b_cov / cov_s / 1e9,
-                                  "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": b_cov / cov_s / 1e9 / HBM_PEAK_GBS, "avg_ms": cov_s * 1e3,
-                                  "bytes_algorithmic": b_cov, "bytes_moved_model": b_cov_moved, "achieved_moved": b_cov_moved / cov_s / 1e9,
-                                  "frac_moved": b_cov_moved / cov_s / 1e9 / HBM_PEAK_GBS,
-                                  "note": "achieved / frac price SURVEY 8d's algorithmic bytes 16 A + 16 G; the stage no longer clears the whole difference arrays, so "
-                                          "the bytes it actually moves are ~ 8 G + 48 A (achieved_moved / frac_moved): part of the gain is work not done, not bandwidth"},
-            "stage_ms": {"coverage": cov_s * 1e3, "candidate_rest": float(np.mean(rest_ms)), "fold": fold_s * 1e3, "fold_fill_kernel": fill_s * 1e3,
-                         "fold_epilogue_kernel": epi_s * 1e3, "predict": float(np.mean(pred_ms)),
-                         "per_step": {"fold": [round(x, 3) for x in fold_ms], "predict": [round(x, 3) for x in pred_ms]}},
         }
+        if a.full:          # roofline figures: the relaxation count of the batch and a micro-benchmark run of their own, after the timing
+            cov_fused = ctx.last_coverage_fused()
+            wins = ctx.get_windows()
+            W = wins["windows"]
+            lens = W["seq_len"].astype(np.int64)
+            # ---- dominant kernel: the fill kernel (dynamic program).  Unit of algorithmic work = one relaxation; R is counted
+            # exactly for this rank's batch from its pair-type counts (a sample of 20,000 windows, scaled, when the batch is larger).  Roofs:
+            # LDS = 2 reads per relaxation at the ds_read_b32 rate -- measured on this GPU now, and the MI355X figure (LDS_GUIDE_RELAX_PER_S) beside it;
+            # VALU = 3 integer lane-operations per relaxation at the measured 32-bit issue rate.
+            nsmp = min(len(W), 20000)
+            R = relaxation_count(wins["seq"], W["seq_off"].astype(np.int64)[:nsmp], lens[:nsmp], L)
+            if nsmp < len(W):
+                R = {k: v * len(W) / nsmp for k, v in R.items()}
+            mb = ctx.microbench()
+            lds_roof = mb["ds_read_b32_per_s"] * 64.0 / 2.0
+            valu_roof = mb["valu_u32_per_s"] * 64.0 / 3.0
+            roof = min(lds_roof, valu_roof)
+            achieved = R["total"] / fill_s if fill_s > 0 else 0.0
+            D = np.minimum(L - 1, lens - 1)
+            cells = np.where(D > 3, (D - 3) * lens - (D * (D + 1) // 2 - 6), 0)
+            b_fold = float((lens + 64 + 10 * cells + 6000).sum())     # c, fML, trace-back triangles written once (16-bit), c + fML read once, ~6 KB of lines
+            prof = {}
+            try:
+                prof = json.load(open(os.path.join(ROOT, "profiles", "CURRENT.json")))
+            except Exception:
+                pass
+            pipe = prof.get("fold_fill_pipe_busy") if (a.workload == "config1" and a.fold_model == "vienna-2.1.2") else None
+            same_workload = headline and a.fold_model == "vienna-2.1.2"
+            traffic = prof.get("fold_fill_hbm_bytes_per_launch") if same_workload else None
+            g_tot = float(sum(len(sq) + 1 for _, sq in contigs))
+            b_cov = 16.0 * len(alns) + 16.0 * g_tot
+            # what the stage moves since the clearing pass is gone: the scan reads 8 B per position; a record is read by the scatter and by the un-scatter
+            # (16 B each) and touches 2 x 2 x 4 B of the arrays
+            b_cov_moved = 48.0 * len(alns) + 8.0 * g_tot
+            line["roofline"] = {"kernel": "fold_lds_kernel<0, true>" if a.fold_model == "vienna-2.1.2" else "fold_lds_kernel<1, true>",
+                                "bound": "lds", "achieved": achieved / 1e12, "peak": LDS_GUIDE_RELAX_PER_S / 1e12, "unit": "T relaxations/s",
+                                "frac": achieved / LDS_GUIDE_RELAX_PER_S, "peak_measured": roof / 1e12, "frac_measured": achieved / roof if roof > 0 else None,
+                                "bound_measured": "lds" if lds_roof <= valu_roof else "valu", "avg_launch_ms": fill_s * 1e3, "pipe_busy": pipe,
+                                # `frac` prices work the kernel no longer issues.  frac_executed prices what it does issue -- interior candidates + exterior +
+                                # the split-candidate visits (2.5 % of the dense multiloop count on this workload, tests/tools/splitcand_gate.c) -- against the same roof:
+                                # the utilisation-like figure; `frac` stays the contract's algorithmic one (speed-up over a dense kernel running at the roof)
+                                "executed_relaxations_estimate": R["interior_candidates"] + R["exterior"] + 0.025 * R["multiloop_splits"],
+                                "frac_executed": ((R["interior_candidates"] + R["exterior"] + 0.025 * R["multiloop_splits"]) / fill_s / LDS_GUIDE_RELAX_PER_S) if fill_s > 0 else None,
+                                "windows_via_dense_split_pass": int(fb[2]),
+                                "relaxations_per_launch": R, "lds_roof_T": lds_roof / 1e12, "valu_roof_T": valu_roof / 1e12, "microbench_wave_insts_per_s": mb,
+                                "traffic": traffic, "traffic_source": prof.get("source") if traffic is not None else None,
+                                "note": "integer min-plus dynamic program out of LDS, SURVEY.md 8d: achieved = ALGORITHMIC relaxations of the batch (the dense count "
+                                        "R_ml + R_int + R_f3 from its pair-type counts; since round 4 the kernel relaxes the multiloop splits over split candidates only "
+                                        "and executes ~2.5 % of R_ml) / the fill kernel's time; peak = 75 TB/s of ds_read_b32 (MI355X LDS figure) / 8 B per relaxation; "
+                                        "peak_measured = min(LDS, VALU) roofs micro-benchmarked on this GPU in this run; pipe_busy = busy fractions of the LDS array, the "
+                                        "vector and the scalar issue ports from the committed rocprofv3 PMC passes (profiles/CURRENT.json); traffic = HBM bytes per launch from the same"}
+            line["roofline_hbm"] = {"kernel": "fold_lds_kernel + fold_lds_epilogue_kernel", "bound": "hbm", "achieved": b_fold / fold_s / 1e9, "peak": HBM_PEAK_GBS,
+                                    "unit": "GB/s", "frac": b_fold / fold_s / 1e9 / HBM_PEAK_GBS, "avg_launch_ms": fold_s * 1e3,
+                                    "note": "HBM view of the fold (algorithmic bytes / time / 8 TB/s); << 1 is expected: the tables are LDS-resident"}
+            line["roofline_coverage"] = {"kernel": "cov_tile_first_kernel + cov_scan_kernel<fused>" if cov_fused else "cov_scatter_kernel + cov_scan_kernel + cov_unscatter_kernel", "bound": "hbm", "achieved": b_cov / cov_s / 1e9,
+                                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": b_cov / cov_s / 1e9 / HBM_PEAK_GBS, "avg_ms": cov_s * 1e3,
+                                         "bytes_algorithmic": b_cov, "bytes_moved_model": b_cov_moved, "achieved_moved": b_cov_moved / cov_s / 1e9,
+                                         "frac_moved": b_cov_moved / cov_s / 1e9 / HBM_PEAK_GBS,
+                                         "note": "achieved / frac price SURVEY 8d's algorithmic bytes 16 A + 16 G; the stage no longer clears the whole difference arrays, so "
+                                                 "the bytes it actually moves are ~ 8 G + 48 A (achieved_moved / frac_moved): part of the gain is work not done, not bandwidth"}
+        line["stage_ms"] = {"coverage": cov_s * 1e3, "candidate_rest": float(np.mean(rest_ms)), "fold": fold_s * 1e3, "fold_fill_kernel": fill_s * 1e3,
+                            "fold_epilogue_kernel": epi_s * 1e3, "predict": float(np.mean(pred_ms)),
+                            "per_step": {"fold": [round(x, 3) for x in fold_ms], "predict": [round(x, 3) for x in pred_ms]}}
         if ranks:
             line["ranks"] = ranks
-        if world == 1:      # reported side lines and baselines: rank 0 at N = 1 only, AFTER the GPU timing
+        if world == 1 and a.full:      # reported side lines and baselines: rank 0 at N = 1 only, AFTER the GPU timing
             if headline and not a.no_configs:
                 cfgs = {}
                 other = "vienna-1.8.5" if a.fold_model == "vienna-2.1.2" else "vienna-2.1.2"

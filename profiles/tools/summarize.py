@@ -44,7 +44,7 @@ for name in ("L400_counters.txt", "L400_vienna185_counters.txt"):
     fl = glob.glob("gpurun_out/%s_%s" % (tag, name))
     if fl:
         shutil.copy(fl[0], "profiles/%s_%s" % (tag, name))
-# profiles/CURRENT.json: what bench.py reports as roofline.traffic / roofline.pipe_busy, with the commit the counters were collected at
+# profiles/CURRENT.json: what bench.py --full reports as roofline.traffic / roofline.pipe_busy, with the commit the counters were collected at
 import subprocess
 stats = {r["Name"].split("(")[0].replace("void ", "").strip(): float(r["AverageNs"]) for r in csv.DictReader(open("profiles/%s_kernel_stats.csv" % tag))}
 fill_ns = stats.get(FILL)
