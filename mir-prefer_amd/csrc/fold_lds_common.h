@@ -9,8 +9,8 @@
 
 namespace mirp {
 
-#define LNT 1024
-#define LNW (LNT / 64)
+#define LNT 1024            // one window per CU: both vienna-1.8.5 instantiations and the dense pass of the default model
+#define LNT2 512            // two windows per CU: the default model's candidate-pool pass (fML triangle in the archive slab, not in LDS)
 #define LCAP 352            // window length capacity
 #define LDMAX 300           // diagonals 4..LDMAX are allocated: pair distances up to span-1 = 299, plus the fML-only diagonal d = span of the vienna-1.8.5 model
 #define LSPAN 300           // largest span (-L) this kernel supports
@@ -163,8 +163,14 @@ __host__ __device__ constexpr unsigned lds_al(unsigned x) { return (x + 15u) & ~
 // lives behind the window's fML triangle inside the fml region, which then takes everything the other arrays leave of the 160 KB.
 #define FML_REGION_BYTES (lds_al((tri_off(LDMAX + 1, LCAP) + 2) * 2))      // fML triangle, d = 4..LDMAX at n = LCAP
 #define POOL_MIN_CAP 1024    // a window whose length leaves room for fewer candidates goes to the dense kernel right away
-template <int MODEL, bool SPARSE = false>
+// TWO (default model, SPARSE): two workgroups share a CU, so a window has 80 KB.  Its fML triangle is not in LDS at all: phase B keeps the last two
+// diagonals in a ring (FRING_STR shorts each) at the head of the fml region and writes every cell straight to the window's archive slab, from where
+// the sparse splits gather their operands (fold_lds_kernel.hip); the candidate pool takes the rest of the region.
+#define FRING_STR (LCAP + 2)
+#define LDS_TWO_BYTES (80u * 1024u)
+template <int MODEL, bool SPARSE = false, bool TWO = false>
 __host__ __device__ constexpr LdsLayout lds_layout() {
+    static_assert(!TWO || (SPARSE && MODEL == 0), "two windows per CU: candidate-pool pass of the default model only");
     LdsLayout L{};
     unsigned o = 0;
     if (!SPARSE) { L.fml = o; L.fml_bytes = FML_REGION_BYTES; o += L.fml_bytes; }
@@ -180,11 +186,13 @@ __host__ __device__ constexpr LdsLayout lds_layout() {
     L.list = o; o += lds_al(3 * LSEG * 4);      // 32-bit entries (see `list` in the kernel)
     L.tabs = o; o += lds_al((unsigned)sizeof(LdsTables));
     L.misc = o; o += lds_al((48 + ARCH_RB + ((SPARSE && MODEL) ? 48 : 0)) * 4);      // (vienna-1.8.5 candidate pass: + the 4 x 11-word bitmap of pooled pairs)
-    if (SPARSE) { L.fml = o; L.fml_bytes = 160u * 1024u - o; o += L.fml_bytes; }
+    if (SPARSE) { L.fml = o; L.fml_bytes = (TWO ? LDS_TWO_BYTES : 160u * 1024u) - o; o += L.fml_bytes; }
     L.total = o;
     return L;
 }
 static_assert(lds_layout<0>().total <= 160 * 1024 && lds_layout<1>().total <= 160 * 1024, "fill kernel LDS budget");
+static_assert(lds_layout<0, true, true>().total <= LDS_TWO_BYTES, "two workgroups of the candidate-pool pass must fit one CU's 160 KB");
+static_assert((lds_layout<0, true, true>().fml_bytes - lds_al(2 * FRING_STR * 2)) / 6 >= 2 * POOL_MIN_CAP, "two-per-CU layout: room for the candidate pool behind the fML ring");
 
 // ---- phase A1 building blocks.  All take the lane's paired cell (i, j = i + d) and wave-uniform d; r0 = d - 2 (ring row of the
 // stacked pair), um = largest admissible n1 + n2 (inner pair keeps q - p >= TURN + 1).  Running minima are biased uint (65535 = none).

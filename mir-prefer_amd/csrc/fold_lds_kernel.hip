@@ -1,7 +1,9 @@
 // LDS-resident batched L-bounded Zuker local fold for precursor windows (n <= 350, span <= 300):
 // the production case PRECURSOR_LEN = 300 (/root/reference/miR_PREFeR.py:90, RNALfold -L at :3053).
 //
-// One window per workgroup (1024 threads = 16 wavefronts), one workgroup per CU:
+// One window per workgroup.  The geometry described here is the one of the dense pass and of the vienna-1.8.5 model -- 1024 threads = 16 wavefronts, one
+// workgroup per CU; the default model's candidate-pool pass, which folds the product's windows, runs two 512-thread workgroups per CU without the
+// fML triangle in LDS (see NT = LNT2 at the kernel):
 //   * fML lives entirely in LDS as a triangular biased-uint16 table, diagonal-major: (d,i) -> off(d)+i, so
 //     the two operands of a multiloop split are read at consecutive addresses by consecutive lanes;
 //   * c keeps its last 32 anti-diagonals in an LDS ring (interior loops reach back MAXLOOP+2) and is
@@ -45,8 +47,22 @@ namespace mirp {
 // {s-1, j, fML(s,j)} behind the window's fML triangle; phase A2 maps LANE = POOL ENTRY: the entry's column j holds exactly one cell of the
 // diagonal at hand, (j-d, j), which it relaxes with one gather + one LDS atomic minimum.  A row's thread carries DML(i,j-1) in a register.
 // A window whose pool overflows (tandem repeats) or whose length leaves no room for one is handed to the dense instantiation (second launch).
-template <int MODEL, bool SPARSE>
-__global__ void __launch_bounds__(LNT) fold_lds_kernel(
+//
+// NT = LNT2 (the product's first pass of the default model): TWO windows per CU, each on a 512-thread workgroup with half of the LDS.  The fML
+// triangle -- 103 of the 160 KB at n = 325 -- is not kept in LDS: phase B holds the last two diagonals in a ring (all it reads itself) and stores every
+// cell to the window's archive slab in the tiled layout the epilogue reads (so no copy-out pass at the end of a window either); the sparse splits
+// take their one operand per pool entry and diagonal, fML(i, s-1), from that slab.  An entry reads the table at a fixed lag behind the wavefront
+// (the length of its right operand, at least 5 diagonals), so its address is known ahead: the gather is issued before the interior loops of the
+// interval and consumed behind them.
+// Visibility of those cells: producer and consumer are waves of ONE workgroup, i.e. of one CU and one vector L1, and the cell a gather of
+// interval d reads was stored by phase B at least three __syncthreads() earlier.  __syncthreads() is a workgroup-scope release / acquire fence
+// over global memory as well (every wave drains its stores, s_waitcnt vmcnt(0), before it enters the barrier), and stores write through the L1 the
+// loads go through; nothing is handed between workgroups.  Plain loads are therefore enough -- no sc1, no cache invalidate -- and nothing here
+// relies on timing.
+// The 16 interior-loop roles run two to a wave (see `role` in phase A1).  The two workgroups of a CU have independent barrier chains: one window's barrier wait
+// and phase-B chain are covered by the other window's interior loops.
+template <int MODEL, bool SPARSE, int NT = LNT>
+__global__ void __launch_bounds__(NT, 4) fold_lds_kernel(
     const FoldParams* __restrict__ P, const unsigned char* __restrict__ seqs, const long long* __restrict__ offs, const int* __restrict__ win_lens,
     int n_work, int win_base, int span, short* __restrict__ slabs, size_t slab_shorts, int* __restrict__ win_state,
     unsigned int* __restrict__ work_counter, int* __restrict__ fallback_list,
@@ -54,7 +70,10 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
     int* __restrict__ out_nlines, int* __restrict__ out_mfe, int* __restrict__ out_status, int light_clocks_arg, long long* __restrict__ dbg_cycles_arg,
     const int* __restrict__ todo_list, const unsigned int* __restrict__ todo_count, int* __restrict__ dense_list, unsigned int* __restrict__ dense_count) {
     extern __shared__ __align__(16) unsigned char smem[];
-    constexpr LdsLayout LY = lds_layout<MODEL, SPARSE>();
+    constexpr bool TWO = NT != LNT;          // two windows per CU: fML triangle in the archive slab only (see above)
+    static_assert(NT == LNT || NT == LNT2, "workgroup size");
+    constexpr int NW = NT / 64;
+    constexpr LdsLayout LY = lds_layout<MODEL, SPARSE, TWO>();
     // phase clocks exist in the diagnostics build only (make DIAG=1); the product kernel carries none of that code.  Light mode: per wave only the
     // busy time and the barrier wait (two clock reads per wave and interval)
 #ifdef MIRP_DIAG
@@ -104,7 +123,8 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
     // other twelve when a SIMD's arbiter has a choice -- every SIMD holds exactly one of them.  The interval's critical path runs through the waves that
     // own phase-B cells and then their own roles, not through the longest role: raising waves 12-15 instead costs 7 % (63.5 ms), a graded map 14 %,
     // switching the priority around phase B costs more than it gains; this map: 59.55 -> 59.12 ms (profiles/experiments/r6_fill_setprio.txt).
-    if (wave < 12) __builtin_amdgcn_s_setprio(1);
+    // Two windows per CU: the six waves that can own phase-B cells keep the arbiter (the two workgroups of a CU compete on every SIMD).
+    if (wave < (TWO ? 6 : 12)) __builtin_amdgcn_s_setprio(1);
     const int nc = CSTR;
     // Appends this thread's cell (i, pair type t; t = 0: none) to the paired-cell list of diagonal dd: ballot compaction inside the wave, one
     // LDS atomic per wave for its range.  The order of the ranges depends on which wave arrives first; nothing depends on the order of a
@@ -120,15 +140,15 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
     };
 
     // ---- one-time: hot parameter tables into LDS
-    for (int x = tid; x < 64; x += LNT) T.stack[x] = (short)min(P->stack[x >> 3][x & 7], (int)I16_INF);
-    for (int x = tid; x < 31; x += LNT) { T.bulge[x] = (short)min(P->bulge[x], (int)I16_INF); T.internal_loop[x] = (short)min(P->internal_loop[x], (int)I16_INF); }
-    for (int x = tid; x < 200; x += LNT) {
+    for (int x = tid; x < 64; x += NT) T.stack[x] = (short)min(P->stack[x >> 3][x & 7], (int)I16_INF);
+    for (int x = tid; x < 31; x += NT) { T.bulge[x] = (short)min(P->bulge[x], (int)I16_INF); T.internal_loop[x] = (short)min(P->internal_loop[x], (int)I16_INF); }
+    for (int x = tid; x < 200; x += NT) {
         int t = x / 25, a = (x % 25) / 5, b = x % 5;
         T.mismatchI[x] = (short)min(P->mismatchI[t][a][b], (int)I16_INF); T.mismatchH[x] = (short)min(P->mismatchH[t][a][b], (int)I16_INF);
         T.mismatchM[x] = (short)P->mismatchM[t][a][b]; T.mismatch1nI[x] = (short)min(P->mismatch1nI[t][a][b], (int)I16_INF);
         T.mismatch23I[x] = (short)min(P->mismatch23I[t][a][b], (int)I16_INF);
     }
-    xt_fill(T, P, tid, LNT);
+    xt_fill(T, P, tid, NT);
     if (tid < 40) { T.dangle5[tid] = (short)P->dangle5[tid / 5][tid % 5]; T.dangle3[tid] = (short)P->dangle3[tid / 5][tid % 5]; }
     if (tid < 25) T.rt2[tid] = (unsigned char)rtype_of(pair_type(tid / 5, tid % 5));
     if (tid == 0) { T.ML_closing = (short)P->ML_closing; T.ML_intern = (short)P->ML_intern; T.TerminalAU = (short)P->TerminalAU; T.ninio = (short)P->ninio; T.MAX_NINIO = (short)P->MAX_NINIO; }
@@ -147,13 +167,14 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
         const long long o0 = offs[win];
         const int n = win_lens ? win_lens[win] : (int)(offs[win + 1] - o0);
         // sparse splits: the candidate pool (u32 {s-1, j << 9} + u16 fML(s,j) per entry) takes what the window's triangle leaves of the fml region
-        const int pool_off = SPARSE ? (int)lds_al(2u * (unsigned)(tri_off(((span < n - 1) ? span : n - 1) + 1, n > 5 ? n : 5) + 2)) : 0;
+        // (two windows per CU: what the two-diagonal fML ring leaves)
+        const int pool_off = TWO ? (int)lds_al(2u * 2u * FRING_STR) : SPARSE ? (int)lds_al(2u * (unsigned)(tri_off(((span < n - 1) ? span : n - 1) + 1, n > 5 ? n : 5) + 2)) : 0;
         // (vienna-1.8.5: 8-byte entries, one per PAIR -- see "pair pool" at splits_sparse185)
         // A model whose pool is compacted in place (compact_pool: every wave keeps its slice in CPOOL_ROUNDS x 64 registers) cannot hold more than
         // LNW x CPOOL_ROUNDS x 64 entries: short windows leave room for more behind their triangle, the capacity stops there and a larger pool takes
         // the overflow hand-off to the dense instantiation (misc[2]) like any other.
         const int pool_room = SPARSE ? ((((int)LY.fml_bytes - pool_off) / (MODEL ? 8 : 6)) & ~63) : 0;
-        const int pool_cap = (SPARSE && (MODEL ? MIRP_CPERIOD1 : MIRP_CPERIOD0) > 0 && pool_room > LNW * CPOOL_ROUNDS * 64) ? LNW * CPOOL_ROUNDS * 64 : pool_room;
+        const int pool_cap = (SPARSE && (MODEL ? MIRP_CPERIOD1 : MIRP_CPERIOD0) > 0 && pool_room > NW * CPOOL_ROUNDS * 64) ? NW * CPOOL_ROUNDS * 64 : pool_room;
         unsigned* poolA = (unsigned*)(smem + LY.fml + pool_off);
         unsigned short* poolB = (unsigned short*)(poolA + (pool_cap > 0 ? pool_cap : 0));
         unsigned* poolB32 = poolA + (pool_cap > 0 ? pool_cap : 0);
@@ -168,7 +189,7 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
         int xki = 0;
         if constexpr (MODEL != 0) {
             if (n >= 1 && n <= LCAP - 2)
-                for (int x = tid; x < n; x += LNT) { const unsigned u = seqs[o0 + x] & 0xdfu; if (u == 'X' || u == 'K' || u == 'I') misc[4] = 1; }
+                for (int x = tid; x < n; x += NT) { const unsigned u = seqs[o0 + x] & 0xdfu; if (u == 'X' || u == 'K' || u == 'I') misc[4] = 1; }
             __syncthreads();
             xki = misc[4];
             __syncthreads();
@@ -185,7 +206,7 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
         const int D = (span - 1 < n - 1) ? span - 1 : n - 1;      // largest pair distance
         const int Dm = MODEL ? ((span < n - 1) ? span : n - 1) : D;   // last diagonal of the fill (vienna-1.8.5: fML exists at distance span, c does not)
         // ---- stage sequence, codes, special hairpins, pair-code arrays, triangular offsets
-        for (int x = tid; x <= n + 1; x += LNT) {
+        for (int x = tid; x <= n + 1; x += NT) {
             unsigned char ch = 0;
             if (x >= 1 && x <= n) {
                 ch = seqs[o0 + x - 1];
@@ -195,8 +216,8 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
             seq[x] = ch;
             S[x] = ch == 'A' ? 1 : ch == 'C' ? 2 : ch == 'G' ? 3 : ch == 'U' ? 4 : 0;
         }
-        for (int x = tid; x < DMLR * LCAP; x += LNT) dmlring[x] = (short)I16_INF;
-        for (int x = tid; x < NACC * LCAP; x += LNT) acc[x] = x >= 3 * LCAP ? INF : (int)KEY_NONE;   // ckey x 3 | mdec x 2 (3)
+        for (int x = tid; x < DMLR * LCAP; x += NT) dmlring[x] = (short)I16_INF;
+        for (int x = tid; x < NACC * LCAP; x += NT) acc[x] = x >= 3 * LCAP ? INF : (int)KEY_NONE;   // ckey x 3 | mdec x 2 (3)
         if (tid == 0) {
             misc[1] = 0; misc[2] = 0; misc[3] = 0;
             if constexpr (SPARSE && MODEL != 0) for (int x = 0; x < 44; x++) pbits[x] = 0;
@@ -205,7 +226,7 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
         if (tid >= 64 && tid < 64 + ARCH_RB) rbt[tid - 64] = arch_rowblk_off(tid - 64, n, span);
         __syncthreads();
         if (tid == 0) { S[0] = S[n]; S[n + 1] = S[1]; }
-        for (int x = tid; x <= n; x += LNT) {
+        for (int x = tid; x <= n; x += NT) {
             short s3 = -32768, s4 = -32768, s6 = -32768;
             if (x >= 1) {
                 if (x + 4 <= n)
@@ -236,7 +257,7 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
         __syncthreads();
         // byte-shifted copies 1 - 3 of both pair-code arrays (copy 0 = the arrays themselves, a1_codes4); entries past the ends are never used as codes
         if constexpr (SPARSE) {
-            for (int x = tid; x < 8 * CODE_STR; x += LNT) {
+            for (int x = tid; x < 8 * CODE_STR; x += NT) {
                 const int which = x / (4 * CODE_STR), c = (x / CODE_STR) & 3, y = x % CODE_STR + c;
                 if (c) code4[x] = y < CODE_STR ? (which ? (unsigned char)pax[y] : qbr[y]) : (unsigned char)0;
             }
@@ -282,7 +303,7 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
                     const unsigned pa = (unsigned)(size_t)(__attribute__((address_space(3))) int*)&misc[3];
                     asm volatile("ds_read_b32 %0, %1" : "=v"(pnv) : "v"(pa) : "memory");
                 }
-                for (int k = (LNW - 1 - wave) * 64 + lane; k < lim; k += LNT) {
+                for (int k = (NW - 1 - wave) * 64 + lane; k < lim; k += NT) {
                     const unsigned ea = poolA[k];
                     const unsigned vb = poolB[k];
                     const int s1 = (int)(ea & 511u), j = (int)(ea >> 9);
@@ -290,6 +311,55 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
                     const bool ok = i >= 1 && t >= TURN + 1;
                     const int o = 7 - 4 * n + (__mul24(t, 2 * n + 1 - t) >> 1) + ((t - 4 + (n & 1)) >> 1) + i;     // tri_off(t, n) + i
                     const unsigned sum = (unsigned)fml[ok ? o : 1] + vb;
+                    if (ok && sum < 65535u) atomicMin(&mdec[i], (int)sum - 2 * FML_BIAS);
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pnv) : : "memory");
+                { const int pn = __builtin_amdgcn_readfirstlane(pnv); sp_snap = pn < pool_cap ? pn : pool_cap; }
+            };
+            // Two windows per CU: the operand fML(i, s-1) of pool entry k comes from the window's archive slab (visibility: see the kernel's header).  A lane
+            // owns the entries k0 + r NT; the operands of the first A2_PRE of them are fetched ahead of the interior loops (a2_prefetch, one register
+            // each: 1,024 entries, the benchmark windows end at 925), later ones behind them with the L2 round trip exposed.
+            constexpr int A2_PRE = 2;
+            unsigned a2g[A2_PRE] = {};
+            const unsigned short* fml_g = reinterpret_cast<const unsigned short*>(fml_out);
+            auto a2_entry = [&](int k, int& i, bool& ok) -> int {      // archive offset of entry k's operand on diagonal d (a valid cell for a skipped entry)
+                const unsigned ea = poolA[k];
+                const int s1 = (int)(ea & 511u), j = (int)(ea >> 9);
+                i = j - d;
+                const int t = s1 - i;
+                ok = i >= 1 && t >= TURN + 1;
+                const int i0 = ok ? i - 1 : 0;
+                return ok ? rbt[i0 >> 3] + (i0 & 7) + 8 * (t - 4) : 0;
+            };
+            auto a2_prefetch = [&]() {
+#pragma unroll
+                for (int r = 0; r < A2_PRE; r++) {
+                    const int k = (NW - 1 - wave) * 64 + lane + r * NT;
+                    if (k < sp_snap) { int i; bool ok; a2g[r] = fml_g[a2_entry(k, i, ok)]; }
+                }
+            };
+            auto splits_sparse2 = [&]() {
+                const int lim = sp_snap;
+                int pnv;
+                {
+                    const unsigned pa = (unsigned)(size_t)(__attribute__((address_space(3))) int*)&misc[3];
+                    asm volatile("ds_read_b32 %0, %1" : "=v"(pnv) : "v"(pa) : "memory");
+                }
+                const int k0 = (NW - 1 - wave) * 64 + lane;
+#pragma unroll
+                for (int r = 0; r < A2_PRE; r++) {
+                    const int k = k0 + r * NT;
+                    if (k < lim) {
+                        int i; bool ok;
+                        (void)a2_entry(k, i, ok);
+                        const unsigned sum = a2g[r] + (unsigned)poolB[k];
+                        if (ok && sum < 65535u) atomicMin(&mdec[i], (int)sum - 2 * FML_BIAS);
+                    }
+                }
+                for (int k = k0 + A2_PRE * NT; k < lim; k += NT) {
+                    int i; bool ok;
+                    const unsigned g = fml_g[a2_entry(k, i, ok)];
+                    const unsigned sum = g + (unsigned)poolB[k];
                     if (ok && sum < 65535u) atomicMin(&mdec[i], (int)sum - 2 * FML_BIAS);
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pnv) : : "memory");
@@ -307,7 +377,7 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
                     const unsigned pa = (unsigned)(size_t)(__attribute__((address_space(3))) int*)&misc[3];
                     asm volatile("ds_read_b32 %0, %1" : "=v"(pnv) : "v"(pa) : "memory");
                 }
-                for (int k = (LNW - 1 - wave) * 64 + lane; k < lim; k += LNT) {
+                for (int k = (NW - 1 - wave) * 64 + lane; k < lim; k += NT) {
                     const unsigned lo = poolA[k], hi = poolB32[k];
                     const int p = (int)(lo & 511u), q = (int)((lo >> 9) & 511u);
                     const int valb = (int)(hi & 0xffffu), e5 = -(int)((hi >> 16) & 255u), e3 = -(int)(hi >> 24);
@@ -339,7 +409,7 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
                 // instructions than the split loop itself.
                 if (ncpad != sp_ncpad) {
                     sp_ncpad = ncpad;
-                    sp_nsub = (LNT / ncpad) & ~1;     // even, >= 4 for ncell <= 384
+                    sp_nsub = (NT / ncpad) & ~1;     // even, >= 4 for ncell <= 384
                     sp_pair = tid % ncpad;
                     sp_sub = __builtin_amdgcn_readfirstlane(tid / ncpad);
                     const int t0 = 4 + sp_sub, u0 = d - t0 - 1, s1 = sp_nsub;
@@ -420,8 +490,9 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
             // Half of the waves run the splits before the interior loops: the split loop loads the LDS pipe much more than the interior loops do,
             // so the two halves even out the LDS load of the interval (the phases are independent: both only feed phase B of this diagonal).
             const bool swap_order = !SPARSE && (wave & 1);      // (the sparse splits are too short to matter: measured 0.5 ms better behind the interior loops)
-            auto splits = [&]() { if constexpr (SPARSE && MODEL != 0) splits_sparse185(); else if constexpr (SPARSE) splits_sparse(); else splits_dense(); };
+            auto splits = [&]() { if constexpr (SPARSE && MODEL != 0) splits_sparse185(); else if constexpr (TWO) splits_sparse2(); else if constexpr (SPARSE) splits_sparse(); else splits_dense(); };
             if (swap_order) splits();
+            if constexpr (TWO) a2_prefetch();
             if (dbg_cycles && lane == 0 && !light) wt = clock64();
             // phase A1: interior-loop candidates.  The c ring holds G0(p,q) = c(p,q) + mismatchI[rtype(pq)][S[q+1]][S[p-1]] (+ 32768).
             if (d >= 6 && d <= D) {
@@ -456,9 +527,16 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
                 // roles (0-7: generic rows, 8-13: bulges / 1xn, 14-15: small shapes), measured job costs (MIRP_FOLD_CLOCKS): generic 2-row < small
                 // shapes < generic 4-row < bulges / 1xn.  Phase B of the previous diagonal runs on waves 0-5 (one thread per cell, wave 0 always,
                 // wave 5 rarely), so those waves take the cheapest jobs.
-                const int role = wave < 4 ? wave : wave < 6 ? wave + 10 : wave < 12 ? wave + 2 : wave - 8;
+                // Two windows per CU: eight waves, two roles each, one after the other over all blocks.  The phase-B waves 0-3 take a cheap 2-row generic job
+                // and a bulge / 1xn job (roles w, w + 8), the waves 4-5 (phase-B cells on the first diagonals only) a small-shape and a 3-4-row generic job
+                // (14 | 4, 15 | 5), the waves 6-7 a bulge / 1xn and a 3-4-row generic job (12 | 6, 13 | 7).  Measured against six other maps: all within 2 %,
+                // this one first; three roles on any one wave cost 14 % (profiles/experiments/r7_two_windows_per_cu.txt).
                 A1 a;
                 a.P = P; a.T = &T; a.S = S; a.cring = cring; a.pax = pax; a.qbr = qbr; a.code4 = code4; a.n = n;
+#pragma nounroll
+                for (int pass = 0; pass < (TWO ? 2 : 1); pass++) {
+                const int role = TWO ? (wave < 4 ? wave + 8 * pass : wave < 6 ? (pass ? wave : wave + 10) : (pass ? wave : wave + 6))
+                                     : wave < 4 ? wave : wave < 6 ? wave + 10 : wave < 12 ? wave + 2 : wave - 8;
                 for (int blk = 0; blk < nblk; blk++) {
                     {   // re-materialise the wave-uniform loop parameters per block: keeps the admissibility tests and row offsets as plain
                         // scalar compares inside the block instead of dozens of hoisted masks (SGPR spills)
@@ -611,6 +689,7 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
                     a1_small<0, 0>(a, i, j, type, S[i + 1], S[j - 1], res);
                     if (act && res != KEY_NONE) atomicMin(&ckey[i], res);
                 }
+                }      // pass
                 if (dbg_cycles && lane == 0 && wave == 9 && !light) {   // diagnostics: interior-loop time of one wave by number of blocks
                     const int b = nblk < 3 ? nblk : 3;
                     atomicAdd((unsigned long long*)&dbg_cycles[68 + b], (unsigned long long)(clock64() - wt));
@@ -631,7 +710,8 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
             int cbase = 0, cand = 0; unsigned cent = 0, cval = 0;      // sparse splits: this cell as a split candidate
             unsigned long long cbal = 0;
             const int hp_u = P->hairpinE[d - 1 < MIRP_HP_MAX ? d - 1 : MIRP_HP_MAX - 1];
-            const int od = tri_off(d, n), od1 = tri_off(d - 1, n);
+            // (two windows per CU: fml[] is the ring of the last two diagonals)
+            const int od = TWO ? (d & 1) * FRING_STR : tri_off(d, n), od1 = TWO ? ((d - 1) & 1) * FRING_STR : tri_off(d - 1, n);
             const int x = tid;
             int lt = 0, lbase = 0, loi = 0, ent_terms = 0;
             unsigned long long lbal = 0;
@@ -643,7 +723,9 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
                 lds_vu8 Sv = (lds_vu8)S;
                 const int s_im1 = pb_si & 7, s_i = (pb_si >> 3) & 7, s_ip1 = (pb_si >> 6) & 7, s_jm1 = pb_sj & 7, s_j = (pb_sj >> 3) & 7, s_jp1 = (pb_sj >> 6) & 7;
                 const int s_j2 = (pb_sj >> 9) & 7, s_j3 = (pb_sj >> 12) & 7;      // s_j3: far end of cell (i, j+3), the paired-cell list of diagonal d+3
-                pb_sj = (pb_sj >> 3) | ((int)Sv[j + 4] << 12);      // (S holds LCAP + 8 bytes: in range for every j <= n)
+                // S is staged up to n + 1 only; what lies behind (j + 4 > n + 1, stale bytes) is masked to a base code, so that nothing above the five 3-bit fields
+                // ever slides down into them.  Those far fields (s_j2, s_j3) are only consumed under j + 3 <= n.
+                pb_sj = (pb_sj >> 3) | (((int)Sv[j + 4] & 7) << 12);      // (S holds LCAP + 8 bytes: in range for every j <= n)
                 int md = mdec[i];
                 if constexpr (SPARSE) { md = dml_carry < md ? dml_carry : md; dml_carry = md; }      // DML(i,j) = min(DML(i,j-1), candidate splits)
                 const unsigned kk = ckey[i];
@@ -720,6 +802,7 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
                 carch[abase + 8 * d] = c16;
                 tb_out[abase + 8 * d] = (unsigned short)tb;
                 fml[od + i] = m16;
+                if constexpr (TWO) fml_out[abase + 8 * d] = (short)m16;      // the archive copy, in the layout the epilogue reads: the only full copy of the triangle
                 dmlring[(d % DMLR) * LCAP + i] = md >= INF ? (short)I16_INF : (short)md;
                 ckey[i] = KEY_NONE;
                 if constexpr (SPARSE) { mdec_of(d + 2)[i] = INF; cval = m16; }      // the buffer of diagonal d-1 is dead: it serves diagonal d+2 from the next interval on
@@ -872,7 +955,7 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
             int* cnts = misc + 22;                 // [16]
             int total = misc[3];
             total = total < pool_cap ? total : pool_cap;
-            const int per = ((total + LNW * 64 - 1) / (LNW * 64)) * 64;      // entries per wave (multiple of 64)
+            const int per = ((total + NW * 64 - 1) / (NW * 64)) * 64;      // entries per wave (multiple of 64)
             unsigned ea[CR], eb[CR];
             int nal = 0;
             unsigned long long al[CR];
@@ -893,7 +976,7 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
             if (lane == 0) cnts[wave] = nal;
             __syncthreads();
             int pre = 0, tot = 0;
-            for (int w = 0; w < LNW; w++) { const int c = cnts[w]; pre += w < wave ? c : 0; tot += c; }
+            for (int w = 0; w < NW; w++) { const int c = cnts[w]; pre += w < wave ? c : 0; tot += c; }
 #pragma unroll
             for (int r = 0; r < CR; r++) {
                 if ((al[r] >> lane) & 1ull) {
@@ -946,9 +1029,10 @@ __global__ void __launch_bounds__(LNT) fold_lds_kernel(
             // hand the tables to the epilogue kernel: c and the trace-back codes were archived on the fly, fML is copied out now into the same tiled
             // layout.  A wave takes whole row blocks; lane = diagonal, so the 8 rows of a row block on one diagonal are one 16-byte store and a
             // wave stores contiguous kilobytes; all of a row block's LDS reads are issued before the first store.
-            if (Dm >= 4) {
+            // (two windows per CU: phase B has stored fML there already)
+            if (!TWO && Dm >= 4) {
                 constexpr int NGD = (LDMAX + 1 - 4) / 64 + 1;
-                for (int rb = wave; 8 * rb + 1 + 4 <= n; rb += LNW) {
+                for (int rb = wave; 8 * rb + 1 + 4 <= n; rb += NW) {
                     const int dmax_rb = Dm < n - 1 - 8 * rb ? Dm : n - 1 - 8 * rb;      // the block's first row reaches furthest
                     short* dst = fml_out + rbt[rb] - 32;
                     unsigned v[NGD][8];
@@ -1174,7 +1258,7 @@ size_t fold_lds_epilogue_bytes(int max_lines) {
     return b + sizeof(EpiTables) + 16 + sizeof(short) * XTAB_N + nc + sizeof(short) * nc;
 }
 
-size_t fold_lds_bytes(int max_lines) { (void)max_lines; return lds_layout<0, true>().total; }
+size_t fold_lds_bytes(int max_lines) { (void)max_lines; return lds_layout<0>().total; }      // the largest workgroup of the path (dense pass)
 int fold_lds_max_n() { return LCAP - 2; }
 int fold_lds_gen_wing_d() { return 5; }      // GEN_WD of fold_lds_kernel<0>
 int fold_lds_max_span() { return LSPAN; }
@@ -1186,10 +1270,10 @@ hipError_t launch_fold_lds(hipStream_t stream, int model, int grid, int grid_epi
                            unsigned int* fallback_count, int max_lines, int ss_stride, MirpFoldLine* out_lines, char* out_ss, int* out_nlines, int* out_mfe,
                            int* out_status, int light_clocks, long long* dbg_cycles, hipEvent_t ev_between, int* dense_list, int force_dense) {
     const size_t lds = model ? lds_layout<1>().total : lds_layout<0>().total;
-    const size_t lds_sp = lds_layout<0, true>().total, lds_sp1 = lds_layout<1, true>().total;
+    const size_t lds_sp = lds_layout<0, true, true>().total, lds_sp1 = lds_layout<1, true>().total;
     hipError_t e = hipFuncSetAttribute((const void*)fold_lds_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_layout<1>().total);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fold_lds_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_layout<0>().total);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fold_lds_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sp);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fold_lds_kernel<0, true, LNT2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sp);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fold_lds_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_layout<1, true>().total);
     if (e != hipSuccess) return e;
     const int* no_list = nullptr; const unsigned int* no_count = nullptr;
@@ -1216,7 +1300,21 @@ hipError_t launch_fold_lds(hipStream_t stream, int model, int grid, int grid_epi
         // (pool overflow, no room for a pool: zero on the benchmark inputs; the launch then finds an empty list).  force_dense (tests, A/B timing): the
         // dense instantiation folds everything.
         if (!force_dense) {
-            hipLaunchKernelGGL((fold_lds_kernel<0, true>), dim3(grid), dim3(LNT), lds_sp, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter,
+            // The first pass runs two 512-thread workgroups per CU, which is the whole point of its LDS layout: refuse to run at half the occupancy if a
+            // later change of its LDS or register budget no longer lets two of them share a CU.
+            static int wg_per_cu = 0;
+            if (wg_per_cu == 0) {
+                int nb = 0;
+                e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)fold_lds_kernel<0, true, LNT2>, LNT2, lds_sp);
+                if (e != hipSuccess) return e;
+                wg_per_cu = nb > 0 ? nb : -1;
+            }
+            if (wg_per_cu != 2) {
+                std::fprintf(stderr, "[mirp] fold_lds_kernel<0, true, %d>: %d workgroups per CU instead of 2 (%zu bytes of LDS)\n", LNT2, wg_per_cu, lds_sp);
+                return hipErrorLaunchOutOfResources;
+            }
+            const int grid2 = n_work < 2 * grid ? n_work : 2 * grid;
+            hipLaunchKernelGGL((fold_lds_kernel<0, true, LNT2>), dim3(grid2), dim3(LNT2), lds_sp, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter,
                                fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, light_clocks, dbg_cycles,
                                no_list, no_count, dense_list, work_counter + 3);
             e = hipGetLastError();

@@ -346,7 +346,7 @@ int mirp_run_fold(mirp_ctx* c, const unsigned char* d_seqs, const long long* d_o
     const int* work_list = nullptr;
     int n_generic = n_work;
     if (span <= mirp::fold_lds_max_span() && mirp::fold_lds_bytes(max_lines) <= 160 * 1024) {
-        // fill kernel (one 1024-thread workgroup per CU, tables in LDS) + epilogue kernel (many small workgroups) per sub-batch;
+        // fill kernel (default model: two 512-thread workgroups per CU; dense pass and vienna-1.8.5: one of 1024; tables in LDS) + epilogue kernel (many small workgroups) per sub-batch;
         // the two exchange the c / fML triangles of every window through per-window slabs in HBM
         const size_t slab = mirp::fold_lds_slab_shorts(std::min(n_cap, mirp::fold_lds_max_n() + 2));
         const int sub = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_work, ((size_t)8 << 30) / (slab * 6)));   // three 16-bit triangles per window: c, fML, trace-back codes

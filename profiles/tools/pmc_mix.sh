@@ -8,7 +8,7 @@ import csv, glob, collections
 for f in glob.glob("gpurun_out/mix/**/*counter_collection.csv", recursive=True):
     agg = collections.defaultdict(float); n = collections.defaultdict(set)
     for r in csv.DictReader(open(f)):
-        if "fold_lds_kernel<0, true>" in r["Kernel_Name"]:
+        if "fold_lds_kernel<0, true" in r["Kernel_Name"]:
             agg[r["Counter_Name"]] += float(r["Counter_Value"]); n[r["Counter_Name"]].add(r["Dispatch_Id"])
     for k in sorted(agg): print("mix %-28s %.4g per launch" % (k, agg[k] / max(1, len(n[k]))))
 PY
