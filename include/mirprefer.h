@@ -508,6 +508,29 @@ typedef struct {
 int mirp_cluster_scan(mirp_ctx* ctx, const MirpClusterOpts* opts, MirpCluster** clusters, int64_t* n_clusters, int64_t** sample_counts,
                       int64_t stats[5]);
 
+/* Degradome (PARE / GMUCT) evidence of miRNA-guided cleavage on the context's resident alignments (after any SAM ingest, or after
+ * mirp_load_alignments): the degradome reads aligned to the transcripts.  A sense record (plus strand, 1 <= pos <= LN) is a read of the unit (tid,
+ * pos); a unit's abundance is the sum of its records' depths; its category 0..4 follows CleaveLand's (4: one read; 0: the transcript's only maximum;
+ * 1: one of several maxima; 2: above the transcript's mean over occupied positions; 3: the rest).  Every miRNA is evaluated at every unit of category
+ * <= max_category, only at the site whose position 10 pairs with the unit's position, with the score and the cleavage_site rule of mirp_target_scan;
+ * a hit has half-score <= max_half_score and p <= alpha, p = 1 - (1 - c_k / P)^N with N = the miRNA's plus-strand sites in all transcripts at or
+ * below the hit's score, c_k = the units of the hit's category or better, P = the transcripts' bases.  contig_names (n_contigs NUL-terminated
+ * strings) and contig_len are the @SQ lines the records' tids index: each must be a transcript of the FASTA with that length. */
+typedef struct {
+    int32_t max_half_score, cleavage_site, max_category, n_contigs;
+    double alpha;                   /* 0 < alpha <= 1 */
+    const char* contig_names;
+    const int64_t* contig_len;
+} MirpDegradomeOpts;
+/* Reads the miRNA FASTA and the transcript FASTA as mirp_target_scan does (same refusals) and writes the TSV of §18 to out_path: a header line, then
+ * one line per hit ordered by miRNA (file order), category, score, transcript (FASTA order), cleavage position.  Further refusals (-10): an @SQ contig
+ * that is not in the FASTA or has another length there.  On any error the file at out_path is removed.  Out: stats = {miRNAs, transcripts, bases,
+ * records, sense records, minus-strand records, units, C_0 .. C_4, evaluations (kept units x miRNAs), hits written, passes}; seconds = {parse, upload,
+ * units + categories, site counts, anchored counts, key passes + sort + write}.  Passes hold at most mirp_set_target_capacity keys.  Nothing
+ * resident changes. */
+int mirp_degradome_scan(mirp_ctx* ctx, const char* mirna_path, const char* transcripts_path, const MirpDegradomeOpts* opts, const char* out_path,
+                        int64_t stats[15], double seconds[6]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import early
 from .early import LIB_PATH, FastaData, SamData
-ABI_VERSION = 13     # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
+ABI_VERSION = 14     # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
 
 
 class MirpError(RuntimeError):
@@ -60,6 +60,15 @@ CLUSTER_DTYPE = np.dtype([("tid", "<i4"), ("major_strand", "<i4"), ("major_len",
                           ("reads", "<i8"), ("plus_reads", "<i8"), ("placements", "<i8"), ("major_pos", "<i8"), ("major_reads", "<i8"),
                           ("sizes", "<i8", (7,))])
 CLUSTER_STATS = ("records", "total", "islands", "clusters", "assigned")
+
+
+class DegradomeOpts(C.Structure):
+    """MirpDegradomeOpts of include/mirprefer.h."""
+    _fields_ = [("max_half_score", C.c_int32), ("cleavage_site", C.c_int32), ("max_category", C.c_int32), ("n_contigs", C.c_int32), ("alpha", C.c_double),
+                ("contig_names", C.c_char_p), ("contig_len", C.c_void_p)]
+
+
+DEGRADOME_STATS = ("mirnas", "transcripts", "bases", "records", "sense", "minus", "units", "c0", "c1", "c2", "c3", "c4", "evaluations", "hits", "passes")
 
 
 def report_readmapping(loci, ss_list, alns, contig_arrays, sample_names, counts0):
@@ -393,6 +402,8 @@ def load_library():
     lib.mirp_phase_scan.restype = C.c_int
     lib.mirp_cluster_scan.argtypes = [vp, C.POINTER(ClusterOpts), C.POINTER(vp), i64p, C.POINTER(vp), i64p]
     lib.mirp_cluster_scan.restype = C.c_int
+    lib.mirp_degradome_scan.argtypes = [vp, C.c_char_p, C.c_char_p, C.POINTER(DegradomeOpts), C.c_char_p, i64p, C.POINTER(C.c_double)]
+    lib.mirp_degradome_scan.restype = C.c_int
     lib.mirp_dist_unique_id.argtypes = [vp]
     lib.mirp_dist_unique_id.restype = C.c_int
     lib.mirp_dist_init.argtypes = [vp, vp, C.c_int32, C.c_int32]
@@ -538,6 +549,26 @@ class Context:
         clusters = _copy_out(self.lib, ptr, CLUSTER_DTYPE, nc.value)
         counts = _copy_out(self.lib, cnt, np.dtype("<i8"), nc.value * int(n_samples)).reshape(nc.value, int(n_samples))
         return clusters, counts, dict(zip(CLUSTER_STATS, list(st)))
+
+    def degradome_scan(self, mirna_path, transcripts_path, out_path, contig_names, contig_lens, max_half_score=8, cleavage_site=False, max_category=4,
+                       alpha=1.0):
+        """Degradome (PARE) evidence of miRNA-guided cleavage on this context's resident alignments (mirp_degradome_scan): writes the TSV
+        to out_path.  contig_names / contig_lens: the @SQ lines the records' tids index.  max_half_score = 2 x the -s score.  -> {mirnas, transcripts,
+        bases, records, sense, minus, units, c0 .. c4, evaluations, hits, passes, seconds}; seconds = {parse, upload, units + categories, site counts,
+        anchored counts, key passes + sort + write}."""
+        lens = np.ascontiguousarray(contig_lens, dtype=np.int64)
+        if len(lens) != len(contig_names):
+            raise ValueError("degradome_scan: contig_names and contig_lens differ in length")
+        o = DegradomeOpts()
+        o.max_half_score, o.cleavage_site, o.max_category, o.n_contigs, o.alpha = int(max_half_score), int(bool(cleavage_site)), int(max_category), len(lens), float(alpha)
+        blob = C.create_string_buffer(b"".join((n.encode() if isinstance(n, str) else bytes(n)) + b"\0" for n in contig_names) + b"\0")
+        o.contig_names = C.cast(blob, C.c_char_p)
+        o.contig_len = lens.ctypes.data if len(lens) else None
+        st = (C.c_int64 * 15)()
+        sec = (C.c_double * 6)()
+        self._check(self.lib.mirp_degradome_scan(self.h, os.fsencode(mirna_path), os.fsencode(transcripts_path), C.byref(o), os.fsencode(out_path), st, sec),
+                    "mirp_degradome_scan")
+        return dict(zip(DEGRADOME_STATS, list(st)), seconds=list(sec))
 
     def fold_batch(self, seqs, span, max_lines=96):
         """RNALfold -L replacement. seqs: list of str/bytes. Returns a list (per sequence) of

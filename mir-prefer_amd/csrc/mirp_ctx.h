@@ -159,6 +159,18 @@ int mirp_device_target_scan(mirp_ctx* c, const unsigned long long* pk, const uns
                             const std::vector<unsigned long long>& cstart, const std::string& tnames, const std::vector<long long>& tnoff,
                             std::vector<TgMirna>& mi, const std::vector<unsigned char>& mcodes, const std::string& mnames, const std::vector<long long>& mnoff,
                             const MirpTargetOpts& o, const std::function<int(const char*, size_t)>& sink, long long stats[2], double seconds[4]);
+// degradome_kernels.hip: the cleavage scan of the resident alignments against packed transcripts (mirp_degradome.cpp parses the files and writes the
+// lines).  sqstart / sqlen: first packed position and length of the transcript of every SAM tid; f2s: FASTA index -> SAM tid (-1: no @SQ line);
+// mi / mi_anchored: the masks of make_mirna without / with `anchored`.  Hits arrive at the sink in output order, pass by pass: key = miRNA index in
+// its group of 2^16 << 40 | category << 37 | half-score << 32 | packed position of the cleavage base; sites[mloc * 17 + h] = N_m(h) and
+// pval[(mloc * 5 + category) * 17 + h] belong to the group at mbase.  stats = {records, sense, minus-strand, units, C_0 .. C_4, evaluations, hits,
+// passes}; seconds = {upload, units + categories + windows, site counts, anchored counts, key passes + sort + download + write}.
+struct MirpDgHit { unsigned long long key, reads, tmax; };
+typedef std::function<int(int mbase, const MirpDgHit* hits, size_t n, const unsigned long long* sites, const double* pval)> MirpDgSink;
+int mirp_device_degradome(mirp_ctx* c, const unsigned long long* pk, const unsigned* amb, const unsigned* cst, long long total,
+                          const std::vector<unsigned long long>& cstart, const std::vector<int>& f2s, const std::vector<unsigned long long>& sqstart,
+                          const std::vector<long long>& sqlen, std::vector<TgMirna>& mi, std::vector<TgMirna>& mi_anchored, int max_half, int max_cat, double alpha,
+                          const MirpDgSink& sink, long long stats[12], double seconds[6]);
 int mirp_device_mask_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long* n_io, MirpAln* d_segs, MirpAln* d_segtmp, const int* d_owner, const int* d_seg_span,
                           long long* nseg_io,
                           const long long* d_rfirst, const int* d_rstart, const int* d_remax);

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include "mirp_fasta.h"
+#include "mirp_mirna.h"
 
 namespace {
 
@@ -24,12 +25,9 @@ const RnaCodes kRna;
 
 const long long kMaxMirnas = 1ll << 24;
 
-struct Mirnas {
-    std::string names;                  // concatenated
-    std::vector<long long> noff{0};
-    std::vector<unsigned char> codes;   // 32 per miRNA
-    std::vector<int> lens;
-};
+}  // namespace
+
+namespace mirp {
 
 // the miRNA FASTA of §14; refusals name the 1-based record
 int parse_mirnas(mirp_ctx* c, const char* path, Mirnas& M) {
@@ -77,17 +75,20 @@ int parse_mirnas(mirp_ctx* c, const char* path, Mirnas& M) {
     return finish();
 }
 
-// the masks of one miRNA (codes cd[0 .. L), position i = 1 .. L at cd[i - 1]) for both strands; -c sets the cleavage masks
-TgMirna make_mirna(const unsigned char* cd, int L, bool cleavage) {
+// the masks of one miRNA (codes cd[0 .. L), position i = 1 .. L at cd[i - 1]) for both strands; -c sets the cleavage masks.  anchored: the plus
+// strand's masks for a window whose last base pairs with miRNA position 1 (position i at j = 32 - i; the degradome scan), s[1] unused
+TgMirna make_mirna(const unsigned char* cd, int L, bool cleavage, bool anchored) {
     TgMirna m;
     std::memset(&m, 0, sizeof m);
     m.L = L;
     m.lmask = L == 32 ? 0xffffffffu : (1u << L) - 1u;
+    if (anchored) m.lmask <<= 32 - L;
     for (int i = 1; i <= L; i++) {
         const unsigned k = cd[i - 1];
         for (int s = 0; s < 2; s++) {
             TgStrand& S = m.s[s];
-            const int j = s ? i - 1 : L - i;             // window position paired with miRNA position i
+            if (anchored && s) continue;
+            const int j = anchored ? 32 - i : s ? i - 1 : L - i;      // window position paired with miRNA position i
             const unsigned bit = 1u << j;
             if (k > 3) S.unk |= bit;
             else {
@@ -104,7 +105,11 @@ TgMirna make_mirna(const unsigned char* cd, int L, bool cleavage) {
     return m;
 }
 
-}  // namespace
+}  // namespace mirp
+
+using mirp::Mirnas;
+using mirp::make_mirna;
+using mirp::parse_mirnas;
 
 extern "C" int mirp_set_target_capacity(mirp_ctx* c, int64_t keys) {
     if (!c) return -1;
@@ -127,7 +132,7 @@ extern "C" int mirp_target_scan(mirp_ctx* c, const char* mirna_path, const char*
     if (int rc = mirp::pack_fasta(c, target_paths, n_targets, ref)) { std::remove(out_path); return rc; }
     const long long n_mi = (long long)M.lens.size();
     std::vector<TgMirna> mi((size_t)n_mi);
-    for (long long m = 0; m < n_mi; m++) mi[(size_t)m] = make_mirna(M.codes.data() + 32 * m, M.lens[(size_t)m], o->cleavage_site != 0);
+    for (long long m = 0; m < n_mi; m++) mi[(size_t)m] = make_mirna(M.codes.data() + 32 * m, M.lens[(size_t)m], o->cleavage_site != 0, false);
     ref.pk.resize((size_t)(2 * ((ref.total + 31) / 32 + 2)), 0u);          // whole 64-bit words, one past the last window
     sec[0] = tg_clock() - t;
 

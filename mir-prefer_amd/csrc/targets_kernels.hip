@@ -11,7 +11,8 @@
 //     mm    = nonwc & ~gu
 //     half  = popc(nonwc) + popc(mm) + popc(nonwc & seed) + popc(mm & seed)      the score in half-units: mismatch 2, G:U 1, doubled in the seed
 // and the site is a hit when smin <= half <= smax, mm & cleave == 0 and L <= stop, stop = the distance to the first ambiguous base or to the next
-// contig start (per lane, computed once).
+// contig start (per lane, computed once).  The packed-target types, the evaluation and the scan kernel are in targets_device.h, which the degradome
+// scan (degradome_kernels.hip) shares.
 //
 //   scan   tg_scan_kernel<0>: one lane per target offset, miRNAs of the pass in wave-uniform (scalar) loads; every hit appends the key
 //          mloc << 38 | half << 33 | o << 1 | strand (mloc = the miRNA's index in its group of <= 2^16) to a buffer of `cap` keys and counts it.
@@ -29,87 +30,10 @@
 #include <string>
 #include <vector>
 #include "mirp_ctx.h"
+#include "targets_device.h"
 #include "text_out.h"
 
 namespace mirp {
-
-#define TG_GROUP (1 << 16)           // miRNAs per group (the key holds 16 bits of miRNA index)
-#define TG_NHALF 17                  // half-scores 0 .. 16
-#define TG_LAUNCH_POS (1ll << 30)    // offsets per scan launch (the grid's work-items stay below 2^32)
-
-struct TgRef {
-    const unsigned long long* pk;
-    const unsigned* amb;
-    const unsigned* cst;
-    unsigned long long total;
-};
-
-__device__ __forceinline__ unsigned tg_base(const unsigned long long* __restrict__ pk, unsigned long long q) { return (unsigned)(pk[q >> 5] >> (2 * (q & 31))) & 3u; }
-
-// the even bits of x, packed into 32 bits
-__device__ __forceinline__ unsigned tg_even(unsigned long long x) {
-    x &= 0x5555555555555555ull;
-    x = (x | (x >> 1)) & 0x3333333333333333ull;
-    x = (x | (x >> 2)) & 0x0f0f0f0f0f0f0f0full;
-    x = (x | (x >> 4)) & 0x00ff00ff00ff00ffull;
-    x = (x | (x >> 8)) & 0x0000ffff0000ffffull;
-    x = (x | (x >> 16)) & 0x00000000ffffffffull;
-    return (unsigned)x;
-}
-
-__device__ __forceinline__ unsigned tg_bits32(const unsigned* __restrict__ bm, unsigned long long p) {
-    const unsigned long long w = bm[p >> 5] | ((unsigned long long)bm[(p >> 5) + 1] << 32);
-    return (unsigned)(w >> (p & 31));
-}
-
-// one strand of one miRNA: a hit when (half - smin) <= span (unsigned) and no mismatch under the cleavage mask
-__device__ __forceinline__ bool tg_eval(const TgStrand& S, unsigned lmask, unsigned wl, unsigned wh, unsigned x1, unsigned x2, unsigned smin, unsigned span,
-                                        unsigned* half) {
-    const unsigned nonwc = ((wl ^ S.pl) | (wh ^ S.ph) | S.unk) & lmask;
-    const unsigned gu = (x1 & S.g1) | (x2 & S.g2);
-    const unsigned mm = nonwc & ~gu;
-    const unsigned h = __popc(nonwc) + __popc(mm) + __popc(nonwc & S.seed) + __popc(mm & S.seed);
-    *half = h;
-    return h - smin <= span && (mm & S.cleave) == 0;
-}
-
-// MODE 0: keys (keys[0 .. cap), counter[0] = hits, also past cap); MODE 1: hist[mloc * 17 + half] += hits.  miRNAs [m0, m1) of the group's
-// array, offsets [p0, p1).
-template <int MODE, bool BOTH>
-__global__ __launch_bounds__(256) void tg_scan_kernel(TgRef R, const TgMirna* __restrict__ mi, int m0, int m1, unsigned long long p0, unsigned long long p1,
-                                                      unsigned long long* __restrict__ keys, unsigned long long cap, unsigned long long* __restrict__ counter,
-                                                      unsigned long long* __restrict__ hist) {
-    const unsigned long long o = p0 + (unsigned long long)blockIdx.x * 256u + threadIdx.x;
-    unsigned wl = 0, wh = 0, stop = 0;                         // a lane past p1 has stop 0: no miRNA (L >= 12) fits
-    if (o < p1) {
-        const unsigned long long q = o >> 5;
-        const unsigned sh = 2 * (unsigned)(o & 31);
-        unsigned long long w = R.pk[q];
-        if (sh) w = (w >> sh) | (R.pk[q + 1] << (64 - sh));
-        wl = tg_even(w);
-        wh = tg_even(w >> 1);
-        const unsigned sm = tg_bits32(R.amb, o) | (tg_bits32(R.cst, o) & ~1u);
-        stop = sm ? (unsigned)(__ffs(sm) - 1) : 32u;
-    }
-    const unsigned tA = ~(wl | wh), tC = wl & ~wh, tG = ~wl & wh, tT = wl & wh;
-    for (int m = m0; m < m1; m++) {
-        const TgMirna& M = mi[m];
-        if ((unsigned)M.L > stop) continue;
-        const unsigned span = (unsigned)(M.smax - M.smin);
-        unsigned h;
-        #pragma unroll
-        for (int s = 0; s < (BOTH ? 2 : 1); s++) {
-            if (tg_eval(M.s[s], M.lmask, wl, wh, s ? tA : tT, s ? tC : tG, (unsigned)M.smin, span, &h)) {
-                if (MODE == 0) {
-                    const unsigned long long i = atomicAdd(counter, 1ull);
-                    if (i < cap) keys[i] = ((unsigned long long)m << 38) | ((unsigned long long)h << 33) | (o << 1) | (unsigned long long)s;
-                } else {
-                    atomicAdd(&hist[(long long)m * TG_NHALF + h], 1ull);
-                }
-            }
-        }
-    }
-}
 
 // ---------------------------------------------------------------- text
 struct TgText {
