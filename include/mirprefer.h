@@ -531,6 +531,27 @@ typedef struct {
 int mirp_degradome_scan(mirp_ctx* ctx, const char* mirna_path, const char* transcripts_path, const MirpDegradomeOpts* opts, const char* out_path,
                         int64_t stats[15], double seconds[6]);
 
+/* Annotation of miRNAs against known miRNAs: every query against every kept known sequence, same sense, ungapped.  At shift d
+ * query position i lies on known position i + d; offset5 = d, offset3 = Lq + d - Lk, mismatches over the overlap (an unknown letter mismatches
+ * everything); a shift is admissible when |offset5| <= max_offset (0..4), |offset3| <= max_offset and mismatches <= max_mismatches (0..6); a pair
+ * with an admissible shift is a hit, reported at the shift that minimises (distance = mismatches + |offset5| + |offset3|, mismatches, |d|, d).
+ * max_lines: the first N lines per query in output order (0 = all).  species: n_species NUL-terminated prefixes; with n_species > 0 only the known
+ * sequences whose id starts with one of them followed by '-' are kept. */
+typedef struct {
+    int32_t max_offset, max_mismatches, n_species, reserved;
+    int64_t max_lines;
+    const char* species;
+} MirpAnnotateOpts;
+/* Reads the query FASTA as mirp_target_scan reads its miRNA FASTA (same refusals) and the known FASTA files known_paths[0 .. n_known) with the same
+ * rules, except that a record of length outside 12..32 is skipped and counted and that the id is the first word of the header; at most 2^24 known
+ * sequences are kept (-10 beyond).  Writes the hits TSV of §19 to out_path (a header line, then one line per hit ordered by query (file order),
+ * distance, mismatches, known (file order)) and one line per query to summary_path.  On any error both files are removed.  Out: stats = {queries,
+ * known kept, known skipped, pairs, evaluations (pairs x shifts with both offsets within max_offset), hits, identical, isomir, homolog, novel, lines
+ * written, passes}, seconds = {parse, upload, counting scan, key scans, sort + cut, download + write}.  Passes hold at most
+ * mirp_set_target_capacity keys.  Nothing resident changes. */
+int mirp_annotate_scan(mirp_ctx* ctx, const char* query_path, const char* const* known_paths, int32_t n_known, const MirpAnnotateOpts* opts,
+                       const char* out_path, const char* summary_path, int64_t stats[12], double seconds[6]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import early
 from .early import LIB_PATH, FastaData, SamData
-ABI_VERSION = 14     # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
+ABI_VERSION = 15     # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
 
 
 class MirpError(RuntimeError):
@@ -38,6 +38,15 @@ class TargetOpts(C.Structure):
 
 
 TARGET_STATS = ("mirnas", "targets", "bases", "evaluations", "sites", "passes")
+
+
+class AnnotateOpts(C.Structure):
+    """MirpAnnotateOpts of include/mirprefer.h."""
+    _fields_ = [("max_offset", C.c_int32), ("max_mismatches", C.c_int32), ("n_species", C.c_int32), ("reserved", C.c_int32), ("max_lines", C.c_int64),
+                ("species", C.c_char_p)]
+
+
+ANNOTATE_STATS = ("queries", "known", "skipped", "pairs", "evaluations", "hits", "identical", "isomir", "homolog", "novel", "lines", "passes")
 
 
 class PhaseOpts(C.Structure):
@@ -396,6 +405,9 @@ def load_library():
     lib.mirp_trim_reads.restype = C.c_int
     lib.mirp_target_scan.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(TargetOpts), C.c_char_p, i64p, C.POINTER(C.c_double)]
     lib.mirp_target_scan.restype = C.c_int
+    lib.mirp_annotate_scan.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(AnnotateOpts), C.c_char_p, C.c_char_p, i64p,
+                                       C.POINTER(C.c_double)]
+    lib.mirp_annotate_scan.restype = C.c_int
     lib.mirp_set_target_capacity.argtypes = [vp, C.c_int64]
     lib.mirp_set_target_capacity.restype = C.c_int
     lib.mirp_phase_scan.argtypes = [vp, C.POINTER(PhaseOpts), vp, C.POINTER(vp), i64p, i64p]
@@ -521,6 +533,24 @@ class Context:
     def set_target_capacity(self, keys):
         """Sites one target_scan pass holds on the device (0 = the default, 2^26; at least 2): lowered only to test the overflow path."""
         self._check(self.lib.mirp_set_target_capacity(self.h, int(keys)), "mirp_set_target_capacity")
+
+    def annotate_scan(self, query_path, known_paths, out_path, summary_path, max_offset=2, max_mismatches=2, max_lines=0, species=()):
+        """Known-miRNA annotation (mirp_annotate_scan): every sequence of query_path against the known FASTA files, in order; writes
+        the hits TSV to out_path and one line per query to summary_path.  species: prefixes of the known ids to keep (empty = all).  -> {queries,
+        known, skipped, pairs, evaluations, hits, identical, isomir, homolog, novel, lines, passes, seconds}; seconds = {parse, upload, counting
+        scan, key scans, sort + cut, download + write}.  Passes hold at most set_target_capacity keys."""
+        o = AnnotateOpts()
+        o.max_offset, o.max_mismatches, o.max_lines = int(max_offset), int(max_mismatches), int(max_lines)
+        sp = [x.encode() if isinstance(x, str) else bytes(x) for x in species]
+        blob = C.create_string_buffer(b"".join(x + b"\0" for x in sp) + b"\0")
+        o.n_species = len(sp)
+        o.species = C.cast(blob, C.c_char_p)
+        arr = (C.c_char_p * len(known_paths))(*[os.fsencode(p) for p in known_paths])
+        st = (C.c_int64 * 12)()
+        sec = (C.c_double * 6)()
+        self._check(self.lib.mirp_annotate_scan(self.h, os.fsencode(query_path), arr, len(known_paths), C.byref(o), os.fsencode(out_path),
+                                                os.fsencode(summary_path), st, sec), "mirp_annotate_scan")
+        return dict(zip(ANNOTATE_STATS, list(st)), seconds=list(sec))
 
     def phase_scan(self, length, cycles, kmin, min_phased=3, min_depth=1):
         """Phased siRNA windows on this context's resident alignments (mirp_phase_scan).  kmin: the int32 table of the smallest

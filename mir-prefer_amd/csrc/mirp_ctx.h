@@ -120,6 +120,9 @@ struct mirp_ctx {
     DevBuf tg_pk, tg_amb, tg_cst, tg_cstart, tg_names, tg_noff, tg_mcodes, tg_mnames, tg_mnoff, tg_mi, tg_emitted, tg_hist, tg_small, tg_keys, tg_ktmp,
         tg_size, tg_toff, tg_text;
     long long tg_cap = 0;             // keys held per pass; 0 = the default, 2^26 (mirp_set_target_capacity)
+    // ---- known-miRNA annotation (annotate_kernels.hip, mirp_annotate.cpp): the packed and the planar sequences, the hits per query and the cut
+    // tables of one pass; the keys use tg_keys / tg_ktmp / tg_small / tg_hist
+    DevBuf an_pack, an_q, an_k, an_cnt, an_run, an_out, an_kept;
     long long n_result = 0;           // records of the last mirp_predict (p_res / p_text), what mirp_gather_loci sends
     bool have_result = false;
 };
@@ -171,6 +174,15 @@ int mirp_device_degradome(mirp_ctx* c, const unsigned long long* pk, const unsig
                           const std::vector<unsigned long long>& cstart, const std::vector<int>& f2s, const std::vector<unsigned long long>& sqstart,
                           const std::vector<long long>& sqlen, std::vector<TgMirna>& mi, std::vector<TgMirna>& mi_anchored, int max_half, int max_cat, double alpha,
                           const MirpDgSink& sink, long long stats[12], double seconds[6]);
+// annotate_kernels.hip: the comparison of packed queries with packed known sequences (mirp_annotate.cpp parses the files and writes the lines).
+// AnPacked: position i's 2-bit code (A C G U = 0..3, 0 where unknown) at bits 2 i of `word`, bit i of `unk` set where unknown, `len` 12..32.
+// hits_per_query is filled (hits before the -k cut) before the first sink call.  Kept keys arrive at the sink in output order, group by group:
+// key = query index - qbase << 35 | distance << 31 | mismatches << 28 | known index << 4 | shift + 4.  stats = {hits, keys kept, passes};
+// seconds = {upload, counting scan, key scans, sort + cut, download + write}.
+struct AnPacked { unsigned long long word; unsigned unk; int len; };
+typedef std::function<int(long long qbase, const unsigned long long* keys, size_t n)> MirpAnSink;
+int mirp_device_annotate(mirp_ctx* c, const std::vector<AnPacked>& q, const std::vector<AnPacked>& k, int max_offset, int max_mismatches, long long max_lines,
+                         std::vector<unsigned>& hits_per_query, const MirpAnSink& sink, long long stats[3], double seconds[5]);
 int mirp_device_mask_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long* n_io, MirpAln* d_segs, MirpAln* d_segtmp, const int* d_owner, const int* d_seg_span,
                           long long* nseg_io,
                           const long long* d_rfirst, const int* d_rstart, const int* d_remax);

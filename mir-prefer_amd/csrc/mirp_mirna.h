@@ -1,4 +1,5 @@
-// The miRNA FASTA of DESIGN.md §14 and the per-miRNA masks of the scans (mirp_targets.cpp), shared by mirp_target_scan and mirp_degradome_scan.
+// The miRNA FASTA of DESIGN.md §14 and the per-miRNA masks of the scans (mirp_targets.cpp), shared by mirp_target_scan, mirp_degradome_scan
+// and mirp_annotate_scan.
 #pragma once
 #include <string>
 #include <vector>
@@ -13,8 +14,9 @@ struct Mirnas {
     std::vector<int> lens;
 };
 
-// parses path with §14's rules; refusals (-10) name the 1-based record
-int parse_mirnas(mirp_ctx* c, const char* path, Mirnas& M);
+// parses path with §14's rules and appends its records to M; refusals (-10) name the 1-based record.  With `skipped` (the known sequences of
+// §19) a record whose length is outside 12..32 is dropped and counted there instead of refused, and the caller bounds the number of records.
+int parse_mirnas(mirp_ctx* c, const char* path, Mirnas& M, long long* skipped = nullptr);
 // the masks of one miRNA (codes cd[0 .. L)); anchored: plus strand only, miRNA position i at window position 32 - i
 TgMirna make_mirna(const unsigned char* cd, int L, bool cleavage, bool anchored);
 

@@ -29,8 +29,8 @@ const long long kMaxMirnas = 1ll << 24;
 
 namespace mirp {
 
-// the miRNA FASTA of §14; refusals name the 1-based record
-int parse_mirnas(mirp_ctx* c, const char* path, Mirnas& M) {
+// the miRNA FASTA of §14; refusals name the 1-based record.  skipped: lengths outside 12..32 are dropped and counted, not refused (§19)
+int parse_mirnas(mirp_ctx* c, const char* path, Mirnas& M, long long* skipped) {
     std::string buf;
     if (int rc = mirp::read_whole(c, path, buf)) return rc;
     long long rec = 0, len = 0;
@@ -39,6 +39,13 @@ int parse_mirnas(mirp_ctx* c, const char* path, Mirnas& M) {
     auto finish = [&]() -> int {
         if (!open) return 0;
         open = false;
+        if ((len < 12 || len > 32) && skipped) {
+            M.noff.pop_back();
+            M.names.resize((size_t)M.noff.back());
+            M.codes.resize(M.codes.size() - 32);
+            ++*skipped;
+            return 0;
+        }
         if (len < 12 || len > 32) return refuse("the sequence has " + std::to_string(len) + " nt (12..32 allowed)");
         M.lens.push_back((int)len);
         return 0;
@@ -52,7 +59,7 @@ int parse_mirnas(mirp_ctx* c, const char* path, Mirnas& M) {
         if (*raw == '>') {
             if (int r = finish()) return r;
             rec++;
-            if (rec > kMaxMirnas) return refuse("more than 16,777,216 miRNAs");
+            if (rec > kMaxMirnas && !skipped) return refuse("more than 16,777,216 miRNAs");
             const char* h = raw + 1;
             while (h < b && mirp::fa_ws((unsigned char)*h)) h++;
             if (h == b) return refuse("a header without a name");
