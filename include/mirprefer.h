@@ -451,22 +451,24 @@ int mirp_trim_reads(mirp_ctx* ctx, const char* data, int64_t n, const char* name
 /* Plant miRNA target sites: every miRNA against every offset of every target, ungapped, scored by position-weighted mismatches
  * (mismatch 1, G:U 0.5, doubled at miRNA positions 2..13) in half-units.  max_half_score 0..16 (= 2 x the -s score); both_strands: also the minus
  * strand; cleavage_site: reject a site with a mismatch (not a G:U) at miRNA position 10 or 11; max_sites: the first N sites per miRNA in output
- * order (0 = all). */
+ * order (0 = all); bulge (0 or 1): also the sites with exactly one unpaired nucleotide, on the target (tP) or on the miRNA (mP), and a last
+ * column `bulge` on every line (§14, "Bulged sites"); 0 leaves every byte of the output as it was. */
 typedef struct {
-    int32_t max_half_score, both_strands, cleavage_site, reserved;
+    int32_t max_half_score, both_strands, cleavage_site, bulge;
     int64_t max_sites;
 } MirpTargetOpts;
 /* Reads the miRNA FASTA mirna_path (name = the whole header after '>', stripped, tabs turned into spaces; multi-line sequences concatenated; A C G U T
  * in either case, T = U, any other letter unknown) and the target FASTA files target_paths[0 .. n_targets) (parsed and packed as mirp_align_index
  * does), and writes the TSV of §14 to out_path: a header line, then one line per site ordered by miRNA (file order), score, target (file order),
- * start, + before -.  Refusals, each before out_path is opened (-10, the 1-based record in mirp_last_error): a miRNA of length outside 12..32, an
+ * start, + before -, end.  Refusals, each before out_path is opened (-10, the 1-based record in mirp_last_error): a miRNA of length outside 12..32, an
  * empty name, a byte >= 0x80, more than 2^24 miRNAs; and the target refusals of mirp_align_index.  On any error the file at out_path is removed.
  * Out: stats = {miRNAs, targets, target bases, evaluations (offsets x miRNAs x strands), sites written, passes}, seconds = {parse, upload, scan,
  * sort + cut, emit + download + write}. */
 int mirp_target_scan(mirp_ctx* ctx, const char* mirna_path, const char* const* target_paths, int32_t n_targets, const MirpTargetOpts* opts,
                      const char* out_path, int64_t stats[6], double seconds[5]);
 /* Keys (sites before the -k cut) one pass of mirp_target_scan holds on the device, at least 2; 0 = the default, 2^26.  A pass that finds more is
- * split into passes by (miRNA, score) and by ranges of offsets; lowered only to test that path. */
+ * split into passes by (miRNA, score) and by ranges of offsets; lowered only to test that path.  With bulge a pass holds at least 4 keys whatever
+ * is set here: the most one offset can hold of one miRNA and score (t and m on both strands), so that the split always ends. */
 int mirp_set_target_capacity(mirp_ctx* ctx, int64_t keys);
 
 /* Phased siRNA (PHAS) windows on the context's resident alignments (after any SAM ingest, or after mirp_load_alignments).  A record

@@ -34,7 +34,7 @@ TRIM_STATS = ("reads", "quality_trimmed", "adapter", "untrimmed", "too_short", "
 
 class TargetOpts(C.Structure):
     """MirpTargetOpts of include/mirprefer.h."""
-    _fields_ = [("max_half_score", C.c_int32), ("both_strands", C.c_int32), ("cleavage_site", C.c_int32), ("reserved", C.c_int32), ("max_sites", C.c_int64)]
+    _fields_ = [("max_half_score", C.c_int32), ("both_strands", C.c_int32), ("cleavage_site", C.c_int32), ("bulge", C.c_int32), ("max_sites", C.c_int64)]
 
 
 TARGET_STATS = ("mirnas", "targets", "bases", "evaluations", "sites", "passes")
@@ -517,12 +517,14 @@ class Context:
         self._check(self.lib.mirp_trim_reads(self.h, data, len(data), os.fsencode(name), C.byref(o), os.fsencode(out_path), st, sec), "mirp_trim_reads")
         return dict(zip(TRIM_STATS, list(st)), seconds=list(sec))
 
-    def target_scan(self, mirna_path, target_paths, out_path, max_half_score=8, both_strands=False, cleavage_site=False, max_sites=0):
+    def target_scan(self, mirna_path, target_paths, out_path, max_half_score=8, both_strands=False, cleavage_site=False, max_sites=0, bulge=False):
         """Plant miRNA target sites (mirp_target_scan): every miRNA of mirna_path against the target FASTA files, in order; writes
-        the TSV to out_path.  max_half_score = 2 x the -s score.  -> {mirnas, targets, bases, evaluations, sites, passes, seconds}; seconds =
+        the TSV to out_path.  max_half_score = 2 x the -s score.  bulge: also the sites with one unpaired nucleotide, and a last column `bulge`
+        on every line.  -> {mirnas, targets, bases, evaluations, sites, passes, seconds}; seconds =
         {parse, upload, scan, sort + cut, emit + download + write}."""
         o = TargetOpts()
         o.max_half_score, o.both_strands, o.cleavage_site, o.max_sites = int(max_half_score), int(bool(both_strands)), int(bool(cleavage_site)), int(max_sites)
+        o.bulge = int(bool(bulge))
         arr = (C.c_char_p * len(target_paths))(*[os.fsencode(p) for p in target_paths])
         st = (C.c_int64 * 6)()
         sec = (C.c_double * 5)()

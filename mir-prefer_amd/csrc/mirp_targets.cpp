@@ -150,7 +150,7 @@ extern "C" int mirp_target_scan(mirp_ctx* c, const char* mirna_path, const char*
         if (std::fwrite(p, 1, len, f) != len) { ok = false; return fail(c, -8, std::string("cannot write ") + out_path); }
         return 0;
     };
-    const std::string head = "miRNA\ttarget\tstart\tend\tstrand\tscore\tmismatches\tgu\tmirna_5to3\tpairs\ttarget_3to5\n";
+    const std::string head = std::string("miRNA\ttarget\tstart\tend\tstrand\tscore\tmismatches\tgu\tmirna_5to3\tpairs\ttarget_3to5") + (o->bulge ? "\tbulge\n" : "\n");
     int rc = sink(head.data(), head.size());
     long long st2[2] = {0, 0};
     double dsec[4] = {0, 0, 0, 0};

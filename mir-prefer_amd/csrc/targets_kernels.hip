@@ -21,6 +21,8 @@
 //   order  mirp_device_sort_u64 by the whole key: per miRNA, (score, target, start, + before -) = the output order.
 //   cut    tg_size_kernel: -k from the rank inside the miRNA's run plus what earlier passes emitted; the line's length; launch_excl_scan.
 //   emit   tg_emit_kernel writes the lines; the text goes to the sink in pieces of at most 1 GiB.
+// With --bulge the scan is tg_bulge_scan_kernel (targets_bulge_device.h), which also finds the sites with one unpaired base; its keys are
+// mloc << 45 | half << 40 | start << 8 | strand << 7 | kind << 5 | P, again in output order, and order, cut and emit run as their <true> instances.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -30,7 +32,7 @@
 #include <string>
 #include <vector>
 #include "mirp_ctx.h"
-#include "targets_device.h"
+#include "targets_bulge_device.h"
 #include "text_out.h"
 
 namespace mirp {
@@ -108,37 +110,118 @@ __device__ long long tg_line(const TgText& T, unsigned long long key, char* out)
     return o.n;
 }
 
+// one line of a --bulge run: the columns of tg_line and the bulge column (. / tP / mP).  Column c of the three aligned strings holds miRNA position
+// i(c) and the target base q(c); the t site has one column more (the unpaired target base under a '-'), the m site a '-' under miRNA position P.
+template <bool WRITE>
+__device__ long long tg_bulge_line(const TgText& T, unsigned long long key, char* out) {
+    TextOut<WRITE> o{out};
+    const int mloc = (int)(key >> TG_BULGE_SHIFT);
+    const unsigned half = (unsigned)(key >> 40) & 31u;
+    const unsigned long long g = (key >> 8) & 0xffffffffull;
+    const int strand = (int)(key >> 7) & 1, kind = (int)(key >> 5) & 3, P = (int)(key & 31);
+    const long long m = (long long)T.mbase + mloc;
+    const int L = T.mi[mloc].L;
+    const int W = L + (kind == 2);                  // columns
+    const unsigned char* mc = T.mcodes + 32 * m;
+    int a = 0, z = T.n_contigs;                 // target: last cstart <= g
+    while (z - a > 1) { const int md = (a + z) >> 1; if (T.cstart[md] <= g) a = md; else z = md; }
+    // column c = 1 .. W: the miRNA position (0 = none) and the target-strand base (-1 = none)
+    auto pos = [&](int c) { return kind != 2 || c <= P ? c : c == P + 1 ? 0 : c - 1; };
+    auto base = [&](int c) -> int {
+        unsigned long long q;
+        if (kind == 2) q = strand ? g + c - 1 : g + L + 1 - c;
+        else if (kind == 1) q = strand ? g + c - 1 : g + L - c;
+        else if (c == P) return -1;
+        else if (c < P) q = strand ? g + c - 1 : g + L - 1 - c;
+        else q = strand ? g + c - 2 : g + L - c;
+        const unsigned b = tg_base(T.pk, q);
+        return (int)(strand ? 3u - b : b);
+    };
+    int nmm = 0, ngu = 0;
+    for (int c = 1; c <= W; c++) {
+        const int i = pos(c), y = base(c);
+        if (i == 0 || y < 0) continue;
+        const int k = tg_class(mc[i - 1], (unsigned)y);
+        nmm += k == 2;
+        ngu += k == 1;
+    }
+    o.str(T.mnames + T.mnoff[m], T.mnoff[m + 1] - T.mnoff[m]);
+    o.ch('\t');
+    o.str(T.tnames + T.tnoff[a], T.tnoff[a + 1] - T.tnoff[a]);
+    o.ch('\t');
+    o.num(g - T.cstart[a] + 1);
+    o.ch('\t');
+    o.num(g - T.cstart[a] + L + kind - 1);
+    o.ch('\t');
+    o.ch(strand ? '-' : '+');
+    o.ch('\t');
+    o.num(half >> 1);
+    o.ch('.');
+    o.ch(half & 1 ? '5' : '0');
+    o.ch('\t');
+    o.num((unsigned long long)nmm);
+    o.ch('\t');
+    o.num((unsigned long long)ngu);
+    o.ch('\t');
+    const char* RNA = "ACGUN";
+    for (int c = 1; c <= W; c++) { const int i = pos(c); o.ch(i ? RNA[mc[i - 1]] : '-'); }
+    o.ch('\t');
+    for (int c = 1; c <= W; c++) {
+        const int i = pos(c), y = base(c);
+        const int k = i == 0 || y < 0 ? 3 : tg_class(mc[i - 1], (unsigned)y);
+        o.ch(k == 0 ? '|' : k == 1 ? 'o' : k == 2 ? 'x' : '-');
+    }
+    o.ch('\t');
+    for (int c = 1; c <= W; c++) { const int y = base(c); o.ch(y < 0 ? '-' : RNA[y]); }
+    o.ch('\t');
+    if (kind == 1) o.ch('.');
+    else { o.ch(kind == 2 ? 't' : 'm'); o.num((unsigned long long)P); }
+    o.ch('\n');
+    return o.n;
+}
+
+// the bits of a key below the miRNA index: 38 for the ungapped scan's keys, 45 for the --bulge scan's
+template <bool BULGE> struct TgKey { static constexpr int shift = BULGE ? TG_BULGE_SHIFT : 38; };
+
 // first index of the miRNA run that holds keys[i] (the keys are sorted)
+template <bool BULGE>
 __device__ __forceinline__ long long tg_run_first(const unsigned long long* __restrict__ keys, long long i) {
-    const unsigned long long lo = keys[i] >> 38 << 38;
+    const unsigned long long lo = keys[i] >> TgKey<BULGE>::shift << TgKey<BULGE>::shift;
     long long a = 0, z = i;
     while (a < z) { const long long md = (a + z) >> 1; if (keys[md] < lo) a = md + 1; else z = md; }
     return a;
 }
 
 // size[i] of sorted key i, 0 when -k cuts it (emitted[mloc] = lines of the miRNA written by earlier passes); kept[0] += lines kept
+template <bool BULGE>
 __global__ void tg_size_kernel(TgText T, const unsigned long long* __restrict__ keys, long long n, long long k, const unsigned long long* __restrict__ emitted,
                                int* __restrict__ size, unsigned long long* __restrict__ kept) {
     unsigned long long cnt = 0;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const unsigned long long key = keys[i];
-        const bool keep = k == 0 || emitted[key >> 38] + (unsigned long long)(i - tg_run_first(keys, i)) < (unsigned long long)k;
-        size[i] = keep ? (int)tg_line<false>(T, key, nullptr) : 0;
+        const bool keep = k == 0 || emitted[key >> TgKey<BULGE>::shift] + (unsigned long long)(i - tg_run_first<BULGE>(keys, i)) < (unsigned long long)k;
+        size[i] = !keep ? 0 : BULGE ? (int)tg_bulge_line<false>(T, key, nullptr) : (int)tg_line<false>(T, key, nullptr);
         cnt += keep;
     }
     for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(kept, cnt);
 }
 // emitted[mloc] += the miRNA's keys in this pass (after tg_size_kernel)
+template <bool BULGE>
 __global__ void tg_emitted_kernel(const unsigned long long* __restrict__ keys, long long n, unsigned long long* __restrict__ emitted) {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        if (i == n - 1 || (keys[i + 1] >> 38) != (keys[i] >> 38)) emitted[keys[i] >> 38] += (unsigned long long)(i + 1 - tg_run_first(keys, i));
+        if (i == n - 1 || (keys[i + 1] >> TgKey<BULGE>::shift) != (keys[i] >> TgKey<BULGE>::shift))
+            emitted[keys[i] >> TgKey<BULGE>::shift] += (unsigned long long)(i + 1 - tg_run_first<BULGE>(keys, i));
 }
+template <bool BULGE>
 __global__ void tg_emit_kernel(TgText T, const unsigned long long* __restrict__ keys, long long i0, long long i1, const long long* __restrict__ toff,
                                char* __restrict__ text) {
     const long long base = toff[i0];
     for (long long i = i0 + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < i1; i += (long long)gridDim.x * blockDim.x)
-        if (toff[i + 1] != toff[i]) (void)tg_line<true>(T, keys[i], text + (toff[i] - base));
+        if (toff[i + 1] != toff[i]) {
+            if (BULGE) (void)tg_bulge_line<true>(T, keys[i], text + (toff[i] - base));
+            else (void)tg_line<true>(T, keys[i], text + (toff[i] - base));
+        }
 }
 
 }  // namespace mirp
@@ -178,7 +261,11 @@ struct TgRun {
             const TgMirna* d_mi = (const TgMirna*)c->tg_mi.p;
             unsigned long long* d_keys = (unsigned long long*)c->tg_keys.p;
             unsigned long long* d_hist = (unsigned long long*)c->tg_hist.p;
-            if (mode == 0 && o->both_strands) hipLaunchKernelGGL((tg_scan_kernel<0, true>), grid, dim3(256), 0, st, R, d_mi, a, b, q, q1, d_keys, (unsigned long long)cap, d_small, d_hist);
+            if (o->bulge && mode == 0 && o->both_strands) hipLaunchKernelGGL((tg_bulge_scan_kernel<0, true>), grid, dim3(256), 0, st, R, d_mi, a, b, q, q1, d_keys, (unsigned long long)cap, d_small, d_hist);
+            else if (o->bulge && mode == 0) hipLaunchKernelGGL((tg_bulge_scan_kernel<0, false>), grid, dim3(256), 0, st, R, d_mi, a, b, q, q1, d_keys, (unsigned long long)cap, d_small, d_hist);
+            else if (o->bulge && o->both_strands) hipLaunchKernelGGL((tg_bulge_scan_kernel<1, true>), grid, dim3(256), 0, st, R, d_mi, a, b, q, q1, d_keys, (unsigned long long)cap, d_small, d_hist);
+            else if (o->bulge) hipLaunchKernelGGL((tg_bulge_scan_kernel<1, false>), grid, dim3(256), 0, st, R, d_mi, a, b, q, q1, d_keys, (unsigned long long)cap, d_small, d_hist);
+            else if (mode == 0 && o->both_strands) hipLaunchKernelGGL((tg_scan_kernel<0, true>), grid, dim3(256), 0, st, R, d_mi, a, b, q, q1, d_keys, (unsigned long long)cap, d_small, d_hist);
             else if (mode == 0) hipLaunchKernelGGL((tg_scan_kernel<0, false>), grid, dim3(256), 0, st, R, d_mi, a, b, q, q1, d_keys, (unsigned long long)cap, d_small, d_hist);
             else if (o->both_strands) hipLaunchKernelGGL((tg_scan_kernel<1, true>), grid, dim3(256), 0, st, R, d_mi, a, b, q, q1, d_keys, (unsigned long long)cap, d_small, d_hist);
             else hipLaunchKernelGGL((tg_scan_kernel<1, false>), grid, dim3(256), 0, st, R, d_mi, a, b, q, q1, d_keys, (unsigned long long)cap, d_small, d_hist);
@@ -202,14 +289,16 @@ struct TgRun {
         unsigned long long* d_keys = (unsigned long long*)c->tg_keys.p;
         int mbits = 0;                                         // the key's bits above the miRNA index are 0
         while ((1 << mbits) < group_n) mbits++;
-        if (int rc = mirp_device_sort_u64(c, d_keys, (unsigned long long*)c->tg_ktmp.p, n, 0, (38 + mbits + 7) / 8 * 8)) return rc;
+        const bool bulge = o->bulge != 0;
+        if (int rc = mirp_device_sort_u64(c, d_keys, (unsigned long long*)c->tg_ktmp.p, n, 0, ((bulge ? TG_BULGE_SHIFT : 38) + mbits + 7) / 8 * 8)) return rc;
         T.mbase = mbase;
         unsigned long long* d_small = (unsigned long long*)c->tg_small.p;
         long long* d_toff = (long long*)c->tg_toff.p;
         HIPCHK(c, hipMemsetAsync(d_small + 1, 0, 8, st));
-        hipLaunchKernelGGL(tg_size_kernel, dim3(tg_grid(n)), dim3(256), 0, st, T, (const unsigned long long*)d_keys, n, (long long)o->max_sites,
-                           (const unsigned long long*)c->tg_emitted.p, (int*)c->tg_size.p, d_small + 1);
-        hipLaunchKernelGGL(tg_emitted_kernel, dim3(tg_grid(n)), dim3(256), 0, st, (const unsigned long long*)d_keys, n, (unsigned long long*)c->tg_emitted.p);
+        hipLaunchKernelGGL(bulge ? tg_size_kernel<true> : tg_size_kernel<false>, dim3(tg_grid(n)), dim3(256), 0, st, T, (const unsigned long long*)d_keys, n,
+                           (long long)o->max_sites, (const unsigned long long*)c->tg_emitted.p, (int*)c->tg_size.p, d_small + 1);
+        hipLaunchKernelGGL(bulge ? tg_emitted_kernel<true> : tg_emitted_kernel<false>, dim3(tg_grid(n)), dim3(256), 0, st, (const unsigned long long*)d_keys, n,
+                           (unsigned long long*)c->tg_emitted.p);
         launch_excl_scan(st, (const int*)c->tg_size.p, d_toff, n);
         long long bytes = 0;
         unsigned long long kept = 0;
@@ -240,7 +329,7 @@ struct TgRun {
             const long long len = end - base;
             if (len > 0) {
                 if (c->tg_text.ensure((size_t)len + 16)) return fail(c, -6, "device allocation failed (targets: text)");
-                hipLaunchKernelGGL(tg_emit_kernel, dim3(tg_grid(i1 - i0)), dim3(256), 0, st, T, (const unsigned long long*)d_keys, i0, i1, (const long long*)d_toff,
+                hipLaunchKernelGGL(bulge ? tg_emit_kernel<true> : tg_emit_kernel<false>, dim3(tg_grid(i1 - i0)), dim3(256), 0, st, T, (const unsigned long long*)d_keys, i0, i1, (const long long*)d_toff,
                                    (char*)c->tg_text.p);
                 HIPCHK(c, hipStreamSynchronize(st));
                 HIPCHK(c, hipGetLastError());
@@ -317,6 +406,7 @@ struct TgRun {
                     const unsigned long long p1 = std::min(total, p + len);
                     long long got = 0;
                     if (int rc = scan(0, mbase, m, m + 1, p, p1, &got)) return rc;
+                    if (got > cap && p1 - p == 1) return fail(c, -5, "targets: one offset holds more sites of one miRNA and score than a pass");
                     if (got > cap) { len = std::max<unsigned long long>(1, len / 2); continue; }
                     if (int rc = finish(mbase, got)) return rc;
                     p = p1;
@@ -339,7 +429,9 @@ int mirp_device_target_scan(mirp_ctx* c, const unsigned long long* pk, const uns
     hipStream_t st = c->stream;
     const long long n_pk = (total + 31) / 32 + 2, n_bm = (total + 31) / 32 + 2;
     const long long n_mi = (long long)mi.size();
-    const long long cap = c->tg_cap > 0 ? c->tg_cap : (1ll << 26);
+    long long cap = c->tg_cap > 0 ? c->tg_cap : (1ll << 26);
+    if (o.bulge && cap < 4) cap = 4;            // one offset can hold 4 sites of one (miRNA, score): t and m on both strands (an ungapped site of
+                                                // that score dominates both); without bulge it holds 2, the smallest capacity the ABI takes
     double t = tg_now();
     if (c->tg_pk.ensure(8 * (size_t)n_pk) || c->tg_amb.ensure(4 * (size_t)n_bm) || c->tg_cst.ensure(4 * (size_t)n_bm) || c->tg_cstart.ensure(8 * cstart.size()) ||
         c->tg_names.ensure(tnames.size() + 1) || c->tg_noff.ensure(8 * tnoff.size()) || c->tg_mcodes.ensure(mcodes.size() + 32) ||

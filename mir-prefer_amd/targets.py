@@ -20,6 +20,10 @@ HELP = """python -m mir_prefer_amd.targets [options] <mirna.fa> <target.fa> [<ta
     Every miRNA (12..32 nt, A C G U/T; any other letter mismatches) is paired with every
     offset of every target, without gaps. A site's score sums 1 per mismatch and 0.5 per
     G:U pair, doubled at miRNA positions 2..13; sites scoring at most -s are written.
+    With -g, sites with one unpaired nucleotide (a bulge on the target or on the miRNA,
+    costing 1, or 2 inside positions 2..13) are written too, and every line ends with a
+    column `bulge`: `.`, `tP` or `mP`, P = the miRNA position before the unpaired target
+    base, or the unpaired miRNA position itself.
 
     Example:
     python -m mir_prefer_amd.targets -s 3 -c out/prefix_miRNA.mature.fa cdna.fa
@@ -31,6 +35,7 @@ def make_parser():
     parser.add_option("-s", "--max-score", default="4", help="Highest score written, a multiple of 0.5 in 0..8. Default 4.")
     parser.add_option("-b", "--both-strands", action="store_true", help="Also scan the minus strand of the targets (for genome-sized targets).")
     parser.add_option("-c", "--cleavage-site", action="store_true", help="Reject sites with a mismatch (not a G:U) at miRNA position 10 or 11.")
+    parser.add_option("-g", "--bulge", action="store_true", help="Also write sites with exactly one unpaired nucleotide; adds the column `bulge`.")
     parser.add_option("-k", "--max-sites", type=int, default=0, help="Write the first N sites per miRNA, in output order; 0 = all (default).")
     parser.add_option("-o", "--output", help="Output file. Default <mirna.fa>.targets.tsv.")
     parser.add_option("--device", type=int, default=0, help="GPU device index. Default is 0.")
@@ -91,7 +96,7 @@ def main(argv=None):
         return _fail("the target search runs on the GPU and none is usable (%s); there is no CPU path." % e)
     try:
         res = ctx.target_scan(mirna, targets, out, max_half_score=half, both_strands=bool(options.both_strands),
-                              cleavage_site=bool(options.cleavage_site), max_sites=options.max_sites)
+                              cleavage_site=bool(options.cleavage_site), max_sites=options.max_sites, bulge=bool(options.bulge))
     except (OSError, capi.MirpError) as e:
         return _fail(str(e))
     finally:
