@@ -554,6 +554,34 @@ typedef struct {
 int mirp_annotate_scan(mirp_ctx* ctx, const char* query_path, const char* const* known_paths, int32_t n_known, const MirpAnnotateOpts* opts,
                        const char* out_path, const char* summary_path, int64_t stats[12], double seconds[6]);
 
+/* Shuffle test of precursor MFEs (randfold): every sequence is shuffled n_shuffles times on the device, the sequence and its shuffles
+ * are folded with the context's fold model (mirp_set_fold_model) and the MFEs are reduced on the device to one record per sequence.  Letters: A C G U
+ * in either case, T = U, codes 0..3; every other letter is code 4 and goes to the fold as N.  dinucleotide = 0: Fisher-Yates over the letters; 1: the
+ * Altschul-Erikson shuffle that keeps every dinucleotide count and both ends.  The random numbers are a stateless function of (seed, sequence index
+ * in this call, shuffle index, draw number), §20.  capacity: sequences folded per pass (0 = the default, 262,144); no result depends on it. */
+typedef struct {
+    uint64_t seed;
+    int32_t n_shuffles;   /* 1..100000 */
+    int32_t dinucleotide; /* 0 mono, 1 di */
+    int64_t capacity;     /* 0 = default */
+} MirpRandfoldOpts;
+/* len; gc = letters C and G; mfe of the sequence (0.01 kcal/mol, the global minimum: mirp_fold_batch's mfe at any span >= len); le = shuffles with
+ * mfe <= the sequence's; min_mfe = the smallest shuffled mfe; sum / sum_sq = the sum of the shuffled mfes / of their squares. */
+typedef struct {
+    int32_t len, gc, mfe, le, min_mfe, reserved;
+    int64_t sum, sum_sq;
+} MirpRandfoldRec;
+/* seqs / offsets as mirp_fold_batch.  Refused with -10 and the record (1-based) named in mirp_last_error: an empty sequence, a sequence longer than
+ * 3,000 nt, a byte >= 0x80, n_seqs x (n_shuffles + 1) beyond 2^40.  Out: recs[n_seqs] (library-owned, mirp_free); stats = {sequences, folds, passes,
+ * fold fallbacks}; seconds = {upload, shuffle, fold, statistics, download}.  Only the records come back: no shuffled sequence and no per-shuffle MFE
+ * leaves the device.  Nothing resident changes. */
+int mirp_randfold(mirp_ctx* ctx, const char* seqs, const int64_t* offsets, int32_t n_seqs, const MirpRandfoldOpts* opts, MirpRandfoldRec** recs,
+                  int64_t stats[4], double seconds[5]);
+/* For tests: the shuffles k = k0 .. k0 + n_k - 1 (k0 >= 0, n_k >= 1, k0 + n_k <= 100000) of every sequence as ACGUN bytes, row-major, sequence q's
+ * rows len(q) wide back to back (library-owned, mirp_free).  Same refusals as mirp_randfold. */
+int mirp_shuffle_batch(mirp_ctx* ctx, const char* seqs, const int64_t* offsets, int32_t n_seqs, const MirpRandfoldOpts* opts, int32_t k0, int32_t n_k,
+                       char** out, int64_t* n_bytes);
+
 #ifdef __cplusplus
 }
 #endif

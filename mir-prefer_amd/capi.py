@@ -8,7 +8,7 @@ import numpy as np
 
 from . import early
 from .early import LIB_PATH, FastaData, SamData
-ABI_VERSION = 15     # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
+ABI_VERSION = 16     # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
 
 
 class MirpError(RuntimeError):
@@ -47,6 +47,17 @@ class AnnotateOpts(C.Structure):
 
 
 ANNOTATE_STATS = ("queries", "known", "skipped", "pairs", "evaluations", "hits", "identical", "isomir", "homolog", "novel", "lines", "passes")
+
+
+class RandfoldOpts(C.Structure):
+    """MirpRandfoldOpts of include/mirprefer.h."""
+    _fields_ = [("seed", C.c_uint64), ("n_shuffles", C.c_int32), ("dinucleotide", C.c_int32), ("capacity", C.c_int64)]
+
+
+# MirpRandfoldRec of include/mirprefer.h: one sequence of mirp_randfold
+RANDFOLD_DTYPE = np.dtype([("len", "<i4"), ("gc", "<i4"), ("mfe", "<i4"), ("le", "<i4"), ("min_mfe", "<i4"), ("reserved", "<i4"), ("sum", "<i8"),
+                           ("sum_sq", "<i8")])
+RANDFOLD_STATS = ("sequences", "folds", "passes", "fallbacks")
 
 
 class PhaseOpts(C.Structure):
@@ -408,6 +419,10 @@ def load_library():
     lib.mirp_annotate_scan.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(AnnotateOpts), C.c_char_p, C.c_char_p, i64p,
                                        C.POINTER(C.c_double)]
     lib.mirp_annotate_scan.restype = C.c_int
+    lib.mirp_randfold.argtypes = [vp, C.c_char_p, i64p, C.c_int32, C.POINTER(RandfoldOpts), C.POINTER(vp), i64p, C.POINTER(C.c_double)]
+    lib.mirp_randfold.restype = C.c_int
+    lib.mirp_shuffle_batch.argtypes = [vp, C.c_char_p, i64p, C.c_int32, C.POINTER(RandfoldOpts), C.c_int32, C.c_int32, C.POINTER(vp), i64p]
+    lib.mirp_shuffle_batch.restype = C.c_int
     lib.mirp_set_target_capacity.argtypes = [vp, C.c_int64]
     lib.mirp_set_target_capacity.restype = C.c_int
     lib.mirp_phase_scan.argtypes = [vp, C.POINTER(PhaseOpts), vp, C.POINTER(vp), i64p, i64p]
@@ -553,6 +568,42 @@ class Context:
         self._check(self.lib.mirp_annotate_scan(self.h, os.fsencode(query_path), arr, len(known_paths), C.byref(o), os.fsencode(out_path),
                                                 os.fsencode(summary_path), st, sec), "mirp_annotate_scan")
         return dict(zip(ANNOTATE_STATS, list(st)), seconds=list(sec))
+
+    @staticmethod
+    def _randfold_input(seqs, n_shuffles, dinucleotide, seed, capacity):
+        bs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        offs = np.zeros(len(bs) + 1, dtype=np.int64)
+        if bs:
+            offs[1:] = np.cumsum([len(b) for b in bs])
+        o = RandfoldOpts()
+        o.seed, o.n_shuffles, o.dinucleotide, o.capacity = int(seed), int(n_shuffles), int(bool(dinucleotide)), int(capacity)
+        return bs, b"".join(bs), offs, o
+
+    def randfold(self, seqs, n_shuffles=999, dinucleotide=True, seed=0, capacity=0):
+        """Shuffle test of precursor MFEs (mirp_randfold): seqs (list of str / bytes) are shuffled n_shuffles times each on the
+        device, folded with this context's fold model and reduced to one record per sequence.  capacity: sequences folded per pass (0 = the
+        default), lowered only in tests.  -> (RANDFOLD_DTYPE array, {sequences, folds, passes, fallbacks, seconds}); seconds = {upload, shuffle,
+        fold, statistics, download}."""
+        bs, blob, offs, o = self._randfold_input(seqs, n_shuffles, dinucleotide, seed, capacity)
+        ptr = C.c_void_p()
+        st = (C.c_int64 * 4)()
+        sec = (C.c_double * 5)()
+        self._check(self.lib.mirp_randfold(self.h, blob, offs.ctypes.data_as(C.POINTER(C.c_int64)), len(bs), C.byref(o), C.byref(ptr), st, sec), "mirp_randfold")
+        return _copy_out(self.lib, ptr, RANDFOLD_DTYPE, len(bs)), dict(zip(RANDFOLD_STATS, list(st)), seconds=list(sec))
+
+    def shuffle_batch(self, seqs, k0, n_k, dinucleotide=True, seed=0, capacity=0):
+        """The shuffles k0 .. k0 + n_k - 1 of every sequence as the device makes them for randfold (mirp_shuffle_batch; for tests).
+        -> list (per sequence) of n_k bytes objects of ACGUN letters."""
+        bs, blob, offs, o = self._randfold_input(seqs, 1, dinucleotide, seed, capacity)
+        ptr, nb = C.c_void_p(), C.c_int64()
+        self._check(self.lib.mirp_shuffle_batch(self.h, blob, offs.ctypes.data_as(C.POINTER(C.c_int64)), len(bs), C.byref(o), int(k0), int(n_k), C.byref(ptr),
+                                                C.byref(nb)), "mirp_shuffle_batch")
+        raw = _copy_out(self.lib, ptr, np.uint8, nb.value).tobytes()
+        out, at = [], 0
+        for b in bs:
+            out.append([raw[at + k * len(b):at + (k + 1) * len(b)] for k in range(int(n_k))])
+            at += int(n_k) * len(b)
+        return out
 
     def phase_scan(self, length, cycles, kmin, min_phased=3, min_depth=1):
         """Phased siRNA windows on this context's resident alignments (mirp_phase_scan).  kmin: the int32 table of the smallest

@@ -123,7 +123,10 @@ struct mirp_ctx {
     // ---- known-miRNA annotation (annotate_kernels.hip, mirp_annotate.cpp): the packed and the planar sequences, the hits per query and the cut
     // tables of one pass; the keys use tg_keys / tg_ktmp / tg_small / tg_hist
     DevBuf an_pack, an_q, an_k, an_cnt, an_run, an_out, an_kept;
-    long long n_result = 0;           // records of the last mirp_predict (p_res / p_text), what mirp_gather_loci sends
+    // ---- shuffle test of precursor MFEs (randfold_kernels.hip, mirp_randfold.cpp): the sequences of the call (codes, offsets, order, cumulated lengths,
+    // records) and the buffers of one pass: the shuffled sequences and their offsets as the fold reads them, the successor lists, the fold's outputs
+    DevBuf rf_codes, rf_offs, rf_perm, rf_cum, rf_rec, rf_bad, rf_seq, rf_soffs, rf_slab, rf_lines, rf_ss, rf_nlines, rf_mfe, rf_status;
+    long long n_result = 0;          // records of the last mirp_predict (p_res / p_text), what mirp_gather_loci sends
     bool have_result = false;
 };
 
@@ -183,6 +186,17 @@ struct AnPacked { unsigned long long word; unsigned unk; int len; };
 typedef std::function<int(long long qbase, const unsigned long long* keys, size_t n)> MirpAnSink;
 int mirp_device_annotate(mirp_ctx* c, const std::vector<AnPacked>& q, const std::vector<AnPacked>& k, int max_offset, int max_mismatches, long long max_lines,
                          std::vector<unsigned>& hits_per_query, const MirpAnSink& sink, long long stats[3], double seconds[5]);
+// randfold_kernels.hip: the shuffles and the statistics of one pass (mirp_randfold.cpp plans the passes).  The sequences stand in the order d_perm
+// (position -> index in the call), d_cum[position] = letters before it; every sequence has jps consecutive jobs, with has_native the first one is
+// the sequence itself; job j's row starts at d_cum[j / jps] * jps + (j % jps) * len.  shuffle: jobs [j0, j0 + n_jobs) -> rows at d_out + row - base
+// and d_out_offs[0 .. n_jobs]; d_slab: as many bytes as d_out (dinucleotide only).  stats: the MFEs of those jobs into the records.
+struct RfPlan {
+    const unsigned char* d_codes; const long long* d_offs; const int* d_perm; const long long* d_cum;
+    long long jps, k_first; int has_native, dinucleotide; unsigned long long seed;
+};
+void mirp_device_rf_shuffle(mirp_ctx* c, const RfPlan& p, long long j0, int n_jobs, long long base, unsigned char* d_out, long long* d_out_offs,
+                            unsigned char* d_slab);
+void mirp_device_rf_stats(mirp_ctx* c, const RfPlan& p, long long j0, int n_jobs, const int* d_mfe, const int* d_status, MirpRandfoldRec* d_rec, int* d_bad);
 int mirp_device_mask_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long* n_io, MirpAln* d_segs, MirpAln* d_segtmp, const int* d_owner, const int* d_seg_span,
                           long long* nseg_io,
                           const long long* d_rfirst, const int* d_rstart, const int* d_remax);
