@@ -452,10 +452,14 @@ int mirp_trim_reads(mirp_ctx* ctx, const char* data, int64_t n, const char* name
  * (mismatch 1, G:U 0.5, doubled at miRNA positions 2..13) in half-units.  max_half_score 0..16 (= 2 x the -s score); both_strands: also the minus
  * strand; cleavage_site: reject a site with a mismatch (not a G:U) at miRNA position 10 or 11; max_sites: the first N sites per miRNA in output
  * order (0 = all); bulge (0 or 1): also the sites with exactly one unpaired nucleotide, on the target (tP) or on the miRNA (mP), and a last
- * column `bulge` on every line (§14, "Bulged sites"); 0 leaves every byte of the output as it was. */
+ * column `bulge` on every line (§14, "Bulged sites"); 0 leaves every byte of the output as it was.  energy (0 or 1): four more last columns on
+ * every line, `mfe mfe_perfect mfe_ratio duplex` (§21, "targets -e"): the free energy of the duplex of the miRNA with the site and one flanking
+ * base on each side (mirp_duplex_batch's fold, not forced onto the alignment of `pairs`), that of the miRNA with its reverse complement, their
+ * ratio to three decimals (NA when the perfect duplex is unbound) and the structure text; 0 leaves every byte of the output as it was. */
 typedef struct {
     int32_t max_half_score, both_strands, cleavage_site, bulge;
     int64_t max_sites;
+    int32_t energy, reserved;
 } MirpTargetOpts;
 /* Reads the miRNA FASTA mirna_path (name = the whole header after '>', stripped, tabs turned into spaces; multi-line sequences concatenated; A C G U T
  * in either case, T = U, any other letter unknown) and the target FASTA files target_paths[0 .. n_targets) (parsed and packed as mirp_align_index
@@ -463,7 +467,7 @@ typedef struct {
  * start, + before -, end.  Refusals, each before out_path is opened (-10, the 1-based record in mirp_last_error): a miRNA of length outside 12..32, an
  * empty name, a byte >= 0x80, more than 2^24 miRNAs; and the target refusals of mirp_align_index.  On any error the file at out_path is removed.
  * Out: stats = {miRNAs, targets, target bases, evaluations (offsets x miRNAs x strands), sites written, passes}, seconds = {parse, upload, scan,
- * sort + cut, emit + download + write}. */
+ * sort + cut (with energy: and the folds of the pass's keys), emit + download + write}. */
 int mirp_target_scan(mirp_ctx* ctx, const char* mirna_path, const char* const* target_paths, int32_t n_targets, const MirpTargetOpts* opts,
                      const char* out_path, int64_t stats[6], double seconds[5]);
 /* Keys (sites before the -k cut) one pass of mirp_target_scan holds on the device, at least 2; 0 = the default, 2^26.  A pass that finds more is
@@ -581,6 +585,22 @@ int mirp_randfold(mirp_ctx* ctx, const char* seqs, const int64_t* offsets, int32
  * rows len(q) wide back to back (library-owned, mirp_free).  Same refusals as mirp_randfold. */
 int mirp_shuffle_batch(mirp_ctx* ctx, const char* seqs, const int64_t* offsets, int32_t n_seqs, const MirpRandfoldOpts* opts, int32_t k0, int32_t n_k,
                        char** out, int64_t* n_bytes);
+
+/* Two-strand (intermolecular) minimum free energy fold: the RNAduplex recursion on the Turner-2004 tables with dangles = 2,
+ * whatever mirp_set_fold_model says.  Strands a and b are both 5'->3'; A C G U in either case, T = U, every other byte N, which pairs with
+ * nothing.  mfe in 0.01 kcal/mol, 0 = unbound (then pairs and the four bounds are 0); pairs = base pairs of the structure; a_first .. a_last and
+ * b_first .. b_last = the 1-based ends of the paired stretch of either strand. */
+typedef struct { int32_t mfe, pairs, a_first, a_last, b_first, b_last; } MirpDuplexRec;
+/* Pair q = a_blob[a_off[q] .. a_off[q + 1]) with b_blob[b_off[q] .. b_off[q + 1]), q < n.  Every strand has 1..64 nt: another length is refused
+ * with -10 and the 1-based pair in mirp_last_error; n < 0 is refused with -1; n = 0 is fine.  Out: recs[n]; structures (may be NULL): the text of
+ * pair q -- a as ( and ., then &, then b as ) and . -- NUL-terminated, at the sum over the pairs before q of len a + len b + 2.  The pairs are
+ * folded in passes of bounded device memory (mirp_set_duplex_capacity); no result depends on the split.  Nothing resident changes. */
+int mirp_duplex_batch(mirp_ctx* ctx, const char* a_blob, const int64_t* a_off, const char* b_blob, const int64_t* b_off, int32_t n, MirpDuplexRec* recs,
+                      char* structures);
+/* Pairs one pass of mirp_duplex_batch holds on the device; 0 = the default, 2^20.  Lowered only to test the split. */
+int mirp_set_duplex_capacity(mirp_ctx* ctx, int64_t pairs);
+/* stats = {pairs, passes, loop evaluations (predecessor cells read)} of the last mirp_duplex_batch. */
+int mirp_duplex_last_stats(mirp_ctx* ctx, int64_t stats[3]);
 
 #ifdef __cplusplus
 }

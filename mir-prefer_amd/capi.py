@@ -8,7 +8,7 @@ import numpy as np
 
 from . import early
 from .early import LIB_PATH, FastaData, SamData
-ABI_VERSION = 16     # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
+ABI_VERSION = 17     # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
 
 
 class MirpError(RuntimeError):
@@ -34,7 +34,8 @@ TRIM_STATS = ("reads", "quality_trimmed", "adapter", "untrimmed", "too_short", "
 
 class TargetOpts(C.Structure):
     """MirpTargetOpts of include/mirprefer.h."""
-    _fields_ = [("max_half_score", C.c_int32), ("both_strands", C.c_int32), ("cleavage_site", C.c_int32), ("bulge", C.c_int32), ("max_sites", C.c_int64)]
+    _fields_ = [("max_half_score", C.c_int32), ("both_strands", C.c_int32), ("cleavage_site", C.c_int32), ("bulge", C.c_int32), ("max_sites", C.c_int64),
+                ("energy", C.c_int32), ("reserved", C.c_int32)]
 
 
 TARGET_STATS = ("mirnas", "targets", "bases", "evaluations", "sites", "passes")
@@ -58,6 +59,10 @@ class RandfoldOpts(C.Structure):
 RANDFOLD_DTYPE = np.dtype([("len", "<i4"), ("gc", "<i4"), ("mfe", "<i4"), ("le", "<i4"), ("min_mfe", "<i4"), ("reserved", "<i4"), ("sum", "<i8"),
                            ("sum_sq", "<i8")])
 RANDFOLD_STATS = ("sequences", "folds", "passes", "fallbacks")
+
+# MirpDuplexRec of include/mirprefer.h: one pair of mirp_duplex_batch
+DUPLEX_DTYPE = np.dtype([("mfe", "<i4"), ("pairs", "<i4"), ("a_first", "<i4"), ("a_last", "<i4"), ("b_first", "<i4"), ("b_last", "<i4")])
+DUPLEX_STATS = ("pairs", "passes", "evaluations")
 
 
 class PhaseOpts(C.Structure):
@@ -423,6 +428,12 @@ def load_library():
     lib.mirp_randfold.restype = C.c_int
     lib.mirp_shuffle_batch.argtypes = [vp, C.c_char_p, i64p, C.c_int32, C.POINTER(RandfoldOpts), C.c_int32, C.c_int32, C.POINTER(vp), i64p]
     lib.mirp_shuffle_batch.restype = C.c_int
+    lib.mirp_duplex_batch.argtypes = [vp, C.c_char_p, i64p, C.c_char_p, i64p, C.c_int32, vp, vp]
+    lib.mirp_duplex_batch.restype = C.c_int
+    lib.mirp_set_duplex_capacity.argtypes = [vp, C.c_int64]
+    lib.mirp_set_duplex_capacity.restype = C.c_int
+    lib.mirp_duplex_last_stats.argtypes = [vp, i64p]
+    lib.mirp_duplex_last_stats.restype = C.c_int
     lib.mirp_set_target_capacity.argtypes = [vp, C.c_int64]
     lib.mirp_set_target_capacity.restype = C.c_int
     lib.mirp_phase_scan.argtypes = [vp, C.POINTER(PhaseOpts), vp, C.POINTER(vp), i64p, i64p]
@@ -532,14 +543,16 @@ class Context:
         self._check(self.lib.mirp_trim_reads(self.h, data, len(data), os.fsencode(name), C.byref(o), os.fsencode(out_path), st, sec), "mirp_trim_reads")
         return dict(zip(TRIM_STATS, list(st)), seconds=list(sec))
 
-    def target_scan(self, mirna_path, target_paths, out_path, max_half_score=8, both_strands=False, cleavage_site=False, max_sites=0, bulge=False):
+    def target_scan(self, mirna_path, target_paths, out_path, max_half_score=8, both_strands=False, cleavage_site=False, max_sites=0, bulge=False,
+                    energy=False):
         """Plant miRNA target sites (mirp_target_scan): every miRNA of mirna_path against the target FASTA files, in order; writes
         the TSV to out_path.  max_half_score = 2 x the -s score.  bulge: also the sites with one unpaired nucleotide, and a last column `bulge`
-        on every line.  -> {mirnas, targets, bases, evaluations, sites, passes, seconds}; seconds =
+        on every line.  energy: the duplex free energy columns `mfe mfe_perfect mfe_ratio duplex` last on every line.  -> {mirnas, targets, bases, evaluations, sites, passes, seconds}; seconds =
         {parse, upload, scan, sort + cut, emit + download + write}."""
         o = TargetOpts()
         o.max_half_score, o.both_strands, o.cleavage_site, o.max_sites = int(max_half_score), int(bool(both_strands)), int(bool(cleavage_site)), int(max_sites)
         o.bulge = int(bool(bulge))
+        o.energy = int(bool(energy))
         arr = (C.c_char_p * len(target_paths))(*[os.fsencode(p) for p in target_paths])
         st = (C.c_int64 * 6)()
         sec = (C.c_double * 5)()
@@ -604,6 +617,45 @@ class Context:
             out.append([raw[at + k * len(b):at + (k + 1) * len(b)] for k in range(int(n_k))])
             at += int(n_k) * len(b)
         return out
+
+    def duplex_batch(self, a_list, b_list, structures=True, capacity=0):
+        """Two-strand minimum free energy fold (mirp_duplex_batch) of a_list[q] with b_list[q] (str / bytes, both 5'->3', 1..64 nt,
+        A C G U/T in either case, anything else N), Turner-2004 whatever the context's fold model.  capacity: pairs per pass (0 = the default),
+        lowered only in tests.  -> (DUPLEX_DTYPE array, [bytes] of the structure texts, or None without structures)."""
+        if len(a_list) != len(b_list):
+            raise ValueError("duplex_batch: %d strands a and %d strands b" % (len(a_list), len(b_list)))
+        blobs, offs = [], []
+        for strands in (a_list, b_list):
+            bs = [s.encode() if isinstance(s, str) else bytes(s) for s in strands]
+            o = np.zeros(len(bs) + 1, dtype=np.int64)
+            if bs:
+                o[1:] = np.cumsum([len(b) for b in bs])
+            blobs.append(b"".join(bs))
+            offs.append(o)
+        n = len(a_list)
+        recs = np.zeros(n, dtype=DUPLEX_DTYPE)
+        sizes = (offs[0][1:] - offs[0][:-1]) + (offs[1][1:] - offs[1][:-1]) + 2
+        text = C.create_string_buffer(int(sizes.sum()) + 1) if structures else None
+        p64 = C.POINTER(C.c_int64)
+        self._check(self.lib.mirp_set_duplex_capacity(self.h, int(capacity)), "mirp_set_duplex_capacity")
+        try:
+            self._check(self.lib.mirp_duplex_batch(self.h, blobs[0], offs[0].ctypes.data_as(p64), blobs[1], offs[1].ctypes.data_as(p64), n,
+                                                   recs.ctypes.data_as(C.c_void_p), C.cast(text, C.c_void_p) if structures else None), "mirp_duplex_batch")
+        finally:
+            self.lib.mirp_set_duplex_capacity(self.h, 0)
+        if not structures:
+            return recs, None
+        raw, at, out = text.raw, 0, []
+        for sz in sizes.tolist():
+            out.append(raw[at:at + sz - 1])
+            at += sz
+        return recs, out
+
+    def duplex_last_stats(self):
+        """{pairs, passes, evaluations} of the last duplex_batch (evaluations = loop energies evaluated)."""
+        st = (C.c_int64 * 3)()
+        self._check(self.lib.mirp_duplex_last_stats(self.h, st), "mirp_duplex_last_stats")
+        return dict(zip(DUPLEX_STATS, list(st)))
 
     def phase_scan(self, length, cycles, kmin, min_phased=3, min_depth=1):
         """Phased siRNA windows on this context's resident alignments (mirp_phase_scan).  kmin: the int32 table of the smallest

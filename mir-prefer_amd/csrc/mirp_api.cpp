@@ -11,7 +11,7 @@
 #include <vector>
 #include "mirp_internal.h"
 
-#define MIRP_ABI_VERSION 16  // 16: mirp_randfold, mirp_shuffle_batch; 15: mirp_annotate_scan; 14: mirp_degradome_scan; 13: mirp_cluster_scan; 12: mirp_phase_scan; 11: mirp_target_scan, mirp_set_target_capacity; 10: mirp_trim_reads; 9: mirp_align_index, mirp_align_reads; 8: mirp_collapse_reads, mirp_last_collapse_collisions; 7: mirp_write_result_reports, mirp_fold_predict_report_stream, mirp_select_windows, mirp_dist_comm_info, MIRP_MAX_SAMPLES 255; 6: mirp_last_coverage_fused, mirp_fold_batch_summary, mirp_predict_batch_reasons, text writers; 5: mirp_dist_*, mirp_gather_loci / mirp_gather_records, mirp_read_fasta, mirp_ingest_sams_shard; 4: MirpSamData.segs, mirp_ingest_sams_gpu, mirp_load_coverage_segments; 2: mirp_set_fold_model, mirp_ingest_sams; 3: mirp_predict returns the per-window capacity status, mirp_get_fold_overflow
+#define MIRP_ABI_VERSION 17  // 17: mirp_duplex_batch, mirp_set_duplex_capacity, mirp_duplex_last_stats, MirpTargetOpts.energy; 16: mirp_randfold, mirp_shuffle_batch; 15: mirp_annotate_scan; 14: mirp_degradome_scan; 13: mirp_cluster_scan; 12: mirp_phase_scan; 11: mirp_target_scan, mirp_set_target_capacity; 10: mirp_trim_reads; 9: mirp_align_index, mirp_align_reads; 8: mirp_collapse_reads, mirp_last_collapse_collisions; 7: mirp_write_result_reports, mirp_fold_predict_report_stream, mirp_select_windows, mirp_dist_comm_info, MIRP_MAX_SAMPLES 255; 6: mirp_last_coverage_fused, mirp_fold_batch_summary, mirp_predict_batch_reasons, text writers; 5: mirp_dist_*, mirp_gather_loci / mirp_gather_records, mirp_read_fasta, mirp_ingest_sams_shard; 4: MirpSamData.segs, mirp_ingest_sams_gpu, mirp_load_coverage_segments; 2: mirp_set_fold_model, mirp_ingest_sams; 3: mirp_predict returns the per-window capacity status, mirp_get_fold_overflow
 #define MIRP_NMAX 3096
 
 #include "mirp_ctx.h"
@@ -111,7 +111,8 @@ extern "C" void mirp_destroy(mirp_ctx* c) {
                       &c->t_namel, &c->t_flen, &c->t_off, &c->t_out, &c->tg_pk, &c->tg_amb, &c->tg_cst, &c->tg_cstart, &c->tg_names, &c->tg_noff, &c->tg_mcodes,
                       &c->tg_mnames, &c->tg_mnoff, &c->tg_mi, &c->tg_emitted, &c->tg_hist, &c->tg_small, &c->tg_keys, &c->tg_ktmp, &c->tg_size, &c->tg_toff,
                       &c->tg_text, &c->an_pack, &c->an_q, &c->an_k, &c->an_cnt, &c->an_run, &c->an_out, &c->an_kept, &c->rf_codes, &c->rf_offs, &c->rf_perm,
-                      &c->rf_cum, &c->rf_rec, &c->rf_bad, &c->rf_seq, &c->rf_soffs, &c->rf_slab, &c->rf_lines, &c->rf_ss, &c->rf_nlines, &c->rf_mfe, &c->rf_status})
+                      &c->rf_cum, &c->rf_rec, &c->rf_bad, &c->rf_seq, &c->rf_soffs, &c->rf_slab, &c->rf_lines, &c->rf_ss, &c->rf_nlines, &c->rf_mfe, &c->rf_status,
+                      &c->dx_a, &c->dx_b, &c->dx_aoff, &c->dx_boff, &c->dx_mfe, &c->dx_ma, &c->dx_mb, &c->dx_small, &c->tg_emfe, &c->tg_ema, &c->tg_emb, &c->tg_perf})
         b->release();
     for (int i = 0; i < 6; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     for (hipEvent_t ev : c->fold_ev) (void)hipEventDestroy(ev);

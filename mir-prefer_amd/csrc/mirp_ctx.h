@@ -126,6 +126,11 @@ struct mirp_ctx {
     // ---- shuffle test of precursor MFEs (randfold_kernels.hip, mirp_randfold.cpp): the sequences of the call (codes, offsets, order, cumulated lengths,
     // records) and the buffers of one pass: the shuffled sequences and their offsets as the fold reads them, the successor lists, the fold's outputs
     DevBuf rf_codes, rf_offs, rf_perm, rf_cum, rf_rec, rf_bad, rf_seq, rf_soffs, rf_slab, rf_lines, rf_ss, rf_nlines, rf_mfe, rf_status;
+    // ---- two-strand fold (duplex_kernels.hip, mirp_duplex.cpp): the coded strands and offsets of one pass of mirp_duplex_batch and its results;
+    // with targets -e the results per key of a pass (tg_e*) and the perfect duplex per miRNA of a group (tg_perf)
+    DevBuf dx_a, dx_b, dx_aoff, dx_boff, dx_mfe, dx_ma, dx_mb, dx_small, tg_emfe, tg_ema, tg_emb, tg_perf;
+    long long dx_cap = 0;             // pairs per pass of mirp_duplex_batch; 0 = the default, 2^20 (mirp_set_duplex_capacity)
+    long long dx_stats[3] = {0, 0, 0};   // the last mirp_duplex_batch: pairs, passes, loop evaluations
     long long n_result = 0;          // records of the last mirp_predict (p_res / p_text), what mirp_gather_loci sends
     bool have_result = false;
 };
@@ -197,6 +202,21 @@ struct RfPlan {
 void mirp_device_rf_shuffle(mirp_ctx* c, const RfPlan& p, long long j0, int n_jobs, long long base, unsigned char* d_out, long long* d_out_offs,
                             unsigned char* d_slab);
 void mirp_device_rf_stats(mirp_ctx* c, const RfPlan& p, long long j0, int n_jobs, const int* d_mfe, const int* d_status, MirpRandfoldRec* d_rec, int* d_bad);
+// duplex_kernels.hip: the two-strand fold of DESIGN.md §21, one wave per duplex; results per job: mfe (0.01 kcal/mol, 0 = unbound) and the 64-bit masks
+// of the paired positions of a and b.  pairs: strands as codes 0..4 (N A C G U) at d_a + d_aoff[q] .. d_aoff[q + 1], likewise b, every length
+// 1..64 and at most max_la / max_lb; d_evals (optional) += loop evaluations.  perfect: miRNA q of the group (codes 0..3 = A C G U, 4 = unknown, 32
+// per miRNA) against its reverse complement.  sites: the sorted keys of a pass of the target search (targets_kernels.hip; bulge: the --bulge key
+// layout); a key that -k cuts (max_sites, d_emitted as tg_size_kernel reads them) is not folded and gets mfe 0 and empty masks.
+struct DxTargets {
+    const unsigned long long* pk; const unsigned* amb; const unsigned char* mcodes; const TgMirna* mi; const unsigned long long* cstart;
+    int n_contigs, mbase;
+};
+int mirp_device_duplex_pairs(mirp_ctx* c, const unsigned char* d_a, const long long* d_aoff, const unsigned char* d_b, const long long* d_boff, long long n,
+                             int max_la, int max_lb, int* d_mfe, unsigned long long* d_ma, unsigned long long* d_mb, unsigned long long* d_evals);
+int mirp_device_duplex_perfect(mirp_ctx* c, const unsigned char* d_mcodes, const TgMirna* d_mi, long long n, int* d_mfe, unsigned long long* d_ma,
+                               unsigned long long* d_mb);
+int mirp_device_duplex_sites(mirp_ctx* c, const DxTargets& T, bool bulge, const unsigned long long* d_keys, long long n, long long max_sites,
+                             const unsigned long long* d_emitted, int* d_mfe, unsigned long long* d_ma, unsigned long long* d_mb);
 int mirp_device_mask_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long* n_io, MirpAln* d_segs, MirpAln* d_segtmp, const int* d_owner, const int* d_seg_span,
                           long long* nseg_io,
                           const long long* d_rfirst, const int* d_rstart, const int* d_remax);

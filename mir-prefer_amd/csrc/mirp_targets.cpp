@@ -129,7 +129,7 @@ extern "C" int mirp_target_scan(mirp_ctx* c, const char* mirna_path, const char*
                                 const char* out_path, int64_t stats[6], double seconds[5]) {
     if (!c) return -1;
     if (!mirna_path || !target_paths || n_targets < 1 || !o || !out_path) return fail(c, -1, "mirp_target_scan: bad argument");
-    if (o->max_half_score < 0 || o->max_half_score > 16 || o->max_sites < 0) return fail(c, -1, "mirp_target_scan: bad options");
+    if (o->max_half_score < 0 || o->max_half_score > 16 || o->max_sites < 0 || (o->energy != 0 && o->energy != 1)) return fail(c, -1, "mirp_target_scan: bad options");
     HIPCHK(c, hipSetDevice(c->device));
     double sec[5] = {0, 0, 0, 0, 0};
     double t = tg_clock();
@@ -150,7 +150,8 @@ extern "C" int mirp_target_scan(mirp_ctx* c, const char* mirna_path, const char*
         if (std::fwrite(p, 1, len, f) != len) { ok = false; return fail(c, -8, std::string("cannot write ") + out_path); }
         return 0;
     };
-    const std::string head = std::string("miRNA\ttarget\tstart\tend\tstrand\tscore\tmismatches\tgu\tmirna_5to3\tpairs\ttarget_3to5") + (o->bulge ? "\tbulge\n" : "\n");
+    const std::string head = std::string("miRNA\ttarget\tstart\tend\tstrand\tscore\tmismatches\tgu\tmirna_5to3\tpairs\ttarget_3to5") + (o->bulge ? "\tbulge" : "") +
+                             (o->energy ? "\tmfe\tmfe_perfect\tmfe_ratio\tduplex\n" : "\n");
     int rc = sink(head.data(), head.size());
     long long st2[2] = {0, 0};
     double dsec[4] = {0, 0, 0, 0};

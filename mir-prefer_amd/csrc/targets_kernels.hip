@@ -23,6 +23,8 @@
 //   emit   tg_emit_kernel writes the lines; the text goes to the sink in pieces of at most 1 GiB.
 // With --bulge the scan is tg_bulge_scan_kernel (targets_bulge_device.h), which also finds the sites with one unpaired base; its keys are
 // mloc << 45 | half << 40 | start << 8 | strand << 7 | kind << 5 | P, again in output order, and order, cut and emit run as their <true> instances.
+// With --energy the sorted keys of a pass are folded (duplex_kernels.hip) before the cut measures the lines, and every line gains
+// the columns mfe, mfe_perfect, mfe_ratio and duplex; without it TgText's energy pointers are null and the lines are as before.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -46,7 +48,43 @@ struct TgText {
     const char* tnames; const long long* tnoff;
     const unsigned long long* cstart; int n_contigs;
     int mbase;                              // the group's first miRNA
+    // --energy, else null: the ambiguity bitmap, the fold of every sorted key of the pass (duplex_kernels.hip: mfe and the masks of
+    // the paired positions of the miRNA and of the target strand) and the perfect duplex of every miRNA of the group
+    const unsigned* amb;
+    const int* e_mfe; const unsigned long long* e_ma; const unsigned long long* e_mb;
+    const int* e_perf;
 };
+
+// the four last columns of an --energy line: mfe, mfe_perfect, mfe_ratio (half up to three decimals; NA when the perfect duplex is unbound) and the
+// structure text of the miRNA (L nt) and the target strand (nb nt: the interval and its flanks)
+template <bool WRITE>
+__device__ void tg_energy_cols(TextOut<WRITE>& o, const TgText& T, long long idx, int mloc, int L, int nb) {
+    const int e = T.e_mfe[idx], pe = T.e_perf[mloc];
+    const int v[2] = {-e, -pe};
+    for (int x = 0; x < 2; x++) {
+        o.ch('\t');
+        if (v[x] > 0) o.ch('-');
+        o.num((unsigned long long)(v[x] / 100));
+        o.ch('.');
+        o.ch((char)('0' + v[x] / 10 % 10));
+        o.ch((char)('0' + v[x] % 10));
+    }
+    o.ch('\t');
+    if (pe == 0) { o.ch('N'); o.ch('A'); }
+    else {
+        const long long q = (2000ll * -e + -pe) / (2ll * -pe);
+        o.num((unsigned long long)(q / 1000));
+        o.ch('.');
+        o.ch((char)('0' + q / 100 % 10));
+        o.ch((char)('0' + q / 10 % 10));
+        o.ch((char)('0' + q % 10));
+    }
+    o.ch('\t');
+    const unsigned long long ma = T.e_ma[idx], mb = T.e_mb[idx];
+    for (int i = 0; i < L; i++) o.ch((ma >> i) & 1 ? '(' : '.');
+    o.ch('&');
+    for (int j = 0; j < nb; j++) o.ch((mb >> j) & 1 ? ')' : '.');
+}
 
 // pair class of miRNA code mc (0..3 A C G U, 4 unknown) with target-strand base y (0..3 A C G U): 0 Watson-Crick, 1 G:U, 2 mismatch
 __device__ __forceinline__ int tg_class(unsigned mc, unsigned y) {
@@ -55,9 +93,9 @@ __device__ __forceinline__ int tg_class(unsigned mc, unsigned y) {
     return (mc == 2 && y == 3) || (mc == 3 && y == 2) ? 1 : 2;
 }
 
-// one line: miRNA target start end strand score mismatches gu mirna_5to3 pairs target_3to5
+// one line: miRNA target start end strand score mismatches gu mirna_5to3 pairs target_3to5 (idx: the key's index in the pass, for --energy)
 template <bool WRITE>
-__device__ long long tg_line(const TgText& T, unsigned long long key, char* out) {
+__device__ long long tg_line(const TgText& T, unsigned long long key, long long idx, char* out) {
     TextOut<WRITE> o{out};
     const int mloc = (int)(key >> 38);
     const unsigned half = (unsigned)(key >> 33) & 31u;
@@ -106,6 +144,7 @@ __device__ long long tg_line(const TgText& T, unsigned long long key, char* out)
         const unsigned b = tg_base(T.pk, strand ? g + i - 1 : g + L - i);
         o.ch(RNA[strand ? 3u - b : b]);
     }
+    if (T.e_mfe) tg_energy_cols(o, T, idx, mloc, L, L + (g > T.cstart[a]) + (g + L < T.cstart[a + 1]));
     o.ch('\n');
     return o.n;
 }
@@ -113,7 +152,7 @@ __device__ long long tg_line(const TgText& T, unsigned long long key, char* out)
 // one line of a --bulge run: the columns of tg_line and the bulge column (. / tP / mP).  Column c of the three aligned strings holds miRNA position
 // i(c) and the target base q(c); the t site has one column more (the unpaired target base under a '-'), the m site a '-' under miRNA position P.
 template <bool WRITE>
-__device__ long long tg_bulge_line(const TgText& T, unsigned long long key, char* out) {
+__device__ long long tg_bulge_line(const TgText& T, unsigned long long key, long long idx, char* out) {
     TextOut<WRITE> o{out};
     const int mloc = (int)(key >> TG_BULGE_SHIFT);
     const unsigned half = (unsigned)(key >> 40) & 31u;
@@ -176,6 +215,10 @@ __device__ long long tg_bulge_line(const TgText& T, unsigned long long key, char
     o.ch('\t');
     if (kind == 1) o.ch('.');
     else { o.ch(kind == 2 ? 't' : 'm'); o.num((unsigned long long)P); }
+    if (T.e_mfe) {
+        const int len = L + kind - 1;
+        tg_energy_cols(o, T, idx, mloc, L, len + (g > T.cstart[a]) + (g + len < T.cstart[a + 1]));
+    }
     o.ch('\n');
     return o.n;
 }
@@ -200,7 +243,7 @@ __global__ void tg_size_kernel(TgText T, const unsigned long long* __restrict__ 
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const unsigned long long key = keys[i];
         const bool keep = k == 0 || emitted[key >> TgKey<BULGE>::shift] + (unsigned long long)(i - tg_run_first<BULGE>(keys, i)) < (unsigned long long)k;
-        size[i] = !keep ? 0 : BULGE ? (int)tg_bulge_line<false>(T, key, nullptr) : (int)tg_line<false>(T, key, nullptr);
+        size[i] = !keep ? 0 : BULGE ? (int)tg_bulge_line<false>(T, key, i, nullptr) : (int)tg_line<false>(T, key, i, nullptr);
         cnt += keep;
     }
     for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
@@ -219,8 +262,8 @@ __global__ void tg_emit_kernel(TgText T, const unsigned long long* __restrict__ 
     const long long base = toff[i0];
     for (long long i = i0 + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < i1; i += (long long)gridDim.x * blockDim.x)
         if (toff[i + 1] != toff[i]) {
-            if (BULGE) (void)tg_bulge_line<true>(T, keys[i], text + (toff[i] - base));
-            else (void)tg_line<true>(T, keys[i], text + (toff[i] - base));
+            if (BULGE) (void)tg_bulge_line<true>(T, keys[i], i, text + (toff[i] - base));
+            else (void)tg_line<true>(T, keys[i], i, text + (toff[i] - base));
         }
 }
 
@@ -295,6 +338,13 @@ struct TgRun {
         unsigned long long* d_small = (unsigned long long*)c->tg_small.p;
         long long* d_toff = (long long*)c->tg_toff.p;
         HIPCHK(c, hipMemsetAsync(d_small + 1, 0, 8, st));
+        if (o->energy) {                                       // the folds of the sorted keys that -k keeps: the width of `mfe` is part of a line's length
+            const DxTargets D{T.pk, T.amb, T.mcodes, T.mi, T.cstart, T.n_contigs, mbase};
+            if (int rc = mirp_device_duplex_sites(c, D, bulge, (const unsigned long long*)d_keys, n, (long long)o->max_sites,
+                                                  (const unsigned long long*)c->tg_emitted.p, (int*)c->tg_emfe.p, (unsigned long long*)c->tg_ema.p,
+                                                  (unsigned long long*)c->tg_emb.p))
+                return rc;
+        }
         hipLaunchKernelGGL(bulge ? tg_size_kernel<true> : tg_size_kernel<false>, dim3(tg_grid(n)), dim3(256), 0, st, T, (const unsigned long long*)d_keys, n,
                            (long long)o->max_sites, (const unsigned long long*)c->tg_emitted.p, (int*)c->tg_size.p, d_small + 1);
         hipLaunchKernelGGL(bulge ? tg_emitted_kernel<true> : tg_emitted_kernel<false>, dim3(tg_grid(n)), dim3(256), 0, st, (const unsigned long long*)d_keys, n,
@@ -360,6 +410,14 @@ struct TgRun {
         for (int m = 0; m < n; m++) set_range(mbase, m, 0, smax);
         long long hits = 0;
         if (int rc = scan(0, mbase, 0, n, 0, total, &hits)) return rc;
+        if (o->energy) {                                       // mfe_perfect, once per miRNA (the scan has uploaded the group's TgMirna)
+            const double t = tg_now();
+            if (int rc = mirp_device_duplex_perfect(c, (const unsigned char*)c->tg_mcodes.p + 32 * (size_t)mbase, (const TgMirna*)c->tg_mi.p, n, (int*)c->tg_perf.p,
+                                                    nullptr, nullptr))
+                return rc;
+            HIPCHK(c, hipStreamSynchronize(st));
+            sec[1] += tg_now() - t;
+        }
         if (hits <= cap) return finish(mbase, hits);
         // overflow: hits per (miRNA, half-score), then passes of at most cap keys in output order
         HIPCHK(c, hipMemsetAsync(c->tg_hist.p, 0, 8 * (size_t)n * TG_NHALF, st));
@@ -439,6 +497,9 @@ int mirp_device_target_scan(mirp_ctx* c, const unsigned long long* pk, const uns
         c->tg_emitted.ensure(8 * (size_t)TG_GROUP) || c->tg_hist.ensure(8 * (size_t)TG_GROUP * TG_NHALF) || c->tg_small.ensure(64) ||
         c->tg_keys.ensure(8 * (size_t)cap) || c->tg_ktmp.ensure(8 * (size_t)cap) || c->tg_size.ensure(4 * (size_t)cap) || c->tg_toff.ensure(8 * (size_t)(cap + 1)))
         return fail(c, -6, "device allocation failed (targets)");
+    if (o.energy && (c->tg_emfe.ensure(4 * (size_t)cap) || c->tg_ema.ensure(8 * (size_t)cap) || c->tg_emb.ensure(8 * (size_t)cap) ||
+                     c->tg_perf.ensure(4 * (size_t)TG_GROUP)))
+        return fail(c, -6, "device allocation failed (targets: energies)");
     HIPCHK(c, hipMemcpyAsync(c->tg_pk.p, pk, 8 * (size_t)n_pk, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->tg_amb.p, amb, 4 * (size_t)n_bm, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->tg_cst.p, cst, 4 * (size_t)n_bm, hipMemcpyHostToDevice, st));
@@ -457,6 +518,13 @@ int mirp_device_target_scan(mirp_ctx* c, const unsigned long long* pk, const uns
     run.T = TgText{(const unsigned long long*)c->tg_pk.p, (const unsigned char*)c->tg_mcodes.p, (const TgMirna*)c->tg_mi.p, (const char*)c->tg_mnames.p,
                    (const long long*)c->tg_mnoff.p, (const char*)c->tg_names.p, (const long long*)c->tg_noff.p, (const unsigned long long*)c->tg_cstart.p,
                    (int)cstart.size() - 1, 0};
+    if (o.energy) {
+        run.T.amb = (const unsigned*)c->tg_amb.p;
+        run.T.e_mfe = (const int*)c->tg_emfe.p;
+        run.T.e_ma = (const unsigned long long*)c->tg_ema.p;
+        run.T.e_mb = (const unsigned long long*)c->tg_emb.p;
+        run.T.e_perf = (const int*)c->tg_perf.p;
+    }
     run.o = &o;
     run.mi = &mi;
     run.sink = &sink;

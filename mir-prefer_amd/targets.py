@@ -24,6 +24,12 @@ HELP = """python -m mir_prefer_amd.targets [options] <mirna.fa> <target.fa> [<ta
     costing 1, or 2 inside positions 2..13) are written too, and every line ends with a
     column `bulge`: `.`, `tP` or `mP`, P = the miRNA position before the unpaired target
     base, or the unpaired miRNA position itself.
+    With -e, every line ends with four more columns: `mfe`, the minimum free energy
+    (kcal/mol, Turner 2004) of the duplex of the miRNA with the site and one flanking base
+    on each side, folded freely; `mfe_perfect`, that of the miRNA with its reverse
+    complement; `mfe_ratio`, mfe / mfe_perfect to three decimals (NA when mfe_perfect is
+    0); and `duplex`, the structure: the miRNA as ( and ., then &, then the target strand
+    5'->3' as ) and .
 
     Example:
     python -m mir_prefer_amd.targets -s 3 -c out/prefix_miRNA.mature.fa cdna.fa
@@ -36,6 +42,7 @@ def make_parser():
     parser.add_option("-b", "--both-strands", action="store_true", help="Also scan the minus strand of the targets (for genome-sized targets).")
     parser.add_option("-c", "--cleavage-site", action="store_true", help="Reject sites with a mismatch (not a G:U) at miRNA position 10 or 11.")
     parser.add_option("-g", "--bulge", action="store_true", help="Also write sites with exactly one unpaired nucleotide; adds the column `bulge`.")
+    parser.add_option("-e", "--energy", action="store_true", help="Fold every site's miRNA:target duplex; adds the columns `mfe mfe_perfect mfe_ratio duplex`.")
     parser.add_option("-k", "--max-sites", type=int, default=0, help="Write the first N sites per miRNA, in output order; 0 = all (default).")
     parser.add_option("-o", "--output", help="Output file. Default <mirna.fa>.targets.tsv.")
     parser.add_option("--device", type=int, default=0, help="GPU device index. Default is 0.")
@@ -96,7 +103,7 @@ def main(argv=None):
         return _fail("the target search runs on the GPU and none is usable (%s); there is no CPU path." % e)
     try:
         res = ctx.target_scan(mirna, targets, out, max_half_score=half, both_strands=bool(options.both_strands),
-                              cleavage_site=bool(options.cleavage_site), max_sites=options.max_sites, bulge=bool(options.bulge))
+                              cleavage_site=bool(options.cleavage_site), max_sites=options.max_sites, bulge=bool(options.bulge), energy=bool(options.energy))
     except (OSError, capi.MirpError) as e:
         return _fail(str(e))
     finally:
