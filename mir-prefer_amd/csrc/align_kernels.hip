@@ -21,7 +21,6 @@
 //   order     mirp_device_sort_u64 by the whole record: per read, (contig, offset, + before -); the first K per read are kept.
 //   emit      al_size_kernel, launch_excl_scan, al_emit_kernel: the SAM records on the device (one shared routine counts and writes).
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -374,7 +373,6 @@ static inline int al_grid(long long n) {
     const long long g = (n + 255) / 256;
     return (int)(g < 1 ? 1 : g > 16384 ? 16384 : g);
 }
-static inline double al_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 static mirp::AlRef al_ref(const mirp_ctx* c) {
     return mirp::AlRef{(const unsigned*)c->a_pk.p, (const unsigned*)c->a_amb.p, (const unsigned*)c->a_cst.p, (const unsigned*)c->a_sa.p,
@@ -389,7 +387,7 @@ int mirp_device_align_index(mirp_ctx* c, const unsigned* pk, const unsigned* amb
     hipStream_t st = c->stream;
     c->a_ready = false;
     const long long n_pk = (total + 15) / 16 + 2, n_bm = (total + 31) / 32 + 2, n_words = (total + 31) / 32;
-    double t = al_now();
+    double t = mirp::now();
     if (c->a_pk.ensure(4 * (size_t)n_pk) || c->a_amb.ensure(4 * (size_t)n_bm) || c->a_cst.ensure(4 * (size_t)n_bm) ||
         c->a_cstart.ensure(8 * cstart.size()) || c->a_names.ensure(names.size() + 1) || c->a_noff.ensure(8 * noff.size()))
         return fail(c, -6, "device allocation failed (align: reference)");
@@ -400,10 +398,10 @@ int mirp_device_align_index(mirp_ctx* c, const unsigned* pk, const unsigned* amb
     if (!names.empty()) HIPCHK(c, hipMemcpyAsync(c->a_names.p, names.data(), names.size(), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->a_noff.p, noff.data(), 8 * noff.size(), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    seconds[0] = al_now() - t;
+    seconds[0] = mirp::now() - t;
 
     // ---- keys of the unambiguous positions, in position order
-    t = al_now();
+    t = mirp::now();
     TmpDevice T;
     int* wcnt = (int*)T.get(4 * (size_t)std::max<long long>(n_words, 1));
     long long* wscan = (long long*)T.get(8 * (size_t)(n_words + 1));
@@ -422,16 +420,16 @@ int mirp_device_align_index(mirp_ctx* c, const unsigned* pk, const unsigned* amb
     if (N > 0) hipLaunchKernelGGL(al_keys_kernel, dim3(al_grid(n_words)), dim3(256), 0, st, R0, n_words, (const long long*)wscan, rec);
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
-    seconds[1] = al_now() - t;
+    seconds[1] = mirp::now() - t;
 
     // ---- stable sort by key
-    t = al_now();
+    t = mirp::now();
     if (int rc = mirp_device_sort_u64(c, rec, rtmp, N, 32, 32)) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
-    seconds[2] = al_now() - t;
+    seconds[2] = mirp::now() - t;
 
     // ---- positions + bucket table
-    t = al_now();
+    t = mirp::now();
     if (c->a_sa.ensure(4 * (size_t)std::max<long long>(N, 1) + 16) || c->a_bkt.ensure(8 * ((size_t)AL_NBKT + 1)))
         return fail(c, -6, "device allocation failed (align: index)");
     int* hist = (int*)rtmp;     // the sort's second buffer is done with (4^12 ints = 64 MiB; N >= 2^23 records or a separate buffer)
@@ -444,7 +442,7 @@ int mirp_device_align_index(mirp_ctx* c, const unsigned* pk, const unsigned* amb
     launch_excl_scan(st, hist, (long long*)c->a_bkt.p, (long long)AL_NBKT);
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
-    seconds[3] = al_now() - t;
+    seconds[3] = mirp::now() - t;
     c->a_total = total;
     c->a_nsa = N;
     c->a_n_contigs = (int)cstart.size() - 1;
@@ -462,7 +460,7 @@ int mirp_device_align_batch(mirp_ctx* c, const unsigned char* codes, const long 
     hipStream_t st = c->stream;
     const AlParams P{v, v / 2, k, m, filter};
     const AlRef R = al_ref(c);
-    double t = al_now();
+    double t = mirp::now();
     const long long nb = roff[n], nq = qoff[n];
     if (c->a_codes.ensure((size_t)nb + 16) || c->a_roff.ensure(8 * (size_t)(n + 1)) || c->a_qn.ensure((size_t)nq + 16) || c->a_qoff.ensure(8 * (size_t)(n + 1)) ||
         c->a_small.ensure(64))
@@ -474,13 +472,13 @@ int mirp_device_align_batch(mirp_ctx* c, const unsigned char* codes, const long 
     unsigned long long* d_small = (unsigned long long*)c->a_small.p;    // [0..2] aligned / unaligned / suppressed, [3] records, [4] overflow flag
     HIPCHK(c, hipMemsetAsync(d_small, 0, 64, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    seconds[0] += al_now() - t;
+    seconds[0] += mirp::now() - t;
     const unsigned char* d_codes = (const unsigned char*)c->a_codes.p;
     const long long* d_roff = (const long long*)c->a_roff.p;
     const int g = al_grid(n);
 
     // ---- seeds
-    t = al_now();
+    t = mirp::now();
     if (c->a_rcnt.ensure(4 * (size_t)n) || c->a_rscan.ensure(8 * (size_t)(n + 1))) return fail(c, -6, "device allocation failed (align: seeds)");
     int* d_rcnt = (int*)c->a_rcnt.p;
     long long* d_rscan = (long long*)c->a_rscan.p;
@@ -505,10 +503,10 @@ int mirp_device_align_batch(mirp_ctx* c, const unsigned char* codes, const long 
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
     if (ovf) return fail(c, -5, "a seed matches 2^31 or more index positions");
-    seconds[1] += al_now() - t;
+    seconds[1] += mirp::now() - t;
 
     // ---- verify: counts, strata, best-stratum hits
-    t = al_now();
+    t = mirp::now();
     if (c->a_lvl.ensure(16 * (size_t)n) || c->a_best.ensure(4 * (size_t)n) || c->a_supp.ensure(4 * (size_t)n) || c->a_slots.ensure(4 * (size_t)n) ||
         c->a_off.ensure(8 * (size_t)(n + 1)) || c->a_cursor.ensure(4 * (size_t)n))
         return fail(c, -6, "device allocation failed (align: strata)");
@@ -536,18 +534,18 @@ int mirp_device_align_batch(mirp_ctx* c, const unsigned char* codes, const long 
     hipLaunchKernelGGL(al_unaln_kernel, dim3(g), dim3(256), 0, st, (const int*)d_best, (const long long*)d_off, n, d_items);
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
-    seconds[2] += al_now() - t;
+    seconds[2] += mirp::now() - t;
 
     // ---- order: by (read, gpos, strand)
-    t = al_now();
+    t = mirp::now();
     int rbits = 0;
     while ((1ll << rbits) < n) rbits++;
     if (int rc = mirp_device_sort_u64(c, d_items, (unsigned long long*)c->a_itmp.p, NI, 0, (33 + rbits + 7) / 8 * 8)) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
-    seconds[3] += al_now() - t;
+    seconds[3] += mirp::now() - t;
 
     // ---- emit + download
-    t = al_now();
+    t = mirp::now();
     if (c->a_size.ensure(4 * (size_t)std::max<long long>(NI, 1)) || c->a_toff.ensure(8 * (size_t)(NI + 1)))
         return fail(c, -6, "device allocation failed (align: text offsets)");
     const AlText TX{d_codes, d_roff, (const char*)c->a_qn.p, (const long long*)c->a_qoff.p, (const char*)c->a_names.p, (const long long*)c->a_noff.p,
@@ -569,15 +567,8 @@ int mirp_device_align_batch(mirp_ctx* c, const unsigned char* codes, const long 
     HIPCHK(c, hipMemcpyAsync(cnt, d_small, 32, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
-    const size_t piece = (size_t)1 << 30;
-    if (bytes > 0 && c->h_text.size() < std::min((size_t)bytes, piece)) c->h_text.resize(std::min((size_t)bytes, piece));
-    for (long long at = 0; at < bytes;) {
-        const size_t len = (size_t)std::min<long long>(bytes - at, (long long)piece);
-        HIPCHK(c, hipMemcpy(c->h_text.data(), (const char*)c->a_text.p + at, len, hipMemcpyDeviceToHost));
-        if (int rc = sink(c->h_text.data(), len)) return rc;
-        at += (long long)len;
-    }
-    seconds[4] += al_now() - t;
+    if (int rc = mirp_download_text(c, (const char*)c->a_text.p, bytes, sink)) return rc;
+    seconds[4] += mirp::now() - t;
     for (int i = 0; i < 4; i++) stats[i] += (long long)cnt[i];
     return 0;
 }

@@ -12,19 +12,19 @@
 //     rank = distance << 7 | mm << 4 | |d| << 1 | (d > 0)             the order in which shifts are preferred; the minimum over admissible s
 // A pair is a hit when some s in -E .. E has |offset3| <= E and mm <= M.  The minimum stays in a register.
 //
-//   count  an_scan_kernel<1>: hits per query (cnt[q]); the host plans the passes from it and it is the summary's `hits` column.
+//   count  an_scan_kernel<1>: hits per query (cnt[q]): the bins of plan_passes (pass_plan.h) and the summary's `hits` column.
 //   keys   an_scan_kernel<0>: queries [q0, q1) (at most 2^16, a group) against known [k0, k1), hits whose (distance, mm) bin lies in [blo, bhi]
 //          append the key qloc << 35 | distance << 31 | mm << 28 | known << 4 | d + 4 to a buffer of `cap` keys and count them.
-//   bins   an_scan_kernel<2>: hits of one query per (distance, mm) bin, for a query whose hits alone exceed `cap`.
+//   bins   an_scan_kernel<2>: hits of one query per (distance, mm) bin, for a query whose hits alone exceed `cap`: planned again by these bins.
 //   order  mirp_device_sort_u64 on bits 4 .. 51: per query, (distance, mismatches, known) = the output order.
 //   cut    an_cut_kernel: -k by the key's rank in its query's run (the runs' starts come from the counts), kept keys compacted in order.
 // The lines are written on the host from the kept keys (mirp_annotate.cpp).
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <vector>
 #include "mirp_ctx.h"
+#include "pass_plan.h"
 #include "targets_device.h"
 #include "wave_atomic.h"
 
@@ -126,8 +126,6 @@ __global__ void an_cut_kernel(const unsigned long long* __restrict__ keys, long 
 
 namespace {
 
-double an_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 struct AnRun {
     mirp_ctx* c;
     const mirp::AnSeq* d_q;
@@ -166,7 +164,7 @@ struct AnRun {
 
     // the keys of queries [q0, q1), bins [blo, bhi], known [k0, k1) into tg_keys; -> hits (maybe > cap)
     int scan_keys(long long q0, long long q1, long long k0, long long k1, unsigned blo, unsigned bhi, long long* hits) {
-        const double t = an_now();
+        const double t = mirp::now();
         hipStream_t st = c->stream;
         HIPCHK(c, hipMemsetAsync(c->tg_small.p, 0, 8, st));
         launch<0>(q0, q1, k0, k1, blo, bhi, q0);
@@ -175,7 +173,7 @@ struct AnRun {
         HIPCHK(c, hipStreamSynchronize(st));
         HIPCHK(c, hipGetLastError());
         *hits = (long long)h;
-        sec[1] += an_now() - t;
+        sec[1] += mirp::now() - t;
         return 0;
     }
 
@@ -186,7 +184,7 @@ struct AnRun {
         hipStream_t st = c->stream;
         stats[2]++;
         if (n == 0) return 0;
-        double t = an_now();
+        double t = mirp::now();
         unsigned long long* d_keys = (unsigned long long*)c->tg_keys.p;
         int qbits = 0;
         while ((1ll << qbits) < q1 - q0) qbits++;
@@ -207,15 +205,15 @@ struct AnRun {
         }
         HIPCHK(c, hipStreamSynchronize(st));
         HIPCHK(c, hipGetLastError());
-        sec[2] += an_now() - t;
-        t = an_now();
+        sec[2] += mirp::now() - t;
+        t = mirp::now();
         if (keep > 0) {
             if ((long long)h_keys.size() < keep) h_keys.resize((size_t)keep);
             HIPCHK(c, hipMemcpy(h_keys.data(), src, 8 * (size_t)keep, hipMemcpyDeviceToHost));
             if (int rc = (*sink)(q0, h_keys.data(), (size_t)keep)) return rc;
             stats[1] += keep;
         }
-        sec[3] += an_now() - t;
+        sec[3] += mirp::now() - t;
         return 0;
     }
 
@@ -237,55 +235,38 @@ struct AnRun {
     // one query with more hits than cap: passes of consecutive (distance, mm) bins, one bin over cap by ranges of known indices
     int oversize(long long q, long long total) {
         hipStream_t st = c->stream;
-        double t = an_now();
+        double t = mirp::now();
         HIPCHK(c, hipMemsetAsync(c->tg_hist.p, 0, 8 * AN_NBIN, st));
         launch<2>(q, q + 1, 0, nk, 0, AN_NBIN - 1, q);
         unsigned long long hist[AN_NBIN];
         HIPCHK(c, hipMemcpyAsync(hist, c->tg_hist.p, sizeof hist, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         HIPCHK(c, hipGetLastError());
-        sec[0] += an_now() - t;
-        long long sum = 0, emitted = 0, pend = 0;
+        sec[0] += mirp::now() - t;
+        long long sum = 0, emitted = 0;
         for (int b = 0; b < AN_NBIN; b++) sum += (long long)hist[b];
         if (sum != total) return fail(c, -5, "annotate: the bins of a query hold a different number of hits than counted");
-        int ba = -1, bb = -1;
-        auto left = [&]() { return K > 0 ? K - emitted : (1ll << 62); };
-        auto flush = [&]() -> int {
-            if (ba < 0) return 0;
+        // the bins are (distance, mm), the positions of a bin over cap are the known indices; -k: the walk ends once the pending
+        // pass holds the lines the query still lacks
+        const auto left = [&]() { return K > 0 ? K - emitted : (1ll << 62); };
+        const auto keep = [&](long long got) {
+            const long long n = std::min(got, left());
+            emitted += n;
+            return n;
+        };
+        const auto flush = [&](long long ba, long long bb, long long expected) -> int {
             long long got = 0;
             if (int rc = scan_keys(q, q + 1, 0, nk, (unsigned)ba, (unsigned)bb, &got)) return rc;
-            if (got != pend) return fail(c, -5, "annotate: a pass found a different number of hits than counted");
-            const long long keep = std::min(got, left());
-            emitted += keep;
-            ba = -1;
-            pend = 0;
-            return finish(q, q + 1, got, nullptr, nullptr, keep);
+            if (got != expected) return fail(c, -5, "annotate: a pass found a different number of hits than counted");
+            return finish(q, q + 1, got, nullptr, nullptr, keep(got));
         };
-        for (int b = 0; b < AN_NBIN && pend < left(); b++) {
-            const long long n = (long long)hist[b];
-            if (n == 0) continue;
-            if (pend + n > cap)
-                if (int rc = flush()) return rc;
-            if (left() <= 0) break;
-            if (n <= cap) {
-                if (ba < 0) ba = b;
-                bb = b;
-                pend += n;
-                continue;
-            }
-            long long len = nk;
-            for (long long p = 0; p < nk && left() > 0;) {
-                const long long p1 = std::min(nk, p + len);
-                long long got = 0;
-                if (int rc = scan_keys(q, q + 1, p, p1, (unsigned)b, (unsigned)b, &got)) return rc;
-                if (got > cap) { len = std::max<long long>(1, len / 2); continue; }
-                const long long keep = std::min(got, left());
-                emitted += keep;
-                if (int rc = finish(q, q + 1, got, nullptr, nullptr, keep)) return rc;
-                p = p1;
-            }
-        }
-        return flush();
+        const auto range = [&](long long b, unsigned long long p, unsigned long long p1, long long* got) -> int {
+            if (int rc = scan_keys(q, q + 1, (long long)p, (long long)p1, (unsigned)b, (unsigned)b, got)) return rc;
+            return *got > cap ? 0 : finish(q, q + 1, *got, nullptr, nullptr, keep(*got));
+        };
+        const int rc = mirp::plan_passes(AN_NBIN, [&](long long b) { return (long long)hist[b]; }, cap, (unsigned long long)nk, flush, range, 0,
+                                         [&](long long pend) { return pend >= left(); });
+        return rc == mirp::PLAN_POSITION_OVER_CAP ? fail(c, -5, "annotate: one known sequence holds more hits of one query than a pass") : rc;
     }
 };
 
@@ -301,7 +282,7 @@ int mirp_device_annotate(mirp_ctx* c, const std::vector<AnPacked>& q, const std:
     hits_per_query.assign((size_t)nq, 0u);
     if (nq == 0 || nk == 0) return 0;
     const long long cap = c->tg_cap > 0 ? c->tg_cap : (1ll << 26);
-    double t = an_now();
+    double t = mirp::now();
     if (c->an_pack.ensure(sizeof(AnPacked) * (size_t)std::max(nq, nk)) || c->an_q.ensure(sizeof(AnSeq) * (size_t)nq) || c->an_k.ensure(sizeof(AnSeq) * (size_t)nk) ||
         c->an_cnt.ensure(4 * (size_t)nq) || c->tg_small.ensure(64) || c->tg_hist.ensure(8 * AN_NBIN))
         return fail(c, -6, "device allocation failed (annotate)");
@@ -312,7 +293,7 @@ int mirp_device_annotate(mirp_ctx* c, const std::vector<AnPacked>& q, const std:
     HIPCHK(c, hipMemsetAsync(c->an_cnt.p, 0, 4 * (size_t)nq, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
-    seconds[0] = an_now() - t;
+    seconds[0] = mirp::now() - t;
 
     AnRun run;
     run.c = c;
@@ -321,12 +302,12 @@ int mirp_device_annotate(mirp_ctx* c, const std::vector<AnPacked>& q, const std:
     run.nq = nq; run.nk = nk; run.cap = cap; run.K = max_lines;
     run.E = max_offset; run.M = max_mismatches;
     run.sink = &sink;
-    t = an_now();
+    t = mirp::now();
     run.launch<1>(0, nq, 0, nk, 0, AN_NBIN - 1, 0);
     HIPCHK(c, hipMemcpyAsync(hits_per_query.data(), c->an_cnt.p, 4 * (size_t)nq, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
-    run.sec[0] += an_now() - t;
+    run.sec[0] += mirp::now() - t;
     const unsigned* cnt = hits_per_query.data();
     long long total = 0;
     for (long long i = 0; i < nq; i++) total += cnt[i];
@@ -336,29 +317,14 @@ int mirp_device_annotate(mirp_ctx* c, const std::vector<AnPacked>& q, const std:
         if (c->tg_keys.ensure(8 * (size_t)hold) || c->tg_ktmp.ensure(8 * (size_t)hold)) return fail(c, -6, "device allocation failed (annotate: keys)");
         run.held = hold;
     }
-    // passes: consecutive queries of one group with at most cap hits together; queries without hits at either end of a range are left out
-    long long qa = -1, qb = -1, pend = 0;
-    auto flush = [&]() -> int {
-        if (qa < 0) return 0;
-        const int rc = run.pass(qa, qb + 1, cnt, pend);
-        qa = -1;
-        pend = 0;
-        return rc;
+    // the bins are the queries, at most AN_GROUP indices to a pass; a query over cap is one position, which oversize() plans by its
+    // own bins and finishes
+    const auto flush = [&](long long qa, long long qb, long long expected) { return run.pass(qa, qb + 1, cnt, expected); };
+    const auto range = [&](long long i, unsigned long long, unsigned long long, long long* got) {
+        *got = 0;
+        return run.oversize(i, cnt[i]);
     };
-    for (long long i = 0; i < nq; i++) {
-        const long long n = cnt[i];
-        if (n == 0) continue;
-        if (qa >= 0 && (pend + n > cap || i - qa >= AN_GROUP))
-            if (int rc = flush()) return rc;
-        if (n > cap) {
-            if (int rc = run.oversize(i, n)) return rc;
-            continue;
-        }
-        if (qa < 0) qa = i;
-        qb = i;
-        pend += n;
-    }
-    if (int rc = flush()) return rc;
+    if (int rc = plan_passes(nq, [&](long long i) { return (long long)cnt[i]; }, cap, 1, flush, range, AN_GROUP)) return rc;
     for (int i = 0; i < 3; i++) stats[i] = run.stats[i];
     for (int i = 0; i < 4; i++) seconds[1 + i] = run.sec[i];
     return 0;

@@ -13,18 +13,19 @@
 //   anchored   dg_scan_kernel: one lane per kept unit, the miRNAs in wave-uniform (scalar) loads, masks anchored at window position 32 - i
 //              (make_mirna(..., anchored)), so one evaluation is tg_eval and nothing else; a miRNA of length L needs L <= avail.
 //              MODE 1 counts hits per (miRNA, category, half-score); the host turns the counts into p-values and keeps the bins with p <= alpha.
-//              MODE 0 appends the key mloc << 40 | category << 37 | half << 32 | packed position for hits in the kept bins of the pass.
+//              MODE 0 appends the key mloc << 40 | category << 37 | half << 32 | packed position for hits in the kept bins of the pass;
+//              the passes are those of plan_passes (pass_plan.h) over the kept bins, with packed positions inside a bin.
 //   order      mirp_device_sort_u64 by the whole key = the output order; dg_hit_kernel looks each key's unit up again (two binary searches) and
 //              adds its reads and its transcript's amax; the 24-byte hit records go to the host, which writes the lines.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <functional>
 #include <string>
 #include <vector>
 #include "mirp_ctx.h"
+#include "pass_plan.h"
 #include "targets_device.h"
 #include "wave_atomic.h"
 
@@ -247,7 +248,6 @@ __global__ void __launch_bounds__(DG_NT) dg_hit_kernel(const unsigned long long*
 
 }  // namespace mirp
 
-static inline double dg_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 #define DG_SYNC(c, st)                          \
     do {                                        \
@@ -266,16 +266,14 @@ int mirp_device_degradome(mirp_ctx* c, const unsigned long long* pk, const unsig
     const MirpAln* alns = (const MirpAln*)c->alns.p;
     const int n_sq = (int)sqlen.size(), n_f = (int)cstart.size() - 1;
     const long long n_mi = (long long)mi.size();
-    const long long n_pk = (total + 31) / 32 + 2, n_bm = (total + 31) / 32 + 2;
     const long long cap = c->tg_cap > 0 ? c->tg_cap : (1ll << 26);
     std::memset(stats, 0, 12 * sizeof(long long));
     std::memset(seconds, 0, 6 * sizeof(double));
     if (n > (1ll << 31) - 2) return fail(c, -5, "mirp_degradome_scan: more than 2^31 records");
     TmpDevice T;
-    double t0 = dg_now();
+    double t0 = mirp::now();
     // ---- upload: the packed transcripts (the buffers of the target-site search) and the tables by SAM tid / FASTA index
-    if (c->tg_pk.ensure(8 * (size_t)n_pk) || c->tg_amb.ensure(4 * (size_t)n_bm) || c->tg_cst.ensure(4 * (size_t)n_bm) || c->tg_cstart.ensure(8 * cstart.size()) ||
-        c->tg_mi.ensure(sizeof(TgMirna) * TG_GROUP) || c->tg_hist.ensure(8 * (size_t)TG_GROUP * TG_NHALF) || c->tg_small.ensure(64))
+    if (c->tg_mi.ensure(sizeof(TgMirna) * TG_GROUP) || c->tg_hist.ensure(8 * (size_t)TG_GROUP * TG_NHALF) || c->tg_small.ensure(64))
         return fail(c, -6, "device allocation failed (degradome)");
     long long* d_sqlen = (long long*)T.get(8 * (size_t)std::max(n_sq, 1));
     unsigned long long* d_sqstart = (unsigned long long*)T.get(8 * (size_t)std::max(n_sq, 1));
@@ -283,10 +281,8 @@ int mirp_device_degradome(mirp_ctx* c, const unsigned long long* pk, const unsig
     unsigned long long* d_tstat = (unsigned long long*)T.get(8 * 4 * (size_t)std::max(n_sq, 1));     // amax, nmax, npos, tot
     unsigned long long* d_counts = (unsigned long long*)T.get(8 * 8);                                 // sense, minus, C_0 .. C_4
     if (!d_sqlen || !d_sqstart || !d_f2s || !d_tstat || !d_counts) return fail(c, -6, "device allocation failed (degradome)");
-    HIPCHK(c, hipMemcpyAsync(c->tg_pk.p, pk, 8 * (size_t)n_pk, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->tg_amb.p, amb, 4 * (size_t)n_bm, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->tg_cst.p, cst, 4 * (size_t)n_bm, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->tg_cstart.p, cstart.data(), 8 * cstart.size(), hipMemcpyHostToDevice, st));
+    TgRef R;
+    if (int rc = tg_upload_packed(c, pk, amb, cst, total, cstart, &R)) return rc;
     if (n_sq > 0) {
         HIPCHK(c, hipMemcpyAsync(d_sqlen, sqlen.data(), 8 * (size_t)n_sq, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemcpyAsync(d_sqstart, sqstart.data(), 8 * (size_t)n_sq, hipMemcpyHostToDevice, st));
@@ -295,15 +291,14 @@ int mirp_device_degradome(mirp_ctx* c, const unsigned long long* pk, const unsig
     HIPCHK(c, hipMemsetAsync(d_tstat, 0, 8 * 4 * (size_t)std::max(n_sq, 1), st));
     HIPCHK(c, hipMemsetAsync(d_counts, 0, 64, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    seconds[0] = dg_now() - t0;
-    const TgRef R{(const unsigned long long*)c->tg_pk.p, (const unsigned*)c->tg_amb.p, (const unsigned*)c->tg_cst.p, (unsigned long long)total};
+    seconds[0] = mirp::now() - t0;
     unsigned long long* amax = d_tstat;
     unsigned long long* nmax = d_tstat + (size_t)std::max(n_sq, 1);
     unsigned long long* npos = d_tstat + 2 * (size_t)std::max(n_sq, 1);
     unsigned long long* tot = d_tstat + 3 * (size_t)std::max(n_sq, 1);
 
     // ---- units, categories, windows
-    t0 = dg_now();
+    t0 = mirp::now();
     long long ns = 0, nu = 0, nk = 0;
     unsigned long long* ukey = nullptr;
     unsigned long long* uab = nullptr;
@@ -358,7 +353,7 @@ int mirp_device_degradome(mirp_ctx* c, const unsigned long long* pk, const unsig
     unsigned long long h_counts[8];
     HIPCHK(c, hipMemcpyAsync(h_counts, d_counts, 64, hipMemcpyDeviceToHost, st));
     DG_SYNC(c, st);
-    seconds[1] = dg_now() - t0;
+    seconds[1] = mirp::now() - t0;
     stats[0] = n;
     stats[1] = (long long)h_counts[0];
     stats[2] = (long long)h_counts[1];
@@ -380,6 +375,7 @@ int mirp_device_degradome(mirp_ctx* c, const unsigned long long* pk, const unsig
     std::vector<unsigned long long> sites((size_t)gmax * TG_NHALF), hist((size_t)gmax * 5 * TG_NHALF);
     std::vector<double> pval((size_t)gmax * 5 * TG_NHALF);
     std::vector<unsigned> bins((size_t)gmax * 5), pbins((size_t)gmax * 5);
+    std::vector<size_t> kept;                       // the kept bins of a group in output order, as indices into hist
     std::vector<MirpDgHit> h_hits;
     for (long long m = 0; m < n_mi; m++) {
         mi[(size_t)m].smin = mi_anchored[(size_t)m].smin = 0;
@@ -388,7 +384,7 @@ int mirp_device_degradome(mirp_ctx* c, const unsigned long long* pk, const unsig
     for (long long mbase = 0; mbase < n_mi; mbase += TG_GROUP) {
         const int gn = (int)std::min<long long>(TG_GROUP, n_mi - mbase);
         // site counts N_m(h): the counting scan of the target-site search over every offset, plus strand
-        t0 = dg_now();
+        t0 = mirp::now();
         HIPCHK(c, hipMemcpyAsync(d_mi, mi.data() + mbase, sizeof(TgMirna) * (size_t)gn, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemcpyAsync(d_mia, mi_anchored.data() + mbase, sizeof(TgMirna) * (size_t)gn, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemsetAsync(c->tg_hist.p, 0, 8 * (size_t)gn * TG_NHALF, st));
@@ -401,18 +397,19 @@ int mirp_device_degradome(mirp_ctx* c, const unsigned long long* pk, const unsig
         DG_SYNC(c, st);
         for (int m = 0; m < gn; m++)
             for (int h = 1; h < TG_NHALF; h++) sites[(size_t)m * TG_NHALF + h] += sites[(size_t)m * TG_NHALF + h - 1];
-        seconds[2] += dg_now() - t0;
+        seconds[2] += mirp::now() - t0;
         // anchored counting pass
-        t0 = dg_now();
+        t0 = mirp::now();
         HIPCHK(c, hipMemsetAsync(d_hist, 0, 8 * (size_t)gn * 5 * TG_NHALF, st));
         hipLaunchKernelGGL((dg_scan_kernel<1>), dim3((unsigned)((nk + DG_NT - 1) / DG_NT)), dim3(DG_NT), 0, st, (const DgWin*)win, nk, 0ull, 0ull, (const TgMirna*)d_mia, 0, gn,
                            (const unsigned*)nullptr, (unsigned long long*)nullptr, 0ull, (unsigned long long*)nullptr, d_hist);
         HIPCHK(c, hipMemcpyAsync(hist.data(), d_hist, 8 * (size_t)gn * 5 * TG_NHALF, hipMemcpyDeviceToHost, st));
         DG_SYNC(c, st);
-        seconds[3] += dg_now() - t0;
+        seconds[3] += mirp::now() - t0;
         // p per (miRNA, category, half-score); the bins at or below alpha stay
-        t0 = dg_now();
+        t0 = mirp::now();
         long long surviving = 0;
+        kept.clear();
         for (int m = 0; m < gn; m++)
             for (int k = 0; k < 5; k++) {
                 unsigned b = 0;
@@ -424,11 +421,12 @@ int mirp_device_degradome(mirp_ctx* c, const unsigned long long* pk, const unsig
                     if (hist[i] && p <= alpha) {
                         b |= 1u << h;
                         surviving += (long long)hist[i];
+                        kept.push_back(i);
                     }
                 }
                 bins[(size_t)m * 5 + k] = b;
             }
-        if (surviving == 0) { seconds[4] += dg_now() - t0; continue; }
+        if (surviving == 0) { seconds[4] += mirp::now() - t0; continue; }
         const long long kcap = std::max(2ll, std::min(cap, surviving));
         TmpDevice K;
         unsigned long long* d_keys = (unsigned long long*)K.get(8 * (size_t)kcap);
@@ -461,48 +459,30 @@ int mirp_device_degradome(mirp_ctx* c, const unsigned long long* pk, const unsig
             stats[10] += *got;
             return sink((int)mbase, h_hits.data(), (size_t)*got, sites.data(), pval.data());
         };
-        // passes of consecutive (miRNA, category, half-score) bins of at most kcap keys, in output order
-        int ma = -1, mb = -1;
-        long long pend = 0;
-        std::fill(pbins.begin(), pbins.end(), 0u);
-        auto flush = [&]() -> int {
-            if (ma < 0) return 0;
+        // the bins are the kept (miRNA, category, half-score), the positions of a bin over kcap are the packed positions.  pbins
+        // holds the bins of the pass under way, bit h of row miRNA * 5 + category as in `bins`, and is cleared after it
+        const auto count = [&](long long i) { return (long long)hist[kept[(size_t)i]]; };
+        const auto flush = [&](long long first, long long last, long long expected) -> int {
+            const size_t ra = kept[(size_t)first] / TG_NHALF, rb = kept[(size_t)last] / TG_NHALF;
+            std::copy(bins.begin() + ra, bins.begin() + rb + 1, pbins.begin() + ra);
+            pbins[ra] &= ~0u << (kept[(size_t)first] % TG_NHALF);
+            pbins[rb] &= (2u << (kept[(size_t)last] % TG_NHALF)) - 1u;
             long long got = 0;
-            const int rc = pass(ma, mb, 0ull, (unsigned long long)total, pend, &got);
-            for (int m = ma; m <= mb; m++)
-                for (int k = 0; k < 5; k++) pbins[(size_t)m * 5 + k] = 0;
-            ma = -1;
-            pend = 0;
+            const int rc = pass((int)(ra / 5), (int)(rb / 5), 0ull, (unsigned long long)total, expected, &got);
+            std::fill(pbins.begin() + ra, pbins.begin() + rb + 1, 0u);
             return rc;
         };
-        for (int m = 0; m < gn; m++)
-            for (int k = 0; k < 5; k++)
-                for (int h = 0; h <= max_half; h++) {
-                    if (!((bins[(size_t)m * 5 + k] >> h) & 1u)) continue;
-                    const long long cnt = (long long)hist[((size_t)m * 5 + k) * TG_NHALF + h];
-                    if (pend + cnt > kcap)
-                        if (int rc = flush()) return rc;
-                    if (cnt <= kcap) {
-                        if (ma < 0) ma = m;
-                        mb = m;
-                        pbins[(size_t)m * 5 + k] |= 1u << h;
-                        pend += cnt;
-                        continue;
-                    }
-                    // one bin over the capacity: ranges of packed positions (the output order inside a bin), halved until a range fits
-                    pbins[(size_t)m * 5 + k] = 1u << h;
-                    unsigned long long len = (unsigned long long)total;
-                    for (unsigned long long g0 = 0; g0 < (unsigned long long)total;) {
-                        const unsigned long long g1 = std::min((unsigned long long)total, g0 + len);
-                        long long got = 0;
-                        if (int rc = pass(m, m, g0, g1, -1, &got)) return rc;
-                        if (got > kcap) { len = std::max<unsigned long long>(1, len / 2); continue; }
-                        g0 = g1;
-                    }
-                    pbins[(size_t)m * 5 + k] = 0;
-                }
-        if (int rc = flush()) return rc;
-        seconds[4] += dg_now() - t0;
+        const auto range = [&](long long bin, unsigned long long g0, unsigned long long g1, long long* got) -> int {
+            const size_t row = kept[(size_t)bin] / TG_NHALF;
+            pbins[row] = 1u << (kept[(size_t)bin] % TG_NHALF);
+            const int rc = pass((int)(row / 5), (int)(row / 5), g0, g1, -1, got);
+            pbins[row] = 0;
+            return rc;
+        };
+        std::fill(pbins.begin(), pbins.end(), 0u);
+        const int rc = plan_passes((long long)kept.size(), count, kcap, (unsigned long long)total, flush, range);
+        if (rc) return rc == PLAN_POSITION_OVER_CAP ? fail(c, -5, "degradome: one position holds more hits of one miRNA, category and score than a pass") : rc;
+        seconds[4] += mirp::now() - t0;
     }
     return 0;
 }

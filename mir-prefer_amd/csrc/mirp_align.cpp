@@ -1,7 +1,6 @@
 // C-ABI of the read alignment (mirp_align_index, mirp_align_reads): the FASTA parsing, the 2-bit packing of the reference, the SAM
 // header and the batching of the reads on the host; align_kernels.hip does the index, the search and the SAM records on the device.
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -12,7 +11,6 @@
 
 namespace {
 
-double al_clock() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // base codes: A C G T in either case 0..3, anything else 4
 struct Codes {
@@ -121,11 +119,11 @@ extern "C" int mirp_align_index(mirp_ctx* c, const char* const* paths, int32_t n
     HIPCHK(c, hipSetDevice(c->device));
     c->a_ready = false;
     double sec[5] = {0, 0, 0, 0, 0};
-    double t = al_clock();
+    double t = mirp::now();
     mirp::PackedFasta ref;
     if (int rc = mirp::pack_fasta(c, paths, n_paths, ref)) return rc;
     std::vector<std::string>().swap(c->a_contig_names);
-    sec[0] = al_clock() - t;
+    sec[0] = mirp::now() - t;
     double dsec[4] = {0, 0, 0, 0};
     if (int rc = mirp_device_align_index(c, ref.pk.data(), ref.amb.data(), ref.cst.data(), ref.total, ref.cstart, ref.blob, ref.noff, dsec)) return rc;
     for (int i = 0; i < 4; i++) sec[1 + i] = dsec[i];
@@ -147,7 +145,7 @@ extern "C" int mirp_align_reads(mirp_ctx* c, const char* reads_path, const char*
     if (!c->a_ready) return fail(c, -1, "mirp_align_reads: no index (mirp_align_index first)");
     HIPCHK(c, hipSetDevice(c->device));
     double sec[6] = {0, 0, 0, 0, 0, 0};
-    double t = al_clock();
+    double t = mirp::now();
     std::string buf;
     if (int rc = mirp::read_whole(c, reads_path, buf)) return rc;
     std::vector<unsigned char> codes;
@@ -180,25 +178,21 @@ extern "C" int mirp_align_reads(mirp_ctx* c, const char* reads_path, const char*
     if (open) roff.push_back((long long)codes.size());
     std::string().swap(buf);
     const long long n = (long long)roff.size() - 1;
-    sec[0] = al_clock() - t;
+    sec[0] = mirp::now() - t;
 
-    FILE* o = std::fopen(out_path, "wb");
-    if (!o) return fail(c, -8, std::string("cannot write ") + out_path);
-    bool ok = true;
+    mirp::OutFile out(out_path);
+    if (!out.open()) return fail(c, -8, std::string("cannot write ") + out_path);
     std::string head = "@HD\tVN:1.0\tSO:unsorted\n";
     for (size_t i = 0; i < c->a_contig_names.size(); i++)
         head += "@SQ\tSN:" + c->a_contig_names[i] + "\tLN:" + std::to_string(c->a_contig_lens[i]) + "\n";
     head += std::string("@PG\tID:mir_prefer_amd.align\tCL:\"") + pg_cl + "\"\n";
-    ok = std::fwrite(head.data(), 1, head.size(), o) == head.size();
-    auto sink = [&](const char* p, size_t len) -> int {
-        if (std::fwrite(p, 1, len, o) != len) { ok = false; return fail(c, -8, std::string("cannot write ") + out_path); }
-        return 0;
-    };
+    auto sink = [&](const char* p, size_t len) -> int { return out.write(p, len) ? 0 : fail(c, -8, std::string("cannot write ") + out_path); };
+    rc = sink(head.data(), head.size());
     long long st4[4] = {0, 0, 0, 0};
     double dsec[5] = {0, 0, 0, 0, 0};
     // batches: bounded reads, bases and seeds (with e = 1 a read has up to 2 * (2 + 4 L) seeds)
     long long r0 = 0;
-    while (ok && r0 < n) {
+    while (!rc && r0 < n) {
         long long r1 = r0, seeds = 0;
         while (r1 < n && r1 - r0 < (1ll << 22) && roff[r1] - roff[r0] < (1ll << 28)) {
             const long long L = roff[r1 + 1] - roff[r1];
@@ -212,14 +206,10 @@ extern "C" int mirp_align_reads(mirp_ctx* c, const char* reads_path, const char*
         for (auto& x : qb) x -= qoff[r0];
         rc = mirp_device_align_batch(c, codes.data() + roff[r0], rb.data(), qn.data() + qoff[r0], qb.data(), r1 - r0, v, k, m, filter_unmapped, sink, st4,
                                      dsec);
-        if (rc) break;
         r0 = r1;
     }
-    if (std::fclose(o) != 0) ok = false;
-    if (rc || !ok) {
-        std::remove(out_path);
-        return rc ? rc : fail(c, -8, std::string("cannot write ") + out_path);
-    }
+    if (rc) return rc;
+    if (!out.commit()) return fail(c, -8, std::string("cannot write ") + out_path);
     for (int i = 0; i < 5; i++) sec[1 + i] = dsec[i];
     if (stats) {
         stats[0] = n;

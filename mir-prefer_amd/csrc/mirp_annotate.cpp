@@ -3,7 +3,6 @@
 // annotate_kernels.hip finds, orders and cuts the hits; the lines of both files are written here from the downloaded keys (8 bytes per hit: the
 // text needs nothing the host does not hold, and the summary joins each query's first line with its hit count in the same walk).
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -13,7 +12,6 @@
 
 namespace {
 
-double an_clock() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 const long long kMaxKnown = 1ll << 24;
 
@@ -65,25 +63,21 @@ extern "C" int mirp_annotate_scan(mirp_ctx* c, const char* query_path, const cha
     if (o->max_offset < 0 || o->max_offset > 4 || o->max_mismatches < 0 || o->max_mismatches > 6 || o->max_lines < 0 || o->n_species < 0)
         return fail(c, -1, "mirp_annotate_scan: bad options");
     HIPCHK(c, hipSetDevice(c->device));
-    auto drop = [&](int rc) {                       // a refused or failed run has no output, not even an old one
-        std::remove(out_path);
-        std::remove(summary_path);
-        return rc;
-    };
+    mirp::OutFile fh(out_path), fs(summary_path);   // every return before the commits discards both: a refused or failed run has no output, not even an old one
     double sec[6] = {0, 0, 0, 0, 0, 0};
-    double t = an_clock();
+    double t = mirp::now();
     mirp::Mirnas Q, A;
     long long skipped = 0;
-    if (int rc = mirp::parse_mirnas(c, query_path, Q)) return drop(rc);
+    if (int rc = mirp::parse_mirnas(c, query_path, Q)) return rc;
     for (int f = 0; f < n_known; f++)
-        if (int rc = mirp::parse_mirnas(c, known_paths[f], A, &skipped)) return drop(rc);
+        if (int rc = mirp::parse_mirnas(c, known_paths[f], A, &skipped)) return rc;
     // the kept known sequences: the printed id is the first word of the header; --species keeps the ids that start with a listed prefix and '-'
     std::vector<std::string> species;
     const char* sp = o->species;
     for (int i = 0; i < o->n_species; i++) {
         species.emplace_back(sp);
         sp += species.back().size() + 1;
-        if (species.back().empty()) return drop(fail(c, -1, "mirp_annotate_scan: an empty species prefix"));
+        if (species.back().empty()) return fail(c, -1, "mirp_annotate_scan: an empty species prefix");
     }
     std::vector<long long> src;                     // kept known -> record of A
     std::vector<std::string> kid, kfam;
@@ -97,7 +91,7 @@ extern "C" int mirp_annotate_scan(mirp_ctx* c, const char* query_path, const cha
         for (const std::string& s : species)
             if (id.size() > s.size() && id.compare(0, s.size(), s) == 0 && id[s.size()] == '-') { keep = true; break; }
         if (!keep) continue;
-        if ((long long)src.size() >= kMaxKnown) return drop(fail(c, -10, "more than 16,777,216 known sequences are kept"));
+        if ((long long)src.size() >= kMaxKnown) return fail(c, -10, "more than 16,777,216 known sequences are kept");
         src.push_back(r);
         kfam.push_back(family_of(id));
         kid.push_back(std::move(id));
@@ -111,16 +105,13 @@ extern "C" int mirp_annotate_scan(mirp_ctx* c, const char* query_path, const cha
     long long evals = 0;                            // pairs x admissible shifts: 2 E + 1 - |Lq - Lk| shifts have both offsets within E
     for (int a = 12; a <= 32; a++)
         for (int b = 12; b <= 32; b++) evals += lq[a] * lk[b] * std::max(0, 2 * E + 1 - std::abs(a - b));
-    sec[0] = an_clock() - t;
+    sec[0] = mirp::now() - t;
 
-    FILE* fh = std::fopen(out_path, "wb");
-    if (!fh) return drop(fail(c, -8, std::string("cannot write ") + out_path));
-    FILE* fs = std::fopen(summary_path, "wb");
-    if (!fs) { std::fclose(fh); return drop(fail(c, -8, std::string("cannot write ") + summary_path)); }
-    bool ok = true;
+    if (!fh.open()) return fail(c, -8, std::string("cannot write ") + out_path);
+    if (!fs.open()) return fail(c, -8, std::string("cannot write ") + summary_path);
     std::string text = "query\tknown\tfamily\tdistance\tmismatches\toffset5\toffset3\tquery_5to3\tpairs\tknown_5to3\n", summ;
-    auto flush = [&](std::string& s, FILE* f, const char* path) -> int {
-        if (!s.empty() && std::fwrite(s.data(), 1, s.size(), f) != s.size()) { ok = false; return fail(c, -8, std::string("cannot write ") + path); }
+    auto flush = [&](std::string& s, mirp::OutFile& f, const char* path) -> int {
+        if (!f.write(s.data(), s.size())) return fail(c, -8, std::string("cannot write ") + path);
         s.clear();
         return 0;
     };
@@ -192,9 +183,11 @@ extern "C" int mirp_annotate_scan(mirp_ctx* c, const char* query_path, const cha
         rc = flush(text, fh, out_path);
         if (!rc) rc = flush(summ, fs, summary_path);
     }
-    if (std::fclose(fh) != 0) ok = false;
-    if (std::fclose(fs) != 0) ok = false;
-    if (rc || !ok) return drop(rc ? rc : fail(c, -8, std::string("cannot write ") + out_path));
+    if (rc) return rc;
+    if (!fh.commit() || !fs.commit()) {
+        fh.discard();
+        return fail(c, -8, std::string("cannot write ") + out_path);
+    }
     for (int i = 0; i < 5; i++) sec[1 + i] = dsec[i];
     if (stats) {
         stats[0] = nq;

@@ -3,7 +3,6 @@
 // if no gfx950 device / HIP runtime is usable.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,6 +14,7 @@
 #define MIRP_NMAX 3096
 
 #include "mirp_ctx.h"
+#include "mirp_fasta.h"
 
 extern "C" int mirp_abi_version(void) { return MIRP_ABI_VERSION; }
 
@@ -430,9 +430,8 @@ extern "C" int mirp_collapse_reads(mirp_ctx* c, const char* path, const char* pr
     if (!c) return -1;
     if (!path || !prefix || !out_path || hash_bits < 1 || hash_bits > 64) return fail(c, -1, "mirp_collapse_reads: bad argument");
     double sec[6] = {0, 0, 0, 0, 0, 0};
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     HIPCHK(c, hipSetDevice(c->device));
-    double t = now();
+    double t = mirp::now();
     FILE* f = std::fopen(path, "rb");
     if (!f) return fail(c, -8, std::string("cannot open ") + path);
     fseeko(f, 0, SEEK_END);
@@ -443,7 +442,7 @@ extern "C" int mirp_collapse_reads(mirp_ctx* c, const char* path, const char* pr
     const size_t got = n > 0 ? std::fread(text, 1, (size_t)n, f) : 0;
     std::fclose(f);
     if ((long long)got != n) { std::free(text); return fail(c, -8, std::string("cannot read ") + path); }
-    sec[0] = now() - t;
+    sec[0] = mirp::now() - t;
     char* out = nullptr;
     long long out_len = 0, nr = 0, nu = 0, bad = -1;
     const int rc = mirp_device_collapse_reads(c, text, n, prefix, hash_bits, &out, &out_len, &nr, &nu, &bad, sec);
@@ -454,13 +453,12 @@ extern "C" int mirp_collapse_reads(mirp_ctx* c, const char* path, const char* pr
     }
     std::free(text);
     if (rc) return rc;
-    t = now();
-    FILE* o = std::fopen(out_path, "wb");
-    bool ok = o && (out_len == 0 || std::fwrite(out, 1, (size_t)out_len, o) == (size_t)out_len);
-    if (o && std::fclose(o) != 0) ok = false;
+    t = mirp::now();
+    mirp::OutFile o(out_path);
+    const bool ok = o.write(out, (size_t)out_len) && o.commit();
     std::free(out);
     if (!ok) return fail(c, -8, std::string("cannot write ") + out_path);
-    sec[5] = now() - t;
+    sec[5] = mirp::now() - t;
     if (n_reads) *n_reads = nr;
     if (n_unique) *n_unique = nu;
     if (seconds) std::memcpy(seconds, sec, sizeof sec);

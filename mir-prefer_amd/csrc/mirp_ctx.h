@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <chrono>
 #include <cstdlib>
 #include <functional>
 #include <memory>
@@ -145,6 +146,26 @@ static inline int fail(mirp_ctx* c, int code, const std::string& msg) {
         if (e_ != hipSuccess) return fail((c), -2, std::string(#call) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+namespace mirp {
+// seconds on the steady clock: what every `seconds[]` of the C ABI is measured with
+inline double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+}  // namespace mirp
+
+// Copies `bytes` of device text to the host through c->h_text in pieces of at most 1 GiB and hands every piece to the sink; the seconds spent inside
+// the sink are added to *in_sink when it is given.
+inline int mirp_download_text(mirp_ctx* c, const char* d_text, long long bytes, const std::function<int(const char*, size_t)>& sink, double* in_sink = nullptr) {
+    const size_t piece = (size_t)1 << 30;
+    if (bytes > 0 && c->h_text.size() < std::min((size_t)bytes, piece)) c->h_text.resize(std::min((size_t)bytes, piece));
+    for (long long at = 0; at < bytes;) {
+        const size_t len = (size_t)std::min<long long>(bytes - at, (long long)piece);
+        HIPCHK(c, hipMemcpy(c->h_text.data(), d_text + at, len, hipMemcpyDeviceToHost));
+        const double t = mirp::now();
+        if (int rc = sink(c->h_text.data(), len)) return rc;
+        if (in_sink) *in_sink += mirp::now() - t;
+        at += (long long)len;
+    }
+    return 0;
+}
 
 // Folds n_work device-resident windows (seqs/offs/lens as the kernels expect) into the context's fold output buffers.
 // Uses the LDS-resident kernel when span allows and re-runs flagged windows (length / int16 range) with the generic kernel.

@@ -2,7 +2,6 @@
 // for mirp_target_scan, the @SQ contigs of the resident alignments are matched to the transcripts, degradome_kernels.hip finds the hits, and the
 // lines are written here from the downloaded hit records (a few thousand after the evidence filter; the text needs nothing the host does not hold).
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -13,7 +12,6 @@
 
 namespace {
 
-double dg_clock() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // pair class of miRNA code mc (0..3 A C G U, 4 unknown) with target base y (0..3 A C G U): 0 Watson-Crick, 1 G:U, 2 mismatch
 int pair_class(unsigned mc, unsigned y) {
@@ -33,11 +31,12 @@ extern "C" int mirp_degradome_scan(mirp_ctx* c, const char* mirna_path, const ch
         return fail(c, -1, "mirp_degradome_scan: bad options");
     HIPCHK(c, hipSetDevice(c->device));
     double sec[6] = {0, 0, 0, 0, 0, 0};
-    double t = dg_clock();
+    double t = mirp::now();
     mirp::Mirnas M;
     mirp::PackedFasta ref;
-    if (int rc = mirp::parse_mirnas(c, mirna_path, M)) { std::remove(out_path); return rc; }      // a refused input has no output, not even an old one
-    if (int rc = mirp::pack_fasta(c, &transcripts_path, 1, ref)) { std::remove(out_path); return rc; }
+    mirp::OutFile out(out_path);                    // every return before commit() discards: a refused input has no output, not even an old one
+    if (int rc = mirp::parse_mirnas(c, mirna_path, M)) return rc;
+    if (int rc = mirp::pack_fasta(c, &transcripts_path, 1, ref)) return rc;
     // every @SQ contig is a transcript of the FASTA with the same length
     const int n_f = (int)ref.names.size();
     std::unordered_map<std::string, int> by_name;
@@ -50,16 +49,11 @@ extern "C" int mirp_degradome_scan(mirp_ctx* c, const char* mirna_path, const ch
         const std::string name(nm);
         nm += name.size() + 1;
         const auto it = by_name.find(name);
-        if (it == by_name.end()) {
-            std::remove(out_path);
-            return fail(c, -10, "contig " + name + " of the SAM header is not in " + transcripts_path);
-        }
+        if (it == by_name.end()) return fail(c, -10, "contig " + name + " of the SAM header is not in " + transcripts_path);
         const int f = it->second;
-        if (ref.lens[(size_t)f] != o->contig_len[s]) {
-            std::remove(out_path);
+        if (ref.lens[(size_t)f] != o->contig_len[s])
             return fail(c, -10, "contig " + name + " has " + std::to_string(ref.lens[(size_t)f]) + " bases in " + transcripts_path + " but LN:" +
                                     std::to_string((long long)o->contig_len[s]) + " in the SAM header");
-        }
         if (f2s[(size_t)f] < 0) f2s[(size_t)f] = s;          // (a name twice in the header: the ingest refuses that)
         sqstart[(size_t)s] = ref.cstart[(size_t)f];
         sqlen[(size_t)s] = ref.lens[(size_t)f];
@@ -72,14 +66,12 @@ extern "C" int mirp_degradome_scan(mirp_ctx* c, const char* mirna_path, const ch
         mia[(size_t)m] = mirp::make_mirna(M.codes.data() + 32 * m, M.lens[(size_t)m], cleave, true);
     }
     ref.pk.resize((size_t)(2 * ((ref.total + 31) / 32 + 2)), 0u);          // whole 64-bit words, one past the last window
-    sec[0] = dg_clock() - t;
+    sec[0] = mirp::now() - t;
 
-    FILE* f = std::fopen(out_path, "wb");
-    if (!f) return fail(c, -8, std::string("cannot write ") + out_path);
-    bool ok = true;
+    if (!out.open()) return fail(c, -8, std::string("cannot write ") + out_path);
     std::string text = "miRNA\ttarget\tcleavage\tstart\tend\tscore\tcategory\treads\ttranscript_max\tsites\tpvalue\tmismatches\tgu\tmirna_5to3\tpairs\ttarget_3to5\n";
     auto flush = [&]() -> int {
-        if (!text.empty() && std::fwrite(text.data(), 1, text.size(), f) != text.size()) { ok = false; return fail(c, -8, std::string("cannot write ") + out_path); }
+        if (!out.write(text.data(), text.size())) return fail(c, -8, std::string("cannot write ") + out_path);
         text.clear();
         return 0;
     };
@@ -132,11 +124,8 @@ extern "C" int mirp_degradome_scan(mirp_ctx* c, const char* mirna_path, const ch
     int rc = mirp_device_degradome(c, (const unsigned long long*)ref.pk.data(), ref.amb.data(), ref.cst.data(), ref.total, ref.cstart, f2s, sqstart, sqlen, mi, mia,
                                    o->max_half_score, o->max_category, o->alpha, sink, st2, dsec);
     if (!rc) rc = flush();
-    if (std::fclose(f) != 0) ok = false;
-    if (rc || !ok) {
-        std::remove(out_path);
-        return rc ? rc : fail(c, -8, std::string("cannot write ") + out_path);
-    }
+    if (rc) return rc;
+    if (!out.commit()) return fail(c, -8, std::string("cannot write ") + out_path);
     for (int i = 0; i < 5; i++) sec[1 + i] = dsec[i];
     if (stats) {
         stats[0] = n_mi;

@@ -1,6 +1,7 @@
 // FASTA reading shared by the C-ABI translation units: whole-file reads, the universal-newline line walk, and the parse and 2-bit packing of
 // reference / target FASTA files (mirp_align_index, mirp_target_scan).
 #pragma once
+#include <cstdio>
 #include <string>
 #include <vector>
 #include "mirp_ctx.h"
@@ -10,6 +11,35 @@ namespace mirp {
 inline bool fa_ws(unsigned char ch) { return ch == 32 || (ch >= 9 && ch <= 13) || (ch >= 0x1c && ch <= 0x1f); }   // str.strip() / str.split(), ASCII
 
 int read_whole(mirp_ctx* c, const char* path, std::string& buf);
+
+// The output file of a run: there when the run ended well and otherwise not, not even one an earlier run left at the path.  It is opened by
+// open() or the first write(); commit() closes it (an unopened one as an empty file); discard() closes and removes it, and a guard that goes
+// without commit() discards.  open, write and commit return false when the file cannot be written.
+class OutFile {
+    std::string path_;
+    FILE* f_ = nullptr;
+    bool committed_ = false;
+
+  public:
+    explicit OutFile(const char* path) : path_(path) {}
+    OutFile(const OutFile&) = delete;
+    OutFile& operator=(const OutFile&) = delete;
+    ~OutFile() { if (!committed_) discard(); }
+    bool open() { return f_ || (f_ = std::fopen(path_.c_str(), "wb")) != nullptr; }
+    bool write(const char* p, size_t len) { return open() && (len == 0 || std::fwrite(p, 1, len, f_) == len); }
+    bool commit() {
+        if (!open()) return false;
+        committed_ = std::fclose(f_) == 0;
+        f_ = nullptr;
+        return committed_;
+    }
+    void discard() {
+        if (f_) std::fclose(f_);
+        f_ = nullptr;
+        committed_ = false;
+        std::remove(path_.c_str());
+    }
+};
 
 // Calls fn(raw, begin, end) for every line of buf (ends at \n, \r\n or a lone \r: Python's universal newlines; an empty line between \r and \n is
 // harmless to every parser here).  [begin, end) is the line stripped of surrounding whitespace; raw is its first byte.  fn returns nonzero to stop.

@@ -14,7 +14,6 @@
 #include <sys/stat.h>
 #include <unistd.h>
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -348,7 +347,6 @@ int fill_meta(const Parsed& P, MirpSamData* out) {
     return 0;
 }
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 }  // namespace
 
@@ -416,7 +414,7 @@ static int ingest_impl(mirp_ctx* c, const char* const* paths, int32_t n_paths, i
     HIPCHK(c, hipSetDevice(c->device));
     const int W = shard ? c->dist_world : 1, me = shard ? c->dist_rank : 0;
     if (shard && W > 1 && !owner_of_tid) return fail(c, -1, std::string(who) + ": owner_of_tid is required with more than one rank");
-    const double t0 = now_s();
+    const double t0 = mirp::now();
     Parsed P_own;
     Parsed& P = pre ? *pre : P_own;          // pre: the files were tokenized before the device was open (mirp_tokenize_sams)
     std::string err;
@@ -445,7 +443,7 @@ static int ingest_impl(mirp_ctx* c, const char* const* paths, int32_t n_paths, i
             if (all[(size_t)r] && !bad) { bad = 1; err = std::string(who) + ": rank " + std::to_string(r) + " failed to parse its part of the SAM files"; }
     }
     if (bad) return fail(c, -1, err);
-    const double t1 = now_s();
+    const double t1 = mirp::now();
     MirpAln* all = nullptr;
     MirpAln* segs = nullptr;
     std::vector<int32_t> owner, span;
@@ -604,13 +602,13 @@ static int ingest_impl(mirp_ctx* c, const char* const* paths, int32_t n_paths, i
             std::free(all); std::free(segs); mirp_free_sam_data(out); return rc;
         }
     }
-    const double t2 = now_s();
+    const double t2 = mirp::now();
     if (int rc = mirp_device_sort_alns(c, (MirpAln*)c->alns.p, (MirpAln*)c->sort_tmp.p, n, posbits, tidbits)) { std::free(all); std::free(segs); mirp_free_sam_data(out); return rc; }
     if (hipStreamSynchronize(c->stream) != hipSuccess) return bail(-2, "device sort failed");
-    const double t3 = now_s();
+    const double t3 = mirp::now();
     if (n && hipMemcpy(all, c->alns.p, sizeof(MirpAln) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) return bail(-2, "D2H failed");
     if (ns && hipMemcpy(segs, c->segs.p, sizeof(MirpAln) * (size_t)ns, hipMemcpyDeviceToHost) != hipSuccess) return bail(-2, "D2H failed");
-    const double t4 = now_s();
+    const double t4 = mirp::now();
     if (fill_meta(P, out)) return bail(-6, "out of memory");
     out->alns = all; out->n_alns = n; out->segs = segs; out->n_segs = ns;
     c->n_alns = n; c->n_segs = ns; c->max_aln_len = -1;

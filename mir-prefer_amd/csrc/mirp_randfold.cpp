@@ -6,7 +6,6 @@
 // records come back.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <chrono>
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
@@ -17,7 +16,6 @@
 
 namespace {
 
-double rf_clock() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 const int kMaxLen = 3000;                  // PRECURSOR_LEN's limit in the reference, what the fold path serves
 const int kLdsLen = 300;                   // up to here at span 300 on the LDS-resident kernels
@@ -139,11 +137,11 @@ extern "C" int mirp_randfold(mirp_ctx* c, const char* seqs, const int64_t* offse
     HIPCHK(c, hipSetDevice(c->device));
     double sec[5] = {0, 0, 0, 0, 0};
     long long passes = 0, fallbacks = 0;
-    double t = rf_clock();
+    double t = mirp::now();
     RfHost H;
     std::vector<MirpRandfoldRec> h_rec;
     if (int rc = rf_prepare(c, "mirp_randfold", seqs, offsets, n_seqs, o, true, H, &h_rec)) return rc;
-    sec[0] = rf_clock() - t;
+    sec[0] = mirp::now() - t;
     H.jps = (long long)o->n_shuffles + 1;
     H.plan.jps = H.jps;
     H.plan.k_first = 0;
@@ -163,27 +161,27 @@ extern "C" int mirp_randfold(mirp_ctx* c, const char* seqs, const int64_t* offse
             if (c->rf_lines.ensure(sizeof(MirpFoldLine) * (size_t)n) || c->rf_ss.ensure((size_t)n * stride) || c->rf_nlines.ensure(4 * (size_t)n) ||
                 c->rf_mfe.ensure(4 * (size_t)n) || c->rf_status.ensure(4 * (size_t)n))
                 return fail(c, -6, "mirp_randfold: device allocation failed (a pass's fold output)");
-            t = rf_clock();
+            t = mirp::now();
             mirp_device_rf_shuffle(c, H.plan, j0, n, base, (unsigned char*)c->rf_seq.p, (long long*)c->rf_soffs.p, (unsigned char*)c->rf_slab.p);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipStreamSynchronize(st));
-            sec[1] += rf_clock() - t;
-            t = rf_clock();
+            sec[1] += mirp::now() - t;
+            t = mirp::now();
             if (int rc = mirp_run_fold(c, (const unsigned char*)c->rf_seq.p, (const long long*)c->rf_soffs.p, nullptr, n, n_max, span, 1, stride,
                                        (MirpFoldLine*)c->rf_lines.p, (char*)c->rf_ss.p, (int*)c->rf_nlines.p, (int*)c->rf_mfe.p, (int*)c->rf_status.p))
                 return rc;
             HIPCHK(c, hipStreamSynchronize(st));
             fallbacks += c->last_fallback;
-            sec[2] += rf_clock() - t;
-            t = rf_clock();
+            sec[2] += mirp::now() - t;
+            t = mirp::now();
             mirp_device_rf_stats(c, H.plan, j0, n, (const int*)c->rf_mfe.p, (const int*)c->rf_status.p, (MirpRandfoldRec*)c->rf_rec.p, (int*)c->rf_bad.p);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipStreamSynchronize(st));
-            sec[3] += rf_clock() - t;
+            sec[3] += mirp::now() - t;
             passes++;
         }
     }
-    t = rf_clock();
+    t = mirp::now();
     MirpRandfoldRec* out = (MirpRandfoldRec*)std::calloc(std::max(n_seqs, 1), sizeof(MirpRandfoldRec));
     if (!out) return fail(c, -7, "mirp_randfold: host allocation failed (records)");
     if (n_seqs > 0) {
@@ -198,7 +196,7 @@ extern "C" int mirp_randfold(mirp_ctx* c, const char* seqs, const int64_t* offse
             return fail(c, -5, "mirp_randfold: the fold reported status " + std::to_string(bad) + " for a sequence");
         }
     }
-    sec[4] = rf_clock() - t;
+    sec[4] = mirp::now() - t;
     *recs = out;
     if (stats) { stats[0] = n_seqs; stats[1] = H.jobs(); stats[2] = passes; stats[3] = fallbacks; }
     if (seconds) std::memcpy(seconds, sec, sizeof sec);

@@ -1,7 +1,6 @@
 // C-ABI of the plant miRNA target-site search (mirp_target_scan): the miRNA FASTA parse and the per-miRNA masks, the target packing
 // (shared with mirp_align_index) and the output file on the host; targets_kernels.hip scans, sorts, cuts and writes the lines on the device.
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -11,7 +10,6 @@
 
 namespace {
 
-double tg_clock() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // miRNA letters: A C G U in either case 0..3, T = U, anything else 4 (unknown)
 struct RnaCodes {
@@ -132,24 +130,19 @@ extern "C" int mirp_target_scan(mirp_ctx* c, const char* mirna_path, const char*
     if (o->max_half_score < 0 || o->max_half_score > 16 || o->max_sites < 0 || (o->energy != 0 && o->energy != 1)) return fail(c, -1, "mirp_target_scan: bad options");
     HIPCHK(c, hipSetDevice(c->device));
     double sec[5] = {0, 0, 0, 0, 0};
-    double t = tg_clock();
+    double t = mirp::now();
     Mirnas M;
     mirp::PackedFasta ref;
-    if (int rc = parse_mirnas(c, mirna_path, M)) { std::remove(out_path); return rc; }      // a refused input has no output, not even an old one
-    if (int rc = mirp::pack_fasta(c, target_paths, n_targets, ref)) { std::remove(out_path); return rc; }
+    mirp::OutFile out(out_path);                    // every return before commit() discards: a refused input has no output, not even an old one
+    if (int rc = parse_mirnas(c, mirna_path, M)) return rc;
+    if (int rc = mirp::pack_fasta(c, target_paths, n_targets, ref)) return rc;
     const long long n_mi = (long long)M.lens.size();
     std::vector<TgMirna> mi((size_t)n_mi);
     for (long long m = 0; m < n_mi; m++) mi[(size_t)m] = make_mirna(M.codes.data() + 32 * m, M.lens[(size_t)m], o->cleavage_site != 0, false);
     ref.pk.resize((size_t)(2 * ((ref.total + 31) / 32 + 2)), 0u);          // whole 64-bit words, one past the last window
-    sec[0] = tg_clock() - t;
+    sec[0] = mirp::now() - t;
 
-    FILE* f = std::fopen(out_path, "wb");
-    if (!f) return fail(c, -8, std::string("cannot write ") + out_path);
-    bool ok = true;
-    auto sink = [&](const char* p, size_t len) -> int {
-        if (std::fwrite(p, 1, len, f) != len) { ok = false; return fail(c, -8, std::string("cannot write ") + out_path); }
-        return 0;
-    };
+    auto sink = [&](const char* p, size_t len) -> int { return out.write(p, len) ? 0 : fail(c, -8, std::string("cannot write ") + out_path); };
     const std::string head = std::string("miRNA\ttarget\tstart\tend\tstrand\tscore\tmismatches\tgu\tmirna_5to3\tpairs\ttarget_3to5") + (o->bulge ? "\tbulge" : "") +
                              (o->energy ? "\tmfe\tmfe_perfect\tmfe_ratio\tduplex\n" : "\n");
     int rc = sink(head.data(), head.size());
@@ -158,11 +151,8 @@ extern "C" int mirp_target_scan(mirp_ctx* c, const char* mirna_path, const char*
     if (!rc)
         rc = mirp_device_target_scan(c, (const unsigned long long*)ref.pk.data(), ref.amb.data(), ref.cst.data(), ref.total, ref.cstart, ref.blob, ref.noff, mi,
                                      M.codes, M.names, M.noff, *o, sink, st2, dsec);
-    if (std::fclose(f) != 0) ok = false;
-    if (rc || !ok) {
-        std::remove(out_path);
-        return rc ? rc : fail(c, -8, std::string("cannot write ") + out_path);
-    }
+    if (rc) return rc;
+    if (!out.commit()) return fail(c, -8, std::string("cannot write ") + out_path);
     for (int i = 0; i < 4; i++) sec[1 + i] = dsec[i];
     if (stats) {
         stats[0] = n_mi;

@@ -4,7 +4,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
-#include "mirp_ctx.h"
+#include "mirp_fasta.h"
 
 // Trims one FASTQ / FASTA text held in host memory and writes the FASTA of the kept reads to out_path.  out_path is opened only once every refusal
 // has been ruled out; on a refusal or a later error the file at out_path is removed, a partial one or one left by an earlier run, so a refused
@@ -22,20 +22,10 @@ extern "C" int mirp_trim_reads(mirp_ctx* c, const char* data, int64_t n, const c
     HIPCHK(c, hipSetDevice(c->device));
     double sec[6] = {0, 0, 0, 0, 0, 0};
     long long st[7];
-    FILE* f = nullptr;
-    bool ok = true;
-    auto sink = [&](const char* p, size_t len) -> int {
-        if (!f && !(f = std::fopen(out_path, "wb"))) { ok = false; return fail(c, -8, std::string("cannot write ") + out_path); }
-        if (std::fwrite(p, 1, len, f) != len) { ok = false; return fail(c, -8, std::string("cannot write ") + out_path); }
-        return 0;
-    };
-    int rc = mirp_device_trim_reads(c, data, (long long)n, name, *o, sink, st, sec);
-    if (!rc && !f) rc = sink("", 0);          // nothing kept: the output is an empty file
-    if (f && std::fclose(f) != 0) ok = false;
-    if (rc || !ok) {
-        std::remove(out_path);
-        return rc ? rc : fail(c, -8, std::string("cannot write ") + out_path);
-    }
+    mirp::OutFile out(out_path);              // opened by the first piece of text, after every refusal
+    auto sink = [&](const char* p, size_t len) -> int { return out.write(p, len) ? 0 : fail(c, -8, std::string("cannot write ") + out_path); };
+    if (int rc = mirp_device_trim_reads(c, data, (long long)n, name, *o, sink, st, sec)) return rc;
+    if (!out.commit()) return fail(c, -8, std::string("cannot write ") + out_path);          // nothing kept: the output is an empty file
     if (stats) for (int i = 0; i < 7; i++) stats[i] = st[i];
     if (seconds) std::memcpy(seconds, sec, sizeof sec);
     return 0;

@@ -17,7 +17,6 @@
 //           launch_excl_scan      of the head flags in file order = A
 //   emit    reads_size_kernel, launch_excl_scan, reads_emit_kernel   record sizes, their offsets, the text; one download
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -254,7 +253,6 @@ static inline int rd_grid(long long n) {
     const long long g = (n + 255) / 256;
     return (int)(g < 1 ? 1 : g > 16384 ? 16384 : g);
 }
-static inline double rd_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // The collapse of one file held in host memory.  seconds[0] gains the upload, [1] .. [4] are split, hash + sort, verify + rank, emit + download.
 // -9 with *bad_offset set: a byte >= 0x80 (the caller names the file).
@@ -265,7 +263,7 @@ int mirp_device_collapse_reads(mirp_ctx* c, const char* text, long long n, const
     c->last_collapse_collisions = 0;
     hipStream_t st = c->stream;
     const int plen = (int)std::strlen(prefix);
-    double t = rd_now();
+    double t = mirp::now();
     if (c->r_text.ensure((size_t)n + RD_PAD) || c->r_small.ensure(64 + (size_t)plen)) return fail(c, -6, "device allocation failed (collapse: text)");
     unsigned char* d_text = (unsigned char*)c->r_text.p;
     unsigned long long* d_small = (unsigned long long*)c->r_small.p;     // [0] first byte >= 0x80, [1] longest read, then the prefix
@@ -276,10 +274,10 @@ int mirp_device_collapse_reads(mirp_ctx* c, const char* text, long long n, const
     HIPCHK(c, hipMemcpyAsync(d_small, init, sizeof init, hipMemcpyHostToDevice, st));
     if (plen) HIPCHK(c, hipMemcpyAsync(d_prefix, prefix, (size_t)plen, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    seconds[0] += rd_now() - t;
+    seconds[0] += mirp::now() - t;
 
     // ---- split
-    t = rd_now();
+    t = mirp::now();
     long long n_lines = 0, R = 0;
     if (n > 0) {
         if (int rc = mirp_device_split_lines(c, d_text, n, 0x7fffffffll, c->r_bcnt, c->r_bscan, c->r_starts, d_small, &n_lines, bad_offset)) return rc;
@@ -291,12 +289,12 @@ int mirp_device_collapse_reads(mirp_ctx* c, const char* text, long long n, const
         HIPCHK(c, hipStreamSynchronize(st));
         HIPCHK(c, hipGetLastError());
     }
-    seconds[1] += rd_now() - t;
+    seconds[1] += mirp::now() - t;
     *n_reads = R;
     if (R == 0) return 0;
 
     // ---- hash + sort
-    t = rd_now();
+    t = mirp::now();
     if (c->r_span.ensure(16 * (size_t)R) || c->r_rec.ensure(sizeof(MirpHashRec) * (size_t)R) || c->r_rectmp.ensure(sizeof(MirpHashRec) * (size_t)R))
         return fail(c, -6, "device allocation failed (collapse: reads)");
     longlong2* d_span = (longlong2*)c->r_span.p;
@@ -309,10 +307,10 @@ int mirp_device_collapse_reads(mirp_ctx* c, const char* text, long long n, const
     if (int rc = mirp_device_sort_hashes(c, d_rec, (MirpHashRec*)c->r_rectmp.p, R, (hash_bits + 7) / 8 * 8)) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
     if (max_len > (1ull << 30)) return fail(c, -5, "a read longer than 2^30 bytes");
-    seconds[2] += rd_now() - t;
+    seconds[2] += mirp::now() - t;
 
     // ---- verify + rank
-    t = rd_now();
+    t = mirp::now();
     if (c->r_rscan.ensure(8 * (size_t)(R + 1)) || c->r_first.ensure(8 * (size_t)(R + 1)) || c->r_bad.ensure(4 * (size_t)R) || c->r_cnt.ensure(4 * (size_t)R) ||
         c->r_isfirst.ensure(4 * (size_t)R) || c->r_inbad.ensure(4 * (size_t)R) || c->r_rank.ensure(8 * (size_t)(R + 1)))
         return fail(c, -6, "device allocation failed (collapse: runs)");
@@ -377,10 +375,10 @@ int mirp_device_collapse_reads(mirp_ctx* c, const char* text, long long n, const
     HIPCHK(c, hipMemcpyAsync(&U, d_rank + R, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
-    seconds[3] += rd_now() - t;
+    seconds[3] += mirp::now() - t;
 
     // ---- emit + download
-    t = rd_now();
+    t = mirp::now();
     int* d_size = d_head;                     // run heads are done with
     long long* d_off = d_bscan;
     hipLaunchKernelGGL(reads_size_kernel, dim3(g), dim3(256), 0, st, (const int*)d_isfirst, (const long long*)d_rank, (const int*)d_cnt, (const longlong2*)d_span, R,
@@ -401,7 +399,7 @@ int mirp_device_collapse_reads(mirp_ctx* c, const char* text, long long n, const
     }
     const hipError_t e3 = hipGetLastError();
     if (e3 != hipSuccess) { std::free(h_out); return fail(c, -2, std::string("collapse: ") + hipGetErrorString(e3)); }
-    seconds[4] += rd_now() - t;
+    seconds[4] += mirp::now() - t;
     *out = h_out;
     *out_len = total;
     *n_unique = U;

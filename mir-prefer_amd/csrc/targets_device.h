@@ -13,7 +13,8 @@
 // and the site is a hit when smin <= half <= smax and mm & cleave == 0.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "mirp_internal.h"
+#include <vector>
+#include "mirp_ctx.h"
 
 namespace mirp {
 
@@ -27,6 +28,21 @@ struct TgRef {
     const unsigned* cst;
     unsigned long long total;
 };
+
+// Host: sizes tg_pk / tg_amb / tg_cst / tg_cstart for a packed FASTA of `total` bases (pk: (total + 31) / 32 + 2 u64 words; amb / cst: as many u32
+// words) and enqueues its upload on the context's stream; the caller synchronises before its host arrays go.
+inline int tg_upload_packed(mirp_ctx* c, const unsigned long long* pk, const unsigned* amb, const unsigned* cst, long long total,
+                            const std::vector<unsigned long long>& cstart, TgRef* R) {
+    const size_t n_w = (size_t)((total + 31) / 32 + 2);
+    if (c->tg_pk.ensure(8 * n_w) || c->tg_amb.ensure(4 * n_w) || c->tg_cst.ensure(4 * n_w) || c->tg_cstart.ensure(8 * cstart.size()))
+        return fail(c, -6, "device allocation failed (packed targets)");
+    HIPCHK(c, hipMemcpyAsync(c->tg_pk.p, pk, 8 * n_w, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->tg_amb.p, amb, 4 * n_w, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->tg_cst.p, cst, 4 * n_w, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->tg_cstart.p, cstart.data(), 8 * cstart.size(), hipMemcpyHostToDevice, c->stream));
+    *R = TgRef{(const unsigned long long*)c->tg_pk.p, (const unsigned*)c->tg_amb.p, (const unsigned*)c->tg_cst.p, (unsigned long long)total};
+    return 0;
+}
 
 __device__ __forceinline__ unsigned tg_base(const unsigned long long* __restrict__ pk, unsigned long long q) { return (unsigned)(pk[q >> 5] >> (2 * (q & 31))) & 3u; }
 

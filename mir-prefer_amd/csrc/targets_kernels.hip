@@ -16,8 +16,8 @@
 //
 //   scan   tg_scan_kernel<0>: one lane per target offset, miRNAs of the pass in wave-uniform (scalar) loads; every hit appends the key
 //          mloc << 38 | half << 33 | o << 1 | strand (mloc = the miRNA's index in its group of <= 2^16) to a buffer of `cap` keys and counts it.
-//          tg_scan_kernel<1>: the same scan counting hits per (miRNA, half-score) only, run when a pass's hits overflow the buffer: the host then
-//          plans passes of at most cap keys each, by ranges of (miRNA, half-score) and, for one (miRNA, half-score) over cap, by ranges of offsets.
+//          tg_scan_kernel<1>: the same scan counting hits per (miRNA, half-score) only, run when a pass's hits overflow the buffer: the counts go
+//          to plan_passes (pass_plan.h) with (miRNA, half-score) as the bins and the target offsets as the positions.
 //   order  mirp_device_sort_u64 by the whole key: per miRNA, (score, target, start, + before -) = the output order.
 //   cut    tg_size_kernel: -k from the rank inside the miRNA's run plus what earlier passes emitted; the line's length; launch_excl_scan.
 //   emit   tg_emit_kernel writes the lines; the text goes to the sink in pieces of at most 1 GiB.
@@ -27,13 +27,13 @@
 // the columns mfe, mfe_perfect, mfe_ratio and duplex; without it TgText's energy pointers are null and the lines are as before.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <functional>
 #include <string>
 #include <vector>
 #include "mirp_ctx.h"
+#include "pass_plan.h"
 #include "targets_bulge_device.h"
 #include "text_out.h"
 
@@ -273,7 +273,6 @@ static inline int tg_grid(long long n) {
     const long long g = (n + 255) / 256;
     return (int)(g < 1 ? 1 : g > 16384 ? 16384 : g);
 }
-static inline double tg_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 namespace {
 
@@ -292,7 +291,7 @@ struct TgRun {
     // scan miRNAs [a, b) of the group at mbase (their smin / smax as set in *mi) over offsets [p0, p1): keys in tg_keys; -> hits (maybe > cap)
     int scan(int mode, int mbase, int a, int b, unsigned long long p0, unsigned long long p1, long long* hits) {
         using namespace mirp;
-        const double t = tg_now();
+        const double t = mirp::now();
         hipStream_t st = c->stream;
         const int n = b - a;
         HIPCHK(c, hipMemcpyAsync((TgMirna*)c->tg_mi.p + a, mi->data() + mbase + a, sizeof(TgMirna) * (size_t)n, hipMemcpyHostToDevice, st));
@@ -318,7 +317,7 @@ struct TgRun {
         HIPCHK(c, hipStreamSynchronize(st));
         HIPCHK(c, hipGetLastError());
         *hits = (long long)h;
-        sec[0] += tg_now() - t;
+        sec[0] += mirp::now() - t;
         return 0;
     }
 
@@ -328,7 +327,7 @@ struct TgRun {
         hipStream_t st = c->stream;
         stats[1]++;
         if (n == 0) return 0;
-        double t = tg_now();
+        double t = mirp::now();
         unsigned long long* d_keys = (unsigned long long*)c->tg_keys.p;
         int mbits = 0;                                         // the key's bits above the miRNA index are 0
         while ((1 << mbits) < group_n) mbits++;
@@ -357,8 +356,8 @@ struct TgRun {
         HIPCHK(c, hipStreamSynchronize(st));
         HIPCHK(c, hipGetLastError());
         stats[0] += (long long)kept;
-        sec[1] += tg_now() - t;
-        t = tg_now();
+        sec[1] += mirp::now() - t;
+        t = mirp::now();
         // pieces of at most 1 GiB of text (at least one line each)
         const long long piece = 1ll << 30;
         for (long long i0 = 0; i0 < n;) {
@@ -389,7 +388,7 @@ struct TgRun {
             }
             i0 = i1;
         }
-        sec[2] += tg_now() - t;
+        sec[2] += mirp::now() - t;
         return 0;
     }
 
@@ -411,12 +410,12 @@ struct TgRun {
         long long hits = 0;
         if (int rc = scan(0, mbase, 0, n, 0, total, &hits)) return rc;
         if (o->energy) {                                       // mfe_perfect, once per miRNA (the scan has uploaded the group's TgMirna)
-            const double t = tg_now();
+            const double t = mirp::now();
             if (int rc = mirp_device_duplex_perfect(c, (const unsigned char*)c->tg_mcodes.p + 32 * (size_t)mbase, (const TgMirna*)c->tg_mi.p, n, (int*)c->tg_perf.p,
                                                     nullptr, nullptr))
                 return rc;
             HIPCHK(c, hipStreamSynchronize(st));
-            sec[1] += tg_now() - t;
+            sec[1] += mirp::now() - t;
         }
         if (hits <= cap) return finish(mbase, hits);
         // overflow: hits per (miRNA, half-score), then passes of at most cap keys in output order
@@ -433,44 +432,24 @@ struct TgRun {
                     if (cum >= (unsigned long long)o->max_sites) { lim[m] = h; break; }
                 }
             }
-        int ma = -1, ha = 0, mb = -1, hb = 0;        // the pending pass: (ma, ha) .. (mb, hb) in (miRNA, half-score) order
-        long long pend = 0;
-        auto flush = [&]() -> int {
-            if (ma < 0) return 0;
+        // the bins are (miRNA, half-score) up to lim[], the positions of a bin over cap are the target offsets
+        const auto count = [&](long long i) { return (int)(i % TG_NHALF) <= lim[(size_t)(i / TG_NHALF)] ? (long long)hist[(size_t)i] : 0ll; };
+        const auto flush = [&](long long first, long long last, long long expected) -> int {
+            const int ma = (int)(first / TG_NHALF), ha = (int)(first % TG_NHALF), mb = (int)(last / TG_NHALF), hb = (int)(last % TG_NHALF);
             for (int m = ma; m <= mb; m++) set_range(mbase, m, m == ma ? ha : 0, m == mb ? hb : lim[m]);
             long long got = 0;
             if (int rc = scan(0, mbase, ma, mb + 1, 0, total, &got)) return rc;
-            if (got != pend) return fail(c, -5, "targets: a pass found a different number of sites than counted");
-            ma = -1;
-            pend = 0;
+            if (got != expected) return fail(c, -5, "targets: a pass found a different number of sites than counted");
             return finish(mbase, got);
         };
-        for (int m = 0; m < n; m++)
-            for (int h = 0; h <= lim[m]; h++) {
-                const long long cnt = (long long)hist[(size_t)m * TG_NHALF + h];
-                if (cnt == 0) continue;
-                if (pend + cnt > cap)
-                    if (int rc = flush()) return rc;
-                if (cnt <= cap) {
-                    if (ma < 0) { ma = m; ha = h; }
-                    mb = m; hb = h;
-                    pend += cnt;
-                    continue;
-                }
-                // one (miRNA, half-score) over cap: ranges of offsets, halved until a range fits
-                set_range(mbase, m, h, h);
-                unsigned long long len = total;
-                for (unsigned long long p = 0; p < total;) {
-                    const unsigned long long p1 = std::min(total, p + len);
-                    long long got = 0;
-                    if (int rc = scan(0, mbase, m, m + 1, p, p1, &got)) return rc;
-                    if (got > cap && p1 - p == 1) return fail(c, -5, "targets: one offset holds more sites of one miRNA and score than a pass");
-                    if (got > cap) { len = std::max<unsigned long long>(1, len / 2); continue; }
-                    if (int rc = finish(mbase, got)) return rc;
-                    p = p1;
-                }
-            }
-        return flush();
+        const auto range = [&](long long bin, unsigned long long p, unsigned long long p1, long long* got) -> int {
+            const int m = (int)(bin / TG_NHALF), h = (int)(bin % TG_NHALF);
+            set_range(mbase, m, h, h);
+            if (int rc = scan(0, mbase, m, m + 1, p, p1, got)) return rc;
+            return *got > cap ? 0 : finish(mbase, *got);
+        };
+        const int rc = plan_passes((long long)n * TG_NHALF, count, cap, total, flush, range);
+        return rc == PLAN_POSITION_OVER_CAP ? fail(c, -5, "targets: one offset holds more sites of one miRNA and score than a pass") : rc;
     }
 };
 
@@ -485,14 +464,12 @@ int mirp_device_target_scan(mirp_ctx* c, const unsigned long long* pk, const uns
                             const MirpTargetOpts& o, const std::function<int(const char*, size_t)>& sink, long long stats[2], double seconds[4]) {
     using namespace mirp;
     hipStream_t st = c->stream;
-    const long long n_pk = (total + 31) / 32 + 2, n_bm = (total + 31) / 32 + 2;
     const long long n_mi = (long long)mi.size();
     long long cap = c->tg_cap > 0 ? c->tg_cap : (1ll << 26);
     if (o.bulge && cap < 4) cap = 4;            // one offset can hold 4 sites of one (miRNA, score): t and m on both strands (an ungapped site of
                                                 // that score dominates both); without bulge it holds 2, the smallest capacity the ABI takes
-    double t = tg_now();
-    if (c->tg_pk.ensure(8 * (size_t)n_pk) || c->tg_amb.ensure(4 * (size_t)n_bm) || c->tg_cst.ensure(4 * (size_t)n_bm) || c->tg_cstart.ensure(8 * cstart.size()) ||
-        c->tg_names.ensure(tnames.size() + 1) || c->tg_noff.ensure(8 * tnoff.size()) || c->tg_mcodes.ensure(mcodes.size() + 32) ||
+    double t = mirp::now();
+    if (c->tg_names.ensure(tnames.size() + 1) || c->tg_noff.ensure(8 * tnoff.size()) || c->tg_mcodes.ensure(mcodes.size() + 32) ||
         c->tg_mnames.ensure(mnames.size() + 1) || c->tg_mnoff.ensure(8 * mnoff.size()) || c->tg_mi.ensure(sizeof(TgMirna) * TG_GROUP) ||
         c->tg_emitted.ensure(8 * (size_t)TG_GROUP) || c->tg_hist.ensure(8 * (size_t)TG_GROUP * TG_NHALF) || c->tg_small.ensure(64) ||
         c->tg_keys.ensure(8 * (size_t)cap) || c->tg_ktmp.ensure(8 * (size_t)cap) || c->tg_size.ensure(4 * (size_t)cap) || c->tg_toff.ensure(8 * (size_t)(cap + 1)))
@@ -500,21 +477,17 @@ int mirp_device_target_scan(mirp_ctx* c, const unsigned long long* pk, const uns
     if (o.energy && (c->tg_emfe.ensure(4 * (size_t)cap) || c->tg_ema.ensure(8 * (size_t)cap) || c->tg_emb.ensure(8 * (size_t)cap) ||
                      c->tg_perf.ensure(4 * (size_t)TG_GROUP)))
         return fail(c, -6, "device allocation failed (targets: energies)");
-    HIPCHK(c, hipMemcpyAsync(c->tg_pk.p, pk, 8 * (size_t)n_pk, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->tg_amb.p, amb, 4 * (size_t)n_bm, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->tg_cst.p, cst, 4 * (size_t)n_bm, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->tg_cstart.p, cstart.data(), 8 * cstart.size(), hipMemcpyHostToDevice, st));
+    TgRun run;
+    if (int rc = tg_upload_packed(c, pk, amb, cst, total, cstart, &run.R)) return rc;
     if (!tnames.empty()) HIPCHK(c, hipMemcpyAsync(c->tg_names.p, tnames.data(), tnames.size(), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->tg_noff.p, tnoff.data(), 8 * tnoff.size(), hipMemcpyHostToDevice, st));
     if (!mcodes.empty()) HIPCHK(c, hipMemcpyAsync(c->tg_mcodes.p, mcodes.data(), mcodes.size(), hipMemcpyHostToDevice, st));
     if (!mnames.empty()) HIPCHK(c, hipMemcpyAsync(c->tg_mnames.p, mnames.data(), mnames.size(), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->tg_mnoff.p, mnoff.data(), 8 * mnoff.size(), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    seconds[0] = tg_now() - t;
+    seconds[0] = mirp::now() - t;
 
-    TgRun run;
     run.c = c;
-    run.R = TgRef{(const unsigned long long*)c->tg_pk.p, (const unsigned*)c->tg_amb.p, (const unsigned*)c->tg_cst.p, (unsigned long long)total};
     run.T = TgText{(const unsigned long long*)c->tg_pk.p, (const unsigned char*)c->tg_mcodes.p, (const TgMirna*)c->tg_mi.p, (const char*)c->tg_mnames.p,
                    (const long long*)c->tg_mnoff.p, (const char*)c->tg_names.p, (const long long*)c->tg_noff.p, (const unsigned long long*)c->tg_cstart.p,
                    (int)cstart.size() - 1, 0};

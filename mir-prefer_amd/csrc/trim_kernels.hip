@@ -12,7 +12,6 @@
 //                                the 3' quality trim and the adapter scan, bit-parallel on 2-bit codes (one xor / or / popcount per shift)
 //   emit     trim_size_kernel, launch_excl_scan, trim_emit_kernel   record sizes, their offsets, the text; downloaded in pieces of at most 1 GiB
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -263,7 +262,6 @@ static inline int tr_grid(long long n) {
     const long long g = (n + 255) / 256;
     return (int)(g < 1 ? 1 : g > 16384 ? 16384 : g);
 }
-static inline double tr_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static inline bool tr_host_ws(unsigned char ch) { return ch == 32 || (ch >= 9 && ch <= 13) || (ch >= 0x1c && ch <= 0x1f); }
 
 static const char* const kTrimReason[] = {"line 1 does not start with '@'", "line 3 does not start with '+'", "the read is longer than 1,024 nt (not supported)",
@@ -282,7 +280,7 @@ int mirp_device_trim_reads(mirp_ctx* c, const char* text, long long n, const cha
     for (int i = 0; i < 7; i++) stats[i] = 0;
     if (n == 0) return 0;
     hipStream_t st = c->stream;
-    double t = tr_now();
+    double t = mirp::now();
     if (c->t_text.ensure((size_t)n + TR_PAD) || c->t_small.ensure(64)) return fail(c, -6, "device allocation failed (trim: text)");
     unsigned char* d_text = (unsigned char*)c->t_text.p;
     unsigned long long* d_small = (unsigned long long*)c->t_small.p;   // [0] first byte >= 0x80, [1] first bad record key, [2 .. 8) counts
@@ -291,10 +289,10 @@ int mirp_device_trim_reads(mirp_ctx* c, const char* text, long long n, const cha
     unsigned long long init[8] = {~0ull, ~0ull, 0, 0, 0, 0, 0, 0};
     HIPCHK(c, hipMemcpyAsync(d_small, init, sizeof init, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    seconds[0] += tr_now() - t;
+    seconds[0] += mirp::now() - t;
 
     // ---- split
-    t = tr_now();
+    t = mirp::now();
     long long n_lines = 0, bad = -1;
     if (int rc = mirp_device_split_lines(c, d_text, n, 0x7fffffffffffffffll, c->t_bcnt, c->t_bscan, c->t_starts, d_small, &n_lines, &bad)) {
         if (rc == -9) {
@@ -305,10 +303,10 @@ int mirp_device_trim_reads(mirp_ctx* c, const char* text, long long n, const cha
         return rc;
     }
     const long long* d_starts = (const long long*)c->t_starts.p;
-    seconds[1] += tr_now() - t;
+    seconds[1] += mirp::now() - t;
 
     // ---- records
-    t = tr_now();
+    t = mirp::now();
     const bool fq = text[0] == '@';
     if (!fq && text[0] != '>') return fail(c, -10, std::string(name) + ": the first byte is neither '@' (FASTQ) nor '>' (FASTA)");
     if (!fq && o.quality_cutoff > 0) return fail(c, -10, std::string(name) + ": quality trimming needs FASTQ input, this file is FASTA");
@@ -370,10 +368,10 @@ int mirp_device_trim_reads(mirp_ctx* c, const char* text, long long n, const cha
     }
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
-    seconds[2] += tr_now() - t;
+    seconds[2] += mirp::now() - t;
 
     // ---- trim
-    t = tr_now();
+    t = mirp::now();
     TrimArgs a{};
     a.m = o.adapter_len; a.e_pm = o.error_permille; a.ovl = o.min_overlap; a.q = o.quality_cutoff;
     a.min_len = o.min_length; a.max_len = o.max_length; a.discard = o.discard_untrimmed;
@@ -392,10 +390,10 @@ int mirp_device_trim_reads(mirp_ctx* c, const char* text, long long n, const cha
     HIPCHK(c, hipGetLastError());
     if (res[0] != ~0ull) return tr_refuse_record(c, name, (long long)(res[0] >> 3), (int)(res[0] & 7));
     if (rem) return tr_refuse_record(c, name, R, 6);
-    seconds[3] += tr_now() - t;
+    seconds[3] += mirp::now() - t;
 
     // ---- emit + download
-    t = tr_now();
+    t = mirp::now();
     long long total = 0;
     long long* d_off = (long long*)c->t_off.p;
     if (R > 0) {
@@ -411,18 +409,9 @@ int mirp_device_trim_reads(mirp_ctx* c, const char* text, long long n, const cha
                            (const int*)d_namel, (const long long*)d_src, (const int*)d_flen, (const long long*)d_off, R, (char*)c->t_out.p);
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
-    const size_t piece = (size_t)1 << 30;
-    if (total > 0 && c->h_text.size() < std::min((size_t)total, piece)) c->h_text.resize(std::min((size_t)total, piece));
     double in_sink = 0;
-    for (long long at = 0; at < total;) {
-        const size_t len = (size_t)std::min<long long>(total - at, (long long)piece);
-        HIPCHK(c, hipMemcpy(c->h_text.data(), (const char*)c->t_out.p + at, len, hipMemcpyDeviceToHost));
-        const double ts = tr_now();
-        if (int rc = sink(c->h_text.data(), len)) return rc;
-        in_sink += tr_now() - ts;
-        at += (long long)len;
-    }
-    seconds[4] += tr_now() - t - in_sink;
+    if (int rc = mirp_download_text(c, (const char*)c->t_out.p, total, sink, &in_sink)) return rc;
+    seconds[4] += mirp::now() - t - in_sink;
     seconds[5] += in_sink;
     stats[0] = R;
     for (int i = 0; i < 6; i++) stats[1 + i] = (long long)res[1 + i];

@@ -131,17 +131,20 @@ def test_forced_capacities_give_identical_files(gpu_ctx, small, tmp_path):
     (tmp_path / "k3.fa").write_bytes(b"".join(b">ath-miR%d\n%s\n" % (i, seq if i % 3 else seq[:-1] + b"G") for i in range(130)))
     (tmp_path / "q.fa").write_bytes((small / "q.fa").read_bytes() + b">many\n" + seq + b"\n>tail\n" + seq[1:] + b"\n")
     paths.append(tmp_path / "k3.fa")
+    # the pass counts are those of the hand-written pass loops that pass_plan.h replaced, recorded on an MI355X before the change: (E, M, k) -> capacity 0, 2, 40
+    recorded = {(2, 2, 0): (1, 205, 21), (4, 6, 0): (1, 4616, 180), (4, 6, 3): (1, 361, 101), (2, 2, 1): (1, 71, 7), (2, 2, 50): (1, 119, 9),
+                (2, 2, 100): (1, 175, 19)}
     try:
         for E, M, k in ((2, 2, 0), (4, 6, 0), (4, 6, 3), (2, 2, 1), (2, 2, 50), (2, 2, 100)):
             gpu_ctx.set_target_capacity(0)
             ref = _scan(gpu_ctx, tmp_path, tmp_path / "q.fa", paths, E=E, M=M, k=k)
             assert ref[:2] == restate_files(tmp_path / "q.fa", paths, E=E, M=M, k=k)[:2]
-            assert ref[2]["passes"] <= 2
-            for cap in (2, 40):
+            assert ref[2]["passes"] <= 2 and ref[2]["passes"] == recorded[E, M, k][0]
+            for cap, passes in zip((2, 40), recorded[E, M, k][1:]):
                 gpu_ctx.set_target_capacity(cap)
                 got = _scan(gpu_ctx, tmp_path, tmp_path / "q.fa", paths, E=E, M=M, k=k)
                 assert got[0] == ref[0] and got[1] == ref[1], (E, M, k, cap)
-                assert got[2]["passes"] > ref[2]["passes"]
+                assert got[2]["passes"] > ref[2]["passes"] and got[2]["passes"] == passes, (E, M, k, cap, got[2])
                 assert {x: got[2][x] for x in got[2] if x not in ("passes", "seconds")} == {x: ref[2][x] for x in ref[2] if x not in ("passes", "seconds")}
     finally:
         gpu_ctx.set_target_capacity(0)

@@ -95,10 +95,12 @@ def test_forced_capacities_give_the_same_bytes(gpu_ctx, sweep_input, tmp_path):
     want, base = _scan(gpu_ctx, d, case, max_half_score=16)
     assert base["hits"] >= 50 and base["passes"] == 1
     try:
-        for cap in (2, 40):
+        # the pass counts are those of the hand-written pass loops that pass_plan.h replaced, recorded on an MI355X before the change
+        for cap, passes in ((2, 63), (40, 4)):
             gpu_ctx.set_target_capacity(cap)
             got, res = _scan(gpu_ctx, d, case, out=tmp_path / "cap.tsv", max_half_score=16)
             assert got == want, cap
+            assert res["passes"] == passes, (cap, res)
             assert res["passes"] > base["hits"] // max(cap, 1) // 2 and res["hits"] == base["hits"]
     finally:
         gpu_ctx.set_target_capacity(0)
@@ -204,7 +206,8 @@ def test_word_boundaries_and_the_ends_of_the_packed_text(gpu_ctx, tmp_path):
     case, texts, mirs = boundary_case()
     _write_inputs(tmp_path, case, texts, mirs)
     _load(gpu_ctx, case.recs, len(case.sq_names))
-    for half, cleavage, cap in ((0, False, 0), (16, False, 0), (16, True, 0), (16, False, 2), (16, False, 40)):
+    # the pass counts are those of the hand-written pass loops that pass_plan.h replaced, recorded on an MI355X before the change
+    for (half, cleavage, cap), passes in zip(((0, False, 0), (16, False, 0), (16, True, 0), (16, False, 2), (16, False, 40)), (1, 1, 1, 28, 2)):
         try:
             gpu_ctx.set_target_capacity(cap)
             got, res = _scan(gpu_ctx, tmp_path, case, max_half_score=half, cleavage_site=cleavage)
@@ -214,6 +217,7 @@ def test_word_boundaries_and_the_ends_of_the_packed_text(gpu_ctx, tmp_path):
         assert got == want, (half, cleavage, cap)
         assert (got, stats) == restate_plain(case, max_half=half, cleavage=cleavage)
         assert {k: res[k] for k in STAT_KEYS} == stats
+        assert res["passes"] == passes, (half, cleavage, cap, res)
         if cap == 2:                                  # some (miRNA, category, score) holds more hits than the capacity: split by position
             rows = _rows(got)
             bins = {}

@@ -225,15 +225,18 @@ def test_targets_energy_capacities(gpu_ctx, energy_input, energy_want, tmp_path)
     d, _ = energy_input
     paths = [d / "t1.fa", d / "t2.fa"]
     split = set()
+    # the pass counts are those of the hand-written pass loops that pass_plan.h replaced, recorded on an MI355X before the change, per capacity in the order of OPTIONS
+    recorded = {4: (10, 19, 15, 27), 40: (1, 2, 2, 3)}
     try:
         for cap in (4, 40):
             gpu_ctx.set_target_capacity(cap)
-            for kw, want in zip(OPTIONS, energy_want):
+            for kw, want, passes in zip(OPTIONS, energy_want, recorded[cap]):
                 got, res = _scan(gpu_ctx, tmp_path, d / "m.fa", paths, energy=True, **kw)
                 assert got == want, (cap, kw)
                 # the keys of a run are at least its lines (-k cuts keys, not passes): more than one pass whenever they exceed the capacity
                 lines = want.count(b"\n") - 1
                 assert lines > 4
+                assert res["passes"] == passes, (cap, kw, res)
                 if lines > cap:
                     assert res["passes"] > 1, (cap, kw, res)
                     split.add(cap)

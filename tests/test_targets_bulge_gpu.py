@@ -114,14 +114,16 @@ def test_forced_capacities_give_the_same_bytes(gpu_ctx, tmp_path):
     write_fasta(tmp_path / "t.fa", [("a", bytes(text[:7000])), ("b", bytes(text[7000:]))])
     write_fasta(tmp_path / "m.fa", [("m%d" % i, m) for i, m in enumerate(mirs)])
     try:
-        for cap, (half, both, cleavage, k) in ((40, (6, True, False, 0)), (40, (6, True, False, 30)), (2, (4, False, True, 0)), (2, (5, True, False, 3)),
-                                                (0, (6, True, False, 0))):
+        # the pass counts are those of the hand-written pass loops that pass_plan.h replaced, recorded on an MI355X before the change
+        for cap, (half, both, cleavage, k), passes in ((40, (6, True, False, 0), 4), (40, (6, True, False, 30), 4), (2, (4, False, True, 0), 21),
+                                                        (2, (5, True, False, 3), 33), (0, (6, True, False, 0), 1)):
             gpu_ctx.set_target_capacity(cap)
             got, res = _scan(gpu_ctx, tmp_path, tmp_path / "m.fa", [tmp_path / "t.fa"], max_half_score=half, both_strands=both, cleavage_site=cleavage,
                              max_sites=k, bulge=True)
             want = _restate_files(tmp_path / "m.fa", [tmp_path / "t.fa"], half, both, cleavage, k)
             assert got == want, (cap, half, both, cleavage, k)
             assert (res["passes"] > 3) == (cap > 0), (cap, res)
+            assert res["passes"] == passes, (cap, half, both, cleavage, k, res)
             assert k or {b"t", b"m", b"."} <= {tag for _, tag in _tags(want)}
     finally:
         gpu_ctx.set_target_capacity(0)
@@ -140,11 +142,13 @@ def test_capacity_2_with_three_sites_of_one_score_at_one_offset(gpu_ctx, tmp_pat
         per[(f[2], f[5])] = per.get((f[2], f[5]), 0) + 1
     assert max(per.values()) >= 3
     try:
-        for cap in (2, 3, 40, 0):
+        # the pass counts are those of the hand-written pass loops that pass_plan.h replaced, recorded on an MI355X before the change (2 and 3 are both raised to 4)
+        for cap, passes in ((2, 212), (3, 212), (40, 12), (0, 1)):
             gpu_ctx.set_target_capacity(cap)
             got, res = _scan(gpu_ctx, tmp_path, tmp_path / "m.fa", [tmp_path / "t.fa"], max_half_score=16, both_strands=True, bulge=True)
             assert got == want, cap
             assert (res["passes"] > 3) == (cap > 0)
+            assert res["passes"] == passes, (cap, res)
     finally:
         gpu_ctx.set_target_capacity(0)
 

@@ -108,11 +108,14 @@ def test_capacity_overflow(gpu_ctx, tmp_path):
     write_fasta(tmp_path / "t.fa", [("a", bytes(text[:14000])), ("b", bytes(text[14000:]))])
     write_fasta(tmp_path / "m.fa", [("m%d" % i, m) for i, m in enumerate(mirs)])
     try:
-        for cap, kw in ((40, _kw(6, True)), (40, _kw(6, True, k=70)), (2, _kw(4, False, True)), (40, _kw(8, True, k=5)), (0, _kw(6, True))):
+        # the pass counts are those of the hand-written pass loops that pass_plan.h replaced, recorded on an MI355X before the change
+        for cap, kw, passes in ((40, _kw(6, True), 12), (40, _kw(6, True, k=70), 12), (2, _kw(4, False, True), 120), (40, _kw(8, True, k=5), 10),
+                                (0, _kw(6, True), 1)):
             gpu_ctx.set_target_capacity(cap)
             got, res = _scan(gpu_ctx, tmp_path, tmp_path / "m.fa", [tmp_path / "t.fa"], **kw[0])
             assert got == restate_files(tmp_path / "m.fa", [tmp_path / "t.fa"], **kw[1]), (cap, kw)
             assert (res["passes"] > 3) == (cap > 0), (cap, res)
+            assert res["passes"] == passes, (cap, kw, res)
     finally:
         gpu_ctx.set_target_capacity(0)
 
