@@ -602,6 +602,39 @@ int mirp_set_duplex_capacity(mirp_ctx* ctx, int64_t pairs);
 /* stats = {pairs, passes, loop evaluations (predecessor cells read)} of the last mirp_duplex_batch. */
 int mirp_duplex_last_stats(mirp_ctx* ctx, int64_t stats[3]);
 
+/* Partition function of whole sequences (McCaskill inside / outside fold): Turner-2004 with dangles = 2, whatever
+ * mirp_set_fold_model says.  Letters as mirp_duplex_batch.  bpp_cutoff: with want_bpp the pairs with p >= bpp_cutoff come back (0 <= cutoff <= 1). */
+typedef struct {
+    double bpp_cutoff;
+    int32_t want_bpp;
+    int32_t reserved;
+} MirpEnsembleOpts;
+/* len; mfe = the global minimum free energy (0.01 kcal/mol; mirp_fold_batch's mfe with the default model); efe = -kT ln Z (kcal/mol); mfe_freq =
+ * exp(-(mfe / 100 - efe) / kT); diversity = 2 sum p (1 - p), the mean pair distance of the ensemble; the centroid holds the centroid_pairs pairs
+ * with p > 0.5; centroid_dist = its mean pair distance to the ensemble. */
+typedef struct {
+    int32_t len, mfe;
+    double efe, mfe_freq, diversity, centroid_dist;
+    int32_t centroid_pairs, reserved;
+} MirpEnsembleRec;
+/* one pair of sequence `seq` (0-based index in the call), 1-based positions i < j */
+typedef struct {
+    int32_t seq, i, j, reserved;
+    double p;
+} MirpBpp;
+/* seqs / offsets as mirp_randfold, with its refusals (-10 and the 1-based record in mirp_last_error: an empty sequence, one longer than 3,000 nt, a
+ * byte >= 0x80); n_seqs = 0 is fine.  Out: recs[n_seqs] (caller's); centroids (caller's, the sum of len + 1 bytes): the dot-bracket texts,
+ * NUL-terminated, back to back; with opts->want_bpp, *bpp (library-owned, mirp_free) holds the *n_bpp pairs with p >= bpp_cutoff ordered by
+ * (seq, i, j) -- bpp and n_bpp may be NULL otherwise.  The sequences are folded in passes whose slabs fit mirp_set_ensemble_capacity; a
+ * sequence's results are bit-identical whatever else is in the call and however it is split.  Nothing resident changes. */
+int mirp_ensemble(mirp_ctx* ctx, const char* seqs, const int64_t* offsets, int32_t n_seqs, const MirpEnsembleOpts* opts, MirpEnsembleRec* recs,
+                  char* centroids, MirpBpp** bpp, int64_t* n_bpp);
+/* Bytes of table slabs one pass of mirp_ensemble holds on the device; 0 = the default, 2^35.  A sequence whose slab alone is larger runs in a
+ * pass of its own.  Lowered only to test the split. */
+int mirp_set_ensemble_capacity(mirp_ctx* ctx, int64_t bytes);
+/* stats = {sequences, passes, cells (i < j pairs of positions, summed over the sequences)} of the last mirp_ensemble. */
+int mirp_ensemble_last_stats(mirp_ctx* ctx, int64_t stats[3]);
+
 #ifdef __cplusplus
 }
 #endif

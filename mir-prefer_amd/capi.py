@@ -65,6 +65,19 @@ DUPLEX_DTYPE = np.dtype([("mfe", "<i4"), ("pairs", "<i4"), ("a_first", "<i4"), (
 DUPLEX_STATS = ("pairs", "passes", "evaluations")
 
 
+class EnsembleOpts(C.Structure):
+    """MirpEnsembleOpts of include/mirprefer.h."""
+    _fields_ = [("bpp_cutoff", C.c_double), ("want_bpp", C.c_int32), ("reserved", C.c_int32)]
+
+
+# MirpEnsembleRec of include/mirprefer.h: one sequence of mirp_ensemble
+ENSEMBLE_DTYPE = np.dtype([("len", "<i4"), ("mfe", "<i4"), ("efe", "<f8"), ("mfe_freq", "<f8"), ("diversity", "<f8"), ("centroid_dist", "<f8"),
+                           ("centroid_pairs", "<i4"), ("reserved", "<i4")])
+# MirpBpp of include/mirprefer.h: one pair of mirp_ensemble's list, positions 1-based
+BPP_DTYPE = np.dtype([("seq", "<i4"), ("i", "<i4"), ("j", "<i4"), ("reserved", "<i4"), ("p", "<f8")])
+ENSEMBLE_STATS = ("sequences", "passes", "cells")
+
+
 class PhaseOpts(C.Structure):
     """MirpPhaseOpts of include/mirprefer.h."""
     _fields_ = [(f, C.c_int32) for f in ("length", "cycles", "min_phased", "min_depth")]
@@ -434,6 +447,12 @@ def load_library():
     lib.mirp_set_duplex_capacity.restype = C.c_int
     lib.mirp_duplex_last_stats.argtypes = [vp, i64p]
     lib.mirp_duplex_last_stats.restype = C.c_int
+    lib.mirp_ensemble.argtypes = [vp, C.c_char_p, i64p, C.c_int32, C.POINTER(EnsembleOpts), vp, vp, C.POINTER(vp), i64p]
+    lib.mirp_ensemble.restype = C.c_int
+    lib.mirp_set_ensemble_capacity.argtypes = [vp, C.c_int64]
+    lib.mirp_set_ensemble_capacity.restype = C.c_int
+    lib.mirp_ensemble_last_stats.argtypes = [vp, i64p]
+    lib.mirp_ensemble_last_stats.restype = C.c_int
     lib.mirp_set_target_capacity.argtypes = [vp, C.c_int64]
     lib.mirp_set_target_capacity.restype = C.c_int
     lib.mirp_phase_scan.argtypes = [vp, C.POINTER(PhaseOpts), vp, C.POINTER(vp), i64p, i64p]
@@ -656,6 +675,40 @@ class Context:
         st = (C.c_int64 * 3)()
         self._check(self.lib.mirp_duplex_last_stats(self.h, st), "mirp_duplex_last_stats")
         return dict(zip(DUPLEX_STATS, list(st)))
+
+    def ensemble(self, seqs, bpp_cutoff=None, capacity=0):
+        """Partition function of whole sequences (mirp_ensemble): seqs (list of str / bytes, 1..3000 nt, A C G U/T in either
+        case, anything else N), Turner-2004 with dangles 2 whatever the context's fold model.  bpp_cutoff: None, or the pairs with p >= it come
+        back.  capacity: bytes of table slabs per pass (0 = the default), lowered only in tests.  -> (ENSEMBLE_DTYPE array, [bytes] of the
+        centroid texts, BPP_DTYPE array ordered by (seq, i, j) or None)."""
+        bs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        offs = np.zeros(len(bs) + 1, dtype=np.int64)
+        if bs:
+            offs[1:] = np.cumsum([len(b) for b in bs])
+        o = EnsembleOpts()
+        o.bpp_cutoff, o.want_bpp, o.reserved = (0.0 if bpp_cutoff is None else float(bpp_cutoff)), int(bpp_cutoff is not None), 0
+        recs = np.zeros(len(bs), dtype=ENSEMBLE_DTYPE)
+        text = C.create_string_buffer(int(offs[-1]) + len(bs) + 1)
+        ptr, nb = C.c_void_p(), C.c_int64()
+        self._check(self.lib.mirp_set_ensemble_capacity(self.h, int(capacity)), "mirp_set_ensemble_capacity")
+        try:
+            self._check(self.lib.mirp_ensemble(self.h, b"".join(bs), offs.ctypes.data_as(C.POINTER(C.c_int64)), len(bs), C.byref(o),
+                                               recs.ctypes.data_as(C.c_void_p), C.cast(text, C.c_void_p), C.byref(ptr), C.byref(nb)), "mirp_ensemble")
+        finally:
+            self.lib.mirp_set_ensemble_capacity(self.h, 0)
+        raw, at, cen = text.raw, 0, []
+        for b in bs:
+            cen.append(raw[at:at + len(b)])
+            at += len(b) + 1
+        if bpp_cutoff is None:
+            return recs, cen, None
+        return recs, cen, (_copy_out(self.lib, ptr, BPP_DTYPE, nb.value) if ptr.value else np.zeros(0, dtype=BPP_DTYPE))
+
+    def ensemble_last_stats(self):
+        """{sequences, passes, cells} of the last ensemble."""
+        st = (C.c_int64 * 3)()
+        self._check(self.lib.mirp_ensemble_last_stats(self.h, st), "mirp_ensemble_last_stats")
+        return dict(zip(ENSEMBLE_STATS, list(st)))
 
     def phase_scan(self, length, cycles, kmin, min_phased=3, min_depth=1):
         """Phased siRNA windows on this context's resident alignments (mirp_phase_scan).  kmin: the int32 table of the smallest

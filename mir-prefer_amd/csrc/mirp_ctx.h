@@ -132,6 +132,11 @@ struct mirp_ctx {
     DevBuf dx_a, dx_b, dx_aoff, dx_boff, dx_mfe, dx_ma, dx_mb, dx_small, tg_emfe, tg_ema, tg_emb, tg_perf;
     long long dx_cap = 0;             // pairs per pass of mirp_duplex_batch; 0 = the default, 2^20 (mirp_set_duplex_capacity)
     long long dx_stats[3] = {0, 0, 0};   // the last mirp_duplex_batch: pairs, passes, loop evaluations
+    // ---- partition function (ensemble_kernels.hip, mirp_ensemble.cpp): the letters and codes of the call, the MFE fold's outputs, the jobs, slabs,
+    // records, texts and pair lists of one pass
+    DevBuf en_seq, en_soffs, en_codes, en_lines, en_ss, en_nlines, en_mfe, en_status, en_jobs, en_slab, en_recs, en_texts, en_rowcnt, en_rowat, en_bpp;
+    long long en_cap = 0;             // slab bytes per pass of mirp_ensemble; 0 = the default, 2^35 (mirp_set_ensemble_capacity)
+    long long en_stats[3] = {0, 0, 0};   // the last mirp_ensemble: sequences, passes, cells
     long long n_result = 0;          // records of the last mirp_predict (p_res / p_text), what mirp_gather_loci sends
     bool have_result = false;
 };
@@ -238,6 +243,18 @@ int mirp_device_duplex_perfect(mirp_ctx* c, const unsigned char* d_mcodes, const
                                unsigned long long* d_mb);
 int mirp_device_duplex_sites(mirp_ctx* c, const DxTargets& T, bool bulge, const unsigned long long* d_keys, long long n, long long max_sites,
                              const unsigned long long* d_emitted, int* d_mfe, unsigned long long* d_ma, unsigned long long* d_mb);
+// ensemble_kernels.hip: the inside / outside fold of DESIGN.md §23, one workgroup per job.  A job: the codes (N A C G U = 0..4) of its sequence at
+// d_codes + code_off, its slab of mirp_ensemble_slab_doubles(n) doubles at d_slab + slab_off, its centroid text at d_texts + text_off, its rows of
+// the pair counts at row_off + i, its record and MFE at index rec.  fold: jobs [0, n_ring) have at most MIRP_ENSEMBLE_RING_N nt (Qb's diagonals
+// ringed in LDS), the longest of them max_ring_n; the others read them from the slab.  reduce: p into the slab, the record and the centroid text.  bpp: with d_out null the
+// number of pairs with p >= cutoff per row, else the pairs themselves at d_row_at[row].
+#define MIRP_ENSEMBLE_RING_N 300
+struct EnJob { long long code_off, slab_off, text_off, row_off; int n, rec; };
+size_t mirp_ensemble_slab_doubles(int n);
+int mirp_device_ensemble_fold(mirp_ctx* c, const unsigned char* d_codes, const EnJob* d_jobs, int n_ring, int n_jobs, int max_ring_n, double* d_slab);
+int mirp_device_ensemble_reduce(mirp_ctx* c, const EnJob* d_jobs, int n_jobs, double* d_slab, const int* d_mfe, MirpEnsembleRec* d_recs, char* d_texts);
+int mirp_device_ensemble_bpp(mirp_ctx* c, const EnJob* d_jobs, int n_jobs, const double* d_slab, double cutoff, int* d_row_cnt, const long long* d_row_at,
+                             MirpBpp* d_out);
 int mirp_device_mask_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long* n_io, MirpAln* d_segs, MirpAln* d_segtmp, const int* d_owner, const int* d_seg_span,
                           long long* nseg_io,
                           const long long* d_rfirst, const int* d_rstart, const int* d_remax);
