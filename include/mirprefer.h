@@ -455,11 +455,14 @@ int mirp_trim_reads(mirp_ctx* ctx, const char* data, int64_t n, const char* name
  * column `bulge` on every line (§14, "Bulged sites"); 0 leaves every byte of the output as it was.  energy (0 or 1): four more last columns on
  * every line, `mfe mfe_perfect mfe_ratio duplex` (§21, "targets -e"): the free energy of the duplex of the miRNA with the site and one flanking
  * base on each side (mirp_duplex_batch's fold, not forced onto the alignment of `pairs`), that of the miRNA with its reverse complement, their
- * ratio to three decimals (NA when the perfect duplex is unbound) and the structure text; 0 leaves every byte of the output as it was. */
+ * ratio to three decimals (NA when the perfect duplex is unbound) and the structure text; 0 leaves every byte of the output as it was.
+ * accessibility (0 or 1): a last column `upe` on every line (§24, "targets -u"): the energy in kcal/mol, to three decimals, that opens the site
+ * inside its window of the target strand -- the site's interval and mirp_set_target_flanks' bases beside it, clipped to the contig
+ * (mirp_unpaired_batch's upe of that window); 0 leaves every byte of the output as it was. */
 typedef struct {
     int32_t max_half_score, both_strands, cleavage_site, bulge;
     int64_t max_sites;
-    int32_t energy, reserved;
+    int32_t energy, accessibility;
 } MirpTargetOpts;
 /* Reads the miRNA FASTA mirna_path (name = the whole header after '>', stripped, tabs turned into spaces; multi-line sequences concatenated; A C G U T
  * in either case, T = U, any other letter unknown) and the target FASTA files target_paths[0 .. n_targets) (parsed and packed as mirp_align_index
@@ -467,7 +470,7 @@ typedef struct {
  * start, + before -, end.  Refusals, each before out_path is opened (-10, the 1-based record in mirp_last_error): a miRNA of length outside 12..32, an
  * empty name, a byte >= 0x80, more than 2^24 miRNAs; and the target refusals of mirp_align_index.  On any error the file at out_path is removed.
  * Out: stats = {miRNAs, targets, target bases, evaluations (offsets x miRNAs x strands), sites written, passes}, seconds = {parse, upload, scan,
- * sort + cut (with energy: and the folds of the pass's keys), emit + download + write}. */
+ * sort + cut (with energy / accessibility: and the folds of the pass's keys), emit + download + write}. */
 int mirp_target_scan(mirp_ctx* ctx, const char* mirna_path, const char* const* target_paths, int32_t n_targets, const MirpTargetOpts* opts,
                      const char* out_path, int64_t stats[6], double seconds[5]);
 /* Keys (sites before the -k cut) one pass of mirp_target_scan holds on the device, at least 2; 0 = the default, 2^26.  A pass that finds more is
@@ -634,6 +637,23 @@ int mirp_ensemble(mirp_ctx* ctx, const char* seqs, const int64_t* offsets, int32
 int mirp_set_ensemble_capacity(mirp_ctx* ctx, int64_t bytes);
 /* stats = {sequences, passes, cells (i < j pairs of positions, summed over the sequences)} of the last mirp_ensemble. */
 int mirp_ensemble_last_stats(mirp_ctx* ctx, int64_t stats[3]);
+
+/* Accessibility of an interval: with the model of mirp_ensemble, efe = -kT ln Z over all structures of the sequence, efe_open =
+ * -kT ln Z_open over those in which no position of the interval is paired (pairs that enclose it are allowed), and upe = efe_open - efe >= 0 =
+ * -kT ln P(the interval is unpaired), all in kcal/mol. */
+typedef struct { double efe, efe_open, upe; } MirpUnpairedRec;
+/* Window q = blob[off[q] .. off[q + 1]) with the 1-based interval lo[q] .. hi[q], q < n; letters as mirp_duplex_batch.  Refusals (-10 and the
+ * 1-based record in mirp_last_error): an empty sequence, one longer than 128 nt, a byte >= 0x80, an interval outside 1 <= lo <= hi <= length;
+ * n < 0 is refused with -1; n = 0 is fine.  Out: recs[n].  The windows are folded in passes of at most mirp_set_unpaired_capacity windows; a
+ * window's record is bit-identical whatever else is in the call and however it is split.  Nothing resident changes. */
+int mirp_unpaired_batch(mirp_ctx* ctx, const char* blob, const int64_t* off, const int32_t* lo, const int32_t* hi, int32_t n, MirpUnpairedRec* recs);
+/* Windows one pass of mirp_unpaired_batch holds on the device; 0 = the default, 2^20.  Lowered only to test the split. */
+int mirp_set_unpaired_capacity(mirp_ctx* ctx, int64_t windows);
+/* stats = {windows, passes, cells (i < j pairs of positions, summed over the windows)} of the last mirp_unpaired_batch. */
+int mirp_unpaired_last_stats(mirp_ctx* ctx, int64_t stats[3]);
+/* The flanks of the windows of mirp_target_scan's accessibility column: `up` bases towards the 5' end of the target strand and `down` towards
+ * its 3' end (defaults 17 and 13).  Each >= 0, up + down <= 95 (a window never exceeds 33 + 95 = 128 nt); anything else is refused with -1. */
+int mirp_set_target_flanks(mirp_ctx* ctx, int32_t up, int32_t down);
 
 #ifdef __cplusplus
 }

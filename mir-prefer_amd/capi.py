@@ -35,7 +35,7 @@ TRIM_STATS = ("reads", "quality_trimmed", "adapter", "untrimmed", "too_short", "
 class TargetOpts(C.Structure):
     """MirpTargetOpts of include/mirprefer.h."""
     _fields_ = [("max_half_score", C.c_int32), ("both_strands", C.c_int32), ("cleavage_site", C.c_int32), ("bulge", C.c_int32), ("max_sites", C.c_int64),
-                ("energy", C.c_int32), ("reserved", C.c_int32)]
+                ("energy", C.c_int32), ("accessibility", C.c_int32)]
 
 
 TARGET_STATS = ("mirnas", "targets", "bases", "evaluations", "sites", "passes")
@@ -76,6 +76,10 @@ ENSEMBLE_DTYPE = np.dtype([("len", "<i4"), ("mfe", "<i4"), ("efe", "<f8"), ("mfe
 # MirpBpp of include/mirprefer.h: one pair of mirp_ensemble's list, positions 1-based
 BPP_DTYPE = np.dtype([("seq", "<i4"), ("i", "<i4"), ("j", "<i4"), ("reserved", "<i4"), ("p", "<f8")])
 ENSEMBLE_STATS = ("sequences", "passes", "cells")
+
+# MirpUnpairedRec of include/mirprefer.h: one window of mirp_unpaired_batch, kcal/mol
+UNPAIRED_DTYPE = np.dtype([("efe", "<f8"), ("efe_open", "<f8"), ("upe", "<f8")])
+UNPAIRED_STATS = ("windows", "passes", "cells")
 
 
 class PhaseOpts(C.Structure):
@@ -453,6 +457,14 @@ def load_library():
     lib.mirp_set_ensemble_capacity.restype = C.c_int
     lib.mirp_ensemble_last_stats.argtypes = [vp, i64p]
     lib.mirp_ensemble_last_stats.restype = C.c_int
+    lib.mirp_unpaired_batch.argtypes = [vp, C.c_char_p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, vp]
+    lib.mirp_unpaired_batch.restype = C.c_int
+    lib.mirp_set_unpaired_capacity.argtypes = [vp, C.c_int64]
+    lib.mirp_set_unpaired_capacity.restype = C.c_int
+    lib.mirp_unpaired_last_stats.argtypes = [vp, i64p]
+    lib.mirp_unpaired_last_stats.restype = C.c_int
+    lib.mirp_set_target_flanks.argtypes = [vp, C.c_int32, C.c_int32]
+    lib.mirp_set_target_flanks.restype = C.c_int
     lib.mirp_set_target_capacity.argtypes = [vp, C.c_int64]
     lib.mirp_set_target_capacity.restype = C.c_int
     lib.mirp_phase_scan.argtypes = [vp, C.POINTER(PhaseOpts), vp, C.POINTER(vp), i64p, i64p]
@@ -563,20 +575,28 @@ class Context:
         return dict(zip(TRIM_STATS, list(st)), seconds=list(sec))
 
     def target_scan(self, mirna_path, target_paths, out_path, max_half_score=8, both_strands=False, cleavage_site=False, max_sites=0, bulge=False,
-                    energy=False):
+                    energy=False, accessibility=False, flanks=None):
         """Plant miRNA target sites (mirp_target_scan): every miRNA of mirna_path against the target FASTA files, in order; writes
         the TSV to out_path.  max_half_score = 2 x the -s score.  bulge: also the sites with one unpaired nucleotide, and a last column `bulge`
-        on every line.  energy: the duplex free energy columns `mfe mfe_perfect mfe_ratio duplex` last on every line.  -> {mirnas, targets, bases, evaluations, sites, passes, seconds}; seconds =
+        on every line.  energy: the duplex free energy columns `mfe mfe_perfect mfe_ratio duplex` last on every line.  accessibility: a last
+        column `upe`, the energy that opens the site's window of the target; flanks: (up, down) bases of that window beside the
+        site, None = (17, 13).  -> {mirnas, targets, bases, evaluations, sites, passes, seconds}; seconds =
         {parse, upload, scan, sort + cut, emit + download + write}."""
         o = TargetOpts()
         o.max_half_score, o.both_strands, o.cleavage_site, o.max_sites = int(max_half_score), int(bool(both_strands)), int(bool(cleavage_site)), int(max_sites)
         o.bulge = int(bool(bulge))
         o.energy = int(bool(energy))
+        o.accessibility = int(bool(accessibility))
         arr = (C.c_char_p * len(target_paths))(*[os.fsencode(p) for p in target_paths])
         st = (C.c_int64 * 6)()
         sec = (C.c_double * 5)()
-        self._check(self.lib.mirp_target_scan(self.h, os.fsencode(mirna_path), arr, len(target_paths), C.byref(o), os.fsencode(out_path), st, sec),
-                    "mirp_target_scan")
+        up, down = (17, 13) if flanks is None else flanks
+        self._check(self.lib.mirp_set_target_flanks(self.h, int(up), int(down)), "mirp_set_target_flanks")
+        try:
+            self._check(self.lib.mirp_target_scan(self.h, os.fsencode(mirna_path), arr, len(target_paths), C.byref(o), os.fsencode(out_path), st, sec),
+                        "mirp_target_scan")
+        finally:
+            self.lib.mirp_set_target_flanks(self.h, 17, 13)
         return dict(zip(TARGET_STATS, list(st)), seconds=list(sec))
 
     def set_target_capacity(self, keys):
@@ -709,6 +729,33 @@ class Context:
         st = (C.c_int64 * 3)()
         self._check(self.lib.mirp_ensemble_last_stats(self.h, st), "mirp_ensemble_last_stats")
         return dict(zip(ENSEMBLE_STATS, list(st)))
+
+    def unpaired_batch(self, seqs, lo, hi, capacity=0):
+        """Accessibility of intervals (mirp_unpaired_batch): for seqs[q] (str / bytes, 1..128 nt, letters as duplex_batch) and the
+        1-based interval lo[q] .. hi[q], efe = -kT ln Z, efe_open = -kT ln Z over the structures that leave the interval unpaired, and upe = their
+        difference, in kcal/mol.  capacity: windows per pass (0 = the default), lowered only in tests.  -> UNPAIRED_DTYPE array."""
+        if not len(seqs) == len(lo) == len(hi):
+            raise ValueError("unpaired_batch: %d sequences, %d lo and %d hi" % (len(seqs), len(lo), len(hi)))
+        bs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        offs = np.zeros(len(bs) + 1, dtype=np.int64)
+        if bs:
+            offs[1:] = np.cumsum([len(b) for b in bs])
+        lo32, hi32 = np.ascontiguousarray(lo, dtype=np.int32), np.ascontiguousarray(hi, dtype=np.int32)
+        recs = np.zeros(len(bs), dtype=UNPAIRED_DTYPE)
+        p32 = C.POINTER(C.c_int32)
+        self._check(self.lib.mirp_set_unpaired_capacity(self.h, int(capacity)), "mirp_set_unpaired_capacity")
+        try:
+            self._check(self.lib.mirp_unpaired_batch(self.h, b"".join(bs), offs.ctypes.data_as(C.POINTER(C.c_int64)), lo32.ctypes.data_as(p32),
+                                                     hi32.ctypes.data_as(p32), len(bs), recs.ctypes.data_as(C.c_void_p)), "mirp_unpaired_batch")
+        finally:
+            self.lib.mirp_set_unpaired_capacity(self.h, 0)
+        return recs
+
+    def unpaired_last_stats(self):
+        """{windows, passes, cells} of the last unpaired_batch."""
+        st = (C.c_int64 * 3)()
+        self._check(self.lib.mirp_unpaired_last_stats(self.h, st), "mirp_unpaired_last_stats")
+        return dict(zip(UNPAIRED_STATS, list(st)))
 
     def phase_scan(self, length, cycles, kmin, min_phased=3, min_depth=1):
         """Phased siRNA windows on this context's resident alignments (mirp_phase_scan).  kmin: the int32 table of the smallest

@@ -137,6 +137,12 @@ struct mirp_ctx {
     DevBuf en_seq, en_soffs, en_codes, en_lines, en_ss, en_nlines, en_mfe, en_status, en_jobs, en_slab, en_recs, en_texts, en_rowcnt, en_rowat, en_bpp;
     long long en_cap = 0;             // slab bytes per pass of mirp_ensemble; 0 = the default, 2^35 (mirp_set_ensemble_capacity)
     long long en_stats[3] = {0, 0, 0};   // the last mirp_ensemble: sequences, passes, cells
+    // ---- accessibility of intervals (unpaired_kernels.hip, mirp_unpaired.cpp): the coded windows, offsets, intervals, binned order and records of
+    // one pass, and the wave-private slabs of the windows too long for LDS; with targets -u the records per key of a pass (tg_upe)
+    DevBuf up_codes, up_offs, up_lo, up_hi, up_order, up_recs, up_slab, tg_upe;
+    long long up_cap = 0;             // windows per pass of mirp_unpaired_batch; 0 = the default, 2^20 (mirp_set_unpaired_capacity)
+    long long up_stats[3] = {0, 0, 0};   // the last mirp_unpaired_batch: windows, passes, cells
+    int tg_up = 17, tg_down = 13;     // the flanks of targets -u (mirp_set_target_flanks)
     long long n_result = 0;          // records of the last mirp_predict (p_res / p_text), what mirp_gather_loci sends
     bool have_result = false;
 };
@@ -255,6 +261,17 @@ int mirp_device_ensemble_fold(mirp_ctx* c, const unsigned char* d_codes, const E
 int mirp_device_ensemble_reduce(mirp_ctx* c, const EnJob* d_jobs, int n_jobs, double* d_slab, const int* d_mfe, MirpEnsembleRec* d_recs, char* d_texts);
 int mirp_device_ensemble_bpp(mirp_ctx* c, const EnJob* d_jobs, int n_jobs, const double* d_slab, double cutoff, int* d_row_cnt, const long long* d_row_at,
                              MirpBpp* d_out);
+// unpaired_kernels.hip: Z and Z_open of DESIGN.md §24, one wave per window of at most MIRP_UNPAIRED_MAX nt.  batch: window w = the codes (N A C G U =
+// 0..4) at d_codes + d_offs[w] .. d_offs[w + 1] with the 1-based interval d_lo[w] .. d_hi[w]; the launch folds the n windows d_order[0 .. n), none
+// longer than n_max, into d_recs[w].  mirp_unpaired_class(len): the n_max of the launch a window of that length belongs to.  sites: the sorted keys
+// of a pass of the target search, as mirp_device_duplex_sites reads them; the window is the site's interval with `up` / `down` more bases towards
+// the 5' / 3' end of the target strand, clipped to the contig; longest: the longest interval among the keys (at most 33); d_milli[key] = upe x 1000 rounded to nearest; a key that -k cuts is not folded and gets 0.
+#define MIRP_UNPAIRED_MAX 128
+int mirp_unpaired_class(int len);
+int mirp_device_unpaired_batch(mirp_ctx* c, const unsigned char* d_codes, const long long* d_offs, const int* d_lo, const int* d_hi, const int* d_order,
+                               long long n, int n_max, MirpUnpairedRec* d_recs);
+int mirp_device_unpaired_sites(mirp_ctx* c, const DxTargets& T, bool bulge, const unsigned long long* d_keys, long long n, long long max_sites,
+                               const unsigned long long* d_emitted, int longest, int up, int down, int* d_milli);
 int mirp_device_mask_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long* n_io, MirpAln* d_segs, MirpAln* d_segtmp, const int* d_owner, const int* d_seg_span,
                           long long* nseg_io,
                           const long long* d_rfirst, const int* d_rstart, const int* d_remax);

@@ -127,7 +127,9 @@ extern "C" int mirp_target_scan(mirp_ctx* c, const char* mirna_path, const char*
                                 const char* out_path, int64_t stats[6], double seconds[5]) {
     if (!c) return -1;
     if (!mirna_path || !target_paths || n_targets < 1 || !o || !out_path) return fail(c, -1, "mirp_target_scan: bad argument");
-    if (o->max_half_score < 0 || o->max_half_score > 16 || o->max_sites < 0 || (o->energy != 0 && o->energy != 1)) return fail(c, -1, "mirp_target_scan: bad options");
+    if (o->max_half_score < 0 || o->max_half_score > 16 || o->max_sites < 0 || (o->energy != 0 && o->energy != 1) ||
+        (o->accessibility != 0 && o->accessibility != 1))
+        return fail(c, -1, "mirp_target_scan: bad options");
     HIPCHK(c, hipSetDevice(c->device));
     double sec[5] = {0, 0, 0, 0, 0};
     double t = mirp::now();
@@ -144,7 +146,7 @@ extern "C" int mirp_target_scan(mirp_ctx* c, const char* mirna_path, const char*
 
     auto sink = [&](const char* p, size_t len) -> int { return out.write(p, len) ? 0 : fail(c, -8, std::string("cannot write ") + out_path); };
     const std::string head = std::string("miRNA\ttarget\tstart\tend\tstrand\tscore\tmismatches\tgu\tmirna_5to3\tpairs\ttarget_3to5") + (o->bulge ? "\tbulge" : "") +
-                             (o->energy ? "\tmfe\tmfe_perfect\tmfe_ratio\tduplex\n" : "\n");
+                             (o->energy ? "\tmfe\tmfe_perfect\tmfe_ratio\tduplex" : "") + (o->accessibility ? "\tupe\n" : "\n");
     int rc = sink(head.data(), head.size());
     long long st2[2] = {0, 0};
     double dsec[4] = {0, 0, 0, 0};

@@ -25,6 +25,7 @@
 // mloc << 45 | half << 40 | start << 8 | strand << 7 | kind << 5 | P, again in output order, and order, cut and emit run as their <true> instances.
 // With --energy the sorted keys of a pass are folded (duplex_kernels.hip) before the cut measures the lines, and every line gains
 // the columns mfe, mfe_perfect, mfe_ratio and duplex; without it TgText's energy pointers are null and the lines are as before.
+// With --accessibility the windows of the sorted keys are folded as well (unpaired_kernels.hip) and every line gains the column upe.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
@@ -53,6 +54,8 @@ struct TgText {
     const unsigned* amb;
     const int* e_mfe; const unsigned long long* e_ma; const unsigned long long* e_mb;
     const int* e_perf;
+    // --accessibility, else null: upe x 1000, rounded, of every sorted key of the pass (unpaired_kernels.hip)
+    const int* upe;
 };
 
 // the four last columns of an --energy line: mfe, mfe_perfect, mfe_ratio (half up to three decimals; NA when the perfect duplex is unbound) and the
@@ -84,6 +87,18 @@ __device__ void tg_energy_cols(TextOut<WRITE>& o, const TgText& T, long long idx
     for (int i = 0; i < L; i++) o.ch((ma >> i) & 1 ? '(' : '.');
     o.ch('&');
     for (int j = 0; j < nb; j++) o.ch((mb >> j) & 1 ? ')' : '.');
+}
+
+// the last column of an --accessibility line: upe in kcal/mol to three decimals
+template <bool WRITE>
+__device__ void tg_upe_col(TextOut<WRITE>& o, const TgText& T, long long idx) {
+    const int v = T.upe[idx];
+    o.ch('\t');
+    o.num((unsigned long long)(v / 1000));
+    o.ch('.');
+    o.ch((char)('0' + v / 100 % 10));
+    o.ch((char)('0' + v / 10 % 10));
+    o.ch((char)('0' + v % 10));
 }
 
 // pair class of miRNA code mc (0..3 A C G U, 4 unknown) with target-strand base y (0..3 A C G U): 0 Watson-Crick, 1 G:U, 2 mismatch
@@ -145,6 +160,7 @@ __device__ long long tg_line(const TgText& T, unsigned long long key, long long 
         o.ch(RNA[strand ? 3u - b : b]);
     }
     if (T.e_mfe) tg_energy_cols(o, T, idx, mloc, L, L + (g > T.cstart[a]) + (g + L < T.cstart[a + 1]));
+    if (T.upe) tg_upe_col(o, T, idx);
     o.ch('\n');
     return o.n;
 }
@@ -219,6 +235,7 @@ __device__ long long tg_bulge_line(const TgText& T, unsigned long long key, long
         const int len = L + kind - 1;
         tg_energy_cols(o, T, idx, mloc, L, len + (g > T.cstart[a]) + (g + len < T.cstart[a + 1]));
     }
+    if (T.upe) tg_upe_col(o, T, idx);
     o.ch('\n');
     return o.n;
 }
@@ -342,6 +359,14 @@ struct TgRun {
             if (int rc = mirp_device_duplex_sites(c, D, bulge, (const unsigned long long*)d_keys, n, (long long)o->max_sites,
                                                   (const unsigned long long*)c->tg_emitted.p, (int*)c->tg_emfe.p, (unsigned long long*)c->tg_ema.p,
                                                   (unsigned long long*)c->tg_emb.p))
+                return rc;
+        }
+        if (o->accessibility) {                                // likewise the windows of the kept keys: the width of `upe` is part of a line's length
+            const DxTargets D{T.pk, (const unsigned*)c->tg_amb.p, T.mcodes, T.mi, T.cstart, T.n_contigs, mbase};
+            int longest = 0;                                   // the group's longest interval sizes the launch's tables
+            for (int m = 0; m < group_n; m++) longest = std::max(longest, (int)(*mi)[(size_t)(mbase + m)].L + (bulge ? 1 : 0));
+            if (int rc = mirp_device_unpaired_sites(c, D, bulge, (const unsigned long long*)d_keys, n, (long long)o->max_sites,
+                                                    (const unsigned long long*)c->tg_emitted.p, longest, c->tg_up, c->tg_down, (int*)c->tg_upe.p))
                 return rc;
         }
         hipLaunchKernelGGL(bulge ? tg_size_kernel<true> : tg_size_kernel<false>, dim3(tg_grid(n)), dim3(256), 0, st, T, (const unsigned long long*)d_keys, n,
@@ -477,6 +502,7 @@ int mirp_device_target_scan(mirp_ctx* c, const unsigned long long* pk, const uns
     if (o.energy && (c->tg_emfe.ensure(4 * (size_t)cap) || c->tg_ema.ensure(8 * (size_t)cap) || c->tg_emb.ensure(8 * (size_t)cap) ||
                      c->tg_perf.ensure(4 * (size_t)TG_GROUP)))
         return fail(c, -6, "device allocation failed (targets: energies)");
+    if (o.accessibility && c->tg_upe.ensure(4 * (size_t)cap)) return fail(c, -6, "device allocation failed (targets: accessibility)");
     TgRun run;
     if (int rc = tg_upload_packed(c, pk, amb, cst, total, cstart, &run.R)) return rc;
     if (!tnames.empty()) HIPCHK(c, hipMemcpyAsync(c->tg_names.p, tnames.data(), tnames.size(), hipMemcpyHostToDevice, st));
@@ -498,6 +524,7 @@ int mirp_device_target_scan(mirp_ctx* c, const unsigned long long* pk, const uns
         run.T.e_mb = (const unsigned long long*)c->tg_emb.p;
         run.T.e_perf = (const int*)c->tg_perf.p;
     }
+    if (o.accessibility) run.T.upe = (const int*)c->tg_upe.p;
     run.o = &o;
     run.mi = &mi;
     run.sink = &sink;

@@ -30,6 +30,11 @@ HELP = """python -m mir_prefer_amd.targets [options] <mirna.fa> <target.fa> [<ta
     complement; `mfe_ratio`, mfe / mfe_perfect to three decimals (NA when mfe_perfect is
     0); and `duplex`, the structure: the miRNA as ( and ., then &, then the target strand
     5'->3' as ) and .
+    With -u, every line ends with a last column `upe`: the energy (kcal/mol, three
+    decimals) that opens the site inside its window of the target strand, i.e. -kT ln of
+    the probability that no base of the site is paired when the window folds alone. The
+    window is the site with --flank-up bases towards the 5' end of the target strand and
+    --flank-down towards its 3' end, clipped to the transcript. 0.000 = already open.
 
     Example:
     python -m mir_prefer_amd.targets -s 3 -c out/prefix_miRNA.mature.fa cdna.fa
@@ -43,6 +48,9 @@ def make_parser():
     parser.add_option("-c", "--cleavage-site", action="store_true", help="Reject sites with a mismatch (not a G:U) at miRNA position 10 or 11.")
     parser.add_option("-g", "--bulge", action="store_true", help="Also write sites with exactly one unpaired nucleotide; adds the column `bulge`.")
     parser.add_option("-e", "--energy", action="store_true", help="Fold every site's miRNA:target duplex; adds the columns `mfe mfe_perfect mfe_ratio duplex`.")
+    parser.add_option("-u", "--accessibility", action="store_true", help="Fold every site's window of the target; adds the column `upe`.")
+    parser.add_option("--flank-up", type=int, default=None, help="With -u: bases of the window 5' of the site on the target strand. Default 17.")
+    parser.add_option("--flank-down", type=int, default=None, help="With -u: bases of the window 3' of the site on the target strand. Default 13.")
     parser.add_option("-k", "--max-sites", type=int, default=0, help="Write the first N sites per miRNA, in output order; 0 = all (default).")
     parser.add_option("-o", "--output", help="Output file. Default <mirna.fa>.targets.tsv.")
     parser.add_option("--device", type=int, default=0, help="GPU device index. Default is 0.")
@@ -76,6 +84,12 @@ def parse_args(argv):
         parser.error("Option --device must be at least 0.")
     if options.output == "":
         parser.error("Option -o needs a file name.")
+    if not options.accessibility and (options.flank_up is not None or options.flank_down is not None):
+        parser.error("Options --flank-up and --flank-down need -u.")
+    options.flank_up = 17 if options.flank_up is None else options.flank_up
+    options.flank_down = 13 if options.flank_down is None else options.flank_down
+    if options.flank_up < 0 or options.flank_down < 0 or options.flank_up + options.flank_down > 95:
+        parser.error("Options --flank-up and --flank-down must be at least 0 and at most 95 together.")
     return options, args[0], args[1:], half, options.output or output_name(args[0])
 
 
@@ -103,7 +117,8 @@ def main(argv=None):
         return _fail("the target search runs on the GPU and none is usable (%s); there is no CPU path." % e)
     try:
         res = ctx.target_scan(mirna, targets, out, max_half_score=half, both_strands=bool(options.both_strands),
-                              cleavage_site=bool(options.cleavage_site), max_sites=options.max_sites, bulge=bool(options.bulge), energy=bool(options.energy))
+                              cleavage_site=bool(options.cleavage_site), max_sites=options.max_sites, bulge=bool(options.bulge), energy=bool(options.energy),
+                              accessibility=bool(options.accessibility), flanks=(options.flank_up, options.flank_down))
     except (OSError, capi.MirpError) as e:
         return _fail(str(e))
     finally:
