@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#include <tuple>
 #include <cstdio>
 #include "fold_epilogue.h"
 #include "fold185_device.h"
@@ -62,8 +63,15 @@ __device__ inline void xt_fill(TAB& T, const FoldParams* __restrict__ P, int tid
         T.XB[x] = (unsigned char)(xb + P->xb_bias); T.X1[x] = (unsigned char)(x1 + P->x1_bias);
     }
 }
-#define CSTR 354            // c-ring row stride in shorts (177 dwords: odd, spreads LDS banks)
-static_assert(CSTR == MIRP_RING_CSTR, "FoldParams::ring_rowoff is built for this row stride");
+// c-ring row stride in shorts (189 dwords: odd, spreads LDS banks; even in shorts, see the aligned-dword reads below).  A window has columns 1 .. LCAP - 2;
+// the stride is longer than that because the candidate-pool pass of the default model runs the first diagonals (6 .. 35, not every loop size admissible
+// yet) on the unchecked interior-loop code: a candidate whose inner pair would lie on a diagonal < 4 reads an INF ring row instead of being skipped
+// (see the ring initialisation in fold_lds_kernel.hip).  On those diagonals a lane's column i reaches n - 6, and its reads reach column
+// i + 1 + MAXLOOP + 1 <= n + 26, which at the former stride of 354 fell into the head of the NEXT row for n >= 328 -- for the row of "diagonal 3" that is
+// row 4, whose columns 1 .. 23 hold finite cells of diagonal 4 until diagonal 36 overwrites them: false candidates.  With 378 every such read stays in
+// its own row, in columns that no diagonal ever writes and the initialisation sets to INF (static_assert below).  In the steady state p <= j - 5 keeps
+// the reads inside the window's columns at either stride.
+#define CSTR MIRP_RING_CSTR      // 378 (fold_params.h; the host builds FoldParams::ring_rowoff from the same constant)
 #define MIRP_CK(d) ((d) % 3)
 #define CRING_ROWS 33       // diagonal dd lives in row dd & 31; row 32 mirrors row 0, so "the row after row r" is always r + 1 (phase A1 mixes lanes of two diagonals)
 
@@ -155,13 +163,18 @@ __host__ __device__ inline int arch_rowblk_off(int b, int n, int dcap) {
 }
 
 struct LdsLayout {
-    unsigned fml, aux, S, seq, pax, qb2, list, tabs, misc, total, fml_bytes, code4;
+    unsigned fml, aux, S, seq, pax, qb2, list, tabs, misc, total, fml_bytes, code4, spec;
 };
-#define CODE_STR 368          // bytes per shifted copy of a pair-code array (LCAP + 8 codes + the last job's over-read of 3), a multiple of 16
+// bytes per shifted copy of a pair-code array, a multiple of 16.  The batched jobs (a1_codes4) read the codes of a whole chunk as dwords: the N <= A1_CHUNK
+// codes from index A on, rounded up to four.  In the steady state A + N - 1 <= n; on the first diagonals, which run the same code (see CSTR), a job
+// at i = n - 6 or j = 7 starts at A = n - 5 + LO with LO + N - 1 <= MAXLOOP, so the last byte read is code n - 5 + MAXLOOP + 3 at most.  Codes past n
+// are garbage that only meets INF ring entries; the reads themselves must stay inside the 8 x CODE_STR block, also out of the last copy:
+#define CODE_STR 384
+static_assert(CODE_STR % 16 == 0 && (LCAP - 2) - 5 + MAXLOOP + 3 < CODE_STR, "pair-code reads of the first diagonals stay inside their copy");
 __host__ __device__ constexpr unsigned lds_al(unsigned x) { return (x + 15u) & ~15u; }
 // SPARSE: the multiloop splits run over a pool of split candidates (see "sparse splits" in fold_lds_kernel.hip): a third mdec buffer, and the pool
 // lives behind the window's fML triangle inside the fml region, which then takes everything the other arrays leave of the 160 KB.
-#define FML_REGION_BYTES (lds_al((tri_off(LDMAX + 1, LCAP) + 2) * 2))      // fML triangle, d = 4..LDMAX at n = LCAP
+#define FML_REGION_BYTES (lds_al((tri_off(LDMAX + 1, LCAP - 2) + 2) * 2))      // fML triangle, d = 4..LDMAX at the longest window the kernel takes, n = LCAP - 2 (tri_off grows with n)
 #define POOL_MIN_CAP 1024    // a window whose length leaves room for fewer candidates goes to the dense kernel right away
 // TWO (default model, SPARSE): two workgroups share a CU, so a window has 80 KB.  Its fML triangle is not in LDS at all: phase B keeps the last two
 // diagonals in a ring (FRING_STR shorts each) at the head of the fml region and writes every cell straight to the window's archive slab, from where
@@ -186,6 +199,9 @@ __host__ __device__ constexpr LdsLayout lds_layout() {
     L.list = o; o += lds_al(3 * LSEG * 4);      // 32-bit entries (see `list` in the kernel)
     L.tabs = o; o += lds_al((unsigned)sizeof(LdsTables));
     L.misc = o; o += lds_al((48 + ARCH_RB + ((SPARSE && MODEL) ? 48 : 0)) * 4);      // (vienna-1.8.5 candidate pass: + the 4 x 11-word bitmap of pooled pairs)
+    // two windows per CU: the special-hairpin energies have a region of their own (the other layouts lend them ring rows 29 - 31, which this one
+    // reads as INF rows on the first diagonals): [3][CSTR] shorts, 354 pool entries' worth
+    if (TWO) { L.spec = o; o += lds_al(3 * CSTR * 2); }
     if (SPARSE) { L.fml = o; L.fml_bytes = (TWO ? LDS_TWO_BYTES : 160u * 1024u) - o; o += L.fml_bytes; }
     L.total = o;
     return L;
@@ -226,6 +242,10 @@ static_assert(CSTR % 2 == 0, "the aligned-dword ring reads need dword-aligned ri
 // of ring row <= 32 (the mirror row, CRING_ROWS), so the farthest read lands at most a few entries into the DML ring that follows the c ring in
 // the aux region (lds_layout: at least 3 DML rows of LCAP shorts) -- never outside the aux allocation.
 static_assert((CRING_ROWS - 1) * CSTR + (LCAP - 2) + 1 + MAXLOOP + 1 < CRING_ROWS * CSTR + 3 * LCAP, "the ring over-read stays inside the aux region");
+// First diagonals on the unchecked code (d >= 6, so i <= n - 6 <= LCAP - 8): no read of a lane leaves its ring row (see CSTR).
+#ifndef MIRP_RAMP_OLD_STRIDE      // (a VARIANT build at the old stride shows that tests/test_fold_rampup_gpu.py sees the fault)
+static_assert((LCAP - 2) - 6 + 1 + MAXLOOP + 1 < CSTR, "ramp-up diagonals: a lane's ring reads stay inside their row");
+#endif
 
 // generic loops (n1, n2 >= 2) of size U: one contiguous run of ring row r0 - U.  The reads stay 16-bit on purpose (volatile keeps the
 // compiler from fusing neighbours into b64/b128 reads): a lane's run starts at an arbitrary 2-byte boundary, and a wide DS read off its
@@ -277,10 +297,50 @@ __device__ __forceinline__ unsigned a1_key(unsigned b, int adj) {
 // at the lane's own (2-byte) boundary: they cover the wing from the aligned dword below it -- an entry more at the inner end lands on a centre candidate,
 // whose own key is smaller than the wing key of the same entry, at the outer ends the lane's parity masks (A1::w_lo / w_hie / w_hio) turn the 1 x n / bulge
 // neighbours into INF -- and v_pk_min_u16 folds two entries per instruction as v_min3_u32 did.  A 16-bit read moves 2 of the 4 bytes a lane's bank slot
-// carries: 27 reads of row 30 become 17.  Only rows whose wings hold three entries or more (U >= 14), not on the first diagonals (CHECK).
+// carries: 27 reads of row 30 become 17.  Only rows whose wings hold three entries or more (U >= 14).  On the first diagonals (um < MAXLOOP) of an instantiation
+// that runs them unchecked, a row U <= um is complete -- all its inner cells lie on a real diagonal -- and a row U > um is INF throughout (ring initialisation,
+// fold_lds_kernel.hip), so the same reads hold there; CHECK = the 16-bit form with the admissibility test, for the instantiations that keep it.
+// The scalars of one winged row (rows with wings of three entries or more, see a1_gen_row_w): ring-row offset, wing key, the centre's keys.  None of
+// them depends on data, but read where the arithmetic needs them each sat in front of an `s_waitcnt lgkmcnt(0)` of its own -- the counter LDS reads share,
+// so the wing key's wait in the middle of a row also drained the row's reads, and the next row's reads could not be issued before its offset had come
+// back: three exposed scalar round trips per row.  A job (a1_generic_w) now loads the scalars of ALL its rows first, behind one wait (a1_rows_pin: an
+// ordering point that needs them in SGPRs), and the rows run on LDS reads alone.  At most 7 SGPRs per row, four rows per job.
+#ifndef MIRP_A1_HOIST
+#define MIRP_A1_HOIST 1      // 0: a timing build without the hoist
+#endif
+template <int WD, int U>
+struct A1RowK {
+    static constexpr int nL = (U - WD) / 2, nR = (U + WD + 1) / 2;
+    static constexpr bool kWinged = nL >= 4;
+    static constexpr int NC = kWinged ? nR - nL - 1 : 1;      // centre candidates n1 = nL + 1 .. nR - 1
+    static_assert(NC <= 5, "a1_rows_pin takes five centre keys");
+    int ro;
+    unsigned kw, kc[NC];
+};
+template <bool ON, int WD, int U>
+__device__ __forceinline__ A1RowK<WD, U> a1_row_k(const A1& a) {
+    A1RowK<WD, U> k{};
+    if constexpr (ON && A1RowK<WD, U>::kWinged) {
+        k.ro = a.rowtab[U];
+        k.kw = a.P->gen_wing_key[U - 6];
+#pragma unroll
+        for (int c = 0; c < A1RowK<WD, U>::NC; c++) k.kc[c] = a.P->gen_key[U - 6][A1RowK<WD, U>::nL + 1 + c];
+    }
+    return k;
+}
+template <int WD, int U>
+__device__ __forceinline__ void a1_row_pin(A1RowK<WD, U>& k) {
+    if constexpr (A1RowK<WD, U>::kWinged) {
+        constexpr int NC = A1RowK<WD, U>::NC;
+        if constexpr (NC == 5) asm volatile("" : "+s"(k.ro), "+s"(k.kw), "+s"(k.kc[0]), "+s"(k.kc[1]), "+s"(k.kc[2]), "+s"(k.kc[3]), "+s"(k.kc[4]));
+        else if constexpr (NC == 4) asm volatile("" : "+s"(k.ro), "+s"(k.kw), "+s"(k.kc[0]), "+s"(k.kc[1]), "+s"(k.kc[2]), "+s"(k.kc[3]));
+        else asm volatile("" : "+s"(k.ro), "+s"(k.kw), "+s"(k.kc[0]));
+    }
+}
 template <bool CHECK, int WD, int U>
-__device__ __forceinline__ void a1_gen_row_w(const A1& a, const unsigned short* rb, unsigned& bg) {
+__device__ __forceinline__ void a1_gen_row_w(const A1& a, const unsigned short* rb, unsigned& bg, const A1RowK<WD, U>& rk) {
     constexpr int nL = (U - WD) / 2, nR = (U + WD + 1) / 2;      // last entry of the left wing, first of the right one
+    constexpr bool HOIST = !CHECK && MIRP_A1_HOIST != 0;
     if constexpr (!CHECK && nL < 4 && U >= MIRP_A1_SMALLPACK) {
         // short rows (wings of at most two entries): every entry out of a realigned register, the wing entries with the wing's key term
         lds_vu32 rq = (lds_vu32)(a.rba + a.rowtab[U]);
@@ -308,7 +368,7 @@ __device__ __forceinline__ void a1_gen_row_w(const A1& a, const unsigned short* 
     if constexpr (!CHECK && nL >= 4) {
         // the whole row as contiguous aligned dwords; the centre's entries come out of the same registers: v_alignbit by the lane's parity puts entries
         // (2 m, 2 m + 1) into one register, v_mad_u32_u16 takes either half (op_sel) times 1024 plus the candidate's scalar key term
-        lds_vu32 rq = (lds_vu32)(a.rba + a.rowtab[U]);
+        lds_vu32 rq = (lds_vu32)(a.rba + (HOIST ? rk.ro : a.rowtab[U]));
         constexpr int kL1 = (1 + nL) >> 1, kR0 = nR >> 1, kR1 = (U - 1) >> 1;
         constexpr int m0 = (nL + 1) >> 1, m1 = (nR - 1) >> 1;
         static_assert(m1 + 1 <= kR1, "the centre's realigned dwords lie inside the row's reads");
@@ -326,13 +386,14 @@ __device__ __forceinline__ void a1_gen_row_w(const A1& a, const unsigned short* 
         for (int k = kR0; k < kR1; k++) { __builtin_memcpy(&t, &dw[k], 4); mm = __builtin_elementwise_min(mm, t); }
         { const unsigned l = dw[kR1] | ((U & 1) ? a.w_hio : a.w_hie); __builtin_memcpy(&t, &l, 4); mm = __builtin_elementwise_min(mm, t); }
         const unsigned w0 = mm[0], w1 = mm[1], w = w0 < w1 ? w0 : w1;
-        { const unsigned k = (w << 10) + a.P->gen_wing_key[U - 6]; bg = k < bg ? k : bg; }
+        { const unsigned k = (w << 10) + (HOIST ? rk.kw : a.P->gen_wing_key[U - 6]); bg = k < bg ? k : bg; }
         const unsigned c1024 = 1024u;
 #pragma unroll
         for (int n1 = nL + 1; n1 < nR; n1++) {
             unsigned e;
-            if (n1 & 1) asm("v_mad_u32_u16 %0, %1, %2, %3 op_sel:[1,0,0,0]" : "=v"(e) : "v"(re[(n1 >> 1) - m0]), "v"(c1024), "s"(a.P->gen_key[U - 6][n1]));
-            else asm("v_mad_u32_u16 %0, %1, %2, %3" : "=v"(e) : "v"(re[(n1 >> 1) - m0]), "v"(c1024), "s"(a.P->gen_key[U - 6][n1]));
+            const unsigned kt = HOIST ? rk.kc[n1 - nL - 1] : a.P->gen_key[U - 6][n1];
+            if (n1 & 1) asm("v_mad_u32_u16 %0, %1, %2, %3 op_sel:[1,0,0,0]" : "=v"(e) : "v"(re[(n1 >> 1) - m0]), "v"(c1024), "s"(kt));
+            else asm("v_mad_u32_u16 %0, %1, %2, %3" : "=v"(e) : "v"(re[(n1 >> 1) - m0]), "v"(c1024), "s"(kt));
             bg = e < bg ? e : bg;
         }
     } else
@@ -379,7 +440,10 @@ __device__ __forceinline__ unsigned a1_generic_w(const A1& a0, int i, int j, int
         a.rba = rb - par;
         a.w_lo = par ? 0xffffu : 0u; a.w_hie = par ? 0u : 0xffff0000u; a.w_hio = par ? 0xffff0000u : 0xffffffffu; a.w_sh = par * 16u;
     }
-    (a1_gen_row_w<CHECK, WD, Us>(a, rb, bg), ...);
+    constexpr bool HOIST = !CHECK && MIRP_A1_HOIST != 0;
+    std::tuple<A1RowK<WD, Us>...> ks{a1_row_k<HOIST, WD, Us>(a)...};
+    if constexpr (HOIST) (a1_row_pin<WD, Us>(std::get<A1RowK<WD, Us>>(ks)), ...);
+    (a1_gen_row_w<CHECK, WD, Us>(a, rb, bg, std::get<A1RowK<WD, Us>>(ks)), ...);
     return a1_key(bg, -32768 + mm_outer);
 }
 

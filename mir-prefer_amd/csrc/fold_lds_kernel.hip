@@ -90,6 +90,7 @@ __global__ void __launch_bounds__(NT, 4) fold_lds_kernel(
     const int tau_s = __builtin_amdgcn_readfirstlane(P->TerminalAU);
     constexpr int GEN_WD = 5;                // default model: |n1 - n2| from which the asymmetry term of a generic loop is saturated (checked on the host: FoldParams::gen_wing_d)
     long long tA = 0, tB = 0, tS = 0, tE = 0, t0 = 0;   // diagnostic phase clocks (thread 0 only, dbg_cycles != nullptr)
+    long long tR = 0, nR = 0, nB = 0;                   // of tB: the intervals whose interior loops are on the ramp-up (um < MAXLOOP), and the interval counts
     long long wB = 0, wA1 = 0, wA2 = 0, wW = 0, wt = 0; // per-wave: phase B, interior loops, multiloop splits, barrier wait (lane 0 of each wave)
     unsigned short* fml = (unsigned short*)(smem + LY.fml);   // biased uint16 (see FML_BIAS)
     unsigned short* cring = (unsigned short*)(smem + LY.aux);       // [32][CSTR] G0 + 32768 as uint16, 65535 = INF
@@ -102,9 +103,17 @@ __global__ void __launch_bounds__(NT, 4) fold_lds_kernel(
     pax_t* pax = (pax_t*)(smem + LY.pax);
     unsigned char* qbr = smem + LY.qb2;
     unsigned char* code4 = SPARSE ? smem + LY.code4 : nullptr;      // [2][4][CODE_STR]: shifted byte copies of the q codes, then of the p codes (a1_codes4)
+    // Two windows per CU: the first interior-loop diagonals (6 .. 35: um < MAXLOOP, not every loop size admissible yet) run the unchecked steady-state code.
+    // A candidate with n1 + n2 > um reads the ring row of a diagonal < 4, which the window start has set to INF, and loses every minimum like any other
+    // INF entry: no compare, no branch.  The other instantiations keep the checked forms (MIRP_RAMP_CHECKED: a timing build of this one that does, too).
+#ifdef MIRP_RAMP_CHECKED
+    constexpr bool RAMPF = false;
+#else
+    constexpr bool RAMPF = TWO;
+#endif
     // special-hairpin energies by start position (tri-, tetra-, hexaloops): only read on diagonals 4, 5 and 7, so they borrow the ring rows
-    // of diagonals 29-31, which are first written on diagonal 29
-    short* spec = (short*)(cring + 29 * CSTR);
+    // of diagonals 29-31, which are first written on diagonal 29 -- except where the first diagonals read those rows as INF (RAMPF): a region of their own
+    short* spec = RAMPF ? (short*)(smem + LY.spec) : (short*)(cring + 29 * CSTR);
     // [3][LSEG]: paired cells of diagonal d in buffer d % 3 (compact, unordered).  Default model: i | type << 9 | mmo << 12 | mm1 << 22, mmo / mm1 = the cell's
     // outer-pair terms mismatchI / mismatch1nI [type][S[i+1]][S[j-1]] as 10-bit signed values (ENT_OUTER below): phase B, which has the time, looks them up
     // when it builds the entry, and a block's prologue in phase A1 goes from the entry straight to arithmetic -- no dependent table read in front
@@ -217,6 +226,17 @@ __global__ void __launch_bounds__(NT, 4) fold_lds_kernel(
             S[x] = ch == 'A' ? 1 : ch == 'C' ? 2 : ch == 'G' ? 3 : ch == 'U' ? 4 : 0;
         }
         for (int x = tid; x < DMLR * LCAP; x += NT) dmlring[x] = (short)I16_INF;
+        // RAMPF: all CRING_ROWS rows of the c ring to INF (as dwords), once per window.  During interval d < 36 the unchecked interior loops read, for a loop size
+        // U > um = d - 6, the row (d - 2 - U) & 31 of a diagonal x = d - 2 - U in [d - 32, 3] that does not exist.  That row is the one diagonal x + 32 in
+        // [d, 35] of THIS window will use, and phase B of the interval writes diagonal d - 1: the row has not been written since this initialisation, so it
+        // is INF in every column (the columns behind n included: CSTR).  Row 32 mirrors row 0 for the lanes that go ahead (not before diagonal 36), and a
+        // window that ends below diagonal 35 leaves finite rows behind -- hence every row, every window.  Rows of existing diagonals (U <= um) are complete:
+        // all their candidates' inner cells (p, q), q - p = x >= 4, p >= i + 1, q <= j - 1, were written by phase B of diagonal x.
+        if constexpr (RAMPF) {
+            static_assert((CRING_ROWS * CSTR) % 2 == 0, "ring initialisation by dwords");
+            unsigned* cr32 = reinterpret_cast<unsigned*>(cring);
+            for (int x = tid; x < CRING_ROWS * CSTR / 2; x += NT) cr32[x] = 0xffffffffu;
+        }
         for (int x = tid; x < NACC * LCAP; x += NT) acc[x] = x >= 3 * LCAP ? INF : (int)KEY_NONE;   // ckey x 3 | mdec x 2 (3)
         if (tid == 0) {
             misc[1] = 0; misc[2] = 0; misc[3] = 0;
@@ -592,7 +612,7 @@ __global__ void __launch_bounds__(NT, 4) fold_lds_kernel(
 #define MIRP_ROWS5 21, 18, 11
 #define MIRP_ROWS6 20, 16, 13
 #define MIRP_ROWS7 19, 15, 14, 6
-                            if (a.um >= MAXLOOP) { MIRP_GEN(false) } else { MIRP_GEN(true) }
+                            if (RAMPF || a.um >= MAXLOOP) { MIRP_GEN(false) } else { MIRP_GEN(true) }
 #undef MIRP_A1G
 #undef MIRP_A1WD
 #undef MIRP_ROWS4
@@ -606,7 +626,7 @@ __global__ void __launch_bounds__(NT, 4) fold_lds_kernel(
 #define MIRP_ROWS5 21, 18, 11, 8
 #define MIRP_ROWS6 20, 16, 13, 9
 #define MIRP_ROWS7 19, 15, 14, 10, 6
-                            if (a.um >= MAXLOOP) { MIRP_GEN(false) } else { MIRP_GEN(true) }
+                            if (RAMPF || a.um >= MAXLOOP) { MIRP_GEN(false) } else { MIRP_GEN(true) }
 #undef MIRP_A1G
 #undef MIRP_A1WD
 #undef MIRP_ROWS4
@@ -623,7 +643,7 @@ __global__ void __launch_bounds__(NT, 4) fold_lds_kernel(
 #undef MIRP_GEN
                     } else if (role < 14) {
                         unsigned bb = KEY_INF, bi = KEY_INF;
-                        if (a.um >= MAXLOOP) {
+                        if (RAMPF || a.um >= MAXLOOP) {
                             switch (role) {
                             case 8: a1_b0f<2, 18>(a, i, j, bb); break;
                             case 9: a1_b0f<19, 30>(a, i, j, bb); a1_b1f<2, 6>(a, i, j, bb); break;
@@ -645,7 +665,7 @@ __global__ void __launch_bounds__(NT, 4) fold_lds_kernel(
                         const unsigned rb = a1_key(bb, -32768 - OTH_BIAS + au1);
                         const unsigned ri = a1_key(bi, -32768 - OTH_BIAS + mm1);
                         res = rb < ri ? rb : ri;
-                    } else if (a.um >= MAXLOOP) {
+                    } else if (RAMPF || a.um >= MAXLOOP) {
                         res = role == 14 ? a1_small14f(a, i, j, type, ahead) : a1_small15f(a, i, j, type);
                     } else {
                         const int si1 = S[i + 1], sj1 = S[j - 1];
@@ -670,7 +690,7 @@ __global__ void __launch_bounds__(NT, 4) fold_lds_kernel(
                             unsigned rx = KEY_NONE;
 #define MIRP_A1G a1_generic_w
 #define MIRP_A1WD , GEN_WD
-                            if (a.um >= MAXLOOP) { MIRP_XGEN(false) } else { MIRP_XGEN(true) }
+                            if (RAMPF || a.um >= MAXLOOP) { MIRP_XGEN(false) } else { MIRP_XGEN(true) }
 #undef MIRP_A1G
 #undef MIRP_A1WD
                             res = rx < res ? rx : res;
@@ -1015,7 +1035,13 @@ __global__ void __launch_bounds__(NT, 4) fold_lds_kernel(
             if (dbg_cycles && lane == 0) { const long long t = clock64(); wA2 += t - wt; wt = t; }
             __syncthreads();
             if (dbg_cycles && lane == 0) { const long long t = clock64(); wW += t - wt; wt = t; }
-            if (dbg_cycles && tid == 0 && !light) { long long t = clock64(); tB += t - t0; t0 = t; }
+            if (dbg_cycles && tid == 0 && !light) {
+                long long t = clock64();
+                tB += t - t0; nB++;
+                // interval d runs the interior loops of diagonal d + 1: on the ramp-up while um = d + 1 - 2 - (TURN + 1) < MAXLOOP
+                if (d + 1 >= 6 && d + 1 <= D && d + 1 - 2 - (TURN + 1) < MAXLOOP) { tR += t - t0; nR++; }
+                t0 = t;
+            }
         }
         const int overflow = misc[1];
         __syncthreads();
@@ -1066,6 +1092,8 @@ __global__ void __launch_bounds__(NT, 4) fold_lds_kernel(
     if (dbg_cycles && tid == 0) {
         atomicAdd((unsigned long long*)&dbg_cycles[0], (unsigned long long)tS); atomicAdd((unsigned long long*)&dbg_cycles[1], (unsigned long long)tA);
         atomicAdd((unsigned long long*)&dbg_cycles[2], (unsigned long long)tB); atomicAdd((unsigned long long*)&dbg_cycles[3], (unsigned long long)tE);
+        atomicAdd((unsigned long long*)&dbg_cycles[76], (unsigned long long)tR); atomicAdd((unsigned long long*)&dbg_cycles[77], (unsigned long long)nR);
+        atomicAdd((unsigned long long*)&dbg_cycles[78], (unsigned long long)nB);
     }
 }
 

@@ -7,7 +7,9 @@
 #define MIRP_TURN 3
 #define MIRP_MAXLOOP 30
 #define MIRP_INF 10000000
-#define MIRP_RING_CSTR 354        // row stride (shorts) of the fill kernel's c ring: CSTR of fold_lds_common.h (static_assert there)
+#ifndef MIRP_RING_CSTR
+#define MIRP_RING_CSTR 378        // row stride (shorts) of the fill kernel's c ring: CSTR of fold_lds_common.h (static_assert and the choice of the value there)
+#endif
 #define MIRP_HP_MAX 3104          // hairpin size table (log-extrapolated above 30 on the host)
 
 struct alignas(16) FoldParams {

@@ -405,7 +405,7 @@ int mirp_run_fold(mirp_ctx* c, const unsigned char* d_seqs, const long long* d_o
             if (FILE* f = std::fopen(dump, "wb")) { std::fwrite(h.data(), 2, h.size(), f); std::fclose(f); }
         }
         if (dbg_cycles) {
-            long long cyc[4 + 64 + 8];
+            long long cyc[4 + 64 + 8 + 3];
             HIPCHK(c, hipMemcpy(cyc, dbg_cycles, sizeof(cyc), hipMemcpyDeviceToHost));
             std::fprintf(stderr, "[mirp fold clocks] windows=%d setup=%lld fillA=%lld fillB=%lld writeout=%lld (sum over workgroups, s_memtime ticks)\n", n_work,
                          cyc[0], cyc[1], cyc[2], cyc[3]);
@@ -414,6 +414,8 @@ int mirp_run_fold(mirp_ctx* c, const unsigned char* d_seqs, const long long* d_o
                              cyc[7 + 4 * w]);
             for (int b = 0; b < 4; b++)
                 std::fprintf(stderr, "[mirp fold clocks] wave 9, diagonals with %d%s blocks: %lld, interior ticks %lld\n", b, b == 3 ? "+" : "", cyc[72 + b], cyc[68 + b]);
+            std::fprintf(stderr, "[mirp fold clocks] ramp-up intervals (interior loops with um < MAXLOOP): %lld of %lld intervals, %lld of fillB=%lld ticks (%.1f %%)\n", cyc[77], cyc[78],
+                         cyc[76], cyc[2], cyc[2] ? 100.0 * (double)cyc[76] / (double)cyc[2] : 0.0);
             mirp::fold_lds_epi_clocks_print();
         }
 #endif
