@@ -655,6 +655,37 @@ int mirp_unpaired_last_stats(mirp_ctx* ctx, int64_t stats[3]);
  * its 3' end (defaults 17 and 13).  Each >= 0, up + down <= 95 (a window never exceeds 33 + 95 = 128 nt); anything else is refused with -1. */
 int mirp_set_target_flanks(mirp_ctx* ctx, int32_t up, int32_t down);
 
+/* Gapped local alignment of query sequences (predicted precursors) with known sequences (miRBase hairpins), same sense: Gotoh's
+ * recurrences with +match / -mismatch per column and gap_open + g * gap_extend per gap of g bases; letters A C G U/T in either case, anything
+ * else mismatches everything.  match, mismatch 1..10, gap_open 0..20, gap_extend 1..10, min_score >= 1, max_lines >= 0 (0 = all). */
+typedef struct {
+    int32_t match, mismatch, gap_open, gap_extend, min_score, reserved;
+    int64_t max_lines;
+} MirpHairpinOpts;
+/* One hit: 0-based indices of the query and the known sequence in the call, the score, the aligned spans (1-based, inclusive) and the counts of
+ * the alignment's columns: `=`, `X`, runs of `I` or `D`, and `I` + `D` columns. */
+typedef struct {
+    int32_t query, known, score, q_start, q_end, k_start, k_end, matches, mismatches, gap_opens, gap_bases, reserved;
+} MirpHairpinHit;
+/* Rows of the query a lane of the scoring kernel holds in registers (a strip); for tests of the lengths around it. */
+#define MIRP_HAIRPIN_STRIP 16
+/* q_blob / q_off and k_blob / k_off as mirp_ensemble's seqs / offsets, every length 1..3000.  Refusals (-10 and the side and the 1-based record in
+ * mirp_last_error): an empty sequence, one longer than 3,000 nt, a byte >= 0x80, more than 2^24 known sequences; n_q = 0 or n_k = 0 is fine.
+ * Out (library-owned, mirp_free; NULL when there is no hit): *hits holds the *n_hits pairs with score >= min_score ordered by (query, score
+ * descending, known), at most max_lines per query; *ops one byte (`=` `X` `I` `D`; the query plays the read) per alignment column of every hit
+ * in forward order, hit h at (*ops)[(*ops_off)[h] .. (*ops_off)[h + 1]).  A pair's hit and ops are the same bytes whatever else is in the call
+ * and however it is split into passes.  Nothing resident changes. */
+int mirp_hairpin_align(mirp_ctx* ctx, const char* q_blob, const int64_t* q_off, int32_t n_q, const char* k_blob, const int64_t* k_off, int32_t n_k,
+                       const MirpHairpinOpts* opts, MirpHairpinHit** hits, int64_t* n_hits, char** ops, int64_t** ops_off);
+/* Device bytes one pass of mirp_hairpin_align holds: the scoring stage's result buffer (8 bytes per pair; passes over ranges of queries) and the
+ * traceback stage's direction matrices (1 byte per cell of q_end x k_end; passes over ranges of hits).  0 = the default, 2^31.  A query or a hit
+ * that alone is larger runs in a pass of its own.  Lowered only to test the split. */
+int mirp_set_hairpin_capacity(mirp_ctx* ctx, int64_t bytes);
+/* stats = {queries, known, pairs, cells (query length x known length, summed over the pairs), hits (before the max_lines cut), passes (scoring +
+ * traceback), scoring passes, traceback passes} of the last mirp_hairpin_align; seconds = {upload, scoring, filter + sort + cut, traceback,
+ * download}.  hits_per_query (optional, n_q entries of the last call): the hits of every query before the cut. */
+int mirp_hairpin_last_stats(mirp_ctx* ctx, int64_t stats[8], double seconds[5], int64_t* hits_per_query);
+
 #ifdef __cplusplus
 }
 #endif

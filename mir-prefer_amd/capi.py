@@ -77,6 +77,18 @@ ENSEMBLE_DTYPE = np.dtype([("len", "<i4"), ("mfe", "<i4"), ("efe", "<f8"), ("mfe
 BPP_DTYPE = np.dtype([("seq", "<i4"), ("i", "<i4"), ("j", "<i4"), ("reserved", "<i4"), ("p", "<f8")])
 ENSEMBLE_STATS = ("sequences", "passes", "cells")
 
+class HairpinOpts(C.Structure):
+    """MirpHairpinOpts of include/mirprefer.h."""
+    _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32), ("min_score", C.c_int32),
+                ("reserved", C.c_int32), ("max_lines", C.c_int64)]
+
+
+# MirpHairpinHit of include/mirprefer.h: one hit of mirp_hairpin_align, positions 1-based and inclusive
+HAIRPIN_DTYPE = np.dtype([(f, "<i4") for f in ("query", "known", "score", "q_start", "q_end", "k_start", "k_end", "matches", "mismatches", "gap_opens",
+                                               "gap_bases", "reserved")])
+HAIRPIN_STATS = ("queries", "known", "pairs", "cells", "hits", "passes", "score_passes", "trace_passes")
+HAIRPIN_STRIP = 16          # MIRP_HAIRPIN_STRIP of include/mirprefer.h: query rows a lane of the scoring kernel holds in registers
+
 # MirpUnpairedRec of include/mirprefer.h: one window of mirp_unpaired_batch, kcal/mol
 UNPAIRED_DTYPE = np.dtype([("efe", "<f8"), ("efe_open", "<f8"), ("upe", "<f8")])
 UNPAIRED_STATS = ("windows", "passes", "cells")
@@ -463,6 +475,13 @@ def load_library():
     lib.mirp_set_unpaired_capacity.restype = C.c_int
     lib.mirp_unpaired_last_stats.argtypes = [vp, i64p]
     lib.mirp_unpaired_last_stats.restype = C.c_int
+    lib.mirp_hairpin_align.argtypes = [vp, C.c_char_p, i64p, C.c_int32, C.c_char_p, i64p, C.c_int32, C.POINTER(HairpinOpts), C.POINTER(vp), i64p, C.POINTER(vp),
+                                       C.POINTER(vp)]
+    lib.mirp_hairpin_align.restype = C.c_int
+    lib.mirp_set_hairpin_capacity.argtypes = [vp, C.c_int64]
+    lib.mirp_set_hairpin_capacity.restype = C.c_int
+    lib.mirp_hairpin_last_stats.argtypes = [vp, i64p, C.POINTER(C.c_double), i64p]
+    lib.mirp_hairpin_last_stats.restype = C.c_int
     lib.mirp_set_target_flanks.argtypes = [vp, C.c_int32, C.c_int32]
     lib.mirp_set_target_flanks.restype = C.c_int
     lib.mirp_set_target_capacity.argtypes = [vp, C.c_int64]
@@ -492,6 +511,18 @@ def load_library():
     lib.mirp_gather_records.restype = C.c_int
     _lib = lib
     return lib
+
+
+def cigar_of(ops):
+    """ops (bytes, one of = X I D per alignment column) -> their run-length encoding, e.g. b"===II=" -> "3=2I1=" """
+    out, i = [], 0
+    while i < len(ops):
+        j = i
+        while j < len(ops) and ops[j] == ops[i]:
+            j += 1
+        out.append("%d%s" % (j - i, chr(ops[i])))
+        i = j
+    return "".join(out)
 
 
 def _copy_out(lib, ptr, dtype, count):
@@ -756,6 +787,48 @@ class Context:
         st = (C.c_int64 * 3)()
         self._check(self.lib.mirp_unpaired_last_stats(self.h, st), "mirp_unpaired_last_stats")
         return dict(zip(UNPAIRED_STATS, list(st)))
+
+    def hairpin_align(self, queries, known, match=2, mismatch=3, gap_open=5, gap_extend=2, min_score=60, max_lines=0, capacity=0):
+        """Gapped local alignment of every query with every known sequence (mirp_hairpin_align): queries, known (lists of str /
+        bytes, 1..3000 nt, A C G U/T in either case, anything else mismatches everything).  capacity: device bytes per pass (0 = the default),
+        lowered only in tests.  -> (HAIRPIN_DTYPE array of the hits with score >= min_score ordered by (query, score descending, known), at most
+        max_lines per query (0 = all), [str] of their cigars: runs of = X I D, the query playing the read)."""
+        blobs, offs = [], []
+        for seqs in (queries, known):
+            bs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+            o = np.zeros(len(bs) + 1, dtype=np.int64)
+            if bs:
+                o[1:] = np.cumsum([len(b) for b in bs])
+            blobs.append(b"".join(bs))
+            offs.append(o)
+        o = HairpinOpts()
+        o.match, o.mismatch, o.gap_open, o.gap_extend, o.min_score, o.reserved, o.max_lines = (int(match), int(mismatch), int(gap_open), int(gap_extend),
+                                                                                               int(min_score), 0, int(max_lines))
+        hits, n_hits, ops, ops_off = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p()
+        p64 = C.POINTER(C.c_int64)
+        self._check(self.lib.mirp_set_hairpin_capacity(self.h, int(capacity)), "mirp_set_hairpin_capacity")
+        try:
+            self._check(self.lib.mirp_hairpin_align(self.h, blobs[0], offs[0].ctypes.data_as(p64), len(queries), blobs[1], offs[1].ctypes.data_as(p64), len(known),
+                                                    C.byref(o), C.byref(hits), C.byref(n_hits), C.byref(ops), C.byref(ops_off)), "mirp_hairpin_align")
+        finally:
+            self.lib.mirp_set_hairpin_capacity(self.h, 0)
+        n = n_hits.value
+        if n == 0:
+            return np.zeros(0, dtype=HAIRPIN_DTYPE), []
+        at = _copy_out(self.lib, ops_off, np.int64, n + 1)
+        text = _copy_out(self.lib, ops, np.uint8, int(at[-1])).tobytes()
+        recs = _copy_out(self.lib, hits, HAIRPIN_DTYPE, n)
+        return recs, [cigar_of(text[int(a):int(b)]) for a, b in zip(at[:-1], at[1:])]
+
+    def hairpin_last_stats(self):
+        """{queries, known, pairs, cells, hits (before the max_lines cut), passes, score_passes, trace_passes, seconds, per_query} of the last
+        hairpin_align; seconds = {upload, scoring, filter + sort + cut, traceback, download}; per_query: the hits of every query before the cut."""
+        st = (C.c_int64 * 8)()
+        sec = (C.c_double * 5)()
+        self._check(self.lib.mirp_hairpin_last_stats(self.h, st, sec, None), "mirp_hairpin_last_stats")
+        per = np.zeros(st[0] + 1, dtype=np.int64)          # (st[0] = the queries of that call: what the library writes)
+        self._check(self.lib.mirp_hairpin_last_stats(self.h, st, sec, per.ctypes.data_as(C.POINTER(C.c_int64))), "mirp_hairpin_last_stats")
+        return dict(zip(HAIRPIN_STATS, list(st)), seconds=list(sec), per_query=per[:st[0]].tolist())
 
     def phase_scan(self, length, cycles, kmin, min_phased=3, min_depth=1):
         """Phased siRNA windows on this context's resident alignments (mirp_phase_scan).  kmin: the int32 table of the smallest

@@ -143,6 +143,15 @@ struct mirp_ctx {
     long long up_cap = 0;             // windows per pass of mirp_unpaired_batch; 0 = the default, 2^20 (mirp_set_unpaired_capacity)
     long long up_stats[3] = {0, 0, 0};   // the last mirp_unpaired_batch: windows, passes, cells
     int tg_up = 17, tg_down = 13;     // the flanks of targets -u (mirp_set_target_flanks)
+    // ---- gapped alignment with known hairpins (hairpin_kernels.hip, mirp_hairpin.cpp): the coded queries and known sequences of the call, the
+    // known sequences packed per wave, the boundary rows between strips, the results, keys and cut tables of one scoring pass, the hits, direction
+    // matrices and ops of one traceback pass
+    DevBuf hp_q, hp_qat, hp_qlen, hp_k, hp_kat, hp_kw, hp_waves, hp_korig, hp_carry, hp_res, hp_cnt, hp_small, hp_keys, hp_ktmp, hp_run, hp_out, hp_kept,
+        hp_hits, hp_jobs, hp_dir, hp_ops;
+    long long hp_cap = 0;             // bytes per pass of mirp_hairpin_align; 0 = the default, 2^31 (mirp_set_hairpin_capacity)
+    long long hp_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the last mirp_hairpin_align: queries, known, pairs, cells, hits, passes, scoring passes, traceback passes
+    double hp_sec[5] = {0, 0, 0, 0, 0};                 // upload, scoring, filter + sort + cut, traceback, download
+    std::vector<long long> hp_per_query;                // hits of every query of the last call, before the cut
     long long n_result = 0;          // records of the last mirp_predict (p_res / p_text), what mirp_gather_loci sends
     bool have_result = false;
 };
@@ -272,6 +281,17 @@ int mirp_device_unpaired_batch(mirp_ctx* c, const unsigned char* d_codes, const 
                                long long n, int n_max, MirpUnpairedRec* d_recs);
 int mirp_device_unpaired_sites(mirp_ctx* c, const DxTargets& T, bool bulge, const unsigned long long* d_keys, long long n, long long max_sites,
                                const unsigned long long* d_emitted, int longest, int up, int down, int* d_milli);
+// hairpin_kernels.hip: the gapped local alignment of DESIGN.md §25.  Codes: A C G U = 0..3; an unknown letter is 4 in a query and 5 in a known
+// sequence, so that it equals nothing.  Q: every query starts at a multiple of MIRP_HAIRPIN_STRIP in `codes` and is padded to one with 6; K: the
+// known sequences back to back.  Out: the hits in output order (after the max_lines cut), their ops in forward order and the ops' offsets
+// (hits + 1 entries); c->hp_per_query, c->hp_stats and c->hp_sec are filled.
+struct HpSeqs {
+    std::vector<unsigned char> codes;
+    std::vector<long long> at;
+    std::vector<int> len;
+};
+int mirp_device_hairpin(mirp_ctx* c, const HpSeqs& Q, const HpSeqs& K, const MirpHairpinOpts& o, std::vector<MirpHairpinHit>& hits, std::vector<char>& ops,
+                        std::vector<long long>& ops_off);
 int mirp_device_mask_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long* n_io, MirpAln* d_segs, MirpAln* d_segtmp, const int* d_owner, const int* d_seg_span,
                           long long* nseg_io,
                           const long long* d_rfirst, const int* d_rstart, const int* d_remax);
