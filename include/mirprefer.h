@@ -243,8 +243,19 @@ int mirp_set_fold_split_path(mirp_ctx* ctx, int32_t mode);
 /* Number of windows of the last fold call that the candidate-pool pass handed to the dense fill kernel (pool overflow or no room for a pool). */
 int64_t mirp_last_fold_dense(mirp_ctx* ctx);
 
-/* Device time of the kernels of the last mirp_fold, HIP events on the context's stream: ms[0] = fill kernel(s) (fold_lds_kernel: the
- * dynamic program), ms[1] = epilogue kernel(s) (exterior sweep, enumeration, backtracks), summed over the sub-batches of the main pass. */
+/* Fold overlap: a batch of the default model is folded in chunks of windows, the epilogue kernel of a chunk (exterior sweep, enumeration,
+ * backtracks: it waits on memory) on a second stream beside the fill kernel of the next chunk (it computes out of LDS).  chunk_windows = -1:
+ * automatic (default; batches of at least 8 rounds of the fill grid in 4 chunks, smaller ones serially), 0: off, the serial path, N > 0: chunks of
+ * N windows whatever the batch size.  Every output is identical either way.  vienna-1.8.5, mirp_set_fold_split_path(1), spans outside the
+ * LDS-resident kernels and a device whose resources leave no room for an epilogue workgroup beside the fill always take the serial path. */
+int mirp_set_fold_overlap(mirp_ctx* ctx, int32_t chunk_windows);
+/* Chunks the last fold call ran in (0: the serial path). */
+int mirp_last_fold_overlap_chunks(mirp_ctx* ctx);
+
+/* Device time of the kernels of the last mirp_fold, HIP events: two numbers whose sum is the device time of the fold's main pass.  Serial path:
+ * ms[0] = fill kernel(s) (fold_lds_kernel: the dynamic program), ms[1] = epilogue kernel(s) (exterior sweep, enumeration, backtracks), summed
+ * over the sub-batches.  With fold overlap: ms[0] = from the first fill's start to the last fill's end, dense passes included, ms[1] = the
+ * rest, i.e. the part of the epilogues that no fill covers. */
 int mirp_last_fold_kernel_ms(mirp_ctx* ctx, double ms[2]);
 /* Measures the two roofs of the fold's fill kernel on this GPU with its own geometry (one 1024-thread workgroup per CU): out[0] ds_read_b32 and
  * out[1] ds_read_u16 wave-instructions per second (conflict-free, reads in flight), out[2] packed 16-bit add+min and out[3] 32-bit shift-add+min

@@ -406,6 +406,10 @@ def load_library():
     lib.mirp_exchange_bytes.restype = C.c_int
     lib.mirp_set_fold_split_path.argtypes = [vp, C.c_int32]
     lib.mirp_set_fold_split_path.restype = C.c_int
+    lib.mirp_set_fold_overlap.argtypes = [vp, C.c_int32]
+    lib.mirp_set_fold_overlap.restype = C.c_int
+    lib.mirp_last_fold_overlap_chunks.argtypes = [vp]
+    lib.mirp_last_fold_overlap_chunks.restype = C.c_int
     lib.mirp_last_fold_dense.argtypes = [vp]
     lib.mirp_last_fold_dense.restype = C.c_int64
     lib.mirp_write_fold_text.argtypes = [vp, C.c_char_p, C.c_char_p]
@@ -1218,6 +1222,14 @@ class Context:
         """0: multiloop splits over split candidates (default), 1: the dense split loop for every window (same tables either way)."""
         self._check(self.lib.mirp_set_fold_split_path(self.h, int(mode)), "mirp_set_fold_split_path")
 
+    def set_fold_overlap(self, chunk_windows):
+        """-1: automatic (default), 0: off (serial path), N > 0: the epilogue of every chunk of N windows beside the fill of the next chunk."""
+        self._check(self.lib.mirp_set_fold_overlap(self.h, int(chunk_windows)), "mirp_set_fold_overlap")
+
+    def last_fold_overlap_chunks(self):
+        """Chunks the last fold ran in; 0: the serial path."""
+        return int(self.lib.mirp_last_fold_overlap_chunks(self.h))
+
     def last_fold_dense(self):
         return int(self.lib.mirp_last_fold_dense(self.h))
 
@@ -1353,7 +1365,7 @@ class Context:
         return a
 
     def last_fold_kernel_ms(self):
-        """(fill kernel ms, epilogue kernel ms) of the last fold(), HIP events on the context's stream."""
+        """(fill ms, epilogue ms) of the last fold(), HIP events; with fold overlap: (first fill's start to last fill's end, the exposed rest)."""
         ms = (C.c_double * 2)()
         self.lib.mirp_last_fold_kernel_ms(self.h, ms)
         return ms[0], ms[1]

@@ -176,11 +176,26 @@ __host__ __device__ constexpr unsigned lds_al(unsigned x) { return (x + 15u) & ~
 // lives behind the window's fML triangle inside the fml region, which then takes everything the other arrays leave of the 160 KB.
 #define FML_REGION_BYTES (lds_al((tri_off(LDMAX + 1, LCAP - 2) + 2) * 2))      // fML triangle, d = 4..LDMAX at the longest window the kernel takes, n = LCAP - 2 (tri_off grows with n)
 #define POOL_MIN_CAP 1024    // a window whose length leaves room for fewer candidates goes to the dense kernel right away
-// TWO (default model, SPARSE): two workgroups share a CU, so a window has 80 KB.  Its fML triangle is not in LDS at all: phase B keeps the last two
+// TWO (default model, SPARSE): two workgroups share a CU (and leave room for an epilogue workgroup, see LDS_TWO_BYTES), so a window has 70 KB.  Its fML triangle is not in LDS at all: phase B keeps the last two
 // diagonals in a ring (FRING_STR shorts each) at the head of the fml region and writes every cell straight to the window's archive slab, from where
 // the sparse splits gather their operands (fold_lds_kernel.hip); the candidate pool takes the rest of the region.
 #define FRING_STR (LCAP + 2)
-#define LDS_TWO_BYTES (80u * 1024u)
+// The candidate-pool pass shares its CUs with the epilogue of the chunk before it (mirp_run_fold, "fold overlap"): two of its workgroups leave room for
+// MIRP_OVERLAP_EPI_WGS epilogue workgroup of up to MIRP_OVERLAP_EPI_LDS bytes (fold_lds_epilogue_bytes is 18.4 KB at the default number of structure
+// lines; a call whose epilogue needs more takes the serial path, see fold_lds_overlap_epi_wgs).  gfx950 hands out LDS in granules of 1280 bytes, 128
+// per CU: 2 x 56 + 16.  The pool keeps 3,477 of its 5,184 entries; no benchmark window fills more than 1,328, and a window that does
+// overflow is folded by the dense pass as before.  (Two epilogue workgroups per CU would need 62,720 bytes, a pool of 1,984, and a fill kernel of
+// 96 VGPRs, which spills.)
+#ifndef MIRP_FILL_TWO_BYTES
+#define MIRP_FILL_TWO_BYTES 71680
+#endif
+#ifndef MIRP_OVERLAP_EPI_WGS
+#define MIRP_OVERLAP_EPI_WGS 1
+#endif
+#define MIRP_OVERLAP_EPI_LDS (16u * 1280u)
+#define LDS_GRANULES(b) (((b) + 1279u) / 1280u)
+#define LDS_TWO_BYTES ((unsigned)(MIRP_FILL_TWO_BYTES))
+static_assert(2u * LDS_GRANULES(LDS_TWO_BYTES) + MIRP_OVERLAP_EPI_WGS * LDS_GRANULES(MIRP_OVERLAP_EPI_LDS) <= 128u, "two fill workgroups and the epilogue workgroups beside them share one CU's 160 KB");
 template <int MODEL, bool SPARSE = false, bool TWO = false>
 __host__ __device__ constexpr LdsLayout lds_layout() {
     static_assert(!TWO || (SPARSE && MODEL == 0), "two windows per CU: candidate-pool pass of the default model only");

@@ -116,6 +116,8 @@ extern "C" void mirp_destroy(mirp_ctx* c) {
         b->release();
     for (int i = 0; i < 6; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     for (hipEvent_t ev : c->fold_ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : c->overlap_ev) (void)hipEventDestroy(ev);
+    if (c->stream_epi) (void)hipStreamDestroy(c->stream_epi);
     if (c->d_params) (void)hipFree(c->d_params);
     if (c->d_params185) (void)hipFree(c->d_params185);
     if (c->d_params185l) (void)hipFree(c->d_params185l);
@@ -311,6 +313,7 @@ int mirp_run_fold(mirp_ctx* c, const unsigned char* d_seqs, const long long* d_o
                   int max_lines, int stride, MirpFoldLine* d_lines, char* d_ss, int* d_nlines, int* d_mfe, int* d_status) {
     if (n_work <= 0) return 0;
     c->last_fallback = 0;
+    c->last_overlap_chunks = 0;
     const bool m185 = c->fold_model == MIRP_FOLD_MODEL_VIENNA_185;
     // generic kernels (tables in a global workspace): every window when the LDS-resident path does not apply, else its flagged windows
     auto run_generic = [&](const int* work_list, int n_generic) -> int {
@@ -368,6 +371,108 @@ int mirp_run_fold(mirp_ctx* c, const unsigned char* d_seqs, const long long* d_o
         const int light_clocks = 0;
         long long* dbg_cycles = nullptr;
 #endif
+        // ---- fold overlap: the batch in chunks, the epilogue of chunk k on a second stream beside the fill of chunk k + 1.  The fill is an LDS / VALU
+        // kernel that moves 3 % of the HBM roof, the epilogue a chain of memory round trips with next to no arithmetic: the candidate-pool pass is built to
+        // leave room for MIRP_OVERLAP_EPI_WGS epilogue workgroups per CU (fold_lds_common.h).  Every dependency is an event: epilogue k waits for fill k
+        // (and its dense pass), fill k + OV_SLOTS for epilogue k, whose slab slot, window states, dense list and work counters it takes over.  Only the
+        // default model's candidate-pool pass; everything else, and a batch of fewer than two chunks, runs the serial loop below.
+        constexpr int OV_SLOTS = 3, OV_CHUNKS = 4;
+        // The plan (automatic): OV_CHUNKS equal chunks of whole rounds of the persistent fill grid (19,686 windows: 3 x 5,120 + 4,326), more of them where
+        // the batch is larger than the ring.  Every chunk boundary costs a tail of idle CUs (about 0.45 ms), the last chunk's epilogue has no fill to hide
+        // behind, and an epilogue at one workgroup per CU needs more than half of its own chunk's fill time, so the chunks cannot shrink towards
+        // the end.  mirp_set_fold_overlap(N > 0): equal chunks of N windows.
+        std::vector<int> csize;
+        int chunk = 0;
+#ifdef MIRP_DIAG
+        if (const char* ov = std::getenv("MIRP_FOLD_OVERLAP")) c->fold_overlap = std::atoi(ov);      // diagnostics build: the switch for tools that cannot call it
+#endif
+        if (!m185 && !c->fold_dense && c->fold_overlap != 0) {
+            if (c->overlap_epi_wgs < 0 || c->overlap_max_lines != max_lines) {
+                c->overlap_epi_wgs = std::max(0, mirp::fold_lds_overlap_epi_wgs(max_lines));
+                c->overlap_max_lines = max_lines;
+                (void)hipGetLastError();
+            }
+            if (c->overlap_epi_wgs >= 1) {
+                const int round = 2 * c->n_cu;      // windows of one round of the persistent fill grid
+                const size_t cap = std::max<size_t>(1, ((size_t)8 << 30) / (slab * 6 * OV_SLOTS));      // windows per slot: the ring stays within the serial path's 8 GB
+                if (c->fold_overlap > 0) {
+                    chunk = (int)std::min<size_t>((size_t)c->fold_overlap, cap);
+                    for (int b0 = 0; b0 < n_work; b0 += chunk) csize.push_back(std::min(chunk, n_work - b0));
+                } else if (n_work >= 2 * OV_CHUNKS * round) {
+                    const size_t cap_r = std::max<size_t>(round, cap / round * round);
+                    chunk = (int)std::min<size_t>((((size_t)n_work + OV_CHUNKS - 1) / OV_CHUNKS + round - 1) / round * round, cap_r);
+                    for (int b0 = 0; b0 < n_work; b0 += chunk) csize.push_back(std::min(chunk, n_work - b0));
+                    if (csize.size() < 2) csize.clear();
+                }
+            }
+        }
+        if (!csize.empty()) {
+            const int n_chunks = (int)csize.size();
+            size_t slot_cap[OV_SLOTS] = {0, 0, 0}, slot_at[OV_SLOTS + 1] = {0, 0, 0, 0};
+            for (int k = 0; k < n_chunks; k++) slot_cap[k % OV_SLOTS] = std::max(slot_cap[k % OV_SLOTS], (size_t)csize[k]);
+            for (int s = 0; s < OV_SLOTS; s++) slot_at[s + 1] = slot_at[s] + slot_cap[s];
+            const size_t slot_windows = slot_at[OV_SLOTS];
+            if (c->carch.ensure(slot_windows * slab * 6) || c->wstate.ensure(4 * slot_windows) || c->dlist.ensure(4 * slot_windows))
+                return fail(c, -6, "device allocation failed (fold LDS kernel)");
+            if (!c->stream_epi) HIPCHK(c, hipStreamCreateWithFlags(&c->stream_epi, hipStreamNonBlocking));
+            while ((int)c->overlap_ev.size() < 2 + 2 * n_chunks) { hipEvent_t ev; HIPCHK(c, hipEventCreate(&ev)); c->overlap_ev.push_back(ev); }
+            hipEvent_t* oev = c->overlap_ev.data();
+            const int k_epi = c->overlap_epi_wgs;
+            HIPCHK(c, hipEventRecord(oev[0], c->stream));
+            for (int k = 0, b0 = 0; k < n_chunks; b0 += csize[k], k++) {
+                const int nb = csize[k], slot = k % OV_SLOTS;
+                // work counters of the chunk: a 64-byte block per slot behind the call's own (ctl[4]: fallbacks, global); [5] of a block keeps adding up
+                // the windows its dense passes took
+                unsigned int* cctl = ctl + 16 * (1 + slot);
+                if (k >= OV_SLOTS) {
+                    HIPCHK(c, hipStreamWaitEvent(c->stream, oev[2 + 2 * (k - OV_SLOTS) + 1], 0));
+                    HIPCHK(c, hipMemsetAsync(cctl, 0, 16, c->stream));
+                }
+                short* slabs_k = (short*)c->carch.p + slot_at[slot] * 3 * slab;
+                int* wstate_k = (int*)c->wstate.p + slot_at[slot];
+                int* dlist_k = (int*)c->dlist.p + slot_at[slot];
+                const int grid = std::min(nb, c->n_cu);
+                // beside a fill: no more persistent epilogue workgroups than fit next to two fill workgroups on every CU; the last one has the device alone
+                const int grid_epi = std::min(nb, c->n_cu * (k + 1 < n_chunks ? k_epi : 8));
+                for (int part : {(int)mirp::MIRP_FOLD_PART_FILL, (int)mirp::MIRP_FOLD_PART_EPI}) {
+                    hipStream_t st = part == mirp::MIRP_FOLD_PART_FILL ? c->stream : c->stream_epi;
+                    if (part == mirp::MIRP_FOLD_PART_EPI) HIPCHK(c, hipStreamWaitEvent(st, oev[2 + 2 * k], 0));
+                    hipError_t e = mirp::launch_fold_lds(st, 0, grid, grid_epi, c->d_params, d_seqs, d_offs + b0, d_lens ? d_lens + b0 : nullptr, nb, b0, span,
+                                                         slabs_k, slab, wstate_k, cctl, (int*)c->flist.p, ctl + 4, max_lines, stride,
+                                                         d_lines + (size_t)b0 * max_lines, d_ss + (size_t)b0 * max_lines * stride, d_nlines + b0, d_mfe + b0,
+                                                         d_status + b0, 0, nullptr, nullptr, dlist_k, 0, part);
+                    if (e != hipSuccess) return fail(c, -2, std::string("fold LDS kernel launch failed: ") + hipGetErrorString(e));
+                    HIPCHK(c, hipEventRecord(oev[2 + 2 * k + (part == mirp::MIRP_FOLD_PART_EPI ? 1 : 0)], st));
+                }
+            }
+            HIPCHK(c, hipStreamWaitEvent(c->stream, oev[2 + 2 * (n_chunks - 1) + 1], 0));      // the epilogues are in order on their stream: the last one ends them all
+            HIPCHK(c, hipEventRecord(oev[1], c->stream));
+            unsigned int hctl[16 * (1 + OV_SLOTS)];
+            HIPCHK(c, hipMemcpyAsync(hctl, ctl, sizeof(hctl), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            const unsigned int nfb = hctl[4];
+            c->last_fallback = nfb;
+            c->last_dense = 0;
+            for (int s = 0; s < OV_SLOTS; s++) c->last_dense += hctl[16 * (1 + s) + 5];
+            c->last_overlap_chunks = n_chunks;
+            // [0]: first fill's start to last fill's end (dense passes included), [1]: the rest of the fold's device time, i.e. the exposed epilogue
+            float fill_ms = 0, all_ms = 0;
+            (void)hipEventElapsedTime(&fill_ms, oev[0], oev[2 + 2 * (n_chunks - 1)]);
+            (void)hipEventElapsedTime(&all_ms, oev[0], oev[1]);
+            c->fold_kernel_ms[0] = fill_ms; c->fold_kernel_ms[1] = std::max(0.0f, all_ms - fill_ms);
+#ifdef MIRP_DIAG
+            if (std::getenv("MIRP_FOLD_OVERLAP_TRACE")) {      // when each kernel ended, ms after the first fill's start
+                for (int k = 0; k < n_chunks; k++) {
+                    float f = 0, e2 = 0;
+                    (void)hipEventElapsedTime(&f, oev[0], oev[2 + 2 * k]); (void)hipEventElapsedTime(&e2, oev[0], oev[2 + 2 * k + 1]);
+                    std::fprintf(stderr, "[mirp fold overlap] chunk %d: %d windows, fill done %.3f ms, epilogue done %.3f ms\n", k, csize[k], f, e2);
+                }
+                std::fprintf(stderr, "[mirp fold overlap] all done %.3f ms, largest pool fill %u entries\n", all_ms, hctl[6]);
+            }
+#endif
+            if (nfb == 0) return 0;
+            return run_generic((const int*)c->flist.p, (int)nfb);
+        }
         int n_sub = 0;
         for (int b0 = 0; b0 < n_work; b0 += sub) {
             const int nb = std::min(sub, n_work - b0);
@@ -391,6 +496,13 @@ int mirp_run_fold(mirp_ctx* c, const unsigned char* d_seqs, const long long* d_o
         const unsigned int nfb = nfb2[0];
         c->last_fallback = nfb;
         c->last_dense = nfb2[1];
+#ifdef MIRP_DIAG
+        if (std::getenv("MIRP_FOLD_OVERLAP_TRACE")) {
+            unsigned int mx = 0;
+            HIPCHK(c, hipMemcpy(&mx, ctl + 6, 4, hipMemcpyDeviceToHost));
+            std::fprintf(stderr, "[mirp fold overlap] serial path, largest pool fill %u entries\n", mx);
+        }
+#endif
         c->fold_kernel_ms[0] = c->fold_kernel_ms[1] = 0;
         for (int k = 0; k < n_sub; k++) {
             float a = 0, b = 0;

@@ -84,6 +84,13 @@ struct mirp_ctx {
     double ms[4] = {0, 0, 0, 0};
     double fold_kernel_ms[2] = {0, 0};   // fill / epilogue kernels of the last mirp_run_fold (LDS-resident path)
     std::vector<hipEvent_t> fold_ev;     // 3 events per sub-batch, created on demand
+    // ---- fold overlap (mirp_run_fold): the epilogue of a chunk of windows runs on a stream of its own beside the fill of the next chunk
+    int fold_overlap = -1;               // mirp_set_fold_overlap: -1 = automatic, 0 = off (serial path), N > 0 = chunks of N windows
+    int overlap_epi_wgs = -1;            // epilogue workgroups a CU holds beside two fill workgroups (fold_lds_overlap_epi_wgs), -1 = not asked yet
+    int overlap_max_lines = -1;          //   ... at this number of structure lines
+    hipStream_t stream_epi = nullptr;    // created on the first chunked fold
+    std::vector<hipEvent_t> overlap_ev;  // [0] first fill starts, [1] all done, then per chunk: fill done, epilogue done; created on demand
+    int last_overlap_chunks = 0;         // chunks of the last mirp_run_fold (0: serial path)
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // ---- multi-GPU (mirp_dist.cpp): RCCL communicator of this context's device, one process per GPU
     void* comm = nullptr;

@@ -60,10 +60,16 @@ void fold_lds_epi_clocks_print();
 int fold_lds_max_n();
 int fold_lds_gen_wing_d();
 int fold_lds_max_span();
+// parts: the fill (candidate-pool pass and the dense pass over its hand-offs) and the epilogue of the windows can be launched apart, on two streams
+enum { MIRP_FOLD_PART_FILL = 1, MIRP_FOLD_PART_EPI = 2, MIRP_FOLD_PARTS_BOTH = 3 };
 hipError_t launch_fold_lds(hipStream_t stream, int model, int grid, int grid_epi, const FoldParams* P, const unsigned char* seqs, const long long* offs, const int* lens,
                            int n_work, int win_base, int span, short* slabs, size_t slab_shorts, int* win_state, unsigned int* work_counter, int* fallback_list,
                            unsigned int* fallback_count, int max_lines, int ss_stride, MirpFoldLine* out_lines, char* out_ss, int* out_nlines, int* out_mfe,
-                           int* out_status, int light_clocks, long long* dbg_cycles, hipEvent_t ev_between, int* dense_list, int force_dense);
+                           int* out_status, int light_clocks, long long* dbg_cycles, hipEvent_t ev_between, int* dense_list, int force_dense,
+                           int parts = MIRP_FOLD_PARTS_BOTH);
+// Epilogue workgroups (fold_lds_epilogue_kernel at max_lines) that registers, wave slots and LDS let a CU hold beside two workgroups of the default
+// model's candidate-pool pass (at most the number its LDS layout was made for), from the kernels' own attributes; 0 = none (the chunked fold then takes the serial path), < 0 = a HIP error.
+int fold_lds_overlap_epi_wgs(int max_lines);
 
 // candidate_kernels.hip
 void launch_cov_scatter(hipStream_t st, const MirpAln* alns, long long n, const long long* goff, const long long* clen, int cutoff, int* diff_p, int* diff_m);

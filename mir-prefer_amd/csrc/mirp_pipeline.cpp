@@ -458,6 +458,7 @@ extern "C" int mirp_fold(mirp_ctx* c, int32_t span, int32_t max_lines) {
         fallbacks = c->last_fallback;
     }
     const double main_kernel_ms[2] = {c->fold_kernel_ms[0], c->fold_kernel_ms[1]};
+    const int main_chunks = c->last_overlap_chunks;
     // RNALfold has no limit on the number of structure lines (MP:3053); a window that produced more than max_lines (tandem repeats: up to
     // one line per start position) was flagged, not truncated.  Only those windows are folded again, at the capacity no window can
     // exceed, into side buffers that the predict stage and the text writers read instead of the window's slot in the main buffers.
@@ -497,6 +498,7 @@ extern "C" int mirp_fold(mirp_ctx* c, int32_t span, int32_t max_lines) {
     }
     c->last_fallback = fallbacks;
     c->fold_kernel_ms[0] = main_kernel_ms[0]; c->fold_kernel_ms[1] = main_kernel_ms[1];
+    c->last_overlap_chunks = main_chunks;
     HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
@@ -695,6 +697,13 @@ extern "C" int mirp_set_fold_split_path(mirp_ctx* c, int32_t mode) {
     c->fold_dense = mode;
     return 0;
 }
+extern "C" int mirp_set_fold_overlap(mirp_ctx* c, int32_t chunk_windows) {
+    if (!c) return -1;
+    if (chunk_windows < -1) return fail(c, -1, "mirp_set_fold_overlap: chunk_windows is -1 (automatic), 0 (off) or a number of windows");
+    c->fold_overlap = chunk_windows;
+    return 0;
+}
+extern "C" int mirp_last_fold_overlap_chunks(mirp_ctx* c) { return c ? c->last_overlap_chunks : -1; }
 extern "C" int64_t mirp_last_fold_dense(mirp_ctx* c) { return c ? (int64_t)c->last_dense : -1; }
 extern "C" int mirp_set_coverage_path(mirp_ctx* c, int32_t mode) {
     if (!c) return -1;
