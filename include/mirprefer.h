@@ -245,17 +245,24 @@ int64_t mirp_last_fold_dense(mirp_ctx* ctx);
 
 /* Fold overlap: a batch of the default model is folded in chunks of windows, the epilogue kernel of a chunk (exterior sweep, enumeration,
  * backtracks: it waits on memory) on a second stream beside the fill kernel of the next chunk (it computes out of LDS).  chunk_windows = -1:
- * automatic (default; batches of at least 8 rounds of the fill grid in 4 chunks, smaller ones serially), 0: off, the serial path, N > 0: chunks of
+ * automatic (default; batches of at least 8 rounds of the fill grid in chunks planned by fold_overlap_plan.h, smaller ones serially), 0: off, the serial path, N > 0: chunks of
  * N windows whatever the batch size.  Every output is identical either way.  vienna-1.8.5, mirp_set_fold_split_path(1), spans outside the
  * LDS-resident kernels and a device whose resources leave no room for an epilogue workgroup beside the fill always take the serial path. */
 int mirp_set_fold_overlap(mirp_ctx* ctx, int32_t chunk_windows);
+/* How the fills of a chunked fold are scheduled.  mode = -1: automatic (default: tail-free wherever the overlap runs), 1: tail-free, 0: ordered.
+ * Tail-free: the fill of chunk k runs on stream k % 2 and does not wait for the fill before it, so the workgroups of the next fill take the places of
+ * those that run out of windows and no CU idles at a chunk boundary; a chunk launches the candidate-pool pass only, and the windows handed to the
+ * dense fill kernel (none on ordinary inputs) are folded chunk by chunk behind the last epilogue.  Ordered: every fill on the context's stream in
+ * order, each followed by its dense pass.  Every output, mirp_last_fold_dense and mirp_last_fold_fallbacks are identical either way. */
+int mirp_set_fold_overlap_tailfree(mirp_ctx* ctx, int32_t mode);
 /* Chunks the last fold call ran in (0: the serial path). */
 int mirp_last_fold_overlap_chunks(mirp_ctx* ctx);
 
 /* Device time of the kernels of the last mirp_fold, HIP events: two numbers whose sum is the device time of the fold's main pass.  Serial path:
  * ms[0] = fill kernel(s) (fold_lds_kernel: the dynamic program), ms[1] = epilogue kernel(s) (exterior sweep, enumeration, backtracks), summed
- * over the sub-batches.  With fold overlap: ms[0] = from the first fill's start to the last fill's end, dense passes included, ms[1] = the
- * rest, i.e. the part of the epilogues that no fill covers. */
+ * over the sub-batches.  With fold overlap: ms[0] = from the first fill's start to the last fill's end, whichever stream that fill is on (ordered
+ * schedule: dense passes included), ms[1] = the rest of the fold's device time: the part of the epilogues that no fill covers and, in the tail-free
+ * schedule, the deferred dense passes with their epilogues, if any. */
 int mirp_last_fold_kernel_ms(mirp_ctx* ctx, double ms[2]);
 /* Measures the two roofs of the fold's fill kernel on this GPU with its own geometry (one 1024-thread workgroup per CU): out[0] ds_read_b32 and
  * out[1] ds_read_u16 wave-instructions per second (conflict-free, reads in flight), out[2] packed 16-bit add+min and out[3] 32-bit shift-add+min

@@ -408,6 +408,8 @@ def load_library():
     lib.mirp_set_fold_split_path.restype = C.c_int
     lib.mirp_set_fold_overlap.argtypes = [vp, C.c_int32]
     lib.mirp_set_fold_overlap.restype = C.c_int
+    lib.mirp_set_fold_overlap_tailfree.argtypes = [vp, C.c_int32]
+    lib.mirp_set_fold_overlap_tailfree.restype = C.c_int
     lib.mirp_last_fold_overlap_chunks.argtypes = [vp]
     lib.mirp_last_fold_overlap_chunks.restype = C.c_int
     lib.mirp_last_fold_dense.argtypes = [vp]
@@ -1225,6 +1227,11 @@ class Context:
     def set_fold_overlap(self, chunk_windows):
         """-1: automatic (default), 0: off (serial path), N > 0: the epilogue of every chunk of N windows beside the fill of the next chunk."""
         self._check(self.lib.mirp_set_fold_overlap(self.h, int(chunk_windows)), "mirp_set_fold_overlap")
+
+    def set_fold_overlap_tailfree(self, mode):
+        """-1: automatic (default: on), 1: the fills of neighbouring chunks on two streams, no idle CUs at a chunk boundary, dense hand-offs folded
+        behind the last epilogue, 0: fills in order on one stream with a dense pass per chunk.  Same results either way."""
+        self._check(self.lib.mirp_set_fold_overlap_tailfree(self.h, int(mode)), "mirp_set_fold_overlap_tailfree")
 
     def last_fold_overlap_chunks(self):
         """Chunks the last fold ran in; 0: the serial path."""

@@ -312,7 +312,8 @@ hipError_t launch_fold_lds(hipStream_t stream, int model, int grid, int grid_epi
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fold_lds_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_layout<1, true>().total);
     if (e != hipSuccess) return e;
     const int* no_list = nullptr; const unsigned int* no_count = nullptr;
-    if (!(parts & MIRP_FOLD_PART_FILL)) {
+    const bool two_pass = !model && !force_dense;      // the only fill that the pool and dense parts divide; any other goes with the pool part
+    if (!(parts & (two_pass ? MIRP_FOLD_PART_FILL : MIRP_FOLD_PART_POOL))) {
     } else
     if (model) {
         // vienna-1.8.5: with dangles 1 every pair gives up to four strictly pair-realised fML cells ((i,j), (i-1,j), (i,j+1), (i-1,j+1)), i.e. about four
@@ -351,14 +352,17 @@ hipError_t launch_fold_lds(hipStream_t stream, int model, int grid, int grid_epi
                 return hipErrorLaunchOutOfResources;
             }
             const int grid2 = n_work < 2 * grid ? n_work : 2 * grid;
-            hipLaunchKernelGGL((fold_lds_kernel<0, true, LNT2>), dim3(grid2), dim3(LNT2), lds_sp, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter,
-                               fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, light_clocks, dbg_cycles,
-                               no_list, no_count, dense_list, work_counter + 3);
-            e = hipGetLastError();
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((fold_lds_kernel<0, false>), dim3(grid), dim3(LNT), lds, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter + 2,
-                               fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, light_clocks, dbg_cycles,
-                               (const int*)dense_list, (const unsigned int*)(work_counter + 3), dense_list, work_counter + 3);
+            if (parts & MIRP_FOLD_PART_POOL) {
+                hipLaunchKernelGGL((fold_lds_kernel<0, true, LNT2>), dim3(grid2), dim3(LNT2), lds_sp, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter,
+                                   fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, light_clocks, dbg_cycles,
+                                   no_list, no_count, dense_list, work_counter + 3);
+                e = hipGetLastError();
+                if (e != hipSuccess) return e;
+            }
+            if (parts & MIRP_FOLD_PART_DENSE)      // launched apart (tail-free fold overlap): over the list and the count a pool pass left in dense_list / work_counter[3]
+                hipLaunchKernelGGL((fold_lds_kernel<0, false>), dim3(grid), dim3(LNT), lds, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter + 2,
+                                   fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, light_clocks, dbg_cycles,
+                                   (const int*)dense_list, (const unsigned int*)(work_counter + 3), dense_list, work_counter + 3);
         } else
             hipLaunchKernelGGL((fold_lds_kernel<0, false>), dim3(grid), dim3(LNT), lds, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter,
                                fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, light_clocks, dbg_cycles,

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include "mirp_internal.h"
+#include "fold_overlap_plan.h"
 
 #define MIRP_ABI_VERSION 17  // 17: mirp_duplex_batch, mirp_set_duplex_capacity, mirp_duplex_last_stats, MirpTargetOpts.energy; 16: mirp_randfold, mirp_shuffle_batch; 15: mirp_annotate_scan; 14: mirp_degradome_scan; 13: mirp_cluster_scan; 12: mirp_phase_scan; 11: mirp_target_scan, mirp_set_target_capacity; 10: mirp_trim_reads; 9: mirp_align_index, mirp_align_reads; 8: mirp_collapse_reads, mirp_last_collapse_collisions; 7: mirp_write_result_reports, mirp_fold_predict_report_stream, mirp_select_windows, mirp_dist_comm_info, MIRP_MAX_SAMPLES 255; 6: mirp_last_coverage_fused, mirp_fold_batch_summary, mirp_predict_batch_reasons, text writers; 5: mirp_dist_*, mirp_gather_loci / mirp_gather_records, mirp_read_fasta, mirp_ingest_sams_shard; 4: MirpSamData.segs, mirp_ingest_sams_gpu, mirp_load_coverage_segments; 2: mirp_set_fold_model, mirp_ingest_sams; 3: mirp_predict returns the per-window capacity status, mirp_get_fold_overflow
 #define MIRP_NMAX 3096
@@ -118,6 +119,7 @@ extern "C" void mirp_destroy(mirp_ctx* c) {
     for (hipEvent_t ev : c->fold_ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->overlap_ev) (void)hipEventDestroy(ev);
     if (c->stream_epi) (void)hipStreamDestroy(c->stream_epi);
+    if (c->stream_fill2) (void)hipStreamDestroy(c->stream_fill2);
     if (c->d_params) (void)hipFree(c->d_params);
     if (c->d_params185) (void)hipFree(c->d_params185);
     if (c->d_params185l) (void)hipFree(c->d_params185l);
@@ -355,10 +357,48 @@ int mirp_run_fold(mirp_ctx* c, const unsigned char* d_seqs, const long long* d_o
         // the two exchange the c / fML triangles of every window through per-window slabs in HBM
         const size_t slab = mirp::fold_lds_slab_shorts(std::min(n_cap, mirp::fold_lds_max_n() + 2));
         const int sub = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_work, ((size_t)8 << 30) / (slab * 6)));   // three 16-bit triangles per window: c, fML, trace-back codes
-        if (c->carch.ensure((size_t)sub * slab * 6) || c->fctl.ensure(1024) || c->flist.ensure(4 * (size_t)n_work) || c->wstate.ensure(4 * (size_t)sub) ||
-            c->dlist.ensure(4 * (size_t)sub))
+        // ---- fold overlap: the batch in chunks, the epilogue of chunk k on a stream of its own beside the fill of chunk k + 1.  The fill is an LDS / VALU
+        // kernel that moves 3 % of the HBM roof, the epilogue a chain of memory round trips with next to no arithmetic: the candidate-pool pass is built to
+        // leave room for MIRP_OVERLAP_EPI_WGS epilogue workgroups per CU (fold_lds_common.h).  The archive is a ring of OV_SLOTS slots (slabs and window
+        // states of one chunk each); every chunk has a 64-byte block of work counters of its own behind the call's block and its own stretch, at its
+        // first window, of one dense list of n_work entries, so nothing is cleared between chunks and the lists outlive the reuse of a slot.  Only the
+        // default model's candidate-pool pass; everything else, and an empty plan (fold_overlap_plan.h), runs the serial loop below.
+        //
+        // Tail-free schedule (mirp_set_fold_overlap_tailfree, the default): fill k goes on stream k % 2 (the context's, stream_fill2) and does not
+        // wait for fill k - 1: both are persistent grids that draw windows from their own counters, and as workgroups of one run out of windows and
+        // exit, workgroups of the next take their places, so no CU idles at a chunk boundary.  The dense pass (1024 threads, 160 KB of LDS: it needs
+        // empty CUs) would drain them, so a chunk launches the candidate-pool pass only; a window it hands over keeps win_state 0, which the
+        // epilogue skips, and is folded behind the last epilogue (below; none on the benchmark inputs).  Ordered schedule (mode 0): every fill on
+        // the context's stream, pool pass and dense pass, as before round 10.
+        //
+        // Every dependency is an event, nothing polls memory: epilogue k waits for fill k, fill k for epilogue k - OV_SLOTS, whose slot it takes over,
+        // and the second fill stream once for the event in front of the first fill (the counters' memset, the caller's uploads).  Every
+        // hipStreamWaitEvent below names an event recorded earlier in host submission order, so the schedule cannot deadlock even where two of the
+        // three streams share a hardware queue: it then only loses overlap.
+        constexpr int OV_SLOTS = 3;
+        std::vector<int> csize;
+#ifdef MIRP_DIAG
+        if (const char* ov = std::getenv("MIRP_FOLD_OVERLAP")) c->fold_overlap = std::atoi(ov);      // diagnostics build: the switches for tools that cannot call them
+        if (const char* tf = std::getenv("MIRP_FOLD_TAILFREE")) c->fold_tailfree = std::atoi(tf);
+#endif
+        const bool tailfree = c->fold_tailfree != 0;
+        if (!m185 && !c->fold_dense && c->fold_overlap != 0) {
+            if (c->overlap_epi_wgs < 0 || c->overlap_max_lines != max_lines) {
+                c->overlap_epi_wgs = std::max(0, mirp::fold_lds_overlap_epi_wgs(max_lines));
+                c->overlap_max_lines = max_lines;
+                (void)hipGetLastError();
+            }
+            if (c->overlap_epi_wgs >= 1) {
+                const size_t cap = std::max<size_t>(1, ((size_t)8 << 30) / (slab * 6 * OV_SLOTS));      // windows per slot: the ring stays within the serial path's 8 GB
+                csize = mirp::fold_overlap_plan(n_work, 2 * c->n_cu, (long long)cap, c->fold_overlap, tailfree ? mirp::FOLD_SCHEDULE_TAILFREE : mirp::FOLD_SCHEDULE_ORDERED);
+            }
+        }
+        const int n_chunks = (int)csize.size();
+        const size_t ctl_bytes = std::max<size_t>(1024, 64 * (size_t)(1 + n_chunks));
+        if (c->carch.ensure((size_t)sub * slab * 6) || c->fctl.ensure(ctl_bytes) || c->flist.ensure(4 * (size_t)n_work) || c->wstate.ensure(4 * (size_t)sub) ||
+            c->dlist.ensure(4 * (size_t)(n_chunks ? n_work : sub)))
             return fail(c, -6, "device allocation failed (fold LDS kernel)");
-        HIPCHK(c, hipMemsetAsync(c->fctl.p, 0, 1024, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->fctl.p, 0, ctl_bytes, c->stream));
         unsigned int* ctl = (unsigned int*)c->fctl.p;
         // diagnostics exist only in a -DMIRP_DIAG build (`make DIAG=1`, profiles/tools/): MIRP_FOLD_CLOCKS=1 prints phase clocks (=2: light mode, per
         // wave only busy time, reported as splits, and barrier wait), MIRP_FOLD_DUMP=<path> dumps slabs; the epilogue's clocks print with the fill's.  The shipped
@@ -371,103 +411,88 @@ int mirp_run_fold(mirp_ctx* c, const unsigned char* d_seqs, const long long* d_o
         const int light_clocks = 0;
         long long* dbg_cycles = nullptr;
 #endif
-        // ---- fold overlap: the batch in chunks, the epilogue of chunk k on a second stream beside the fill of chunk k + 1.  The fill is an LDS / VALU
-        // kernel that moves 3 % of the HBM roof, the epilogue a chain of memory round trips with next to no arithmetic: the candidate-pool pass is built to
-        // leave room for MIRP_OVERLAP_EPI_WGS epilogue workgroups per CU (fold_lds_common.h).  Every dependency is an event: epilogue k waits for fill k
-        // (and its dense pass), fill k + OV_SLOTS for epilogue k, whose slab slot, window states, dense list and work counters it takes over.  Only the
-        // default model's candidate-pool pass; everything else, and a batch of fewer than two chunks, runs the serial loop below.
-        constexpr int OV_SLOTS = 3, OV_CHUNKS = 4;
-        // The plan (automatic): OV_CHUNKS equal chunks of whole rounds of the persistent fill grid (19,686 windows: 3 x 5,120 + 4,326), more of them where
-        // the batch is larger than the ring.  Every chunk boundary costs a tail of idle CUs (about 0.45 ms), the last chunk's epilogue has no fill to hide
-        // behind, and an epilogue at one workgroup per CU needs more than half of its own chunk's fill time, so the chunks cannot shrink towards
-        // the end.  mirp_set_fold_overlap(N > 0): equal chunks of N windows.
-        std::vector<int> csize;
-        int chunk = 0;
-#ifdef MIRP_DIAG
-        if (const char* ov = std::getenv("MIRP_FOLD_OVERLAP")) c->fold_overlap = std::atoi(ov);      // diagnostics build: the switch for tools that cannot call it
-#endif
-        if (!m185 && !c->fold_dense && c->fold_overlap != 0) {
-            if (c->overlap_epi_wgs < 0 || c->overlap_max_lines != max_lines) {
-                c->overlap_epi_wgs = std::max(0, mirp::fold_lds_overlap_epi_wgs(max_lines));
-                c->overlap_max_lines = max_lines;
-                (void)hipGetLastError();
-            }
-            if (c->overlap_epi_wgs >= 1) {
-                const int round = 2 * c->n_cu;      // windows of one round of the persistent fill grid
-                const size_t cap = std::max<size_t>(1, ((size_t)8 << 30) / (slab * 6 * OV_SLOTS));      // windows per slot: the ring stays within the serial path's 8 GB
-                if (c->fold_overlap > 0) {
-                    chunk = (int)std::min<size_t>((size_t)c->fold_overlap, cap);
-                    for (int b0 = 0; b0 < n_work; b0 += chunk) csize.push_back(std::min(chunk, n_work - b0));
-                } else if (n_work >= 2 * OV_CHUNKS * round) {
-                    const size_t cap_r = std::max<size_t>(round, cap / round * round);
-                    chunk = (int)std::min<size_t>((((size_t)n_work + OV_CHUNKS - 1) / OV_CHUNKS + round - 1) / round * round, cap_r);
-                    for (int b0 = 0; b0 < n_work; b0 += chunk) csize.push_back(std::min(chunk, n_work - b0));
-                    if (csize.size() < 2) csize.clear();
-                }
-            }
-        }
-        if (!csize.empty()) {
-            const int n_chunks = (int)csize.size();
+        if (n_chunks) {
             size_t slot_cap[OV_SLOTS] = {0, 0, 0}, slot_at[OV_SLOTS + 1] = {0, 0, 0, 0};
             for (int k = 0; k < n_chunks; k++) slot_cap[k % OV_SLOTS] = std::max(slot_cap[k % OV_SLOTS], (size_t)csize[k]);
             for (int s = 0; s < OV_SLOTS; s++) slot_at[s + 1] = slot_at[s] + slot_cap[s];
             const size_t slot_windows = slot_at[OV_SLOTS];
-            if (c->carch.ensure(slot_windows * slab * 6) || c->wstate.ensure(4 * slot_windows) || c->dlist.ensure(4 * slot_windows))
+            if (c->carch.ensure(slot_windows * slab * 6) || c->wstate.ensure(4 * slot_windows))
                 return fail(c, -6, "device allocation failed (fold LDS kernel)");
             if (!c->stream_epi) HIPCHK(c, hipStreamCreateWithFlags(&c->stream_epi, hipStreamNonBlocking));
-            while ((int)c->overlap_ev.size() < 2 + 2 * n_chunks) { hipEvent_t ev; HIPCHK(c, hipEventCreate(&ev)); c->overlap_ev.push_back(ev); }
+            if (tailfree && !c->stream_fill2) HIPCHK(c, hipStreamCreateWithFlags(&c->stream_fill2, hipStreamNonBlocking));
+            // events: [0] first fill starts, [1] last epilogue done, [2] [3] around the deferred dense passes, then per chunk: fill done, epilogue done
+            while ((int)c->overlap_ev.size() < 4 + 2 * n_chunks) { hipEvent_t ev; HIPCHK(c, hipEventCreate(&ev)); c->overlap_ev.push_back(ev); }
             hipEvent_t* oev = c->overlap_ev.data();
             const int k_epi = c->overlap_epi_wgs;
-            HIPCHK(c, hipEventRecord(oev[0], c->stream));
-            for (int k = 0, b0 = 0; k < n_chunks; b0 += csize[k], k++) {
+            // one chunk's launches: b0 = its first window; ctl block 1 + k ([4] of the call's block: fallbacks, [6]: largest pool fill; both global)
+            auto launch = [&](hipStream_t st, int k, int b0, int grid_epi, int part) -> hipError_t {
                 const int nb = csize[k], slot = k % OV_SLOTS;
-                // work counters of the chunk: a 64-byte block per slot behind the call's own (ctl[4]: fallbacks, global); [5] of a block keeps adding up
-                // the windows its dense passes took
-                unsigned int* cctl = ctl + 16 * (1 + slot);
-                if (k >= OV_SLOTS) {
-                    HIPCHK(c, hipStreamWaitEvent(c->stream, oev[2 + 2 * (k - OV_SLOTS) + 1], 0));
-                    HIPCHK(c, hipMemsetAsync(cctl, 0, 16, c->stream));
-                }
-                short* slabs_k = (short*)c->carch.p + slot_at[slot] * 3 * slab;
-                int* wstate_k = (int*)c->wstate.p + slot_at[slot];
-                int* dlist_k = (int*)c->dlist.p + slot_at[slot];
-                const int grid = std::min(nb, c->n_cu);
+                return mirp::launch_fold_lds(st, 0, std::min(nb, c->n_cu), grid_epi, c->d_params, d_seqs, d_offs + b0, d_lens ? d_lens + b0 : nullptr, nb, b0, span,
+                                             (short*)c->carch.p + slot_at[slot] * 3 * slab, slab, (int*)c->wstate.p + slot_at[slot], ctl + 16 * (1 + k), (int*)c->flist.p,
+                                             ctl + 4, max_lines, stride, d_lines + (size_t)b0 * max_lines, d_ss + (size_t)b0 * max_lines * stride, d_nlines + b0,
+                                             d_mfe + b0, d_status + b0, 0, nullptr, nullptr, (int*)c->dlist.p + b0, 0, part);
+            };
+            HIPCHK(c, hipEventRecord(oev[0], c->stream));
+            if (tailfree) HIPCHK(c, hipStreamWaitEvent(c->stream_fill2, oev[0], 0));
+            for (int k = 0, b0 = 0; k < n_chunks; b0 += csize[k], k++) {
+                hipStream_t sf = tailfree && (k & 1) ? c->stream_fill2 : c->stream;
+                if (k >= OV_SLOTS) HIPCHK(c, hipStreamWaitEvent(sf, oev[4 + 2 * (k - OV_SLOTS) + 1], 0));
+                hipError_t e = launch(sf, k, b0, 0, tailfree ? mirp::MIRP_FOLD_PART_POOL : mirp::MIRP_FOLD_PART_FILL);
+                if (e != hipSuccess) return fail(c, -2, std::string("fold LDS kernel launch failed: ") + hipGetErrorString(e));
+                HIPCHK(c, hipEventRecord(oev[4 + 2 * k], sf));
+                HIPCHK(c, hipStreamWaitEvent(c->stream_epi, oev[4 + 2 * k], 0));
                 // beside a fill: no more persistent epilogue workgroups than fit next to two fill workgroups on every CU; the last one has the device alone
-                const int grid_epi = std::min(nb, c->n_cu * (k + 1 < n_chunks ? k_epi : 8));
-                for (int part : {(int)mirp::MIRP_FOLD_PART_FILL, (int)mirp::MIRP_FOLD_PART_EPI}) {
-                    hipStream_t st = part == mirp::MIRP_FOLD_PART_FILL ? c->stream : c->stream_epi;
-                    if (part == mirp::MIRP_FOLD_PART_EPI) HIPCHK(c, hipStreamWaitEvent(st, oev[2 + 2 * k], 0));
-                    hipError_t e = mirp::launch_fold_lds(st, 0, grid, grid_epi, c->d_params, d_seqs, d_offs + b0, d_lens ? d_lens + b0 : nullptr, nb, b0, span,
-                                                         slabs_k, slab, wstate_k, cctl, (int*)c->flist.p, ctl + 4, max_lines, stride,
-                                                         d_lines + (size_t)b0 * max_lines, d_ss + (size_t)b0 * max_lines * stride, d_nlines + b0, d_mfe + b0,
-                                                         d_status + b0, 0, nullptr, nullptr, dlist_k, 0, part);
-                    if (e != hipSuccess) return fail(c, -2, std::string("fold LDS kernel launch failed: ") + hipGetErrorString(e));
-                    HIPCHK(c, hipEventRecord(oev[2 + 2 * k + (part == mirp::MIRP_FOLD_PART_EPI ? 1 : 0)], st));
-                }
+                e = launch(c->stream_epi, k, b0, std::min(csize[k], c->n_cu * (k + 1 < n_chunks ? k_epi : 8)), mirp::MIRP_FOLD_PART_EPI);
+                if (e != hipSuccess) return fail(c, -2, std::string("fold LDS kernel launch failed: ") + hipGetErrorString(e));
+                HIPCHK(c, hipEventRecord(oev[4 + 2 * k + 1], c->stream_epi));
             }
-            HIPCHK(c, hipStreamWaitEvent(c->stream, oev[2 + 2 * (n_chunks - 1) + 1], 0));      // the epilogues are in order on their stream: the last one ends them all
+            HIPCHK(c, hipStreamWaitEvent(c->stream, oev[4 + 2 * (n_chunks - 1) + 1], 0));      // the epilogues are in order on their stream and each waits for its fill: the last one ends them all
             HIPCHK(c, hipEventRecord(oev[1], c->stream));
-            unsigned int hctl[16 * (1 + OV_SLOTS)];
-            HIPCHK(c, hipMemcpyAsync(hctl, ctl, sizeof(hctl), hipMemcpyDeviceToHost, c->stream));
+            std::vector<unsigned int> hctl(16 * (size_t)(1 + n_chunks));
+            HIPCHK(c, hipMemcpyAsync(hctl.data(), ctl, 4 * hctl.size(), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            const unsigned int nfb = hctl[4];
-            c->last_fallback = nfb;
+            unsigned int nfb = hctl[4];
             c->last_dense = 0;
-            for (int s = 0; s < OV_SLOTS; s++) c->last_dense += hctl[16 * (1 + s) + 5];
+            for (int k = 0; k < n_chunks; k++) c->last_dense += hctl[16 * (1 + k) + 3];      // [3] of a block: the length of the chunk's dense list
             c->last_overlap_chunks = n_chunks;
-            // [0]: first fill's start to last fill's end (dense passes included), [1]: the rest of the fold's device time, i.e. the exposed epilogue
+            float deferred_ms = 0;
+            if (tailfree && c->last_dense) {
+                // the windows the pool passes handed over, chunk by chunk on the context's stream, which has the device alone: their window states cleared,
+                // so that the chunk's second epilogue does nothing but them, the dense pass into the chunk's own slot, the epilogue.  A dense pass may
+                // hand windows on to the generic kernel: the fallback count is read again behind them.
+                HIPCHK(c, hipEventRecord(oev[2], c->stream));
+                for (int k = 0, b0 = 0; k < n_chunks; b0 += csize[k], k++) {
+                    if (hctl[16 * (1 + k) + 3] == 0) continue;
+                    HIPCHK(c, hipMemsetAsync((int*)c->wstate.p + slot_at[k % OV_SLOTS], 0, 4 * (size_t)csize[k], c->stream));
+                    HIPCHK(c, hipMemsetAsync(ctl + 16 * (1 + k) + 1, 0, 4, c->stream));      // the epilogue's work counter
+                    hipError_t e = launch(c->stream, k, b0, std::min(csize[k], c->n_cu * 8), mirp::MIRP_FOLD_PART_DENSE | mirp::MIRP_FOLD_PART_EPI);
+                    if (e != hipSuccess) return fail(c, -2, std::string("fold LDS kernel launch failed: ") + hipGetErrorString(e));
+                }
+                HIPCHK(c, hipEventRecord(oev[3], c->stream));
+                HIPCHK(c, hipMemcpyAsync(&nfb, ctl + 4, 4, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+                (void)hipEventElapsedTime(&deferred_ms, oev[2], oev[3]);
+            }
+            c->last_fallback = nfb;
+            // [0]: first fill's start to last fill's end, whichever stream it ends on (ordered schedule: dense passes included), [1]: the rest of the
+            // fold's device time, i.e. the exposed epilogue and the deferred dense passes with their epilogues
             float fill_ms = 0, all_ms = 0;
-            (void)hipEventElapsedTime(&fill_ms, oev[0], oev[2 + 2 * (n_chunks - 1)]);
+            for (int k = 0; k < n_chunks; k++) {
+                float f = 0;
+                (void)hipEventElapsedTime(&f, oev[0], oev[4 + 2 * k]);
+                fill_ms = std::max(fill_ms, f);
+            }
             (void)hipEventElapsedTime(&all_ms, oev[0], oev[1]);
-            c->fold_kernel_ms[0] = fill_ms; c->fold_kernel_ms[1] = std::max(0.0f, all_ms - fill_ms);
+            c->fold_kernel_ms[0] = fill_ms; c->fold_kernel_ms[1] = std::max(0.0f, all_ms - fill_ms) + deferred_ms;
 #ifdef MIRP_DIAG
             if (std::getenv("MIRP_FOLD_OVERLAP_TRACE")) {      // when each kernel ended, ms after the first fill's start
                 for (int k = 0; k < n_chunks; k++) {
                     float f = 0, e2 = 0;
-                    (void)hipEventElapsedTime(&f, oev[0], oev[2 + 2 * k]); (void)hipEventElapsedTime(&e2, oev[0], oev[2 + 2 * k + 1]);
+                    (void)hipEventElapsedTime(&f, oev[0], oev[4 + 2 * k]); (void)hipEventElapsedTime(&e2, oev[0], oev[4 + 2 * k + 1]);
                     std::fprintf(stderr, "[mirp fold overlap] chunk %d: %d windows, fill done %.3f ms, epilogue done %.3f ms\n", k, csize[k], f, e2);
                 }
-                std::fprintf(stderr, "[mirp fold overlap] all done %.3f ms, largest pool fill %u entries\n", all_ms, hctl[6]);
+                std::fprintf(stderr, "[mirp fold overlap] %s, all done %.3f ms, deferred dense %.3f ms, largest pool fill %u entries\n", tailfree ? "tail-free" : "ordered", all_ms,
+                             deferred_ms, hctl[6]);
             }
 #endif
             if (nfb == 0) return 0;

@@ -88,8 +88,10 @@ struct mirp_ctx {
     int fold_overlap = -1;               // mirp_set_fold_overlap: -1 = automatic, 0 = off (serial path), N > 0 = chunks of N windows
     int overlap_epi_wgs = -1;            // epilogue workgroups a CU holds beside two fill workgroups (fold_lds_overlap_epi_wgs), -1 = not asked yet
     int overlap_max_lines = -1;          //   ... at this number of structure lines
+    int fold_tailfree = -1;              // mirp_set_fold_overlap_tailfree: -1 = automatic (on), 0 = fills in order on one stream and a dense pass per chunk, 1 = on
     hipStream_t stream_epi = nullptr;    // created on the first chunked fold
-    std::vector<hipEvent_t> overlap_ev;  // [0] first fill starts, [1] all done, then per chunk: fill done, epilogue done; created on demand
+    hipStream_t stream_fill2 = nullptr;  // the fills of the odd chunks (tail-free schedule); created on the first fold that needs it
+    std::vector<hipEvent_t> overlap_ev;  // [0] first fill starts, [1] all done, [2] [3] around the deferred dense passes, then per chunk: fill done, epilogue done; created on demand
     int last_overlap_chunks = 0;         // chunks of the last mirp_run_fold (0: serial path)
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // ---- multi-GPU (mirp_dist.cpp): RCCL communicator of this context's device, one process per GPU

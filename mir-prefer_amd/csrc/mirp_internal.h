@@ -60,8 +60,10 @@ void fold_lds_epi_clocks_print();
 int fold_lds_max_n();
 int fold_lds_gen_wing_d();
 int fold_lds_max_span();
-// parts: the fill (candidate-pool pass and the dense pass over its hand-offs) and the epilogue of the windows can be launched apart, on two streams
-enum { MIRP_FOLD_PART_FILL = 1, MIRP_FOLD_PART_EPI = 2, MIRP_FOLD_PARTS_BOTH = 3 };
+// parts: the candidate-pool pass, the dense pass over its hand-offs (together: the fill) and the epilogue of the windows can be launched apart, on
+// streams of their own.  The pool and dense parts divide the default model's two-pass fill only; every other fill (vienna-1.8.5, force_dense) is
+// launched whole by either of them.
+enum { MIRP_FOLD_PART_POOL = 1, MIRP_FOLD_PART_EPI = 2, MIRP_FOLD_PART_DENSE = 4, MIRP_FOLD_PART_FILL = 5, MIRP_FOLD_PARTS_BOTH = 7 };
 hipError_t launch_fold_lds(hipStream_t stream, int model, int grid, int grid_epi, const FoldParams* P, const unsigned char* seqs, const long long* offs, const int* lens,
                            int n_work, int win_base, int span, short* slabs, size_t slab_shorts, int* win_state, unsigned int* work_counter, int* fallback_list,
                            unsigned int* fallback_count, int max_lines, int ss_stride, MirpFoldLine* out_lines, char* out_ss, int* out_nlines, int* out_mfe,

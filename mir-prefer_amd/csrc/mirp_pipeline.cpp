@@ -703,6 +703,12 @@ extern "C" int mirp_set_fold_overlap(mirp_ctx* c, int32_t chunk_windows) {
     c->fold_overlap = chunk_windows;
     return 0;
 }
+extern "C" int mirp_set_fold_overlap_tailfree(mirp_ctx* c, int32_t mode) {
+    if (!c) return -1;
+    if (mode < -1 || mode > 1) return fail(c, -1, "mirp_set_fold_overlap_tailfree: mode is -1 (automatic), 0 (fills in order on one stream) or 1 (tail-free)");
+    c->fold_tailfree = mode;
+    return 0;
+}
 extern "C" int mirp_last_fold_overlap_chunks(mirp_ctx* c) { return c ? c->last_overlap_chunks : -1; }
 extern "C" int64_t mirp_last_fold_dense(mirp_ctx* c) { return c ? (int64_t)c->last_dense : -1; }
 extern "C" int mirp_set_coverage_path(mirp_ctx* c, int32_t mode) {
