@@ -257,6 +257,11 @@ int mirp_set_fold_overlap(mirp_ctx* ctx, int32_t chunk_windows);
 int mirp_set_fold_overlap_tailfree(mirp_ctx* ctx, int32_t mode);
 /* Chunks the last fold call ran in (0: the serial path). */
 int mirp_last_fold_overlap_chunks(mirp_ctx* ctx);
+/* Windows whose slabs (three 16-bit triangles per window) the following folds hold on the device at once.  windows = 0: the default, 8 GiB of slabs;
+ * N > 0: at most N windows, never more than the default: the serial path folds sub-batches of N windows one behind the other, a slot of the chunked
+ * fold's ring of three holds max(1, N / 3).  Every output, mirp_last_fold_dense and mirp_last_fold_fallbacks are identical whatever is set; lowered
+ * only to test the sub-batch path and small ring slots.  A negative value returns -1. */
+int mirp_set_fold_capacity(mirp_ctx* ctx, int64_t windows);
 
 /* Device time of the kernels of the last mirp_fold, HIP events: two numbers whose sum is the device time of the fold's main pass.  Serial path:
  * ms[0] = fill kernel(s) (fold_lds_kernel: the dynamic program), ms[1] = epilogue kernel(s) (exterior sweep, enumeration, backtracks), summed

@@ -410,6 +410,8 @@ def load_library():
     lib.mirp_set_fold_overlap.restype = C.c_int
     lib.mirp_set_fold_overlap_tailfree.argtypes = [vp, C.c_int32]
     lib.mirp_set_fold_overlap_tailfree.restype = C.c_int
+    lib.mirp_set_fold_capacity.argtypes = [vp, C.c_int64]
+    lib.mirp_set_fold_capacity.restype = C.c_int
     lib.mirp_last_fold_overlap_chunks.argtypes = [vp]
     lib.mirp_last_fold_overlap_chunks.restype = C.c_int
     lib.mirp_last_fold_dense.argtypes = [vp]
@@ -1232,6 +1234,10 @@ class Context:
         """-1: automatic (default: on), 1: the fills of neighbouring chunks on two streams, no idle CUs at a chunk boundary, dense hand-offs folded
         behind the last epilogue, 0: fills in order on one stream with a dense pass per chunk.  Same results either way."""
         self._check(self.lib.mirp_set_fold_overlap_tailfree(self.h, int(mode)), "mirp_set_fold_overlap_tailfree")
+
+    def set_fold_capacity(self, windows):
+        """Windows whose slabs the fold holds on the device at once (0 = the default, 8 GiB of slabs): lowered only to test the sub-batch path."""
+        self._check(self.lib.mirp_set_fold_capacity(self.h, int(windows)), "mirp_set_fold_capacity")
 
     def last_fold_overlap_chunks(self):
         """Chunks the last fold ran in; 0: the serial path."""

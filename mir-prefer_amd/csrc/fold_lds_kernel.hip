@@ -25,6 +25,7 @@
 // No MFMA: integer min-plus DP with irregular table lookups.
 #include <algorithm>
 #include "fold_lds_common.h"
+#include "fold_ctl.h"      // the control block's words, named once for fold_lds_kernel_body.h and the driver
 // In-place compaction of the split-candidate pool, period in diagonals per model (0 = never) and the number of 64-entry rounds a wave holds in registers.
 #ifndef MIRP_CPERIOD0
 #define MIRP_CPERIOD0 0       // default model: never (925 entries: a compaction's two barriers cost more than the dead lanes; measured 60.9 / 61.7 / 62.1 / 62.9 ms at never / 128 / 64 / 32)
@@ -298,93 +299,67 @@ int fold_lds_max_n() { return LCAP - 2; }
 int fold_lds_gen_wing_d() { return 5; }      // GEN_WD of fold_lds_kernel<0>
 int fold_lds_max_span() { return LSPAN; }
 
-// ctl (= work_counter): [0] work counter of the fill kernel, [1] of the epilogue, [2] work counter of the dense second pass, [3] windows handed to it
-// (dense_list: their indices), [4] windows handed to the generic kernel, [5] running total of [3] over the sub-batches
-hipError_t launch_fold_lds(hipStream_t stream, int model, int grid, int grid_epi, const FoldParams* P, const unsigned char* seqs, const long long* offs, const int* lens,
-                           int n_work, int win_base, int span, short* slabs, size_t slab_shorts, int* win_state, unsigned int* work_counter, int* fallback_list,
-                           unsigned int* fallback_count, int max_lines, int ss_stride, MirpFoldLine* out_lines, char* out_ss, int* out_nlines, int* out_mfe,
-                           int* out_status, int light_clocks, long long* dbg_cycles, hipEvent_t ev_between, int* dense_list, int force_dense, int parts) {
-    const size_t lds = model ? lds_layout<1>().total : lds_layout<0>().total;
-    const size_t lds_sp = lds_layout<0, true, true>().total, lds_sp1 = lds_layout<1, true>().total;
-    hipError_t e = hipFuncSetAttribute((const void*)fold_lds_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_layout<1>().total);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fold_lds_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_layout<0>().total);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fold_lds_kernel<0, true, LNT2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sp);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)fold_lds_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_layout<1, true>().total);
-    if (e != hipSuccess) return e;
-    const int* no_list = nullptr; const unsigned int* no_count = nullptr;
-    const bool two_pass = !model && !force_dense;      // the only fill that the pool and dense parts divide; any other goes with the pool part
-    if (!(parts & (two_pass ? MIRP_FOLD_PART_FILL : MIRP_FOLD_PART_POOL))) {
-    } else
-    if (model) {
-        // vienna-1.8.5: with dangles 1 every pair gives up to four strictly pair-realised fML cells ((i,j), (i-1,j), (i,j+1), (i-1,j+1)), i.e. about four
-        // times the candidate cells of the default model (3,142 per benchmark window: a cell pool overflowed for most windows, 161 ms = both passes);
-        // the pool of this instantiation holds PAIRS instead (1,283 per window, 8-byte entries: splits_sparse185).
-        const bool sparse185 = !force_dense;
-        if (sparse185) {      // as the default model below: candidate-pool pass, then the dense instantiation over what it handed over
-            hipLaunchKernelGGL((fold_lds_kernel<1, true>), dim3(grid), dim3(LNT), lds_sp1, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter,
-                               fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, light_clocks, dbg_cycles,
-                               no_list, no_count, dense_list, work_counter + 3);
-            e = hipGetLastError();
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((fold_lds_kernel<1, false>), dim3(grid), dim3(LNT), lds, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter + 2,
-                               fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, light_clocks, dbg_cycles,
-                               (const int*)dense_list, (const unsigned int*)(work_counter + 3), dense_list, work_counter + 3);
-        } else
-            hipLaunchKernelGGL((fold_lds_kernel<1, false>), dim3(grid), dim3(LNT), lds, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter,
-                               fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, light_clocks, dbg_cycles,
-                               no_list, no_count, dense_list, work_counter + 3);
-    } else {
-        // product: first pass with sparse multiloop splits (candidate pool), then the dense instantiation over the windows the first pass handed over
-        // (pool overflow, no room for a pool: zero on the benchmark inputs; the launch then finds an empty list).  force_dense (tests, A/B timing): the
-        // dense instantiation folds everything.
-        if (!force_dense) {
-            // The first pass runs two 512-thread workgroups per CU, which is the whole point of its LDS layout: refuse to run at half the occupancy if a
-            // later change of its LDS or register budget no longer lets two of them share a CU.
-            static int wg_per_cu = 0;
-            if (wg_per_cu == 0) {
-                int nb = 0;
-                e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)fold_lds_kernel<0, true, LNT2>, LNT2, lds_sp);
-                if (e != hipSuccess) return e;
-                wg_per_cu = nb > 0 ? nb : -1;
-            }
-            if (wg_per_cu != 2) {
-                std::fprintf(stderr, "[mirp] fold_lds_kernel<0, true, %d>: %d workgroups per CU instead of 2 (%zu bytes of LDS)\n", LNT2, wg_per_cu, lds_sp);
-                return hipErrorLaunchOutOfResources;
-            }
-            const int grid2 = n_work < 2 * grid ? n_work : 2 * grid;
-            if (parts & MIRP_FOLD_PART_POOL) {
-                hipLaunchKernelGGL((fold_lds_kernel<0, true, LNT2>), dim3(grid2), dim3(LNT2), lds_sp, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter,
-                                   fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, light_clocks, dbg_cycles,
-                                   no_list, no_count, dense_list, work_counter + 3);
-                e = hipGetLastError();
-                if (e != hipSuccess) return e;
-            }
-            if (parts & MIRP_FOLD_PART_DENSE)      // launched apart (tail-free fold overlap): over the list and the count a pool pass left in dense_list / work_counter[3]
-                hipLaunchKernelGGL((fold_lds_kernel<0, false>), dim3(grid), dim3(LNT), lds, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter + 2,
-                                   fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, light_clocks, dbg_cycles,
-                                   (const int*)dense_list, (const unsigned int*)(work_counter + 3), dense_list, work_counter + 3);
-        } else
-            hipLaunchKernelGGL((fold_lds_kernel<0, false>), dim3(grid), dim3(LNT), lds, stream, P, seqs, offs, lens, n_work, win_base, span, slabs, slab_shorts, win_state, work_counter,
-                               fallback_list, fallback_count, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status, light_clocks, dbg_cycles,
-                               no_list, no_count, dense_list, work_counter + 3);
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (ev_between) { e = hipEventRecord(ev_between, stream); if (e != hipSuccess) return e; }   // fill | epilogue boundary (mirp_last_fold_kernel_ms)
-    if (!(parts & MIRP_FOLD_PART_EPI)) return hipSuccess;
-    if (model) {
-        const size_t el = fold185_lds_epilogue_bytes(max_lines);
-        if (el > 64 * 1024) {
-            e = hipFuncSetAttribute((const void*)fold185_lds_epilogue_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)el);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(fold185_lds_epilogue_kernel, dim3(grid_epi), dim3(ENT), el, stream, P, seqs, offs, lens, n_work, span, slabs, slab_shorts, win_state,
-                           work_counter + 1, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status);
-    } else {
-        hipLaunchKernelGGL(fold_lds_epilogue_kernel, dim3(grid_epi), dim3(ENT), fold_lds_epilogue_bytes(max_lines), stream, P, seqs, offs, lens, n_work, span,
-                           slabs, slab_shorts, win_state, work_counter + 1, max_lines, ss_stride, out_lines, out_ss, out_nlines, out_mfe, out_status);
-    }
+// ---- launches (mirp_fold.cpp composes them).  One fill pass: a kernel of fold_lds_kernel's signature, its workgroup, its LDS and how many of its
+// workgroups a CU holds -- the grid is that many per CU the caller asks for, at most one per window.
+using FillKernel = decltype(&fold_lds_kernel<0, false, LNT>);
+struct FillPass { FillKernel kernel; int threads; size_t lds; int per_cu; };
+// The dense pass: the dense split loop, over the windows a pool pass handed over (pool overflow, no room for a pool: none on the benchmark inputs, the
+// launch then finds an empty list) or over every window (mirp_set_fold_split_path(1): tests, A/B timing).
+static FillPass dense_pass(int model) {
+    return model ? FillPass{fold_lds_kernel<1, false>, LNT, lds_layout<1>().total, 1} : FillPass{fold_lds_kernel<0, false>, LNT, lds_layout<0>().total, 1};
+}
+// The candidate-pool pass: sparse multiloop splits, the product's first pass.  Default model: two 512-thread workgroups per CU.  vienna-1.8.5: with
+// dangles 1 every pair gives up to four strictly pair-realised fML cells ((i,j), (i-1,j), (i,j+1), (i-1,j+1)), i.e. about four times the candidate
+// cells of the default model (3,142 per benchmark window: a cell pool overflowed for most windows, 161 ms = both passes); the pool of that
+// instantiation holds PAIRS instead (1,283 per window, 8-byte entries: splits_sparse185).
+static FillPass pool_pass(int model) {
+    return model ? FillPass{fold_lds_kernel<1, true>, LNT, lds_layout<1, true>().total, 1} : FillPass{fold_lds_kernel<0, true, LNT2>, LNT2, lds_layout<0, true, true>().total, 2};
+}
+
+// counter: the work counter of the block the pass draws from; from_list: over the block's dense list, which it may itself extend, instead of every window
+static hipError_t launch_fill(const FillPass& f, hipStream_t stream, int grid, const FoldLdsArgs& a, int counter, bool from_list) {
+    unsigned int* const list_len = a.ctl + FOLD_CTL_DENSE_LEN;
+    hipLaunchKernelGGL(f.kernel, dim3(std::min(a.n_work, f.per_cu * grid)), dim3(f.threads), f.lds, stream, a.P, a.seqs, a.offs, a.lens, a.n_work, a.win_base, a.span, a.slabs,
+                       a.slab_shorts, a.win_state, a.ctl + counter, a.fallback_list, a.fallback_count, a.max_lines, a.ss_stride, a.out_lines, a.out_ss, a.out_nlines, a.out_mfe,
+                       a.out_status, a.light_clocks, a.dbg_cycles, from_list ? (const int*)a.dense_list : nullptr, from_list ? (const unsigned int*)list_len : nullptr,
+                       a.dense_list, list_len);
     return hipGetLastError();
+}
+
+hipError_t launch_fold_lds_pool(hipStream_t stream, int model, int grid, const FoldLdsArgs& a) { return launch_fill(pool_pass(model), stream, grid, a, FOLD_CTL_FILL, false); }
+
+hipError_t launch_fold_lds_dense(hipStream_t stream, int model, int grid, const FoldLdsArgs& a, bool every_window) {
+    return launch_fill(dense_pass(model), stream, grid, a, every_window ? FOLD_CTL_FILL : FOLD_CTL_DENSE, !every_window);
+}
+
+template <class K>
+static hipError_t launch_epilogue(K kernel, size_t lds, hipStream_t stream, int grid, const FoldLdsArgs& a) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(ENT), lds, stream, a.P, a.seqs, a.offs, a.lens, a.n_work, a.span, a.slabs, a.slab_shorts, a.win_state, a.ctl + FOLD_CTL_EPILOGUE,
+                       a.max_lines, a.ss_stride, a.out_lines, a.out_ss, a.out_nlines, a.out_mfe, a.out_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_fold_lds_epilogue(hipStream_t stream, int model, int grid, const FoldLdsArgs& a) {
+    return model ? launch_epilogue(fold185_lds_epilogue_kernel, fold185_lds_epilogue_bytes(a.max_lines), stream, grid, a)
+                 : launch_epilogue(fold_lds_epilogue_kernel, fold_lds_epilogue_bytes(a.max_lines), stream, grid, a);
+}
+
+// What the launches above rely on, on the current device: the LDS every fill pass and, where max_lines asks for more than 64 KB, the vienna-1.8.5
+// epilogue may take, and two workgroups of the default model's candidate-pool pass per CU -- the whole point of its LDS layout: refuse to run at half
+// the occupancy if a later change of its LDS or register budget no longer lets two of them share a CU.
+hipError_t fold_lds_prepare(int max_lines) {
+    for (const FillPass& f : {pool_pass(0), pool_pass(1), dense_pass(0), dense_pass(1)})
+        if (hipError_t e = hipFuncSetAttribute((const void*)f.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds)) return e;
+    if (const size_t el = fold185_lds_epilogue_bytes(max_lines); el > 64 * 1024)
+        if (hipError_t e = hipFuncSetAttribute((const void*)fold185_lds_epilogue_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)el)) return e;
+    const FillPass two = pool_pass(0);
+    int per_cu = 0;
+    if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)two.kernel, two.threads, two.lds)) return e;
+    if (per_cu != two.per_cu) {
+        std::fprintf(stderr, "[mirp] fold_lds_kernel<0, true, %d>: %d workgroups per CU instead of 2 (%zu bytes of LDS)\n", LNT2, per_cu > 0 ? per_cu : -1, two.lds);
+        return hipErrorLaunchOutOfResources;
+    }
+    return hipSuccess;
 }
 
 // A SIMD of gfx950 has 512 VGPRs handed out in blocks of 8 and 8 wave slots; a CU has 160 KB of LDS in granules of 1280 bytes.  A workgroup of the

@@ -96,7 +96,7 @@
     __syncthreads();
 
     const int n_todo = todo_count ? (int)*todo_count : n_work;      // second pass: the windows the sparse pass handed over
-    if (todo_count && blockIdx.x == 0 && tid == 0 && n_todo) atomicAdd(const_cast<unsigned int*>(todo_count) + 2, (unsigned)n_todo);   // ctl[5]: running total for mirp_last_fold_dense
+    if (todo_count && blockIdx.x == 0 && tid == 0 && n_todo) atomicAdd(const_cast<unsigned int*>(todo_count) + (FOLD_CTL_DENSE_TOTAL - FOLD_CTL_DENSE_LEN), (unsigned)n_todo);   // running total for mirp_last_fold_dense
     for (;;) {
         if (tid == 0) misc[0] = (int)atomicAdd(work_counter, 1u);
         __syncthreads();
@@ -979,7 +979,7 @@
         if (dbg_cycles && tid == 0) { long long t = clock64(); tE += t - t0; t0 = t; }
         const int pool_over = SPARSE ? misc[2] : 0;
 #ifdef MIRP_DIAG
-        if (SPARSE && TWO && tid == 0) atomicMax(fallback_count + 2, (unsigned)misc[3]);      // ctl[6]: largest pool fill of the call (printed by mirp_run_fold)
+        if (SPARSE && TWO && tid == 0) atomicMax(fallback_count + (FOLD_CTL_POOL_MAX - FOLD_CTL_FALLBACKS), (unsigned)misc[3]);      // largest pool fill of the call (printed by the diagnostics build)
 #endif
         if (overflow) {   // int16 range exceeded: hand the window to the generic kernel
             if (tid == 0) { unsigned int k = atomicAdd(fallback_count, 1u); fallback_list[k] = win_base + win; out_nlines[win] = 0; out_mfe[win] = 0; out_status[win] = 0; win_state[win] = 0; }

@@ -1,6 +1,7 @@
-// The chunk plan of the fold overlap (mirp_run_fold; DESIGN.md §17, rounds 9 and 10).  Host only: no HIP, no context, nothing of the project.
-// A batch of n_work windows is cut into chunks; the epilogue of chunk k runs beside the fill of chunk k + 1, and the archive is a ring of slots that
-// hold one chunk each.  An empty plan means the serial path.
+// The chunk plan and the ring layout of the fold overlap (run_chunked in mirp_fold.cpp; DESIGN.md §17, rounds 9 and 10).  Host only: no HIP, no context,
+// nothing of the project, so that a CPU test can compile it alone.  A batch of n_work windows is cut into chunks (fold_overlap_plan); the epilogue of
+// chunk k runs beside the fill of chunk k + 1, and the archive is a ring of slots that hold one chunk each (fold_overlap_ring).  An empty plan means
+// the serial path.
 #pragma once
 #include <cstddef>
 #include <vector>
@@ -73,6 +74,21 @@ inline std::vector<int> fold_overlap_plan(long long n_work, long long round, lon
     }
     if (plan.size() < 2) plan.clear();
     return plan;
+}
+
+// The archive of a chunked fold: FOLD_RING_SLOTS slots side by side, chunk k in slot k % FOLD_RING_SLOTS, which it takes over from chunk
+// k - FOLD_RING_SLOTS once that chunk's epilogue is done.  A slot is as large as its largest chunk: cap[s] windows from window at[s] of the archive on.
+constexpr int FOLD_RING_SLOTS = 3;
+struct FoldRing {
+    size_t cap[FOLD_RING_SLOTS], at[FOLD_RING_SLOTS + 1];
+    size_t windows() const { return at[FOLD_RING_SLOTS]; }      // of the whole ring
+};
+inline FoldRing fold_overlap_ring(const std::vector<int>& plan) {
+    FoldRing r = {};
+    for (size_t k = 0; k < plan.size(); k++)
+        if ((size_t)plan[k] > r.cap[k % FOLD_RING_SLOTS]) r.cap[k % FOLD_RING_SLOTS] = (size_t)plan[k];
+    for (int s = 0; s < FOLD_RING_SLOTS; s++) r.at[s + 1] = r.at[s] + r.cap[s];
+    return r;
 }
 
 }  // namespace mirp

@@ -25,7 +25,7 @@ struct DevBuf {
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
     DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;              // owns its allocation: never copied, freed when its owner goes (a buffer left out of mirp_destroy's list)
+    DevBuf(const DevBuf&) = delete;              // owns its allocation: never copied, freed when its owner goes (~mirp_ctx frees every buffer of a context)
     DevBuf& operator=(const DevBuf&) = delete;
     ~DevBuf() { release(); }
 };
@@ -83,16 +83,16 @@ struct mirp_ctx {
     int shard_first_run_double = 0;   // contig shard whose first covered contig is not the first covered contig of the whole genome
     double ms[4] = {0, 0, 0, 0};
     double fold_kernel_ms[2] = {0, 0};   // fill / epilogue kernels of the last mirp_run_fold (LDS-resident path)
-    std::vector<hipEvent_t> fold_ev;     // 3 events per sub-batch, created on demand
+    std::vector<hipEvent_t> fold_ev;     // the fold's events, created on demand; mirp_fold.cpp names the ones a path uses
+    int fold_prepared_lines = -1;        // max_lines that fold_lds_prepare and overlap_epi_wgs were last asked at on this context's device, -1 = not yet
     // ---- fold overlap (mirp_run_fold): the epilogue of a chunk of windows runs on a stream of its own beside the fill of the next chunk
     int fold_overlap = -1;               // mirp_set_fold_overlap: -1 = automatic, 0 = off (serial path), N > 0 = chunks of N windows
-    int overlap_epi_wgs = -1;            // epilogue workgroups a CU holds beside two fill workgroups (fold_lds_overlap_epi_wgs), -1 = not asked yet
-    int overlap_max_lines = -1;          //   ... at this number of structure lines
+    int overlap_epi_wgs = -1;            // epilogue workgroups a CU holds beside two fill workgroups (fold_lds_overlap_epi_wgs) at fold_prepared_lines structure lines
     int fold_tailfree = -1;              // mirp_set_fold_overlap_tailfree: -1 = automatic (on), 0 = fills in order on one stream and a dense pass per chunk, 1 = on
     hipStream_t stream_epi = nullptr;    // created on the first chunked fold
     hipStream_t stream_fill2 = nullptr;  // the fills of the odd chunks (tail-free schedule); created on the first fold that needs it
-    std::vector<hipEvent_t> overlap_ev;  // [0] first fill starts, [1] all done, [2] [3] around the deferred dense passes, then per chunk: fill done, epilogue done; created on demand
     int last_overlap_chunks = 0;         // chunks of the last mirp_run_fold (0: serial path)
+    long long fold_cap = 0;              // windows whose slabs are resident at once; 0 = the default, 8 GiB of slabs (mirp_set_fold_capacity)
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // ---- multi-GPU (mirp_dist.cpp): RCCL communicator of this context's device, one process per GPU
     void* comm = nullptr;
@@ -196,8 +196,6 @@ inline int mirp_download_text(mirp_ctx* c, const char* d_text, long long bytes, 
     return 0;
 }
 
-// Folds n_work device-resident windows (seqs/offs/lens as the kernels expect) into the context's fold output buffers.
-// Uses the LDS-resident kernel when span allows and re-runs flagged windows (length / int16 range) with the generic kernel.
 // sort_kernels.hip: stable device sort by (tid, pos) / keep-region filter of the resident record array
 int mirp_device_sort_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long n, int posbits, int tidbits);
 int mirp_device_sort_u64(mirp_ctx* c, unsigned long long* d, unsigned long long* d_tmp, long long n, int base, int bits);
@@ -315,5 +313,7 @@ int dist_allgather_ll(mirp_ctx* c, const long long* mine, int n, std::vector<lon
 int dist_agree(mirp_ctx* c, int local_rc, const char* what);
 }  // namespace mirp
 
+// mirp_fold.cpp: folds n_work device-resident windows (seqs / offs / lens as the kernels expect) into the given output buffers.  Uses the LDS-resident
+// kernels when the span allows and re-runs the windows they flag (length, 16-bit range) with the generic kernel.
 int mirp_run_fold(mirp_ctx* c, const unsigned char* d_seqs, const long long* d_offs, const int* d_lens, int n_work, int n_cap, int span,
                   int max_lines, int stride, MirpFoldLine* d_lines, char* d_ss, int* d_nlines, int* d_mfe, int* d_status);

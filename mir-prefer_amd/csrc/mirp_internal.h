@@ -60,15 +60,26 @@ void fold_lds_epi_clocks_print();
 int fold_lds_max_n();
 int fold_lds_gen_wing_d();
 int fold_lds_max_span();
-// parts: the candidate-pool pass, the dense pass over its hand-offs (together: the fill) and the epilogue of the windows can be launched apart, on
-// streams of their own.  The pool and dense parts divide the default model's two-pass fill only; every other fill (vienna-1.8.5, force_dense) is
-// launched whole by either of them.
-enum { MIRP_FOLD_PART_POOL = 1, MIRP_FOLD_PART_EPI = 2, MIRP_FOLD_PART_DENSE = 4, MIRP_FOLD_PART_FILL = 5, MIRP_FOLD_PARTS_BOTH = 7 };
-hipError_t launch_fold_lds(hipStream_t stream, int model, int grid, int grid_epi, const FoldParams* P, const unsigned char* seqs, const long long* offs, const int* lens,
-                           int n_work, int win_base, int span, short* slabs, size_t slab_shorts, int* win_state, unsigned int* work_counter, int* fallback_list,
-                           unsigned int* fallback_count, int max_lines, int ss_stride, MirpFoldLine* out_lines, char* out_ss, int* out_nlines, int* out_mfe,
-                           int* out_status, int light_clocks, long long* dbg_cycles, hipEvent_t ev_between, int* dense_list, int force_dense,
-                           int parts = MIRP_FOLD_PARTS_BOTH);
+// What the launches of one sub-batch (serial path) or chunk share.  Window w of it is window win_base + w of the call: offs, lens, the outputs and
+// dense_list start at its first window, slabs and win_state at its place in the archive; ctl is its block of the control block (fold_ctl.h).
+struct FoldLdsArgs {
+    const FoldParams* P; const unsigned char* seqs; const long long* offs; const int* lens;
+    int n_work, win_base, span;
+    short* slabs; size_t slab_shorts; int* win_state;
+    unsigned int* ctl; int* fallback_list; unsigned int* fallback_count;      // the fallback list and its length belong to the call
+    MirpFoldLine* out_lines; char* out_ss; int* out_nlines; int* out_mfe; int* out_status;
+    int max_lines, ss_stride;
+    int* dense_list;
+    int light_clocks; long long* dbg_cycles;      // diagnostics build only
+};
+// Once per context (it is bound to one device) and number of structure lines, before the first launch: the kernels' LDS limits, and the check that a
+// CU holds two workgroups of the default model's candidate-pool pass (else a line on stderr and hipErrorLaunchOutOfResources).
+hipError_t fold_lds_prepare(int max_lines);
+// grid: CUs' worth of workgroups (the pass knows how many a CU holds).  The pool pass leaves the windows it cannot fold in the dense list; the dense
+// pass folds that list, or every window without a pool pass before it.  A fill is the pool pass and the dense pass behind it, or the dense pass alone.
+hipError_t launch_fold_lds_pool(hipStream_t stream, int model, int grid, const FoldLdsArgs& a);
+hipError_t launch_fold_lds_dense(hipStream_t stream, int model, int grid, const FoldLdsArgs& a, bool every_window);
+hipError_t launch_fold_lds_epilogue(hipStream_t stream, int model, int grid, const FoldLdsArgs& a);      // grid: workgroups
 // Epilogue workgroups (fold_lds_epilogue_kernel at max_lines) that registers, wave slots and LDS let a CU hold beside two workgroups of the default
 // model's candidate-pool pass (at most the number its LDS layout was made for), from the kernels' own attributes; 0 = none (the chunked fold then takes the serial path), < 0 = a HIP error.
 int fold_lds_overlap_epi_wgs(int max_lines);

@@ -709,6 +709,12 @@ extern "C" int mirp_set_fold_overlap_tailfree(mirp_ctx* c, int32_t mode) {
     c->fold_tailfree = mode;
     return 0;
 }
+extern "C" int mirp_set_fold_capacity(mirp_ctx* c, int64_t windows) {
+    if (!c) return -1;
+    if (windows < 0) return fail(c, -1, "mirp_set_fold_capacity: windows is 0 (the default) or a number of windows");
+    c->fold_cap = windows;
+    return 0;
+}
 extern "C" int mirp_last_fold_overlap_chunks(mirp_ctx* c) { return c ? c->last_overlap_chunks : -1; }
 extern "C" int64_t mirp_last_fold_dense(mirp_ctx* c) { return c ? (int64_t)c->last_dense : -1; }
 extern "C" int mirp_set_coverage_path(mirp_ctx* c, int32_t mode) {

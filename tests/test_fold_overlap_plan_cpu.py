@@ -1,6 +1,7 @@
 """CPU tests of the chunk plan of the fold overlap (mir-prefer_amd/csrc/fold_overlap_plan.h): a small driver that includes the
 header and nothing else of the project is compiled with the host C++ compiler.  It prints the header's constants, then for every input line
-`n_work round cap request schedule` the chunk sizes of the plan on one line (an empty line: the serial path)."""
+`n_work round cap request schedule` the chunk sizes of the plan on one line (an empty line: the serial path); started with the argument `ring` it
+prints the plan's ring layout instead (fold_overlap_ring): the number of slots, their capacities and their first windows, the last being the total."""
 import itertools
 import os
 import shutil
@@ -14,13 +15,21 @@ DRIVER = r"""
 #include <cstdio>
 #include "fold_overlap_plan.h"
 
-int main() {
+int main(int argc, char**) {
     std::printf("%d %d %d %d %d\n", mirp::FOLD_OVERLAP_CHUNKS, mirp::FOLD_OVERLAP_MIN_ROUNDS, mirp::FOLD_OVERLAP_EPI_RATIO_PERMILLE,
                 mirp::FOLD_OVERLAP_TAPER_PERMILLE, mirp::FOLD_OVERLAP_LAST_ROUNDS);
     long long n, round, cap, request;
     int schedule;
     while (std::scanf("%lld %lld %lld %lld %d", &n, &round, &cap, &request, &schedule) == 5) {
         const std::vector<int> plan = mirp::fold_overlap_plan(n, round, cap, request, schedule);
+        if (argc > 1) {
+            const mirp::FoldRing ring = mirp::fold_overlap_ring(plan);
+            std::printf("%d", mirp::FOLD_RING_SLOTS);
+            for (int s = 0; s < mirp::FOLD_RING_SLOTS; s++) std::printf(" %zu", ring.cap[s]);
+            for (int s = 0; s <= mirp::FOLD_RING_SLOTS; s++) std::printf(" %zu", ring.at[s]);
+            std::printf(" %zu\n", ring.windows());
+            continue;
+        }
         for (size_t k = 0; k < plan.size(); k++) std::printf("%s%d", k ? " " : "", plan[k]);
         std::printf("\n");
     }
@@ -40,10 +49,10 @@ def plan(tmp_path_factory):
     (d / "driver.cpp").write_text(DRIVER)
     subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "mir-prefer_amd", "csrc"), str(d / "driver.cpp"), "-o", str(d / "driver")])
 
-    def run(cases):
-        """cases: (n_work, round, cap, request, schedule) each -> (the header's constants, the chunk sizes of each)"""
+    def run(cases, ring=False):
+        """cases: (n_work, round, cap, request, schedule) each -> (the header's constants, the chunk sizes of each, or with `ring` the ring's numbers)"""
         text = "".join("%d %d %d %d %d\n" % c for c in cases)
-        out = subprocess.run([str(d / "driver")], input=text.encode(), capture_output=True, timeout=60, check=True).stdout.decode().split("\n")[:-1]
+        out = subprocess.run([str(d / "driver")] + (["ring"] if ring else []), input=text.encode(), capture_output=True, timeout=60, check=True).stdout.decode().split("\n")[:-1]
         assert len(out) == 1 + len(cases)
         return tuple(int(x) for x in out[0].split()), [[int(x) for x in ln.split()] for ln in out[1:]]
     return run
@@ -116,3 +125,24 @@ def test_the_tailfree_plan_of_the_benchmark_batches(plan):
     for n, sizes in zip((19686, 70244), got):
         assert sum(sizes) == n and sizes[-1] == last_rounds * 512 and max(sizes) <= 7680
         assert sizes[1:] == sorted(sizes[1:], reverse=True)
+
+
+def test_the_ring_holds_every_chunk_in_slot_k_mod_3_without_overlap(plan):
+    """fold_overlap_ring over every plan of GRID: chunk k sits in slot k % 3 and fits it, the slots lie side by side, and the whole ring is the sum of
+    the per-slot maxima, at most three slots of the capacity."""
+    _, plans = plan(GRID)
+    _, rings = plan(GRID, ring=True)
+    n_plans = 0
+    for (n, rnd, cap, req, sched), sizes, ring in zip(GRID, plans, rings):
+        slots, caps, at, total = ring[0], ring[1:4], ring[4:8], ring[8]
+        assert slots == 3 and len(ring) == 9
+        per_slot = [max(sizes[s::3], default=0) for s in range(3)]
+        assert caps == per_slot, (n, rnd, cap, req, sched)
+        for k, size in enumerate(sizes):
+            assert at[k % 3] + size <= at[k % 3] + caps[k % 3] == at[k % 3 + 1]       # chunk k: slot k % 3, inside it, and the next slot starts behind it
+        assert at[0] == 0 and all(at[s] + caps[s] <= at[s + 1] for s in range(3))     # no two slots overlap
+        assert total == at[3] == sum(per_slot)
+        if sizes:
+            n_plans += 1
+            assert total <= 3 * cap, (n, rnd, cap, req, sched)
+    assert n_plans > len(GRID) // 3
