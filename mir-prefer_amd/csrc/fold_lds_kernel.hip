@@ -34,6 +34,12 @@
 #define MIRP_CPERIOD1 64      // vienna-1.8.5 (1,283 pair entries, 70 instructions per visit): 89.5 ms without, 87.3 / 85.9 / 85.6 / 85.0 at 8 / 16 / 32 / 64
 #endif
 #define CPOOL_ROUNDS 4
+#ifndef MIRP_A1_FUSE
+#define MIRP_A1_FUSE 1        // default model, two windows per CU: both roles of a wave in one pass over the blocks (0: timing build, role-outer as before round 12)
+#endif
+#ifndef MIRP_PHASEB_SKIP
+#define MIRP_PHASEB_SKIP 1    // default model, two windows per CU: waves without a cell of the diagonal branch round phase B (0: timing build, see phaseB0)
+#endif
 
 namespace mirp {
 
@@ -58,9 +64,12 @@ namespace mirp {
 // interval and consumed behind them.
 // Visibility of those cells: producer and consumer are waves of ONE workgroup, i.e. of one CU and one vector L1, and the cell a gather of
 // interval d reads was stored by phase B at least three __syncthreads() earlier.  __syncthreads() is a workgroup-scope release / acquire fence
-// over global memory as well (every wave drains its stores, s_waitcnt vmcnt(0), before it enters the barrier), and stores write through the L1 the
-// loads go through; nothing is handed between workgroups.  Plain loads are therefore enough -- no sc1, no cache invalidate -- and nothing here
-// relies on timing.
+// over global memory as well.  What that fence compiles to here is s_waitcnt lgkmcnt(0) alone in front of every s_barrier -- NOT a drain of the
+// stores: the only vmcnt(0) of an interval stands at the top of phase B.  That is the compiler's workgroup-scope rule for a kernel that does not
+// run in threadgroup-split mode (this one does not): all waves of the workgroup sit on one CU, their vector memory operations go through that
+// CU's one L1 in the order they were issued, and stores write through it, so a store issued before the producer's barrier is ahead, in that L1,
+// of any load a consumer issues behind the barrier.  Only tgsplit code objects need vmcnt(0) for workgroup scope.  Nothing is handed between
+// workgroups.  Plain loads are therefore enough -- no sc1, no cache invalidate -- and nothing here relies on timing.
 // The 16 interior-loop roles run two to a wave (see `role` in phase A1).  The two workgroups of a CU have independent barrier chains: one window's barrier wait
 // and phase-B chain are covered by the other window's interior loops.
 template <int MODEL, bool SPARSE, int NT = LNT>
@@ -88,7 +97,11 @@ __device__ __forceinline__ void fold_lds_body(
     unsigned int* __restrict__ fallback_count, int max_lines, int ss_stride, MirpFoldLine* __restrict__ out_lines, char* __restrict__ out_ss,
     int* __restrict__ out_nlines, int* __restrict__ out_mfe, int* __restrict__ out_status, int light_clocks_arg, long long* __restrict__ dbg_cycles_arg,
     const int* __restrict__ todo_list, const unsigned int* __restrict__ todo_count, int* __restrict__ dense_list, unsigned int* __restrict__ dense_count) {
+#if MIRP_A1_FUSE
+#define MIRP_A1_FUSED      // this copy of the body is the two-windows-per-CU instantiation alone: its interior loops run block-outer (see MIRP_A1_FUSED there)
+#endif
 #include "fold_lds_kernel_body.h"
+#undef MIRP_A1_FUSED
 }
 #ifndef MIRP_FILL_TWO_ATTR
 #define MIRP_FILL_TWO_ATTR __attribute__((amdgpu_num_vgpr(56)))

@@ -478,28 +478,51 @@
                 // roles (0-7: generic rows, 8-13: bulges / 1xn, 14-15: small shapes), measured job costs (MIRP_FOLD_CLOCKS): generic 2-row < small
                 // shapes < generic 4-row < bulges / 1xn.  Phase B of the previous diagonal runs on waves 0-5 (one thread per cell, wave 0 always,
                 // wave 5 rarely), so those waves take the cheapest jobs.
-                // Two windows per CU: eight waves, two roles each, one after the other over all blocks.  The phase-B waves 0-3 take a cheap 2-row generic job
+                // Two windows per CU: eight waves, two roles each, one after the other on every block (MIRP_A1_FUSED below).  The phase-B waves 0-3 take a cheap 2-row generic job
                 // and a bulge / 1xn job (roles w, w + 8), the waves 4-5 (phase-B cells on the first diagonals only) a small-shape and a 3-4-row generic job
                 // (14 | 4, 15 | 5), the waves 6-7 a bulge / 1xn and a 3-4-row generic job (12 | 6, 13 | 7).  Measured against six other maps: all within 2 %,
                 // this one first; three roles on any one wave cost 14 % (profiles/experiments/r7_two_windows_per_cu.txt).
                 A1 a;
                 a.P = P; a.T = &T; a.S = S; a.cring = cring; a.pax = pax; a.qbr = qbr; a.code4 = code4; a.n = n;
+                // what a wave does once per block of 64 cells: the wave-uniform loop parameters, re-materialised per block (keeps the admissibility tests and
+                // row offsets as plain scalar compares inside the block instead of dozens of hoisted masks: SGPR spills), and the lanes' list entries
+#define MIRP_A1_BLOCK()                                                                                                        \
+                    {                                                                                                          \
+                        int r0 = d - 2, um = d - 2 - (TURN + 1) < MAXLOOP ? d - 2 - (TURN + 1) : MAXLOOP;                      \
+                        asm volatile("" : "+s"(r0), "+s"(um));                                                                 \
+                        a.r0 = r0; a.um = um;                                                                                  \
+                        a.rowtab = P->ring_rowoff[r0 & 31];                                                                    \
+                    }                                                                                                          \
+                    const int k = blk * 64 + lane;                                                                             \
+                    const bool own = k < rem, ahead = !own && aent != 0;       /* k >= rem only happens in the last block */   \
+                    const bool act = own || ahead;                                                                             \
+                    unsigned ent = own ? clist[done + k] : ahead ? aent : (1u | (1u << 9));   /* idle lanes: harmless dummy cell */
+#ifdef MIRP_A1_FUSED
+                // (round 12) Two windows per CU: block-outer, job-inner.  Job-outer, a wave met every block twice and each time re-did MIRP_A1_BLOCK -- a scalar
+                // load, an LDS read behind a full drain -- and issued an LDS atomic of its own; now the two jobs' results meet in one minimum and one atomic.
+                // What a block carries from job to job is the entry, not its fields: they are decoded per job (the asm below keeps the compiler from
+                // hoisting the decode), because six more live registers do not fit the longest jobs under the 112-VGPR cap (6 spilled, 28 bytes of scratch).
+                const int role1st = wave < 4 ? wave : wave < 6 ? wave + 10 : wave + 6, role2nd = wave < 4 ? wave + 8 : wave;
+                for (int blk = 0; blk < nblk; blk++) {
+                    MIRP_A1_BLOCK()
+                    unsigned best = KEY_NONE;
+                    // the two roles sit in registers and the trip count is opaque, rather than `#pragma nounroll` over a role computed from `pass`: same code
+                    // per job, 82 spilled SGPRs instead of 88 and 1.0 ms of fill (47.8 -> 46.8 ms, profiles/experiments/r12_fused_roles.txt)
+                    int npass = 2;
+                    asm volatile("" : "+s"(npass));
+                    for (int pass = 0; pass < npass; pass++) {
+                    const int role = pass ? role2nd : role1st;
+                    asm volatile("" : "+v"(ent));
+#define MIRP_A1_ROLE14_HERE (wave == 4)      /* the wave that carries role 14 */
+#else
 #pragma nounroll
                 for (int pass = 0; pass < (TWO ? 2 : 1); pass++) {
                 const int role = TWO ? (wave < 4 ? wave + 8 * pass : wave < 6 ? (pass ? wave : wave + 10) : (pass ? wave : wave + 6))
                                      : wave < 4 ? wave : wave < 6 ? wave + 10 : wave < 12 ? wave + 2 : wave - 8;
                 for (int blk = 0; blk < nblk; blk++) {
-                    {   // re-materialise the wave-uniform loop parameters per block: keeps the admissibility tests and row offsets as plain
-                        // scalar compares inside the block instead of dozens of hoisted masks (SGPR spills)
-                        int r0 = d - 2, um = d - 2 - (TURN + 1) < MAXLOOP ? d - 2 - (TURN + 1) : MAXLOOP;
-                        asm volatile("" : "+s"(r0), "+s"(um));
-                        a.r0 = r0; a.um = um;
-                        a.rowtab = P->ring_rowoff[r0 & 31];
-                    }
-                    const int k = blk * 64 + lane;
-                    const bool own = k < rem, ahead = !own && aent != 0;       // k >= rem only happens in the last block
-                    const bool act = own || ahead;
-                    const unsigned ent = own ? clist[done + k] : ahead ? aent : (1u | (1u << 9));   // idle lanes: harmless dummy cell
+                    MIRP_A1_BLOCK()
+#define MIRP_A1_ROLE14_HERE (role == 14)
+#endif
                     const int i = ent & 511, type = (ent >> 9) & 7, j = i + d + (ahead ? 1 : 0);
                     a.cring = cring + (ahead ? CSTR : 0);
                     unsigned* ck = ahead ? ckey2 : ckey;
@@ -627,9 +650,16 @@
                             res = rx < res ? rx : res;
                         }
                     }
+#ifdef MIRP_A1_FUSED
+                    best = res < best ? res : best;
+                    }      // pass
+                    if (act && best != KEY_NONE) atomicMin(&(ahead ? ckey2 : ckey)[ent & 511], best);
+                }
+#else
                     if (act && res != KEY_NONE) atomicMin(&ck[i], res);
                 }
-                if (role == 14 && done > 0) {   // stacked pairs of the cells that went ahead in the previous interval (done <= 63)
+#endif
+                if (MIRP_A1_ROLE14_HERE && done > 0) {   // stacked pairs of the cells that went ahead in the previous interval (done <= 63): once, on role 14's wave
                     const bool act = lane < done;
                     const unsigned ent = act ? clist[lane] : (1u | (1u << 9));
                     const int i = ent & 511, type = (ent >> 9) & 7, j = i + d;
@@ -640,7 +670,11 @@
                     a1_small<0, 0>(a, i, j, type, S[i + 1], S[j - 1], res);
                     if (act && res != KEY_NONE) atomicMin(&ckey[i], res);
                 }
+#ifndef MIRP_A1_FUSED
                 }      // pass
+#endif
+#undef MIRP_A1_ROLE14_HERE
+#undef MIRP_A1_BLOCK
                 if (dbg_cycles && lane == 0 && wave == 9 && !light) {   // diagnostics: interior-loop time of one wave by number of blocks
                     const int b = nblk < 3 ? nblk : 3;
                     atomicAdd((unsigned long long*)&dbg_cycles[68 + b], (unsigned long long)(clock64() - wt));
@@ -656,6 +690,10 @@
         // them) compiled to a chain of a dozen read-wait pairs, which is what the waves that own cells spend their interval on.
         auto phaseB0 = [&](const int d) {
             const int ncell = n - d;
+            // (round 12, two windows per CU) a wave that owns no cell of the diagonal has nothing below but empty exec-mask regions, two ballots of zero and a
+            // full LDS drain in front of an unused readfirstlane: it leaves here.  Wave 0 (the list-length reset by tid 0) always owns cells: ncell >= 1.
+            // (MIRP_PHASEB_SKIP=0: a timing build without the branch)
+            if constexpr (TWO && MIRP_PHASEB_SKIP) { if (wave * 64 >= ncell) return; }
             unsigned* ckey = reinterpret_cast<unsigned*>(acc + MIRP_CK(d) * LCAP);
             int* mdec = mdec_of(d);
             int cbase = 0, cand = 0; unsigned cent = 0, cval = 0;      // sparse splits: this cell as a split candidate
