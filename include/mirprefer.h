@@ -452,6 +452,9 @@ int mirp_align_index(mirp_ctx* ctx, const char* const* paths, int32_t n_paths, i
  * {reads, aligned, unaligned, suppressed, records}, seconds = {read + parse, upload, seeds, verify, sort, emit + download + write}. */
 int mirp_align_reads(mirp_ctx* ctx, const char* reads_path, const char* out_path, const char* pg_cl, int32_t v, int32_t k, int32_t m, int32_t filter_unmapped,
                      int64_t stats[5], double seconds[6]);
+/* Batches the last mirp_align_reads of this context ran on the device (a file is cut into batches of at most 2^22 reads, fewer than 2^28 bases and
+ * at most 2^26 seeds; 0 before the first call and for a file without reads). */
+int64_t mirp_align_last_batches(const mirp_ctx* ctx);
 
 /* 3' adapter and quality trimming of raw reads, the step before mirp_collapse_reads.  adapter[0 .. adapter_len) = A C G T in either
  * case (adapter_len 0..64; 0 = no adapter search); error_permille 0..999 = E in per-mille (an overlap of length l allows floor(E * l / 1000)

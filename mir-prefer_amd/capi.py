@@ -454,6 +454,8 @@ def load_library():
     lib.mirp_align_index.restype = C.c_int
     lib.mirp_align_reads.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i64p, C.POINTER(C.c_double)]
     lib.mirp_align_reads.restype = C.c_int
+    lib.mirp_align_last_batches.argtypes = [vp]
+    lib.mirp_align_last_batches.restype = C.c_int64
     lib.mirp_trim_reads.argtypes = [vp, C.c_char_p, C.c_int64, C.c_char_p, C.POINTER(TrimOpts), C.c_char_p, i64p, C.POINTER(C.c_double)]
     lib.mirp_trim_reads.restype = C.c_int
     lib.mirp_target_scan.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(TargetOpts), C.c_char_p, i64p, C.POINTER(C.c_double)]
@@ -592,12 +594,16 @@ class Context:
     def align_reads(self, reads_path, out_path, pg_cl="", v=0, k=20, m=0, filter_unmapped=False):
         """bowtie -v v --best --strata -k k [-m m] -S on one read FASTA file against the index of align_index (mirp_align_reads): writes out_path.
         m = 0: no -m.  -> {reads, aligned, unaligned, suppressed, records, seconds}; seconds = {read + parse, upload, seeds, verify, sort,
-        emit + download + write}."""
+        emit + download + write}.  A large file runs in several batches on the device; align_last_batches() tells how many the last call took."""
         st = (C.c_int64 * 5)()
         sec = (C.c_double * 6)()
         self._check(self.lib.mirp_align_reads(self.h, os.fsencode(reads_path), os.fsencode(out_path), pg_cl.encode(), int(v), int(k), int(m),
                                               int(bool(filter_unmapped)), st, sec), "mirp_align_reads")
         return dict(zip(("reads", "aligned", "unaligned", "suppressed", "records"), list(st)), seconds=list(sec))
+
+    def align_last_batches(self):
+        """Batches the last align_reads ran on the device (mirp_align_last_batches)."""
+        return int(self.lib.mirp_align_last_batches(self.h))
 
     def trim_reads(self, data, name, out_path, adapter="", error_permille=100, overlap=3, quality=0, min_length=18, max_length=0, discard_untrimmed=False):
         """3' adapter and quality trimming of one FASTQ / FASTA text (bytes, already decompressed) (mirp_trim_reads): writes out_path,

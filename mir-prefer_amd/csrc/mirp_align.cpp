@@ -192,6 +192,7 @@ extern "C" int mirp_align_reads(mirp_ctx* c, const char* reads_path, const char*
     double dsec[5] = {0, 0, 0, 0, 0};
     // batches: bounded reads, bases and seeds (with e = 1 a read has up to 2 * (2 + 4 L) seeds)
     long long r0 = 0;
+    c->a_batches = 0;
     while (!rc && r0 < n) {
         long long r1 = r0, seeds = 0;
         while (r1 < n && r1 - r0 < (1ll << 22) && roff[r1] - roff[r0] < (1ll << 28)) {
@@ -207,6 +208,7 @@ extern "C" int mirp_align_reads(mirp_ctx* c, const char* reads_path, const char*
         rc = mirp_device_align_batch(c, codes.data() + roff[r0], rb.data(), qn.data() + qoff[r0], qb.data(), r1 - r0, v, k, m, filter_unmapped, sink, st4,
                                      dsec);
         r0 = r1;
+        c->a_batches++;
     }
     if (rc) return rc;
     if (!out.commit()) return fail(c, -8, std::string("cannot write ") + out_path);
@@ -218,3 +220,5 @@ extern "C" int mirp_align_reads(mirp_ctx* c, const char* reads_path, const char*
     if (seconds) std::memcpy(seconds, sec, sizeof sec);
     return 0;
 }
+
+extern "C" int64_t mirp_align_last_batches(const mirp_ctx* c) { return c ? c->a_batches : -1; }

@@ -118,6 +118,7 @@ struct mirp_ctx {
     long long a_total = 0, a_nsa = 0;
     int a_n_contigs = 0;
     bool a_ready = false;
+    long long a_batches = 0;          // batches of the last mirp_align_reads (mirp_align_last_batches)
     std::vector<std::string> a_contig_names;
     std::vector<long long> a_contig_lens;
     DevBuf a_codes, a_roff, a_qn, a_qoff, a_small, a_rcnt, a_rscan, a_seeds, a_ccnt, a_cscan, a_lvl, a_best, a_supp, a_slots, a_off, a_cursor, a_items, a_itmp,
