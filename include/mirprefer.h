@@ -712,6 +712,43 @@ int mirp_set_hairpin_capacity(mirp_ctx* ctx, int64_t bytes);
  * download}.  hits_per_query (optional, n_q entries of the last call): the hits of every query before the cut. */
 int mirp_hairpin_last_stats(mirp_ctx* ctx, int64_t stats[8], double seconds[5], int64_t* hits_per_query);
 
+/* Homologs of known mature miRNAs in the genome of mirp_align_index: every placement of a known sequence within max_mismatches
+ * (0..3) substitutions on either strand, all strata; the window of precursor_len (60..3000) around it, folded with span precursor_len; the
+ * structure rules of the predict stage (a8, a9) on the placement's interval, without reads.  A query with more than max_placements (>= 1)
+ * placements yields none.  `reserved` must be 0. */
+typedef struct { int32_t max_mismatches, precursor_len, max_placements, reserved; } MirpHomologOpts;
+/* One locus: the naming query (0-based index in the call) and its mismatches, the contig (index in reference order) and strand (0 '+', 1 '-'), the
+ * mature, star, fold region and window as 1-based contig coordinates with exclusive ends, prime5 (1: the mature lies in the 5' arm), the base
+ * pairs of the mature side of the duplex and the unpaired bases of both sides, the energy (0.01 kcal/mol) and length of the structure line the
+ * structure comes from (normalised energy = energy / 100 / line_len), the structure's length, and n_also further placements at the same interval. */
+typedef struct {
+    int32_t query, contig, strand, mismatches;
+    int32_t mat_s, mat_e, star_s, star_e, fold_s, fold_e, win_s, win_e;
+    int32_t prime5, total_bps, total_dots, energy, line_len, ss_len, n_also, reserved;
+    int64_t text_off, also_off;
+} MirpHomologRec;
+/* q_blob / q_off as mirp_hairpin_align's: n_q distinct known sequences of 18..26 letters A C G T/U in either case (anything else is refused with
+ * -10 and the 1-based record in mirp_last_error).  Called after mirp_align_index; nothing of the index changes.  Out (library-owned, mirp_free;
+ * NULL when there is no locus): *recs holds the *n_recs loci ordered by (contig, fold_s, strand, mat_s, mat_e); *text holds for record r at
+ * text_off the win_e - win_s letters (A C G T N) of its window on its strand, followed by the ss_len characters of its dot-bracket structure,
+ * which covers [fold_s, fold_e); *also holds n_also pairs (query, mismatches) per record from pair also_off on, in query order.  The result is the
+ * same however the placements are split into passes and chunks. */
+int mirp_homolog_scan(mirp_ctx* ctx, const char* q_blob, const int64_t* q_off, int32_t n_q, const MirpHomologOpts* opts, MirpHomologRec** recs,
+                      int64_t* n_recs, char** text, int32_t** also);
+/* The contigs of the resident index in reference order, which MirpHomologRec.contig indexes (library-owned, mirp_free): *names holds the
+ * *n_contigs names, each followed by a NUL, *names_bytes bytes in all; *lens their lengths. */
+int mirp_homolog_contigs(mirp_ctx* ctx, char** names, int64_t* names_bytes, int64_t** lens, int32_t* n_contigs);
+/* Placement keys one scan pass holds on the device (0 = the default, 2^24; at least 1), placements per chunk of windows that is folded and evaluated
+ * at once (0 = as many as 1 GiB of fold output holds, at most 32,768), structure lines the fold keeps per window at first (0 = 96), and the
+ * evaluation kernel's first capacities: pieces per line, structures and staged lines per window (0 = the defaults; all three or none).  Lowered only
+ * to test the multi-pass, multi-chunk and re-run paths. */
+int mirp_set_homolog_capacity(mirp_ctx* ctx, int64_t keys, int64_t chunk, int32_t fold_lines, int32_t pieces, int32_t structures, int32_t staged_lines);
+/* stats = {queries, queries dropped by max_placements, placements (= windows folded), placements with a passing structure, loci, scan passes,
+ * chunks, folds (a chunk is folded again when a window needs more structure lines), evaluation re-runs, 0, then at 10 + k the placements without a
+ * passing structure whose structure of lowest normalised energy has get_maturestar_info code k = 1..12, and at 23 those whose structure list is
+ * empty} of the last mirp_homolog_scan; seconds = {scan, windows, fold, evaluation + download, merge}. */
+int mirp_homolog_last_stats(mirp_ctx* ctx, int64_t stats[24], double seconds[5]);
+
 #ifdef __cplusplus
 }
 #endif

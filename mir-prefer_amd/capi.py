@@ -89,6 +89,17 @@ HAIRPIN_DTYPE = np.dtype([(f, "<i4") for f in ("query", "known", "score", "q_sta
 HAIRPIN_STATS = ("queries", "known", "pairs", "cells", "hits", "passes", "score_passes", "trace_passes")
 HAIRPIN_STRIP = 16          # MIRP_HAIRPIN_STRIP of include/mirprefer.h: query rows a lane of the scoring kernel holds in registers
 
+class HomologOpts(C.Structure):
+    """MirpHomologOpts of include/mirprefer.h."""
+    _fields_ = [("max_mismatches", C.c_int32), ("precursor_len", C.c_int32), ("max_placements", C.c_int32), ("reserved", C.c_int32)]
+
+
+# MirpHomologRec of include/mirprefer.h: one locus of mirp_homolog_scan, coordinates 1-based with exclusive ends
+HOMOLOG_DTYPE = np.dtype([(f, "<i4") for f in ("query", "contig", "strand", "mismatches", "mat_s", "mat_e", "star_s", "star_e", "fold_s", "fold_e", "win_s",
+                                               "win_e", "prime5", "total_bps", "total_dots", "energy", "line_len", "ss_len", "n_also", "reserved")] +
+                         [("text_off", "<i8"), ("also_off", "<i8")])
+HOMOLOG_STATS = ("queries", "repeat_like", "placements", "passing", "loci", "scan_passes", "chunks", "folds", "eval_reruns")
+
 # MirpUnpairedRec of include/mirprefer.h: one window of mirp_unpaired_batch, kcal/mol
 UNPAIRED_DTYPE = np.dtype([("efe", "<f8"), ("efe_open", "<f8"), ("upe", "<f8")])
 UNPAIRED_STATS = ("windows", "passes", "cells")
@@ -492,6 +503,14 @@ def load_library():
     lib.mirp_set_hairpin_capacity.restype = C.c_int
     lib.mirp_hairpin_last_stats.argtypes = [vp, i64p, C.POINTER(C.c_double), i64p]
     lib.mirp_hairpin_last_stats.restype = C.c_int
+    lib.mirp_homolog_scan.argtypes = [vp, C.c_char_p, i64p, C.c_int32, C.POINTER(HomologOpts), C.POINTER(vp), i64p, C.POINTER(vp), C.POINTER(vp)]
+    lib.mirp_homolog_scan.restype = C.c_int
+    lib.mirp_homolog_contigs.argtypes = [vp, C.POINTER(vp), i64p, C.POINTER(vp), C.POINTER(C.c_int32)]
+    lib.mirp_homolog_contigs.restype = C.c_int
+    lib.mirp_set_homolog_capacity.argtypes = [vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.mirp_set_homolog_capacity.restype = C.c_int
+    lib.mirp_homolog_last_stats.argtypes = [vp, i64p, C.POINTER(C.c_double)]
+    lib.mirp_homolog_last_stats.restype = C.c_int
     lib.mirp_set_target_flanks.argtypes = [vp, C.c_int32, C.c_int32]
     lib.mirp_set_target_flanks.restype = C.c_int
     lib.mirp_set_target_capacity.argtypes = [vp, C.c_int64]
@@ -843,6 +862,50 @@ class Context:
         per = np.zeros(st[0] + 1, dtype=np.int64)          # (st[0] = the queries of that call: what the library writes)
         self._check(self.lib.mirp_hairpin_last_stats(self.h, st, sec, per.ctypes.data_as(C.POINTER(C.c_int64))), "mirp_hairpin_last_stats")
         return dict(zip(HAIRPIN_STATS, list(st)), seconds=list(sec), per_query=per[:st[0]].tolist())
+
+    def homolog_scan(self, queries, max_mismatches=1, precursor_len=300, max_placements=100, keys=0, chunk=0, fold_lines=0, eval_caps=(0, 0, 0)):
+        """Homologs of known mature miRNAs in the genome of align_index (mirp_homolog_scan).  queries: distinct sequences (str /
+        bytes) of 18..26 letters A C G T/U.  keys, chunk, fold_lines, eval_caps (pieces, structures, staged lines): the capacities of
+        mirp_set_homolog_capacity, lowered only in tests.  -> (HOMOLOG_DTYPE array of the loci ordered by (contig, fold_s, strand, mat_s, mat_e),
+        the text bytes (per locus at text_off: the window's letters on its strand, then the dot-bracket structure), int32 array [n, 2] of the
+        (query, mismatches) pairs the loci's also_off / n_also point into)."""
+        bs = [q.encode() if isinstance(q, str) else bytes(q) for q in queries]
+        off = np.zeros(len(bs) + 1, dtype=np.int64)
+        if bs:
+            off[1:] = np.cumsum([len(b) for b in bs])
+        o = HomologOpts()
+        o.max_mismatches, o.precursor_len, o.max_placements, o.reserved = int(max_mismatches), int(precursor_len), int(max_placements), 0
+        recs, n_recs, text, also = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p()
+        self._check(self.lib.mirp_set_homolog_capacity(self.h, int(keys), int(chunk), int(fold_lines), *[int(x) for x in eval_caps]), "mirp_set_homolog_capacity")
+        try:
+            self._check(self.lib.mirp_homolog_scan(self.h, b"".join(bs), off.ctypes.data_as(C.POINTER(C.c_int64)), len(bs), C.byref(o), C.byref(recs),
+                                                   C.byref(n_recs), C.byref(text), C.byref(also)), "mirp_homolog_scan")
+        finally:
+            self.lib.mirp_set_homolog_capacity(self.h, 0, 0, 0, 0, 0, 0)
+        n = n_recs.value
+        if n == 0:
+            return np.zeros(0, dtype=HOMOLOG_DTYPE), b"", np.zeros((0, 2), dtype=np.int32)
+        r = _copy_out(self.lib, recs, HOMOLOG_DTYPE, n)
+        t = _copy_out(self.lib, text, np.uint8, int((r["win_e"].astype(np.int64) - r["win_s"] + r["ss_len"]).sum())).tobytes()
+        a = _copy_out(self.lib, also, np.int32, 2 * int(r["n_also"].sum())).reshape(-1, 2)
+        return r, t, a
+
+    def align_contigs(self):
+        """([names as str], int64 array of lengths) of the contigs of align_index in reference order (mirp_homolog_contigs)."""
+        names, size, lens, n = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_int32()
+        self._check(self.lib.mirp_homolog_contigs(self.h, C.byref(names), C.byref(size), C.byref(lens), C.byref(n)), "mirp_homolog_contigs")
+        ln = _copy_out(self.lib, lens, np.int64, n.value)
+        blob = _copy_out(self.lib, names, np.uint8, size.value).tobytes().decode("latin-1")
+        return blob.split("\0")[:-1], ln
+
+    def homolog_last_stats(self):
+        """{queries, repeat_like, placements, passing, loci, scan_passes, chunks, folds, eval_reruns, fail_codes, no_structure, seconds} of the
+        last homolog_scan; fail_codes[k]: placements without a passing structure whose structure of lowest normalised energy has
+        get_maturestar_info code k (index 0 unused); seconds = {scan, windows, fold, evaluation + download, merge}."""
+        st = (C.c_int64 * 24)()
+        sec = (C.c_double * 5)()
+        self._check(self.lib.mirp_homolog_last_stats(self.h, st, sec), "mirp_homolog_last_stats")
+        return dict(zip(HOMOLOG_STATS, list(st)[:9]), fail_codes=[0] + list(st)[11:23], no_structure=int(st[23]), seconds=list(sec))
 
     def phase_scan(self, length, cycles, kmin, min_phased=3, min_depth=1):
         """Phased siRNA windows on this context's resident alignments (mirp_phase_scan).  kmin: the int32 table of the smallest

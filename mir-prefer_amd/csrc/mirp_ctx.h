@@ -162,6 +162,14 @@ struct mirp_ctx {
     long long hp_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the last mirp_hairpin_align: queries, known, pairs, cells, hits, passes, scoring passes, traceback passes
     double hp_sec[5] = {0, 0, 0, 0, 0};                 // upload, scoring, filter + sort + cut, traceback, download
     std::vector<long long> hp_per_query;                // hits of every query of the last call, before the cut
+    // ---- homolog search (homolog_kernels.hip, mirp_homolog.cpp): the queries and keys use the read alignment's buffers (a_*); the keys, windows,
+    // letters, offsets, evaluation records, winning texts, needs and re-run list of one chunk of placements; the fold's output goes to b*
+    DevBuf hm_keys, hm_win, hm_lens, hm_offs, hm_seqs, hm_eval, hm_ss, hm_need, hm_sel;
+    long long hm_cap = 0, hm_chunk = 0;   // keys per scan pass (0 = 2^24) and windows per fold chunk (0 = by the fold output's size) (mirp_set_homolog_capacity)
+    int hm_lines = 0;                     // structure lines the fold keeps per window at first (0 = 96)
+    int hm_eval_caps[3] = {0, 0, 0};      // pieces per line, structures and staged lines of the evaluation's first launch (0 = the defaults)
+    long long hm_stats[24] = {0};         // the last mirp_homolog_scan (mirp_homolog_last_stats)
+    double hm_sec[5] = {0, 0, 0, 0, 0};
     long long n_result = 0;          // records of the last mirp_predict (p_res / p_text), what mirp_gather_loci sends
     bool have_result = false;
 };
@@ -300,6 +308,12 @@ struct HpSeqs {
 };
 int mirp_device_hairpin(mirp_ctx* c, const HpSeqs& Q, const HpSeqs& K, const MirpHairpinOpts& o, std::vector<MirpHairpinHit>& hits, std::vector<char>& ops,
                         std::vector<long long>& ops_off);
+// homolog_kernels.hip: the placements of coded queries (0..3 = A C G T at roff[0 .. nq]) in the resident alignment index as sorted keys
+// (query << 35 | packed position << 3 | strand << 2 | mismatches); windows, fold and evaluation of a chunk of them
+int mirp_device_homolog_scan(mirp_ctx* c, const unsigned char* codes, const long long* roff, long long nq, int v, int max_placements,
+                             std::vector<unsigned long long>& keys, long long stats[3]);
+int mirp_device_homolog_eval(mirp_ctx* c, const unsigned long long* keys, long long n, int precursor_len, int max_lines, HmWin* win, HmEval* ev,
+                             std::vector<char>& text, long long* text_off, long long stats[3], double seconds[3]);
 int mirp_device_mask_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long* n_io, MirpAln* d_segs, MirpAln* d_segtmp, const int* d_owner, const int* d_seg_span,
                           long long* nseg_io,
                           const long long* d_rfirst, const int* d_rstart, const int* d_remax);

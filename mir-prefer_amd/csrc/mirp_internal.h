@@ -17,6 +17,14 @@ struct TgStrand { unsigned pl, ph, unk, g1, g2, seed, cleave, pad; };
 // One miRNA, plus (s[0]) and minus (s[1]) strand; lmask = positions 0 .. L - 1; half-scores smin .. smax are reported in the current pass.
 struct TgMirna { TgStrand s[2]; unsigned lmask; int L, smin, smax; };
 
+// One placement of the homolog search after its evaluation (homolog_kernels.hip): n_structs structures in the window's list; best =
+// index of the passing structure of lowest normalised energy, -1 = none; code = 0 with a best, else the get_maturestar_info code of the structure of
+// lowest normalised energy, -1 = the list is empty; status 2 = a capacity of the launch was exceeded (the window is run again).  With a best: the
+// star and the fold region (1-based, exclusive ends), the figures of the mature / star duplex, the line's energy and length, the structure's length.
+// window of one placement: contig, [ws, we) and the interval [m0, m1) as 1-based contig coordinates with exclusive ends (the pipeline's), strand
+struct HmWin { int tid, ws, we, m0, m1, strand, query, mm; };
+struct HmEval { int n_structs, best, code, status, prime5, total_bps, total_dots, star_s, star_e, fold_s, fold_e, energy, line_len, ss_len; };
+
 namespace mirp {
 
 size_t fold_generic_lds_bytes(int n_cap, int max_lines);
