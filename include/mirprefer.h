@@ -504,6 +504,25 @@ int mirp_target_scan(mirp_ctx* ctx, const char* mirna_path, const char* const* t
  * is set here: the most one offset can hold of one miRNA and score (t and m on both strands), so that the split always ends. */
 int mirp_set_target_capacity(mirp_ctx* ctx, int64_t keys);
 
+/* Endogenous target mimics: sites where a target pairs with a miRNA around a loop of loop_len unpaired target bases opposite the
+ * gap between miRNA positions P and P + 1, P in {9, 10, 11}, so that the site cannot be sliced.  Positions 2..8 are Watson-Crick pairs, the pairs
+ * P and P + 1 that close the loop are not mismatches, and imperfect = mismatches + G:U pairs over positions 1..L is at most max_imperfect; per
+ * (miRNA, interval, strand) the P of lowest imperfect is written, the smallest on a tie.  max_imperfect 0..6; loop_len 2..6; both_strands (0 or 1):
+ * also the minus strand; max_sites: the first N sites per miRNA in output order (0 = all). */
+typedef struct {
+    int32_t max_imperfect, loop_len, both_strands, reserved;
+    int64_t max_sites;
+} MirpMimicOpts;
+/* Reads the miRNA FASTA and the target FASTA files exactly as mirp_target_scan does (same letters, same refusals) and writes the TSV of §27 to
+ * out_path: a header line, then one line per site ordered by miRNA (file order), imperfect, target (file order), start, + before -.  The scan is
+ * anchored on the seed: the 7-mer at every target position and strand selects, through a table of 16,384 buckets, the miRNAs whose positions 2..8
+ * pair with it; a miRNA with an unknown letter in 2..8 is in no bucket and has no sites.  Passes hold at most mirp_set_target_capacity keys.  On any
+ * error the file at out_path is removed.  Out: stats = {miRNAs, miRNAs without a usable seed, targets, target bases, seeds looked up (positions x
+ * strands with a 7-mer of unambiguous bases inside one contig), bucket entries evaluated, sites written, passes}, seconds = {parse + table, upload,
+ * scan, sort + cut, emit + download + write}.  Nothing resident changes. */
+int mirp_mimic_scan(mirp_ctx* ctx, const char* mirna_path, const char* const* target_paths, int32_t n_targets, const MirpMimicOpts* opts,
+                    const char* out_path, int64_t stats[8], double seconds[5]);
+
 /* Phased siRNA (PHAS) windows on the context's resident alignments (after any SAM ingest, or after mirp_load_alignments).  A record
  * with len == length is a read of the unit (tid, strand, c), c = pos on the plus strand and pos + 2 on the minus strand (the 2-nt 3' overhang of a
  * Dicer duplex); its abundance is the sum of the records' depths, and units below min_depth are dropped first.  Every distinct (tid, c) of a unit is

@@ -41,6 +41,14 @@ class TargetOpts(C.Structure):
 TARGET_STATS = ("mirnas", "targets", "bases", "evaluations", "sites", "passes")
 
 
+class MimicOpts(C.Structure):
+    """MirpMimicOpts of include/mirprefer.h."""
+    _fields_ = [("max_imperfect", C.c_int32), ("loop_len", C.c_int32), ("both_strands", C.c_int32), ("reserved", C.c_int32), ("max_sites", C.c_int64)]
+
+
+MIMIC_STATS = ("mirnas", "no_seed", "targets", "bases", "seeds", "entries", "sites", "passes")
+
+
 class AnnotateOpts(C.Structure):
     """MirpAnnotateOpts of include/mirprefer.h."""
     _fields_ = [("max_offset", C.c_int32), ("max_mismatches", C.c_int32), ("n_species", C.c_int32), ("reserved", C.c_int32), ("max_lines", C.c_int64),
@@ -471,6 +479,8 @@ def load_library():
     lib.mirp_trim_reads.restype = C.c_int
     lib.mirp_target_scan.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(TargetOpts), C.c_char_p, i64p, C.POINTER(C.c_double)]
     lib.mirp_target_scan.restype = C.c_int
+    lib.mirp_mimic_scan.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(MimicOpts), C.c_char_p, i64p, C.POINTER(C.c_double)]
+    lib.mirp_mimic_scan.restype = C.c_int
     lib.mirp_annotate_scan.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(AnnotateOpts), C.c_char_p, C.c_char_p, i64p,
                                        C.POINTER(C.c_double)]
     lib.mirp_annotate_scan.restype = C.c_int
@@ -666,6 +676,21 @@ class Context:
     def set_target_capacity(self, keys):
         """Sites one target_scan pass holds on the device (0 = the default, 2^26; at least 2): lowered only to test the overflow path."""
         self._check(self.lib.mirp_set_target_capacity(self.h, int(keys)), "mirp_set_target_capacity")
+
+    def mimic_scan(self, mirna_path, target_paths, out_path, max_imperfect=3, loop_len=3, both_strands=False, max_sites=0):
+        """Endogenous target mimics (mirp_mimic_scan): every miRNA of mirna_path against the target FASTA files, in order, anchored on
+        the seed (positions 2..8); writes the TSV to out_path.  max_imperfect: most mismatches + G:U pairs (0..6); loop_len: unpaired target
+        bases (2..6).  -> {mirnas, no_seed, targets, bases, seeds, entries, sites, passes, seconds}; no_seed = miRNAs with an unknown letter in
+        2..8 (in no bucket), seeds = 7-mers looked up, entries = bucket entries evaluated; seconds = {parse + table, upload, scan, sort + cut,
+        emit + download + write}.  Passes hold at most set_target_capacity keys."""
+        o = MimicOpts()
+        o.max_imperfect, o.loop_len, o.both_strands, o.max_sites = int(max_imperfect), int(loop_len), int(bool(both_strands)), int(max_sites)
+        arr = (C.c_char_p * len(target_paths))(*[os.fsencode(p) for p in target_paths])
+        st = (C.c_int64 * 8)()
+        sec = (C.c_double * 5)()
+        self._check(self.lib.mirp_mimic_scan(self.h, os.fsencode(mirna_path), arr, len(target_paths), C.byref(o), os.fsencode(out_path), st, sec),
+                    "mirp_mimic_scan")
+        return dict(zip(MIMIC_STATS, list(st)), seconds=list(sec))
 
     def annotate_scan(self, query_path, known_paths, out_path, summary_path, max_offset=2, max_mismatches=2, max_lines=0, species=()):
         """Known-miRNA annotation (mirp_annotate_scan): every sequence of query_path against the known FASTA files, in order; writes

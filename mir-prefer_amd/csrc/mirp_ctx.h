@@ -170,6 +170,9 @@ struct mirp_ctx {
     int hm_eval_caps[3] = {0, 0, 0};      // pieces per line, structures and staged lines of the evaluation's first launch (0 = the defaults)
     long long hm_stats[24] = {0};         // the last mirp_homolog_scan (mirp_homolog_last_stats)
     double hm_sec[5] = {0, 0, 0, 0, 0};
+    // ---- target-mimic search (mimic_kernels.hip, mirp_mimics.cpp): the seed start table, the file index of every miRNA in seed order and the
+    // lengths in file order; the packed targets, names, miRNA masks, keys and text use the target-site search's buffers (tg_*)
+    DevBuf mm_start, mm_mid, mm_len;
     long long n_result = 0;          // records of the last mirp_predict (p_res / p_text), what mirp_gather_loci sends
     bool have_result = false;
 };
@@ -227,6 +230,12 @@ int mirp_device_target_scan(mirp_ctx* c, const unsigned long long* pk, const uns
                             const std::vector<unsigned long long>& cstart, const std::string& tnames, const std::vector<long long>& tnoff,
                             std::vector<TgMirna>& mi, const std::vector<unsigned char>& mcodes, const std::string& mnames, const std::vector<long long>& mnoff,
                             const MirpTargetOpts& o, const std::function<int(const char*, size_t)>& sink, long long stats[2], double seconds[4]);
+// mimic_kernels.hip: the seed-anchored target-mimic search over packed targets (mirp_mimics.cpp parses the files and builds the seed table)
+int mirp_device_mimic_scan(mirp_ctx* c, const unsigned long long* pk, const unsigned* amb, const unsigned* cst, long long total,
+                           const std::vector<unsigned long long>& cstart, const std::string& tnames, const std::vector<long long>& tnoff,
+                           std::vector<TgMirna>& mi, const std::vector<unsigned>& mid, const std::vector<unsigned>& slot, const std::vector<unsigned>& start,
+                           const std::vector<unsigned char>& mcodes, const std::vector<int>& mlens, const std::string& mnames, const std::vector<long long>& mnoff,
+                           const MirpMimicOpts& o, const std::function<int(const char*, size_t)>& sink, long long stats[4], double seconds[4]);
 // degradome_kernels.hip: the cleavage scan of the resident alignments against packed transcripts (mirp_degradome.cpp parses the files and writes the
 // lines).  sqstart / sqlen: first packed position and length of the transcript of every SAM tid; f2s: FASTA index -> SAM tid (-1: no @SQ line);
 // mi / mi_anchored: the masks of make_mirna without / with `anchored`.  Hits arrive at the sink in output order, pass by pass: key = miRNA index in
