@@ -199,8 +199,7 @@ __device__ long long al_record(const AlRef& R, const AlText& T, const AlParams& 
     }
     const int strand = (int)(item & 1);
     const unsigned long long g = (item >> 1) & 0xffffffffull;
-    int a = 0, z = T.n_contigs;                 // contig: last cstart <= g
-    while (z - a > 1) { const int md = (a + z) >> 1; if (T.cstart[md] <= g) a = md; else z = md; }
+    const int a = site_contig(T.cstart, T.n_contigs, g);
     o.ch('\t');
     o.num(strand ? 16 : 0);
     o.ch('\t');

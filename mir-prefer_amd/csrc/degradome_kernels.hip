@@ -26,7 +26,7 @@
 #include <vector>
 #include "mirp_ctx.h"
 #include "pass_plan.h"
-#include "targets_device.h"
+#include "site_keys.h"
 #include "wave_atomic.h"
 
 namespace mirp {
@@ -232,8 +232,7 @@ __global__ void __launch_bounds__(DG_NT) dg_hit_kernel(const unsigned long long*
                                                        MirpDgHit* __restrict__ out) {
     for (long long i = (long long)blockIdx.x * DG_NT + threadIdx.x; i < n; i += (long long)gridDim.x * DG_NT) {
         const unsigned long long key = keys[i], g = key & 0xffffffffull;
-        int a = 0, z = n_f;                          // transcript: last cstart <= g
-        while (z - a > 1) { const int md = (a + z) >> 1; if (cstart[md] <= g) a = md; else z = md; }
+        const int a = site_contig(cstart, n_f, g);   // the transcript
         const unsigned long long t = (unsigned long long)(unsigned)f2s[a];
         const unsigned long long uk = (t << 32) | (g - cstart[a] + 1);
         long long lo = 0, hi = nu - 1;               // the unit exists

@@ -17,12 +17,13 @@
 // Three sources of strands share the kernel: DxPairs (mirp_duplex_batch: coded strands and offsets), DxPerfect (a miRNA against its reverse
 // complement, N stays N: `mfe_perfect` of targets -e) and DxSites (targets -e: the sorted keys of a pass; a = the miRNA, b = the site's interval on
 // the forward target plus one base on each side where the contig has one, an ambiguous one as N, reverse-complemented on the minus strand; keys
-// that -k cuts are not folded).
+// that -k cuts are not folded).  DxSites reads the keys through site_keys.h: site_kept is the cut that site_size_kernel applies (site_lines.h),
+// SiteKey the decoder of both key layouts, site_contig the contig lookup.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "mirp_ctx.h"
 #include "fold_device.h"
-#include "targets_bulge_device.h"
+#include "site_keys.h"
 
 namespace mirp {
 
@@ -74,21 +75,12 @@ struct DxSites {
     long long n, k;                         // keys of the pass; -k (0 = all)
     const unsigned long long* emitted;
     __device__ bool load(long long q, int lane, int* la, int* lb, int* ca, int* cb) const {
-        const unsigned long long key = keys[q];
-        constexpr int shift = BULGE ? TG_BULGE_SHIFT : 38;
-        if (k != 0) {                       // the cut of tg_size_kernel: rank in the miRNA's run plus what earlier passes emitted
-            const unsigned long long lo = key >> shift << shift;
-            long long x = 0, z = q;
-            while (x < z) { const long long md = (x + z) >> 1; if (keys[md] < lo) x = md + 1; else z = md; }
-            if (emitted[key >> shift] + (unsigned long long)(q - x) >= (unsigned long long)k) return false;
-        }
-        const int mloc = (int)(key >> shift);
-        const unsigned long long g = BULGE ? (key >> 8) & 0xffffffffull : (key >> 1) & 0xffffffffull;
-        const int strand = BULGE ? (int)(key >> 7) & 1 : (int)(key & 1);
-        const int L = T.mi[mloc].L;
-        const int len = BULGE ? L + ((int)(key >> 5) & 3) - 1 : L;
-        int c0 = 0, z = T.n_contigs;        // contig: last cstart <= g
-        while (z - c0 > 1) { const int md = (c0 + z) >> 1; if (T.cstart[md] <= g) c0 = md; else z = md; }
+        if (!site_kept(keys, q, k, emitted, SiteKey<BULGE>::shift)) return false;
+        const SiteKey<BULGE> K(keys[q]);
+        const int mloc = K.mloc, strand = K.strand;
+        const unsigned long long g = K.g;
+        const int L = T.mi[mloc].L, len = K.len(L);
+        const int c0 = site_contig(T.cstart, T.n_contigs, g);
         const unsigned long long lo = g > T.cstart[c0] ? g - 1 : g, hi = g + len < T.cstart[c0 + 1] ? g + len : g + len - 1;
         const int nb = (int)(hi - lo) + 1;
         *la = L;

@@ -22,6 +22,7 @@
 #include "align_device.h"
 #include "predict_device.h"
 #include "pass_plan.h"
+#include "site_keys.h"
 
 namespace mirp {
 
@@ -132,8 +133,7 @@ __global__ void hm_winlen_kernel(const unsigned long long* __restrict__ keys, lo
         const long long q = (long long)(key >> 35);
         const unsigned long long g = (key >> 3) & 0xffffffffull;
         const int L = (int)(roff[q + 1] - roff[q]);
-        int a = 0, z = n_contigs;                   // contig: last cstart <= g
-        while (z - a > 1) { const int md = (a + z) >> 1; if (cstart[md] <= g) a = md; else z = md; }
+        const int a = site_contig(cstart, n_contigs, g);
         const long long cs = (long long)cstart[a], ce = (long long)cstart[a + 1];
         const long long F = (precursor_len - L) / 2;
         const long long lo = (long long)g - F > cs ? (long long)g - F : cs, hi = (long long)g + L + F < ce ? (long long)g + L + F : ce;

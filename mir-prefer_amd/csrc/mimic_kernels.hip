@@ -11,9 +11,9 @@
 //          its strand's span (from q - 30 on the plus strand, from q - 1 on the minus strand) as 64-bit bit planes once and evaluates every entry of
 //          the bucket from two windows, U(o) and U(o + G): a placement P is a mask select between the two, as in tg_bulge_best<true>.  A hit is the key
 //          miRNA << 38 | imperfect << 35 | o << 3 | strand << 2 | (P - 9) (MODE 0) or a count in hist[miRNA * 8 + imperfect] (MODE 1).
-//   order  mirp_device_sort_u64 by the whole key: miRNA (file order), imperfect, target, start, + before -.
-//   cut    mm_size_kernel (-k from the rank inside the miRNA's run plus what earlier passes emitted), launch_excl_scan; emit: mm_emit_kernel.
-// Passes of at most `cap` keys are planned by plan_passes (pass_plan.h) with (miRNA, imperfect) as the bins and the interval
+//   order, cut, emit   site_finish_pass (site_lines.h) with the line MmLine: the sort by the whole key gives miRNA (file order), imperfect, target,
+//          start, + before -; -k cuts by the rank inside the miRNA's run plus what earlier passes emitted.
+// Passes of at most `cap` keys are planned by site_plan_passes (site_lines.h) with (miRNA, imperfect) as the bins and the interval
 // starts o as the positions (the output order within a bin; the lanes that can hold a start of [o0, o1) are q in [o0, o1 + 30)); one o holds at most
 // two sites of one bin (one per strand), the smallest capacity the ABI takes.
 #include <hip/hip_runtime.h>
@@ -24,7 +24,7 @@
 #include <vector>
 #include "mimic_device.h"
 #include "mirp_ctx.h"
-#include "pass_plan.h"
+#include "site_lines.h"
 #include "text_out.h"
 
 namespace mirp {
@@ -103,109 +103,38 @@ struct MmText {
     int G;
 };
 
-__device__ __forceinline__ int mm_class(unsigned mc, unsigned y) {
-    if (mc > 3) return 2;
-    if (mc + y == 3) return 0;
-    return (mc == 2 && y == 3) || (mc == 3 && y == 2) ? 1 : 2;
-}
-
-// one line: miRNA target start end strand imperfect mismatches gu mirna_5to3 pairs target_3to5 loop.  Column c = 1 .. L + G of the three aligned
+// One line: miRNA target start end strand imperfect mismatches gu mirna_5to3 pairs target_3to5 loop.  Column c = 1 .. L + G of the three aligned
 // strings holds miRNA position c (c <= P), nothing (the G loop bases) or position c - G, over the target-strand base of the column.
-template <bool WRITE>
-__device__ long long mm_line(const MmText& T, unsigned long long key, char* out) {
-    TextOut<WRITE> o{out};
-    const long long m = (long long)(key >> MM_SHIFT);
-    const unsigned imp = (unsigned)(key >> 35) & 7u;
-    const unsigned long long g = (key >> 3) & 0xffffffffull;
-    const int strand = (int)(key >> 2) & 1, P = 9 + (int)(key & 3), G = T.G;
-    const int L = T.mlen[m], W = L + G;
-    const unsigned char* mc = T.mcodes + 32 * m;
-    int a = 0, z = T.n_contigs;                 // target: last cstart <= g
-    while (z - a > 1) { const int md = (a + z) >> 1; if (T.cstart[md] <= g) a = md; else z = md; }
-    auto pos = [&](int c) { return c <= P ? c : c <= P + G ? 0 : c - G; };
-    auto base = [&](int c) -> unsigned {
-        const unsigned b = tg_base(T.pk, strand ? g + c - 1 : g + W - c);
-        return strand ? 3u - b : b;
-    };
-    int nmm = 0, ngu = 0;
-    for (int c = 1; c <= W; c++) {
-        const int i = pos(c);
-        if (!i) continue;
-        const int k = mm_class(mc[i - 1], base(c));
-        nmm += k == 2;
-        ngu += k == 1;
+struct MmLine {
+    MmText T;
+    static constexpr int shift = MM_SHIFT;
+    template <bool WRITE>
+    __device__ long long line(unsigned long long key, long long, char* out) const {
+        TextOut<WRITE> o{out};
+        const long long m = (long long)(key >> MM_SHIFT);
+        const unsigned imp = (unsigned)(key >> 35) & 7u;
+        const unsigned long long g = (key >> 3) & 0xffffffffull;
+        const int strand = (int)(key >> 2) & 1, P = 9 + (int)(key & 3), G = T.G;
+        const int W = T.mlen[m] + G;
+        const int a = site_contig(T.cstart, T.n_contigs, g);
+        text_site_head(o, T.mnames, T.mnoff, m, T.tnames, T.tnoff, a, g - T.cstart[a] + 1, g - T.cstart[a] + W, strand);
+        o.ch('\t');
+        o.num(imp);
+        o.ch('\t');
+        const auto pos = [&](int c) { return c <= P ? c : c <= P + G ? 0 : c - G; };
+        const auto base = [&](int c) -> int {
+            const unsigned b = tg_base(T.pk, strand ? g + c - 1 : g + W - c);
+            return (int)(strand ? 3u - b : b);
+        };
+        text_site_pairing(o, T.mcodes + 32 * m, W, pos, base);
+        o.ch('\t');
+        o.num((unsigned long long)P);
+        o.ch('\n');
+        return o.n;
     }
-    o.str(T.mnames + T.mnoff[m], T.mnoff[m + 1] - T.mnoff[m]);
-    o.ch('\t');
-    o.str(T.tnames + T.tnoff[a], T.tnoff[a + 1] - T.tnoff[a]);
-    o.ch('\t');
-    o.num(g - T.cstart[a] + 1);
-    o.ch('\t');
-    o.num(g - T.cstart[a] + W);
-    o.ch('\t');
-    o.ch(strand ? '-' : '+');
-    o.ch('\t');
-    o.num(imp);
-    o.ch('\t');
-    o.num((unsigned long long)nmm);
-    o.ch('\t');
-    o.num((unsigned long long)ngu);
-    o.ch('\t');
-    const char* RNA = "ACGUN";
-    for (int c = 1; c <= W; c++) { const int i = pos(c); o.ch(i ? RNA[mc[i - 1]] : '-'); }
-    o.ch('\t');
-    for (int c = 1; c <= W; c++) {
-        const int i = pos(c);
-        const int k = i ? mm_class(mc[i - 1], base(c)) : 3;
-        o.ch(k == 0 ? '|' : k == 1 ? 'o' : k == 2 ? 'x' : '-');
-    }
-    o.ch('\t');
-    for (int c = 1; c <= W; c++) o.ch(RNA[base(c)]);
-    o.ch('\t');
-    o.num((unsigned long long)P);
-    o.ch('\n');
-    return o.n;
-}
-
-// first index of the miRNA run that holds keys[i] (the keys are sorted)
-__device__ __forceinline__ long long mm_run_first(const unsigned long long* __restrict__ keys, long long i) {
-    const unsigned long long lo = keys[i] >> MM_SHIFT << MM_SHIFT;
-    long long a = 0, z = i;
-    while (a < z) { const long long md = (a + z) >> 1; if (keys[md] < lo) a = md + 1; else z = md; }
-    return a;
-}
-
-// size[i] of sorted key i, 0 when -k cuts it (emitted[m] = lines of the miRNA written by earlier passes); kept[0] += lines kept
-__global__ void mm_size_kernel(MmText T, const unsigned long long* __restrict__ keys, long long n, long long k, const unsigned long long* __restrict__ emitted,
-                               int* __restrict__ size, unsigned long long* __restrict__ kept) {
-    unsigned long long cnt = 0;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const unsigned long long key = keys[i];
-        const bool keep = k == 0 || emitted[key >> MM_SHIFT] + (unsigned long long)(i - mm_run_first(keys, i)) < (unsigned long long)k;
-        size[i] = keep ? (int)mm_line<false>(T, key, nullptr) : 0;
-        cnt += keep;
-    }
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(kept, cnt);
-}
-// emitted[m] += the miRNA's keys in this pass (after mm_size_kernel)
-__global__ void mm_emitted_kernel(const unsigned long long* __restrict__ keys, long long n, unsigned long long* __restrict__ emitted) {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        if (i == n - 1 || (keys[i + 1] >> MM_SHIFT) != (keys[i] >> MM_SHIFT)) emitted[keys[i] >> MM_SHIFT] += (unsigned long long)(i + 1 - mm_run_first(keys, i));
-}
-__global__ void mm_emit_kernel(MmText T, const unsigned long long* __restrict__ keys, long long i0, long long i1, const long long* __restrict__ toff,
-                               char* __restrict__ text) {
-    const long long base = toff[i0];
-    for (long long i = i0 + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < i1; i += (long long)gridDim.x * blockDim.x)
-        if (toff[i + 1] != toff[i]) (void)mm_line<true>(T, keys[i], text + (toff[i] - base));
-}
+};
 
 }  // namespace mirp
-
-static inline int mm_grid(long long n) {
-    const long long g = (n + 255) / 256;
-    return (int)(g < 1 ? 1 : g > 16384 ? 16384 : g);
-}
 
 namespace {
 
@@ -266,67 +195,6 @@ struct MmRun {
         return 0;
     }
 
-    // sort, cut and write the n <= cap keys of the last scan
-    int finish(long long n) {
-        using namespace mirp;
-        hipStream_t st = c->stream;
-        stats[1]++;
-        if (n == 0) return 0;
-        double t = mirp::now();
-        unsigned long long* d_keys = (unsigned long long*)c->tg_keys.p;
-        int mbits = 0;                                         // the key's bits above the miRNA index are 0
-        while ((1ll << mbits) < n_mi) mbits++;
-        if (int rc = mirp_device_sort_u64(c, d_keys, (unsigned long long*)c->tg_ktmp.p, n, 0, (MM_SHIFT + mbits + 7) / 8 * 8)) return rc;
-        unsigned long long* d_small = (unsigned long long*)c->tg_small.p;
-        long long* d_toff = (long long*)c->tg_toff.p;
-        HIPCHK(c, hipMemsetAsync(d_small + 1, 0, 8, st));
-        hipLaunchKernelGGL(mm_size_kernel, dim3(mm_grid(n)), dim3(256), 0, st, T, (const unsigned long long*)d_keys, n, (long long)o->max_sites,
-                           (const unsigned long long*)c->tg_emitted.p, (int*)c->tg_size.p, d_small + 1);
-        hipLaunchKernelGGL(mm_emitted_kernel, dim3(mm_grid(n)), dim3(256), 0, st, (const unsigned long long*)d_keys, n, (unsigned long long*)c->tg_emitted.p);
-        launch_excl_scan(st, (const int*)c->tg_size.p, d_toff, n);
-        long long bytes = 0;
-        unsigned long long kept = 0;
-        HIPCHK(c, hipMemcpyAsync(&bytes, d_toff + n, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(&kept, d_small + 1, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        HIPCHK(c, hipGetLastError());
-        stats[0] += (long long)kept;
-        sec[1] += mirp::now() - t;
-        t = mirp::now();
-        // pieces of at most 1 GiB of text (at least one line each)
-        const long long piece = 1ll << 30;
-        for (long long i0 = 0; i0 < n;) {
-            long long base = 0;
-            HIPCHK(c, hipMemcpy(&base, d_toff + i0, 8, hipMemcpyDeviceToHost));
-            long long i1 = n, end = bytes;
-            if (bytes - base > piece) {                        // the last i1 in [i0 + 1, n) with toff[i1] - base <= piece
-                long long a = i0 + 1, z = n - 1;
-                while (a < z) {
-                    const long long md = (a + z + 1) >> 1;
-                    long long v = 0;
-                    HIPCHK(c, hipMemcpy(&v, d_toff + md, 8, hipMemcpyDeviceToHost));
-                    if (v - base <= piece) a = md; else z = md - 1;
-                }
-                i1 = a;
-                HIPCHK(c, hipMemcpy(&end, d_toff + i1, 8, hipMemcpyDeviceToHost));
-            }
-            const long long len = end - base;
-            if (len > 0) {
-                if (c->tg_text.ensure((size_t)len + 16)) return fail(c, -6, "device allocation failed (mimics: text)");
-                hipLaunchKernelGGL(mm_emit_kernel, dim3(mm_grid(i1 - i0)), dim3(256), 0, st, T, (const unsigned long long*)d_keys, i0, i1, (const long long*)d_toff,
-                                   (char*)c->tg_text.p);
-                HIPCHK(c, hipStreamSynchronize(st));
-                HIPCHK(c, hipGetLastError());
-                if (c->h_text.size() < (size_t)len) c->h_text.resize((size_t)len);
-                HIPCHK(c, hipMemcpy(c->h_text.data(), c->tg_text.p, (size_t)len, hipMemcpyDeviceToHost));
-                if (int rc = (*sink)(c->h_text.data(), (size_t)len)) return rc;
-            }
-            i0 = i1;
-        }
-        sec[2] += mirp::now() - t;
-        return 0;
-    }
-
     int run() {
         using namespace mirp;
         hipStream_t st = c->stream;
@@ -336,45 +204,18 @@ struct MmRun {
         for (long long m = 0; m < n_mi; m++) set_range(m, 0, nmax);
         long long hits = 0;
         if (int rc = scan(0, 0, total, &hits)) return rc;
-        if (hits <= cap) return finish(hits);
-        // overflow: hits per (miRNA, imperfect), then passes of at most cap keys in output order
-        HIPCHK(c, hipMemsetAsync(c->tg_hist.p, 0, 8 * (size_t)n_mi * MM_NBIN, st));
-        if (int rc = scan(1, 0, total, &hits)) return rc;
-        std::vector<unsigned long long> hist((size_t)n_mi * MM_NBIN);
-        HIPCHK(c, hipMemcpy(hist.data(), c->tg_hist.p, 8 * hist.size(), hipMemcpyDeviceToHost));
-        std::vector<signed char> lim((size_t)n_mi, (signed char)nmax);    // -k: no line of a miRNA past the imperfect at which its first k lines are reached
-        if (o->max_sites > 0)
-            for (long long m = 0; m < n_mi; m++) {
-                unsigned long long cum = 0;
-                for (int h = 0; h <= nmax; h++) {
-                    cum += hist[(size_t)m * MM_NBIN + h];
-                    if (cum >= (unsigned long long)o->max_sites) { lim[(size_t)m] = (signed char)h; break; }
-                }
-            }
-        for (long long m = 0; m < n_mi; m++) set_range(m, 1, 0);          // a pass opens the ranges of its miRNAs and closes them again
-        const auto count = [&](long long i) { return (int)(i % MM_NBIN) <= lim[(size_t)(i / MM_NBIN)] ? (long long)hist[(size_t)i] : 0ll; };
-        const auto flush = [&](long long first, long long last, long long expected) -> int {
-            const long long ma = first / MM_NBIN, mb = last / MM_NBIN;
-            const int ha = (int)(first % MM_NBIN), hb = (int)(last % MM_NBIN);
-            for (long long m = ma; m <= mb; m++) set_range(m, m == ma ? ha : 0, m == mb ? hb : lim[(size_t)m]);
-            long long got = 0;
-            int rc = scan(0, 0, total, &got);
-            for (long long m = ma; m <= mb; m++) set_range(m, 1, 0);
-            if (rc) return rc;
-            if (got != expected) return fail(c, -5, "mimics: a pass found a different number of sites than counted");
-            return finish(got);
+        int mbits = 0;                                         // the key's bits above the miRNA index are 0
+        while ((1ll << mbits) < n_mi) mbits++;
+        const auto write_pass = [&](long long n) {
+            return site_finish_pass(c, MmLine{T}, n, MM_SHIFT + mbits, (long long)o->max_sites, *sink, "mimics", stats, sec);
         };
-        const auto range = [&](long long bin, unsigned long long p, unsigned long long p1, long long* got) -> int {
-            const long long m = bin / MM_NBIN;
-            const int h = (int)(bin % MM_NBIN);
-            set_range(m, h, h);
-            const int rc = scan(0, p, p1, got);
-            set_range(m, 1, 0);
-            if (rc) return rc;
-            return *got > cap ? 0 : finish(*got);
-        };
-        const int rc = plan_passes(n_mi * MM_NBIN, count, cap, total, flush, range);
-        return rc == PLAN_POSITION_OVER_CAP ? fail(c, -5, "mimics: one position holds more sites of one miRNA and imperfect count than a pass") : rc;
+        if (hits <= cap) return write_pass(hits);
+        // overflow: passes of at most cap keys in output order, with (miRNA, imperfect) as the bins and the interval starts as the positions; a
+        // scan takes every miRNA whose range is open
+        return site_plan_passes(
+            c, n_mi, MM_NBIN, nmax, (long long)o->max_sites, cap, total, "mimics",
+            "mimics: one position holds more sites of one miRNA and imperfect count than a pass", [&](long long m, int lo, int hi) { set_range(m, lo, hi); },
+            [&](int mode, long long, long long, unsigned long long p0, unsigned long long p1, long long* got) { return scan(mode, p0, p1, got); }, write_pass);
     }
 };
 

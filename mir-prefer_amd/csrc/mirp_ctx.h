@@ -272,7 +272,7 @@ void mirp_device_rf_stats(mirp_ctx* c, const RfPlan& p, long long j0, int n_jobs
 // of the paired positions of a and b.  pairs: strands as codes 0..4 (N A C G U) at d_a + d_aoff[q] .. d_aoff[q + 1], likewise b, every length
 // 1..64 and at most max_la / max_lb; d_evals (optional) += loop evaluations.  perfect: miRNA q of the group (codes 0..3 = A C G U, 4 = unknown, 32
 // per miRNA) against its reverse complement.  sites: the sorted keys of a pass of the target search (targets_kernels.hip; bulge: the --bulge key
-// layout); a key that -k cuts (max_sites, d_emitted as tg_size_kernel reads them) is not folded and gets mfe 0 and empty masks.
+// layout); a key that -k cuts (max_sites, d_emitted as site_kept of site_keys.h reads them) is not folded and gets mfe 0 and empty masks.
 struct DxTargets {
     const unsigned long long* pk; const unsigned* amb; const unsigned char* mcodes; const TgMirna* mi; const unsigned long long* cstart;
     int n_contigs, mbase;

@@ -17,12 +17,11 @@
 //   scan   tg_scan_kernel<0>: one lane per target offset, miRNAs of the pass in wave-uniform (scalar) loads; every hit appends the key
 //          mloc << 38 | half << 33 | o << 1 | strand (mloc = the miRNA's index in its group of <= 2^16) to a buffer of `cap` keys and counts it.
 //          tg_scan_kernel<1>: the same scan counting hits per (miRNA, half-score) only, run when a pass's hits overflow the buffer: the counts go
-//          to plan_passes (pass_plan.h) with (miRNA, half-score) as the bins and the target offsets as the positions.
-//   order  mirp_device_sort_u64 by the whole key: per miRNA, (score, target, start, + before -) = the output order.
-//   cut    tg_size_kernel: -k from the rank inside the miRNA's run plus what earlier passes emitted; the line's length; launch_excl_scan.
-//   emit   tg_emit_kernel writes the lines; the text goes to the sink in pieces of at most 1 GiB.
+//          to site_plan_passes (site_lines.h) with (miRNA, half-score) as the bins and the target offsets as the positions.
+//   order, cut, emit   site_finish_pass (site_lines.h) with the line TgLine<false>: the sort by the whole key gives, per miRNA, (score, target,
+//          start, + before -) = the output order; -k cuts by the rank inside the miRNA's run plus what earlier passes emitted.
 // With --bulge the scan is tg_bulge_scan_kernel (targets_bulge_device.h), which also finds the sites with one unpaired base; its keys are
-// mloc << 45 | half << 40 | start << 8 | strand << 7 | kind << 5 | P, again in output order, and order, cut and emit run as their <true> instances.
+// mloc << 45 | half << 40 | start << 8 | strand << 7 | kind << 5 | P, again in output order, and the line is TgLine<true>.
 // With --energy the sorted keys of a pass are folded (duplex_kernels.hip) before the cut measures the lines, and every line gains
 // the columns mfe, mfe_perfect, mfe_ratio and duplex; without it TgText's energy pointers are null and the lines are as before.
 // With --accessibility the windows of the sorted keys are folded as well (unpaired_kernels.hip) and every line gains the column upe.
@@ -34,8 +33,7 @@
 #include <string>
 #include <vector>
 #include "mirp_ctx.h"
-#include "pass_plan.h"
-#include "targets_bulge_device.h"
+#include "site_lines.h"
 #include "text_out.h"
 
 namespace mirp {
@@ -101,195 +99,54 @@ __device__ void tg_upe_col(TextOut<WRITE>& o, const TgText& T, long long idx) {
     o.ch((char)('0' + v % 10));
 }
 
-// pair class of miRNA code mc (0..3 A C G U, 4 unknown) with target-strand base y (0..3 A C G U): 0 Watson-Crick, 1 G:U, 2 mismatch
-__device__ __forceinline__ int tg_class(unsigned mc, unsigned y) {
-    if (mc > 3) return 2;
-    if (mc + y == 3) return 0;
-    return (mc == 2 && y == 3) || (mc == 3 && y == 2) ? 1 : 2;
-}
-
-// one line: miRNA target start end strand score mismatches gu mirna_5to3 pairs target_3to5 (idx: the key's index in the pass, for --energy)
-template <bool WRITE>
-__device__ long long tg_line(const TgText& T, unsigned long long key, long long idx, char* out) {
-    TextOut<WRITE> o{out};
-    const int mloc = (int)(key >> 38);
-    const unsigned half = (unsigned)(key >> 33) & 31u;
-    const unsigned long long g = (key >> 1) & 0xffffffffull;
-    const int strand = (int)(key & 1);
-    const long long m = (long long)T.mbase + mloc;
-    const int L = T.mi[mloc].L;
-    const unsigned char* mc = T.mcodes + 32 * m;
-    int a = 0, z = T.n_contigs;                 // target: last cstart <= g
-    while (z - a > 1) { const int md = (a + z) >> 1; if (T.cstart[md] <= g) a = md; else z = md; }
-    int nmm = 0, ngu = 0;
-    for (int i = 1; i <= L; i++) {
-        const unsigned b = tg_base(T.pk, strand ? g + i - 1 : g + L - i);
-        const int k = tg_class(mc[i - 1], strand ? 3u - b : b);
-        nmm += k == 2;
-        ngu += k == 1;
-    }
-    o.str(T.mnames + T.mnoff[m], T.mnoff[m + 1] - T.mnoff[m]);
-    o.ch('\t');
-    o.str(T.tnames + T.tnoff[a], T.tnoff[a + 1] - T.tnoff[a]);
-    o.ch('\t');
-    o.num(g - T.cstart[a] + 1);
-    o.ch('\t');
-    o.num(g - T.cstart[a] + L);
-    o.ch('\t');
-    o.ch(strand ? '-' : '+');
-    o.ch('\t');
-    o.num(half >> 1);
-    o.ch('.');
-    o.ch(half & 1 ? '5' : '0');
-    o.ch('\t');
-    o.num((unsigned long long)nmm);
-    o.ch('\t');
-    o.num((unsigned long long)ngu);
-    o.ch('\t');
-    const char* RNA = "ACGUN";
-    for (int i = 0; i < L; i++) o.ch(RNA[mc[i]]);
-    o.ch('\t');
-    for (int i = 1; i <= L; i++) {
-        const unsigned b = tg_base(T.pk, strand ? g + i - 1 : g + L - i);
-        const int k = tg_class(mc[i - 1], strand ? 3u - b : b);
-        o.ch(k == 0 ? '|' : k == 1 ? 'o' : 'x');
-    }
-    o.ch('\t');
-    for (int i = 1; i <= L; i++) {
-        const unsigned b = tg_base(T.pk, strand ? g + i - 1 : g + L - i);
-        o.ch(RNA[strand ? 3u - b : b]);
-    }
-    if (T.e_mfe) tg_energy_cols(o, T, idx, mloc, L, L + (g > T.cstart[a]) + (g + L < T.cstart[a + 1]));
-    if (T.upe) tg_upe_col(o, T, idx);
-    o.ch('\n');
-    return o.n;
-}
-
-// one line of a --bulge run: the columns of tg_line and the bulge column (. / tP / mP).  Column c of the three aligned strings holds miRNA position
-// i(c) and the target base q(c); the t site has one column more (the unpaired target base under a '-'), the m site a '-' under miRNA position P.
-template <bool WRITE>
-__device__ long long tg_bulge_line(const TgText& T, unsigned long long key, long long idx, char* out) {
-    TextOut<WRITE> o{out};
-    const int mloc = (int)(key >> TG_BULGE_SHIFT);
-    const unsigned half = (unsigned)(key >> 40) & 31u;
-    const unsigned long long g = (key >> 8) & 0xffffffffull;
-    const int strand = (int)(key >> 7) & 1, kind = (int)(key >> 5) & 3, P = (int)(key & 31);
-    const long long m = (long long)T.mbase + mloc;
-    const int L = T.mi[mloc].L;
-    const int W = L + (kind == 2);                  // columns
-    const unsigned char* mc = T.mcodes + 32 * m;
-    int a = 0, z = T.n_contigs;                 // target: last cstart <= g
-    while (z - a > 1) { const int md = (a + z) >> 1; if (T.cstart[md] <= g) a = md; else z = md; }
-    // column c = 1 .. W: the miRNA position (0 = none) and the target-strand base (-1 = none)
-    auto pos = [&](int c) { return kind != 2 || c <= P ? c : c == P + 1 ? 0 : c - 1; };
-    auto base = [&](int c) -> int {
-        unsigned long long q;
-        if (kind == 2) q = strand ? g + c - 1 : g + L + 1 - c;
-        else if (kind == 1) q = strand ? g + c - 1 : g + L - c;
-        else if (c == P) return -1;
-        else if (c < P) q = strand ? g + c - 1 : g + L - 1 - c;
-        else q = strand ? g + c - 2 : g + L - c;
-        const unsigned b = tg_base(T.pk, q);
-        return (int)(strand ? 3u - b : b);
-    };
-    int nmm = 0, ngu = 0;
-    for (int c = 1; c <= W; c++) {
-        const int i = pos(c), y = base(c);
-        if (i == 0 || y < 0) continue;
-        const int k = tg_class(mc[i - 1], (unsigned)y);
-        nmm += k == 2;
-        ngu += k == 1;
-    }
-    o.str(T.mnames + T.mnoff[m], T.mnoff[m + 1] - T.mnoff[m]);
-    o.ch('\t');
-    o.str(T.tnames + T.tnoff[a], T.tnoff[a + 1] - T.tnoff[a]);
-    o.ch('\t');
-    o.num(g - T.cstart[a] + 1);
-    o.ch('\t');
-    o.num(g - T.cstart[a] + L + kind - 1);
-    o.ch('\t');
-    o.ch(strand ? '-' : '+');
-    o.ch('\t');
-    o.num(half >> 1);
-    o.ch('.');
-    o.ch(half & 1 ? '5' : '0');
-    o.ch('\t');
-    o.num((unsigned long long)nmm);
-    o.ch('\t');
-    o.num((unsigned long long)ngu);
-    o.ch('\t');
-    const char* RNA = "ACGUN";
-    for (int c = 1; c <= W; c++) { const int i = pos(c); o.ch(i ? RNA[mc[i - 1]] : '-'); }
-    o.ch('\t');
-    for (int c = 1; c <= W; c++) {
-        const int i = pos(c), y = base(c);
-        const int k = i == 0 || y < 0 ? 3 : tg_class(mc[i - 1], (unsigned)y);
-        o.ch(k == 0 ? '|' : k == 1 ? 'o' : k == 2 ? 'x' : '-');
-    }
-    o.ch('\t');
-    for (int c = 1; c <= W; c++) { const int y = base(c); o.ch(y < 0 ? '-' : RNA[y]); }
-    o.ch('\t');
-    if (kind == 1) o.ch('.');
-    else { o.ch(kind == 2 ? 't' : 'm'); o.num((unsigned long long)P); }
-    if (T.e_mfe) {
-        const int len = L + kind - 1;
-        tg_energy_cols(o, T, idx, mloc, L, len + (g > T.cstart[a]) + (g + len < T.cstart[a + 1]));
-    }
-    if (T.upe) tg_upe_col(o, T, idx);
-    o.ch('\n');
-    return o.n;
-}
-
-// the bits of a key below the miRNA index: 38 for the ungapped scan's keys, 45 for the --bulge scan's
-template <bool BULGE> struct TgKey { static constexpr int shift = BULGE ? TG_BULGE_SHIFT : 38; };
-
-// first index of the miRNA run that holds keys[i] (the keys are sorted)
+// One line: miRNA target start end strand score mismatches gu mirna_5to3 pairs target_3to5, with --bulge the bulge column (. / tP / mP), then the
+// columns of --energy and --accessibility (idx: the key's index in the pass).  Column c of the three aligned strings holds miRNA position i(c) and
+// the target base q(c); the t site has one column more (the unpaired target base under a '-'), the m site a '-' under miRNA position P.
 template <bool BULGE>
-__device__ __forceinline__ long long tg_run_first(const unsigned long long* __restrict__ keys, long long i) {
-    const unsigned long long lo = keys[i] >> TgKey<BULGE>::shift << TgKey<BULGE>::shift;
-    long long a = 0, z = i;
-    while (a < z) { const long long md = (a + z) >> 1; if (keys[md] < lo) a = md + 1; else z = md; }
-    return a;
-}
-
-// size[i] of sorted key i, 0 when -k cuts it (emitted[mloc] = lines of the miRNA written by earlier passes); kept[0] += lines kept
-template <bool BULGE>
-__global__ void tg_size_kernel(TgText T, const unsigned long long* __restrict__ keys, long long n, long long k, const unsigned long long* __restrict__ emitted,
-                               int* __restrict__ size, unsigned long long* __restrict__ kept) {
-    unsigned long long cnt = 0;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const unsigned long long key = keys[i];
-        const bool keep = k == 0 || emitted[key >> TgKey<BULGE>::shift] + (unsigned long long)(i - tg_run_first<BULGE>(keys, i)) < (unsigned long long)k;
-        size[i] = !keep ? 0 : BULGE ? (int)tg_bulge_line<false>(T, key, i, nullptr) : (int)tg_line<false>(T, key, i, nullptr);
-        cnt += keep;
-    }
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(kept, cnt);
-}
-// emitted[mloc] += the miRNA's keys in this pass (after tg_size_kernel)
-template <bool BULGE>
-__global__ void tg_emitted_kernel(const unsigned long long* __restrict__ keys, long long n, unsigned long long* __restrict__ emitted) {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        if (i == n - 1 || (keys[i + 1] >> TgKey<BULGE>::shift) != (keys[i] >> TgKey<BULGE>::shift))
-            emitted[keys[i] >> TgKey<BULGE>::shift] += (unsigned long long)(i + 1 - tg_run_first<BULGE>(keys, i));
-}
-template <bool BULGE>
-__global__ void tg_emit_kernel(TgText T, const unsigned long long* __restrict__ keys, long long i0, long long i1, const long long* __restrict__ toff,
-                               char* __restrict__ text) {
-    const long long base = toff[i0];
-    for (long long i = i0 + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < i1; i += (long long)gridDim.x * blockDim.x)
-        if (toff[i + 1] != toff[i]) {
-            if (BULGE) (void)tg_bulge_line<true>(T, keys[i], i, text + (toff[i] - base));
-            else (void)tg_line<true>(T, keys[i], i, text + (toff[i] - base));
+struct TgLine {
+    TgText T;
+    static constexpr int shift = SiteKey<BULGE>::shift;
+    template <bool WRITE>
+    __device__ long long line(unsigned long long key, long long idx, char* out) const {
+        TextOut<WRITE> o{out};
+        const SiteKey<BULGE> K(key);
+        const unsigned long long g = K.g;
+        const int strand = K.strand, kind = K.kind, P = K.P;
+        const long long m = (long long)T.mbase + K.mloc;
+        const int L = T.mi[K.mloc].L, len = K.len(L);
+        const int a = site_contig(T.cstart, T.n_contigs, g);
+        text_site_head(o, T.mnames, T.mnoff, m, T.tnames, T.tnoff, a, g - T.cstart[a] + 1, g - T.cstart[a] + len, strand);
+        o.ch('\t');
+        o.num(K.half >> 1);
+        o.ch('.');
+        o.ch(K.half & 1 ? '5' : '0');
+        o.ch('\t');
+        // column c = 1 .. W: the miRNA position (0 = none) and the target-strand base (-1 = none)
+        const auto pos = [&](int c) { return kind != 2 || c <= P ? c : c == P + 1 ? 0 : c - 1; };
+        const auto base = [&](int c) -> int {
+            unsigned long long q;
+            if (kind == 2) q = strand ? g + c - 1 : g + L + 1 - c;
+            else if (kind == 1) q = strand ? g + c - 1 : g + L - c;
+            else if (c == P) return -1;
+            else if (c < P) q = strand ? g + c - 1 : g + L - 1 - c;
+            else q = strand ? g + c - 2 : g + L - c;
+            const unsigned b = tg_base(T.pk, q);
+            return (int)(strand ? 3u - b : b);
+        };
+        text_site_pairing(o, T.mcodes + 32 * m, L + (kind == 2), pos, base);
+        if (BULGE) {
+            o.ch('\t');
+            if (kind == 1) o.ch('.');
+            else { o.ch(kind == 2 ? 't' : 'm'); o.num((unsigned long long)P); }
         }
-}
+        if (T.e_mfe) tg_energy_cols(o, T, idx, K.mloc, L, len + (g > T.cstart[a]) + (g + len < T.cstart[a + 1]));
+        if (T.upe) tg_upe_col(o, T, idx);
+        o.ch('\n');
+        return o.n;
+    }
+};
 
 }  // namespace mirp
-
-static inline int tg_grid(long long n) {
-    const long long g = (n + 255) / 256;
-    return (int)(g < 1 ? 1 : g > 16384 ? 16384 : g);
-}
 
 namespace {
 
@@ -338,84 +195,33 @@ struct TgRun {
         return 0;
     }
 
-    // sort, cut and write the n <= cap keys of the last scan
-    int finish(int mbase, long long n) {
+    // sort, cut and write the n <= cap keys of the last scan.  With --energy / --accessibility the sorted keys that -k keeps are folded before the
+    // lines are measured: the widths of `mfe` and `upe` are part of a line's length.
+    template <bool BULGE>
+    int write_pass(int mbase, long long n) {
         using namespace mirp;
-        hipStream_t st = c->stream;
-        stats[1]++;
-        if (n == 0) return 0;
-        double t = mirp::now();
-        unsigned long long* d_keys = (unsigned long long*)c->tg_keys.p;
+        T.mbase = mbase;
         int mbits = 0;                                         // the key's bits above the miRNA index are 0
         while ((1 << mbits) < group_n) mbits++;
-        const bool bulge = o->bulge != 0;
-        if (int rc = mirp_device_sort_u64(c, d_keys, (unsigned long long*)c->tg_ktmp.p, n, 0, ((bulge ? TG_BULGE_SHIFT : 38) + mbits + 7) / 8 * 8)) return rc;
-        T.mbase = mbase;
-        unsigned long long* d_small = (unsigned long long*)c->tg_small.p;
-        long long* d_toff = (long long*)c->tg_toff.p;
-        HIPCHK(c, hipMemsetAsync(d_small + 1, 0, 8, st));
-        if (o->energy) {                                       // the folds of the sorted keys that -k keeps: the width of `mfe` is part of a line's length
-            const DxTargets D{T.pk, T.amb, T.mcodes, T.mi, T.cstart, T.n_contigs, mbase};
-            if (int rc = mirp_device_duplex_sites(c, D, bulge, (const unsigned long long*)d_keys, n, (long long)o->max_sites,
-                                                  (const unsigned long long*)c->tg_emitted.p, (int*)c->tg_emfe.p, (unsigned long long*)c->tg_ema.p,
-                                                  (unsigned long long*)c->tg_emb.p))
-                return rc;
-        }
-        if (o->accessibility) {                                // likewise the windows of the kept keys: the width of `upe` is part of a line's length
+        const auto folds = [&](const unsigned long long* d_keys, long long n) -> int {
             const DxTargets D{T.pk, (const unsigned*)c->tg_amb.p, T.mcodes, T.mi, T.cstart, T.n_contigs, mbase};
-            int longest = 0;                                   // the group's longest interval sizes the launch's tables
-            for (int m = 0; m < group_n; m++) longest = std::max(longest, (int)(*mi)[(size_t)(mbase + m)].L + (bulge ? 1 : 0));
-            if (int rc = mirp_device_unpaired_sites(c, D, bulge, (const unsigned long long*)d_keys, n, (long long)o->max_sites,
-                                                    (const unsigned long long*)c->tg_emitted.p, longest, c->tg_up, c->tg_down, (int*)c->tg_upe.p))
-                return rc;
-        }
-        hipLaunchKernelGGL(bulge ? tg_size_kernel<true> : tg_size_kernel<false>, dim3(tg_grid(n)), dim3(256), 0, st, T, (const unsigned long long*)d_keys, n,
-                           (long long)o->max_sites, (const unsigned long long*)c->tg_emitted.p, (int*)c->tg_size.p, d_small + 1);
-        hipLaunchKernelGGL(bulge ? tg_emitted_kernel<true> : tg_emitted_kernel<false>, dim3(tg_grid(n)), dim3(256), 0, st, (const unsigned long long*)d_keys, n,
-                           (unsigned long long*)c->tg_emitted.p);
-        launch_excl_scan(st, (const int*)c->tg_size.p, d_toff, n);
-        long long bytes = 0;
-        unsigned long long kept = 0;
-        HIPCHK(c, hipMemcpyAsync(&bytes, d_toff + n, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(&kept, d_small + 1, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        HIPCHK(c, hipGetLastError());
-        stats[0] += (long long)kept;
-        sec[1] += mirp::now() - t;
-        t = mirp::now();
-        // pieces of at most 1 GiB of text (at least one line each)
-        const long long piece = 1ll << 30;
-        for (long long i0 = 0; i0 < n;) {
-            long long base = 0;
-            HIPCHK(c, hipMemcpy(&base, d_toff + i0, 8, hipMemcpyDeviceToHost));
-            long long i1 = n, end = bytes;
-            if (bytes - base > piece) {                        // the last i1 in [i0 + 1, n) with toff[i1] - base <= piece
-                long long a = i0 + 1, z = n - 1;
-                while (a < z) {
-                    const long long md = (a + z + 1) >> 1;
-                    long long v = 0;
-                    HIPCHK(c, hipMemcpy(&v, d_toff + md, 8, hipMemcpyDeviceToHost));
-                    if (v - base <= piece) a = md; else z = md - 1;
-                }
-                i1 = a;
-                HIPCHK(c, hipMemcpy(&end, d_toff + i1, 8, hipMemcpyDeviceToHost));
+            const unsigned long long* d_emitted = (const unsigned long long*)c->tg_emitted.p;
+            if (o->energy)
+                if (int rc = mirp_device_duplex_sites(c, D, BULGE, d_keys, n, (long long)o->max_sites, d_emitted, (int*)c->tg_emfe.p,
+                                                      (unsigned long long*)c->tg_ema.p, (unsigned long long*)c->tg_emb.p))
+                    return rc;
+            if (o->accessibility) {
+                int longest = 0;                               // the group's longest interval sizes the launch's tables
+                for (int m = 0; m < group_n; m++) longest = std::max(longest, (int)(*mi)[(size_t)(mbase + m)].L + (BULGE ? 1 : 0));
+                if (int rc = mirp_device_unpaired_sites(c, D, BULGE, d_keys, n, (long long)o->max_sites, d_emitted, longest, c->tg_up, c->tg_down,
+                                                        (int*)c->tg_upe.p))
+                    return rc;
             }
-            const long long len = end - base;
-            if (len > 0) {
-                if (c->tg_text.ensure((size_t)len + 16)) return fail(c, -6, "device allocation failed (targets: text)");
-                hipLaunchKernelGGL(bulge ? tg_emit_kernel<true> : tg_emit_kernel<false>, dim3(tg_grid(i1 - i0)), dim3(256), 0, st, T, (const unsigned long long*)d_keys, i0, i1, (const long long*)d_toff,
-                                   (char*)c->tg_text.p);
-                HIPCHK(c, hipStreamSynchronize(st));
-                HIPCHK(c, hipGetLastError());
-                if (c->h_text.size() < (size_t)len) c->h_text.resize((size_t)len);
-                HIPCHK(c, hipMemcpy(c->h_text.data(), c->tg_text.p, (size_t)len, hipMemcpyDeviceToHost));
-                if (int rc = (*sink)(c->h_text.data(), (size_t)len)) return rc;
-            }
-            i0 = i1;
-        }
-        sec[2] += mirp::now() - t;
-        return 0;
+            return 0;
+        };
+        return site_finish_pass(c, TgLine<BULGE>{T}, n, TgLine<BULGE>::shift + mbits, (long long)o->max_sites, *sink, "targets", stats, sec, folds);
     }
+    int write_pass(int mbase, long long n) { return o->bulge ? write_pass<true>(mbase, n) : write_pass<false>(mbase, n); }
 
     void set_range(int mbase, int m, int smin, int smax) {
         TgMirna& x = (*mi)[(size_t)(mbase + m)];
@@ -442,39 +248,15 @@ struct TgRun {
             HIPCHK(c, hipStreamSynchronize(st));
             sec[1] += mirp::now() - t;
         }
-        if (hits <= cap) return finish(mbase, hits);
-        // overflow: hits per (miRNA, half-score), then passes of at most cap keys in output order
-        HIPCHK(c, hipMemsetAsync(c->tg_hist.p, 0, 8 * (size_t)n * TG_NHALF, st));
-        if (int rc = scan(1, mbase, 0, n, 0, total, &hits)) return rc;
-        std::vector<unsigned long long> hist((size_t)n * TG_NHALF);
-        HIPCHK(c, hipMemcpy(hist.data(), c->tg_hist.p, 8 * hist.size(), hipMemcpyDeviceToHost));
-        std::vector<int> lim(n, smax);               // -k: no line of a miRNA past the half-score at which its first k lines are reached
-        if (o->max_sites > 0)
-            for (int m = 0; m < n; m++) {
-                unsigned long long cum = 0;
-                for (int h = 0; h <= smax; h++) {
-                    cum += hist[(size_t)m * TG_NHALF + h];
-                    if (cum >= (unsigned long long)o->max_sites) { lim[m] = h; break; }
-                }
-            }
-        // the bins are (miRNA, half-score) up to lim[], the positions of a bin over cap are the target offsets
-        const auto count = [&](long long i) { return (int)(i % TG_NHALF) <= lim[(size_t)(i / TG_NHALF)] ? (long long)hist[(size_t)i] : 0ll; };
-        const auto flush = [&](long long first, long long last, long long expected) -> int {
-            const int ma = (int)(first / TG_NHALF), ha = (int)(first % TG_NHALF), mb = (int)(last / TG_NHALF), hb = (int)(last % TG_NHALF);
-            for (int m = ma; m <= mb; m++) set_range(mbase, m, m == ma ? ha : 0, m == mb ? hb : lim[m]);
-            long long got = 0;
-            if (int rc = scan(0, mbase, ma, mb + 1, 0, total, &got)) return rc;
-            if (got != expected) return fail(c, -5, "targets: a pass found a different number of sites than counted");
-            return finish(mbase, got);
-        };
-        const auto range = [&](long long bin, unsigned long long p, unsigned long long p1, long long* got) -> int {
-            const int m = (int)(bin / TG_NHALF), h = (int)(bin % TG_NHALF);
-            set_range(mbase, m, h, h);
-            if (int rc = scan(0, mbase, m, m + 1, p, p1, got)) return rc;
-            return *got > cap ? 0 : finish(mbase, *got);
-        };
-        const int rc = plan_passes((long long)n * TG_NHALF, count, cap, total, flush, range);
-        return rc == PLAN_POSITION_OVER_CAP ? fail(c, -5, "targets: one offset holds more sites of one miRNA and score than a pass") : rc;
+        if (hits <= cap) return write_pass(mbase, hits);
+        // overflow: passes of at most cap keys in output order, with (miRNA, half-score) as the bins and the target offsets as the positions
+        return site_plan_passes(
+            c, n, TG_NHALF, smax, (long long)o->max_sites, cap, total, "targets", "targets: one offset holds more sites of one miRNA and score than a pass",
+            [&](long long m, int lo, int hi) { set_range(mbase, (int)m, lo, hi); },
+            [&](int mode, long long ma, long long mb, unsigned long long p0, unsigned long long p1, long long* got) {
+                return scan(mode, mbase, (int)ma, (int)mb + 1, p0, p1, got);
+            },
+            [&](long long got) { return write_pass(mbase, got); });
     }
 };
 

@@ -17,13 +17,14 @@
 //
 // Two sources of windows share the kernel: UpBatch (mirp_unpaired_batch: coded windows, offsets, intervals, and the order the host binned them
 // in) and UpSites (targets -u: the sorted keys of a pass; the window is the site's interval on the forward target extended by the flanks and
-// clipped to the contig, reverse-complemented on the minus strand; keys that -k cuts are not folded).
+// clipped to the contig, reverse-complemented on the minus strand; keys that -k cuts are not folded).  UpSites reads the keys as DxSites does
+// (duplex_kernels.hip), through site_kept, SiteKey and site_contig of site_keys.h.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "mirp_ctx.h"
 #include "fold_device.h"
 #include "ensemble_device.h"
-#include "targets_bulge_device.h"
+#include "site_keys.h"
 
 namespace mirp {
 
@@ -79,21 +80,12 @@ struct UpSites {
     int up, down;
     __device__ bool load(long long q, int lane, long long* rec, int* n_out, int* lo0, int* hi0, int* c0, int* c1) const {
         *rec = q;
-        const unsigned long long key = keys[q];
-        constexpr int shift = BULGE ? TG_BULGE_SHIFT : 38;
-        if (k != 0) {                       // the cut of tg_size_kernel, as DxSites takes it
-            const unsigned long long lo = key >> shift << shift;
-            long long x = 0, z = q;
-            while (x < z) { const long long md = (x + z) >> 1; if (keys[md] < lo) x = md + 1; else z = md; }
-            if (emitted[key >> shift] + (unsigned long long)(q - x) >= (unsigned long long)k) return false;
-        }
-        const int mloc = (int)(key >> shift);
-        const unsigned long long g = BULGE ? (key >> 8) & 0xffffffffull : (key >> 1) & 0xffffffffull;
-        const int strand = BULGE ? (int)(key >> 7) & 1 : (int)(key & 1);
-        const int L = T.mi[mloc].L;
-        const int len = BULGE ? L + ((int)(key >> 5) & 3) - 1 : L;
-        int c = 0, z = T.n_contigs;         // contig: last cstart <= g
-        while (z - c > 1) { const int md = (c + z) >> 1; if (T.cstart[md] <= g) c = md; else z = md; }
+        if (!site_kept(keys, q, k, emitted, SiteKey<BULGE>::shift)) return false;
+        const SiteKey<BULGE> K(keys[q]);
+        const int strand = K.strand;
+        const unsigned long long g = K.g;
+        const int len = K.len(T.mi[K.mloc].L);
+        const int c = site_contig(T.cstart, T.n_contigs, g);
         // forward bases before / behind the interval: up / down on the plus strand, the other way round on the minus strand
         const unsigned long long before = strand ? (unsigned long long)down : (unsigned long long)up, behind = strand ? (unsigned long long)up : (unsigned long long)down;
         const unsigned long long room0 = g - T.cstart[c], room1 = T.cstart[c + 1] - (g + len);
