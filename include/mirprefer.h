@@ -455,6 +455,28 @@ int mirp_align_reads(mirp_ctx* ctx, const char* reads_path, const char* out_path
 /* Batches the last mirp_align_reads of this context ran on the device (a file is cut into batches of at most 2^22 reads, fewer than 2^28 bases and
  * at most 2^26 seeds; 0 before the first call and for a file without reads). */
 int64_t mirp_align_last_batches(const mirp_ctx* ctx);
+/* Placement of multi-mapped reads (DESIGN.md §12 "Placement", ShortStack's --mmap u / r): every read gets one record.  mode 0: off; 1 (u): a read with
+ * 2..m best-stratum hits goes to one of them with probability proportional to the depths of the uniquely mapped reads of this file that start within
+ * `window` bases of the hit on its contig, or to a uniformly drawn hit where no hit has any; 2 (r): always the uniform draw.  The draw is a hash of
+ * the read's bases xor `seed`. */
+typedef struct {
+    int32_t mode;                            /* 0 off, 1 u, 2 r */
+    int32_t window;                          /* 0..10000 */
+    uint64_t seed;
+} MirpAlignPlaceOpts;
+/* mirp_align_reads with placement.  place == NULL or mode 0: exactly mirp_align_reads.  Otherwise m must be 1..10000 (a read with more than m hits is
+ * suppressed as in mirp_align_reads), k is not consulted, and the record of an aligned read carries NH:i:<hits> XY:Z:<N unique | U by density |
+ * R at random> XW:Z:<weight of the chosen hit>/<sum of the weights> after NM:i:.  A file for which m * (total depth of its unique reads) is 2^63 or
+ * more is refused (-10) before out_path is opened.  Out: stats = mirp_align_reads' five, then {unique, by density, at random}; seconds =
+ * mirp_align_reads' six, then {unique list + sort + prefix + weights + picks, the whole first pass}. */
+int mirp_align_reads_placed(mirp_ctx* ctx, const char* reads_path, const char* out_path, const char* pg_cl, int32_t v, int32_t k, int32_t m,
+                            int32_t filter_unmapped, const MirpAlignPlaceOpts* place, int64_t stats[8], double seconds[8]);
+/* The placement runs a file's batches twice: the first pass finds the unique reads of the whole file and keeps the sorted hits of the batches
+ * resident (8 bytes a hit) up to `items` hits (0 = the default, 2^28); a batch that does not fit is aligned again in the second pass, with the same
+ * output.  A file of one batch is never aligned twice. */
+int mirp_set_align_place_capacity(mirp_ctx* ctx, int64_t items);
+/* Batches the last mirp_align_reads_placed of this context aligned twice. */
+int64_t mirp_align_place_last_realigned(const mirp_ctx* ctx);
 
 /* 3' adapter and quality trimming of raw reads, the step before mirp_collapse_reads.  adapter[0 .. adapter_len) = A C G T in either
  * case (adapter_len 0..64; 0 = no adapter search); error_permille 0..999 = E in per-mille (an overlap of length l allows floor(E * l / 1000)

@@ -5,7 +5,9 @@
 Every read file X (collapsed reads, ids `sample_rA_xN`) gives X.sam next to it.  The options are the script's (-r, -i, -t, -v, -k, -p, -f) plus -m
 (the README's direct `bowtie -m`) and --device.  The reference FASTA files (-r) are indexed once per invocation on the device (mirp_align_index) and
 every read file is aligned against that index in the same device context (mirp_align_reads); there is no CPU path.  What is reported is defined in
-DESIGN.md §12: only the best stratum of hits with at most -v mismatches, the first -k of them in (contig, offset, + before -) order.
+DESIGN.md §12: only the best stratum of hits with at most -v mismatches, the first -k of them in (contig, offset, + before -) order.  With --place u|r (and --window,
+--seed) every read is reported once: a multi-mapped read goes to one of its best hits, chosen by the depth of the file's uniquely mapped reads
+around each hit or at random (§12 "Placement", ShortStack's --mmap u / r).
 
 -i cannot be served (a bowtie index cannot be read): it passes the script's checks and is then refused.  -p is accepted and ignored.  -t is
 accepted and the folder created, as the script does; no index files are written there.  Argument errors exit before a device is opened: option
@@ -38,6 +40,8 @@ READID_ERROR = ("The ID for each read in the output files has the following form
                 "fasta file represents. For example, if the sample name is 'root', and the read occurred 120 times in the library, then it's "
                 "identifier could be root_r23_x120. Here '23' is just a number that donates the order of the reads when processing it, it has no "
                 "use otherwise.\n")
+PLACE_M = 50            # -m where --place is given without it
+PLACE_WINDOW = 50       # --window where --place is given without it
 READID_HINT = ("Please use the provided scripts(process-reads-fasta.py, convert-mirdeep2-fasta.py, convert-readcount-file.py) to preprocess the "
                "read fasta files. Refer to the README file for more information.\n\n")
 
@@ -55,6 +59,12 @@ def make_parser():
     parser.add_option("-p", "--processor", type=int, default=1, help="Accepted for compatibility and ignored.")
     parser.add_option("-f", "--filterunmapped", action="store_true", help="Filter out unmapped alignments in the output.")
     parser.add_option("--device", type=int, default=0, help="GPU device index. Default is 0.")
+    parser.add_option("--place", type="choice", choices=["u", "r"], default=None,
+                      help="Report every read once. A read with several best alignments goes to one of them: 'u' by the depth of the uniquely "
+                           "mapped reads of its file around each alignment (at random where there are none), 'r' always at random. -m then "
+                           "defaults to 50 (1..10000) and -k is not consulted. Default: off.")
+    parser.add_option("--window", type=int, default=None, help="With --place: bases on each side of an alignment in which uniquely mapped reads count, 0..10000. Default is 50.")
+    parser.add_option("--seed", type=int, default=None, help="With --place: seed of the draw, 0..2^64-1. Default is 0.")
     return parser
 
 
@@ -78,6 +88,24 @@ def parse_args(argv):
         parser.error("Option -m must be at least 1.")
     if options.device < 0:
         parser.error("Option --device must be at least 0.")
+    if options.place is None:
+        if options.window is not None:
+            parser.error("Option --window needs --place.")
+        if options.seed is not None:
+            parser.error("Option --seed needs --place.")
+    else:
+        if options.maxmultialignment is None:
+            options.maxmultialignment = PLACE_M
+        if not 1 <= options.maxmultialignment <= 10000:
+            parser.error("Option -m must be between 1 and 10000 with --place.")
+        if options.window is None:
+            options.window = PLACE_WINDOW
+        if not 0 <= options.window <= 10000:
+            parser.error("Option --window must be between 0 and 10000.")
+        if options.seed is None:
+            options.seed = 0
+        if not 0 <= options.seed < 2 ** 64:
+            parser.error("Option --seed must be between 0 and 2^64-1.")
     if options.reference:
         for name in options.reference:
             if not os.path.exists(os.path.abspath(os.path.expanduser(name))):
@@ -152,10 +180,18 @@ def main(argv=None):
             sys.stdout.write("\nMapping file " + name + "\n")
             sys.stdout.flush()
             try:
-                ctx.align_reads(name, outname, cl, options.allowedmismatch, options.multialignment, m, bool(options.filterunmapped))
+                if options.place:
+                    res = ctx.align_reads(name, outname, cl, options.allowedmismatch, options.multialignment, m, bool(options.filterunmapped),
+                                          place=options.place, window=options.window, seed=options.seed)
+                else:
+                    ctx.align_reads(name, outname, cl, options.allowedmismatch, options.multialignment, m, bool(options.filterunmapped))
             except capi.MirpError as e:
                 sys.stderr.write("Error occurred when mapping reads: %s\n" % e)
                 return 255
+            if options.place:
+                sys.stdout.write("Placed: %d unique, %d by density, %d at random, %d suppressed\n"
+                                 % (res["unique"], res["by_density"], res["at_random"], res["suppressed"]))
+                sys.stdout.flush()
             outnames.append(outname)
     finally:
         ctx.close()

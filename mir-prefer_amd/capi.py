@@ -97,6 +97,11 @@ HAIRPIN_DTYPE = np.dtype([(f, "<i4") for f in ("query", "known", "score", "q_sta
 HAIRPIN_STATS = ("queries", "known", "pairs", "cells", "hits", "passes", "score_passes", "trace_passes")
 HAIRPIN_STRIP = 16          # MIRP_HAIRPIN_STRIP of include/mirprefer.h: query rows a lane of the scoring kernel holds in registers
 
+class AlignPlaceOpts(C.Structure):
+    """MirpAlignPlaceOpts of include/mirprefer.h."""
+    _fields_ = [("mode", C.c_int32), ("window", C.c_int32), ("seed", C.c_uint64)]
+
+
 class HomologOpts(C.Structure):
     """MirpHomologOpts of include/mirprefer.h."""
     _fields_ = [("max_mismatches", C.c_int32), ("precursor_len", C.c_int32), ("max_placements", C.c_int32), ("reserved", C.c_int32)]
@@ -475,6 +480,13 @@ def load_library():
     lib.mirp_align_reads.restype = C.c_int
     lib.mirp_align_last_batches.argtypes = [vp]
     lib.mirp_align_last_batches.restype = C.c_int64
+    lib.mirp_align_reads_placed.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlignPlaceOpts),
+                                            i64p, C.POINTER(C.c_double)]
+    lib.mirp_align_reads_placed.restype = C.c_int
+    lib.mirp_set_align_place_capacity.argtypes = [vp, C.c_int64]
+    lib.mirp_set_align_place_capacity.restype = C.c_int
+    lib.mirp_align_place_last_realigned.argtypes = [vp]
+    lib.mirp_align_place_last_realigned.restype = C.c_int64
     lib.mirp_trim_reads.argtypes = [vp, C.c_char_p, C.c_int64, C.c_char_p, C.POINTER(TrimOpts), C.c_char_p, i64p, C.POINTER(C.c_double)]
     lib.mirp_trim_reads.restype = C.c_int
     lib.mirp_target_scan.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(TargetOpts), C.c_char_p, i64p, C.POINTER(C.c_double)]
@@ -620,10 +632,21 @@ class Context:
         self._check(self.lib.mirp_align_index(self.h, arr, len(paths), C.byref(nc), C.byref(tot), sec), "mirp_align_index")
         return {"n_contigs": nc.value, "total": tot.value, "seconds": list(sec)}
 
-    def align_reads(self, reads_path, out_path, pg_cl="", v=0, k=20, m=0, filter_unmapped=False):
+    def align_reads(self, reads_path, out_path, pg_cl="", v=0, k=20, m=0, filter_unmapped=False, place=0, window=50, seed=0):
         """bowtie -v v --best --strata -k k [-m m] -S on one read FASTA file against the index of align_index (mirp_align_reads): writes out_path.
         m = 0: no -m.  -> {reads, aligned, unaligned, suppressed, records, seconds}; seconds = {read + parse, upload, seeds, verify, sort,
-        emit + download + write}.  A large file runs in several batches on the device; align_last_batches() tells how many the last call took."""
+        emit + download + write}.  A large file runs in several batches on the device; align_last_batches() tells how many the last call took.
+        place = "u" / "r" (or 1 / 2): one record per read, multi-mapped reads placed by the density of the file's unique reads within `window`
+        bases, or at random (mirp_align_reads_placed; DESIGN.md §12 "Placement"); m must then be 1..10000 and k is not consulted.  The result has
+        unique, by_density and at_random as well, and seconds two more entries {placement, first pass}."""
+        mode = {0: 0, None: 0, "u": 1, "r": 2, 1: 1, 2: 2}[place]
+        if mode:
+            st = (C.c_int64 * 8)()
+            sec = (C.c_double * 8)()
+            o = AlignPlaceOpts(mode, int(window), int(seed))
+            self._check(self.lib.mirp_align_reads_placed(self.h, os.fsencode(reads_path), os.fsencode(out_path), pg_cl.encode(), int(v), int(k), int(m),
+                                                         int(bool(filter_unmapped)), C.byref(o), st, sec), "mirp_align_reads_placed")
+            return dict(zip(("reads", "aligned", "unaligned", "suppressed", "records", "unique", "by_density", "at_random"), list(st)), seconds=list(sec))
         st = (C.c_int64 * 5)()
         sec = (C.c_double * 6)()
         self._check(self.lib.mirp_align_reads(self.h, os.fsencode(reads_path), os.fsencode(out_path), pg_cl.encode(), int(v), int(k), int(m),
@@ -633,6 +656,14 @@ class Context:
     def align_last_batches(self):
         """Batches the last align_reads ran on the device (mirp_align_last_batches)."""
         return int(self.lib.mirp_align_last_batches(self.h))
+
+    def set_align_place_capacity(self, items):
+        """Hits the first pass of a placed align_reads keeps resident for the second (mirp_set_align_place_capacity); 0 = the default."""
+        self._check(self.lib.mirp_set_align_place_capacity(self.h, int(items)), "mirp_set_align_place_capacity")
+
+    def align_place_last_realigned(self):
+        """Batches the last placed align_reads aligned twice (mirp_align_place_last_realigned)."""
+        return int(self.lib.mirp_align_place_last_realigned(self.h))
 
     def trim_reads(self, data, name, out_path, adapter="", error_permille=100, overlap=3, quality=0, min_length=18, max_length=0, discard_untrimmed=False):
         """3' adapter and quality trimming of one FASTQ / FASTA text (bytes, already decompressed) (mirp_trim_reads): writes out_path,

@@ -9,7 +9,7 @@
 //          al_keys_kernel writes key << 32 | p, mirp_device_sort_u64 sorts by the high 32 bits (4 passes of 8), al_strip_kernel keeps p.
 //          bkt[b] = first SA slot whose key starts with the 12 bases b (4^12 + 1 entries: a histogram in al_strip_kernel + launch_excl_scan).
 //
-// Reads (one batch at a time, see mirp_device_align_batch):
+// Reads (one batch at a time, see mirp_device_align_upload / _hits / _emit):
 //   seeds     al_seedcount_kernel, launch_excl_scan, al_seedfill_kernel.  v = 0: the whole read on each strand.  v > 0: the two halves of the
 //             oriented read (first ceil(L/2) bases, the rest); with e = v / 2 = 1 also every single-substitution variant of a half.  A seed is the
 //             SA range of its first min(len, 16) bases (bucket table, then a binary search inside the bucket that recomputes keys).
@@ -20,6 +20,9 @@
 //             best-stratum hits of the kept reads as (read << 33 | gpos << 1 | strand) at scanned per-read offsets.
 //   order     mirp_device_sort_u64 by the whole record: per read, (contig, offset, + before -); the first K per read are kept.
 //   emit      al_size_kernel, launch_excl_scan, al_emit_kernel: the SAM records on the device (one shared routine counts and writes).
+//   place     (align --place) between order and emit: al_unique_kernel collects the file's unique reads over all batches; after the last batch
+//             one sort by position and two int32 scans give the 64-bit prefix of their depths; al_weight_kernel (one item per thread, two binary
+//             searches) and al_pick_kernel (one read per thread: hash, running sum) choose one item per read, which the emit step then writes.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstring>
@@ -175,9 +178,14 @@ struct AlText {
     const char* qn; const long long* qoff;
     const char* names; const long long* noff;
     const unsigned long long* cstart; int n_contigs;
+    // placement (AlParams::place != 0), per read: hits in the best stratum, class 'N' / 'U' / 'R', weight of the chosen hit, sum of the weights
+    const int* pn; const unsigned char* pcls; const unsigned long long* pw; const unsigned long long* pwt;
 };
 
-// one SAM record: item = read << 33 | gpos << 1 | strand; best < 0: unaligned (XM:i:0, or XM:i:<M+1> when suppressed)
+#define AL_NO_ITEM (~0ull)      // placement: a read without a record (unaligned under -f)
+
+// one SAM record: item = read << 33 | gpos << 1 | strand; best < 0: unaligned (XM:i:0, or XM:i:<M+1> when suppressed).  With P.place the record of
+// an aligned read carries NH:i:<n> XY:Z:<class> XW:Z:<w>/<Wt> after NM:i:
 template <bool WRITE>
 __device__ long long al_record(const AlRef& R, const AlText& T, const AlParams& P, unsigned long long item, int best, int supp, char* out) {
     TextOut<WRITE> o{out};
@@ -226,18 +234,28 @@ __device__ long long al_record(const AlRef& R, const AlText& T, const AlParams& 
     o.num((unsigned long long)run);
     o.lit("\tNM:i:");
     o.num((unsigned long long)best);
+    if (P.place) {
+        o.lit("\tNH:i:");
+        o.num((unsigned long long)T.pn[r]);
+        o.lit("\tXY:Z:");
+        o.ch((char)T.pcls[r]);
+        o.lit("\tXW:Z:");
+        o.num(T.pw[r]);
+        o.ch('/');
+        o.num(T.pwt[r]);
+    }
     o.ch('\n');
     return o.n;
 }
 
-// size[i] of sorted item i (0: cut by -k); records[0] += kept items
+// size[i] of sorted item i (0: cut by -k); records[0] += kept items.  With P.place the items are the picks, one per read (AL_NO_ITEM: no record)
 __global__ void al_size_kernel(AlRef R, AlText T, AlParams P, const unsigned long long* __restrict__ items, long long n, const long long* __restrict__ off,
                                const int* __restrict__ best, const int* __restrict__ supp, int* __restrict__ size, unsigned long long* __restrict__ records) {
     unsigned long long kept = 0;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const unsigned long long it = items[i];
-        const long long r = (long long)(it >> 33);
-        const bool keep = i - off[r] < (long long)P.k;
+        const long long r = P.place ? i : (long long)(it >> 33);
+        const bool keep = P.place ? it != AL_NO_ITEM : i - off[r] < (long long)P.k;
         size[i] = keep ? (int)al_record<false>(R, T, P, it, best[r], supp[r], nullptr) : 0;
         kept += keep;
     }
@@ -251,6 +269,117 @@ __global__ void al_emit_kernel(AlRef R, AlText T, AlParams P, const unsigned lon
         const long long r = (long long)(it >> 33);
         (void)al_record<true>(R, T, P, it, best[r], supp[r], text + toff[i]);
     }
+}
+
+// ---------------------------------------------------------------- placement (align --place, DESIGN.md §12 "Placement")
+// a unique read: one hit in its best stratum.  WRITE = false: flag[r]; WRITE = true: gpos << 32 | depth at uscan[r] of this batch's part of the list
+template <bool WRITE>
+__global__ void al_unique_kernel(const unsigned long long* __restrict__ items, const long long* __restrict__ off, const int* __restrict__ best, long long n,
+                                 const unsigned* __restrict__ depth, int* __restrict__ flag, const long long* __restrict__ uscan,
+                                 unsigned long long* __restrict__ ulist) {
+    for (long long r = blockIdx.x * (long long)blockDim.x + threadIdx.x; r < n; r += (long long)gridDim.x * blockDim.x) {
+        const bool u = best[r] >= 0 && off[r + 1] - off[r] == 1;
+        if (!WRITE) flag[r] = u;
+        else if (u) ulist[uscan[r]] = (((items[off[r]] >> 1) & 0xffffffffull) << 32) | depth[r];
+    }
+}
+// the sorted unique list -> positions, and the depths as their low 30 bits and the rest (two int32 scans make the exact 64-bit prefix)
+__global__ void al_usplit_kernel(const unsigned long long* __restrict__ ulist, long long n, unsigned* __restrict__ upos, int* __restrict__ lo, int* __restrict__ hi) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const unsigned long long u = ulist[i];
+        upos[i] = (unsigned)(u >> 32);
+        lo[i] = (int)(u & 0x3fffffffull);
+        hi[i] = (int)((u >> 30) & 3ull);
+    }
+}
+// upre[i] = sum of the depths of the unique reads before i, i = 0 .. n
+__global__ void al_uprefix_kernel(const long long* __restrict__ lo_scan, const long long* __restrict__ hi_scan, long long n, unsigned long long* __restrict__ upre) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i <= n; i += (long long)gridDim.x * blockDim.x)
+        upre[i] = (unsigned long long)lo_scan[i] + ((unsigned long long)hi_scan[i] << 30);
+}
+
+// first index of upos[0 .. n) with upos[i] >= g (g may be 2^32: past every position)
+__device__ __forceinline__ long long al_ulower(const unsigned* __restrict__ upos, long long n, unsigned long long g) {
+    long long a = 0, z = n;
+    while (a < z) { const long long md = (a + z) >> 1; if ((unsigned long long)upos[md] < g) a = md + 1; else z = md; }
+    return a;
+}
+
+// weight of every best-stratum item of a multi-mapped read: the depths of the unique reads whose position lies in the hit's footprint widened by
+// W on both sides and clipped to the hit's contig.  One item per thread; items of other reads get 0.
+__global__ void al_weight_kernel(const unsigned long long* __restrict__ items, long long n_items, const long long* __restrict__ off,
+                                 const int* __restrict__ best, const long long* __restrict__ roff, const unsigned long long* __restrict__ cstart, int n_contigs,
+                                 int W, const unsigned* __restrict__ upos, const unsigned long long* __restrict__ upre, long long n_unique,
+                                 unsigned long long* __restrict__ w) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n_items; i += (long long)gridDim.x * blockDim.x) {
+        const unsigned long long it = items[i];
+        const long long r = (long long)(it >> 33);
+        unsigned long long wi = 0;
+        if (best[r] >= 0 && off[r + 1] - off[r] > 1) {
+            const unsigned long long g = (it >> 1) & 0xffffffffull;
+            const unsigned long long L = (unsigned long long)(roff[r + 1] - roff[r]);
+            const int a = site_contig(cstart, n_contigs, g);
+            const unsigned long long c0 = cstart[a], c1 = cstart[a + 1];                  // the contig is [c0, c1)
+            const unsigned long long lo = g - c0 > (unsigned long long)W ? g - W : c0;
+            const unsigned long long hi = g + L + W < c1 ? g + L + W : c1;               // one past the last position counted
+            wi = upre[al_ulower(upos, n_unique, hi)] - upre[al_ulower(upos, n_unique, lo)];
+        }
+        w[i] = wi;
+    }
+}
+
+// FNV-1a-64 over the read's codes, xor seed, splitmix64 finaliser
+__device__ __forceinline__ unsigned long long al_draw(const unsigned char* __restrict__ rd, int L, unsigned long long seed) {
+    unsigned long long x = 0xcbf29ce484222325ull;
+    for (int i = 0; i < L; i++) { x ^= rd[i]; x *= 0x100000001b3ull; }
+    x ^= seed;
+    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
+    x ^= x >> 27; x *= 0x94d049bb133111ebull;
+    x ^= x >> 31;
+    return x;
+}
+
+// per read: the one item that is reported (AL_NO_ITEM: none), n, class, w of the chosen hit and Wt; counts += {unique, by density, at random}
+__global__ void al_pick_kernel(const unsigned long long* __restrict__ items, const long long* __restrict__ off, const int* __restrict__ best,
+                               const unsigned char* __restrict__ codes, const long long* __restrict__ roff, long long n, int mode, unsigned long long seed,
+                               const unsigned long long* __restrict__ w, unsigned long long* __restrict__ pick, int* __restrict__ pn,
+                               unsigned char* __restrict__ pcls, unsigned long long* __restrict__ pw, unsigned long long* __restrict__ pwt,
+                               unsigned long long* __restrict__ counts) {
+    unsigned long long cnt[3] = {0, 0, 0};
+    for (long long r = blockIdx.x * (long long)blockDim.x + threadIdx.x; r < n; r += (long long)gridDim.x * blockDim.x) {
+        const long long o = off[r], nh = off[r + 1] - o;
+        unsigned long long it = AL_NO_ITEM, wc = 0, wt = 0;
+        unsigned char cls = 'N';
+        if (best[r] < 0 || nh == 1) {
+            if (nh > 0) it = items[o];
+            if (best[r] >= 0) cnt[0]++;
+        } else {
+            const unsigned long long x = al_draw(codes + roff[r], (int)(roff[r + 1] - roff[r]), seed);
+            long long idx = -1;
+            if (mode == 1) {
+                for (long long i = 0; i < nh; i++) wt += w[o + i];
+                if (wt > 0) {
+                    const unsigned long long t = x % wt;
+                    unsigned long long run = 0;
+                    for (long long i = 0; i < nh; i++) {
+                        run += w[o + i];
+                        if (run > t) { idx = i; break; }
+                    }
+                    wc = w[o + idx];
+                    cls = 'U';
+                }
+            }
+            if (idx < 0) { idx = (long long)(x % (unsigned long long)nh); cls = 'R'; if (mode == 1) wc = 0; }
+            it = items[o + idx];
+            cnt[cls == 'U' ? 1 : 2]++;
+        }
+        pick[r] = it;
+        pn[r] = (int)nh;
+        pcls[r] = cls;
+        pw[r] = wc;
+        pwt[r] = wt;
+    }
+    for (int i = 0; i < 3; i++) al_wave_add(&counts[i], cnt[i]);
 }
 
 }  // namespace mirp
@@ -336,35 +465,46 @@ int mirp_device_align_index(mirp_ctx* c, const unsigned* pk, const unsigned* amb
     return 0;
 }
 
-// One batch of reads: codes (0..3 ACGT, 4 other) at roff[0..n], QNAMEs at qoff[0..n], all on the host.  The batch's SAM text goes to `sink` in
-// pieces of at most 1 GiB.  stats += {aligned, unaligned, suppressed, records}; seconds += [0] upload, [1] seeds, [2] verify, [3] sort, [4] emit
-int mirp_device_align_batch(mirp_ctx* c, const unsigned char* codes, const long long* roff, const char* qn, const long long* qoff, long long n, int v, int k,
-                            int m, int filter, const std::function<int(const char*, size_t)>& sink, long long stats[4], double seconds[5]) {
-    using namespace mirp;
+// A batch of reads runs in three steps that share the context's a_* buffers: upload, hits (seeds .. sort) and emit (size, scan, emit, download).
+// mirp_align_reads runs them back to back; the placement (mirp_align_reads_placed) runs upload + hits of every batch first, then the placing
+// and the emit.  seconds += [0] upload, [1] seeds, [2] verify, [3] sort, [4] emit.
+
+// Upload: codes (0..3 ACGT, 4 other) at roff[0..n], QNAMEs at qoff[0..n], depth[0..n) (placement only, or null), all on the host.
+int mirp_device_align_upload(mirp_ctx* c, const unsigned char* codes, const long long* roff, const char* qn, const long long* qoff, const unsigned* depth,
+                             long long n, double seconds[5]) {
     if (!c->a_ready) return fail(c, -1, "mirp_align_reads: no index (mirp_align_index first)");
-    if (n <= 0) return 0;
     hipStream_t st = c->stream;
-    const AlParams P{v, v / 2, k, m, filter};
-    const AlRef R = al_ref(c);
     double t = mirp::now();
     const long long nb = roff[n], nq = qoff[n];
     if (c->a_codes.ensure((size_t)nb + 16) || c->a_roff.ensure(8 * (size_t)(n + 1)) || c->a_qn.ensure((size_t)nq + 16) || c->a_qoff.ensure(8 * (size_t)(n + 1)) ||
-        c->a_small.ensure(64))
+        c->a_small.ensure(64) || (depth && c->a_depth.ensure(4 * (size_t)n)))
         return fail(c, -6, "device allocation failed (align: reads)");
     if (nb) HIPCHK(c, hipMemcpyAsync(c->a_codes.p, codes, (size_t)nb, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->a_roff.p, roff, 8 * (size_t)(n + 1), hipMemcpyHostToDevice, st));
     if (nq) HIPCHK(c, hipMemcpyAsync(c->a_qn.p, qn, (size_t)nq, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->a_qoff.p, qoff, 8 * (size_t)(n + 1), hipMemcpyHostToDevice, st));
-    unsigned long long* d_small = (unsigned long long*)c->a_small.p;    // [0..2] aligned / unaligned / suppressed, [3] records, [4] overflow flag
-    HIPCHK(c, hipMemsetAsync(d_small, 0, 64, st));
+    if (depth) HIPCHK(c, hipMemcpyAsync(c->a_depth.p, depth, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    // a_small: [0..2] aligned / unaligned / suppressed, [3] records, [4] overflow flag, [5..7] placed unique / by density / at random
+    HIPCHK(c, hipMemsetAsync(c->a_small.p, 0, 64, st));
     HIPCHK(c, hipStreamSynchronize(st));
     seconds[0] += mirp::now() - t;
+    return 0;
+}
+
+// Hits of the uploaded batch: a_items = the *n_items sorted best-stratum items (and one item per unaligned read unless filter), a_off their
+// per-read offsets, a_best / a_supp the per-read stratum and -m decision; a_small[0..2] += {aligned, unaligned, suppressed}.
+int mirp_device_align_hits(mirp_ctx* c, long long n, int v, int m, int filter, long long* n_items, double seconds[5]) {
+    using namespace mirp;
+    hipStream_t st = c->stream;
+    const AlParams P{v, v / 2, 1, m, filter, 0};
+    const AlRef R = al_ref(c);
+    unsigned long long* d_small = (unsigned long long*)c->a_small.p;
     const unsigned char* d_codes = (const unsigned char*)c->a_codes.p;
     const long long* d_roff = (const long long*)c->a_roff.p;
     const int g = al_grid(n);
 
     // ---- seeds
-    t = mirp::now();
+    double t = mirp::now();
     if (c->a_rcnt.ensure(4 * (size_t)n) || c->a_rscan.ensure(8 * (size_t)(n + 1))) return fail(c, -6, "device allocation failed (align: seeds)");
     int* d_rcnt = (int*)c->a_rcnt.p;
     long long* d_rscan = (long long*)c->a_rscan.p;
@@ -429,32 +569,132 @@ int mirp_device_align_batch(mirp_ctx* c, const unsigned char* codes, const long 
     if (int rc = mirp_device_sort_u64(c, d_items, (unsigned long long*)c->a_itmp.p, NI, 0, (33 + rbits + 7) / 8 * 8)) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
     seconds[3] += mirp::now() - t;
+    *n_items = NI;
+    return 0;
+}
 
-    // ---- emit + download
-    t = mirp::now();
+// Emit + download: the records of the batch's items go to `sink` in pieces of at most 1 GiB.  place = 0: the n_items items of
+// mirp_device_align_hits, the first k of every read.  place != 0: the picks of mirp_device_place_pick, one per read, with the placement tags.
+// cnt[0..8) = a_small after the batch ({aligned, unaligned, suppressed, records, -, placed unique, by density, at random}).
+int mirp_device_align_emit(mirp_ctx* c, long long n, long long n_items, int v, int k, int m, int filter, int place,
+                           const std::function<int(const char*, size_t)>& sink, unsigned long long cnt[8], double seconds[5]) {
+    using namespace mirp;
+    hipStream_t st = c->stream;
+    const AlParams P{v, v / 2, k, m, filter, place};
+    const AlRef R = al_ref(c);
+    unsigned long long* d_small = (unsigned long long*)c->a_small.p;
+    const unsigned long long* d_items = (const unsigned long long*)(place ? c->a_pick.p : c->a_items.p);
+    const long long NI = place ? n : n_items;
+    double t = mirp::now();
     if (c->a_size.ensure(4 * (size_t)std::max<long long>(NI, 1)) || c->a_toff.ensure(8 * (size_t)(NI + 1)))
         return fail(c, -6, "device allocation failed (align: text offsets)");
-    const AlText TX{d_codes, d_roff, (const char*)c->a_qn.p, (const long long*)c->a_qoff.p, (const char*)c->a_names.p, (const long long*)c->a_noff.p,
-                    (const unsigned long long*)c->a_cstart.p, c->a_n_contigs};
+    const AlText TX{(const unsigned char*)c->a_codes.p, (const long long*)c->a_roff.p, (const char*)c->a_qn.p, (const long long*)c->a_qoff.p,
+                    (const char*)c->a_names.p, (const long long*)c->a_noff.p, (const unsigned long long*)c->a_cstart.p, c->a_n_contigs,
+                    (const int*)c->a_pn.p, (const unsigned char*)c->a_pcls.p, (const unsigned long long*)c->a_pw.p, (const unsigned long long*)c->a_pwt.p};
+    const long long* d_off = (const long long*)c->a_off.p;
+    const int* d_best = (const int*)c->a_best.p;
+    const int* d_supp = (const int*)c->a_supp.p;
     long long* d_toff = (long long*)c->a_toff.p;
     long long bytes = 0;
     if (NI > 0) {
-        hipLaunchKernelGGL(al_size_kernel, dim3(al_grid(NI)), dim3(256), 0, st, R, TX, P, (const unsigned long long*)d_items, NI, (const long long*)d_off,
-                           (const int*)d_best, (const int*)d_supp, (int*)c->a_size.p, d_small + 3);
+        hipLaunchKernelGGL(al_size_kernel, dim3(al_grid(NI)), dim3(256), 0, st, R, TX, P, d_items, NI, d_off, d_best, d_supp, (int*)c->a_size.p, d_small + 3);
         launch_excl_scan(st, (const int*)c->a_size.p, d_toff, NI);
         HIPCHK(c, hipMemcpyAsync(&bytes, d_toff + NI, 8, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
     }
     if (c->a_text.ensure((size_t)bytes + 16)) return fail(c, -6, "device allocation failed (align: text)");
     if (NI > 0)
-        hipLaunchKernelGGL(al_emit_kernel, dim3(al_grid(NI)), dim3(256), 0, st, R, TX, P, (const unsigned long long*)d_items, NI, (const long long*)d_toff,
-                           (const int*)d_best, (const int*)d_supp, (char*)c->a_text.p);
-    unsigned long long cnt[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(cnt, d_small, 32, hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(al_emit_kernel, dim3(al_grid(NI)), dim3(256), 0, st, R, TX, P, d_items, NI, (const long long*)d_toff, d_best, d_supp,
+                           (char*)c->a_text.p);
+    HIPCHK(c, hipMemcpyAsync(cnt, d_small, 64, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
     if (int rc = mirp_download_text(c, (const char*)c->a_text.p, bytes, sink)) return rc;
     seconds[4] += mirp::now() - t;
-    for (int i = 0; i < 4; i++) stats[i] += (long long)cnt[i];
     return 0;
 }
+
+// ---------------------------------------------------------------- placement, host side
+// Appends the unique reads of the batch whose hits are resident to the context's unique list (a_ulist, *n_unique entries before and after).
+int mirp_device_place_unique(mirp_ctx* c, long long n, long long* n_unique) {
+    using namespace mirp;
+    hipStream_t st = c->stream;
+    if (n <= 0) return 0;
+    int* d_flag = (int*)c->a_rcnt.p;                    // the seed counts and their scan are done with
+    long long* d_uscan = (long long*)c->a_rscan.p;
+    const int g = al_grid(n);
+    hipLaunchKernelGGL(al_unique_kernel<false>, dim3(g), dim3(256), 0, st, (const unsigned long long*)c->a_items.p, (const long long*)c->a_off.p,
+                       (const int*)c->a_best.p, n, (const unsigned*)c->a_depth.p, d_flag, (const long long*)nullptr, (unsigned long long*)nullptr);
+    launch_excl_scan(st, d_flag, d_uscan, n);
+    long long add = 0;
+    HIPCHK(c, hipMemcpyAsync(&add, d_uscan + n, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    const size_t need = 8 * (size_t)(*n_unique + add);
+    if (need > c->a_ulist.cap) {                        // grow and keep what the earlier batches wrote
+        DevBuf bigger;
+        if (bigger.ensure(std::max(need, 2 * c->a_ulist.cap))) return fail(c, -6, "device allocation failed (align: unique reads)");
+        if (*n_unique) HIPCHK(c, hipMemcpyAsync(bigger.p, c->a_ulist.p, 8 * (size_t)*n_unique, hipMemcpyDeviceToDevice, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        std::swap(bigger.p, c->a_ulist.p);
+        std::swap(bigger.cap, c->a_ulist.cap);
+    }
+    if (add > 0)
+        hipLaunchKernelGGL(al_unique_kernel<true>, dim3(g), dim3(256), 0, st, (const unsigned long long*)c->a_items.p, (const long long*)c->a_off.p,
+                           (const int*)c->a_best.p, n, (const unsigned*)c->a_depth.p, (int*)nullptr, (const long long*)d_uscan,
+                           (unsigned long long*)c->a_ulist.p + *n_unique);
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    *n_unique += add;
+    return 0;
+}
+
+// After the last batch: sorts the unique list by position and builds a_upos[n_unique] and the exact 64-bit prefix a_upre[n_unique + 1] of the depths.
+int mirp_device_place_prepare(mirp_ctx* c, long long n_unique, unsigned long long* depth_sum) {
+    using namespace mirp;
+    hipStream_t st = c->stream;
+    const long long NU = n_unique;
+    const size_t one = (size_t)std::max<long long>(NU, 1);
+    if (c->a_ulist.ensure(8) || c->a_utmp.ensure(8 * one) || c->a_upos.ensure(4 * one) || c->a_ulo.ensure(4 * one) || c->a_uhi.ensure(4 * one) ||
+        c->a_uls.ensure(8 * (one + 1)) || c->a_uhs.ensure(8 * (one + 1)) || c->a_upre.ensure(8 * (one + 1)))
+        return fail(c, -6, "device allocation failed (align: unique reads)");
+    *depth_sum = 0;
+    if (NU == 0) {
+        HIPCHK(c, hipMemsetAsync(c->a_upre.p, 0, 8, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        return 0;
+    }
+    if (int rc = mirp_device_sort_u64(c, (unsigned long long*)c->a_ulist.p, (unsigned long long*)c->a_utmp.p, NU, 32, 32)) return rc;
+    hipLaunchKernelGGL(al_usplit_kernel, dim3(al_grid(NU)), dim3(256), 0, st, (const unsigned long long*)c->a_ulist.p, NU, (unsigned*)c->a_upos.p,
+                       (int*)c->a_ulo.p, (int*)c->a_uhi.p);
+    launch_excl_scan(st, (const int*)c->a_ulo.p, (long long*)c->a_uls.p, NU);
+    launch_excl_scan(st, (const int*)c->a_uhi.p, (long long*)c->a_uhs.p, NU);
+    hipLaunchKernelGGL(al_uprefix_kernel, dim3(al_grid(NU + 1)), dim3(256), 0, st, (const long long*)c->a_uls.p, (const long long*)c->a_uhs.p, NU,
+                       (unsigned long long*)c->a_upre.p);
+    HIPCHK(c, hipMemcpyAsync(depth_sum, (unsigned long long*)c->a_upre.p + NU, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// Places the reads of the batch whose hits are resident: a_pick (one item per read) and the tag fields; a_small[5..7] += the class counts.
+int mirp_device_place_pick(mirp_ctx* c, long long n, long long n_items, int mode, int window, unsigned long long seed, long long n_unique) {
+    using namespace mirp;
+    hipStream_t st = c->stream;
+    if (n <= 0) return 0;
+    if (c->a_w.ensure(8 * (size_t)std::max<long long>(n_items, 1)) || c->a_pick.ensure(8 * (size_t)n) || c->a_pn.ensure(4 * (size_t)n) ||
+        c->a_pcls.ensure((size_t)n) || c->a_pw.ensure(8 * (size_t)n) || c->a_pwt.ensure(8 * (size_t)n))
+        return fail(c, -6, "device allocation failed (align: placement)");
+    if (mode == 1 && n_items > 0)
+        hipLaunchKernelGGL(al_weight_kernel, dim3(al_grid(n_items)), dim3(256), 0, st, (const unsigned long long*)c->a_items.p, n_items,
+                           (const long long*)c->a_off.p, (const int*)c->a_best.p, (const long long*)c->a_roff.p, (const unsigned long long*)c->a_cstart.p,
+                           c->a_n_contigs, window, (const unsigned*)c->a_upos.p, (const unsigned long long*)c->a_upre.p, n_unique,
+                           (unsigned long long*)c->a_w.p);
+    hipLaunchKernelGGL(al_pick_kernel, dim3(al_grid(n)), dim3(256), 0, st, (const unsigned long long*)c->a_items.p, (const long long*)c->a_off.p,
+                       (const int*)c->a_best.p, (const unsigned char*)c->a_codes.p, (const long long*)c->a_roff.p, n, mode, seed,
+                       (const unsigned long long*)c->a_w.p, (unsigned long long*)c->a_pick.p, (int*)c->a_pn.p, (unsigned char*)c->a_pcls.p,
+                       (unsigned long long*)c->a_pw.p, (unsigned long long*)c->a_pwt.p, (unsigned long long*)c->a_small.p + 5);
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+

@@ -135,21 +135,38 @@ extern "C" int mirp_align_index(mirp_ctx* c, const char* const* paths, int32_t n
     return 0;
 }
 
-// Aligns the reads of one FASTA file against the resident index and writes the SAM file (DESIGN.md §12).  stats = {reads, aligned, unaligned,
-// suppressed by -m, records written}; seconds = {read + parse, upload, seeds, verify, sort, emit + download + write}.  Refusals (a read longer than
-// 1,024 nt, more than 2^31 - 1 reads, a header without a name) happen before out_path is opened; on a later error the partial file is removed.
-extern "C" int mirp_align_reads(mirp_ctx* c, const char* reads_path, const char* out_path, const char* pg_cl, int32_t v, int32_t k, int32_t m,
-                                int32_t filter_unmapped, int64_t stats[5], double seconds[6]) {
-    if (!c) return -1;
-    if (!reads_path || !out_path || !pg_cl || v < 0 || v > 3 || k < 1 || m < 0) return fail(c, -1, "mirp_align_reads: bad argument");
-    if (!c->a_ready) return fail(c, -1, "mirp_align_reads: no index (mirp_align_index first)");
-    HIPCHK(c, hipSetDevice(c->device));
-    double sec[6] = {0, 0, 0, 0, 0, 0};
+namespace {
+
+// depth of a read for the placement: the number after the last _x of a QNAME that matches _x[0-9]+$, if it is <= 2^32 - 1; otherwise 1
+unsigned depth_of(const char* q, size_t len) {
+    size_t i = len;
+    while (i > 0 && q[i - 1] >= '0' && q[i - 1] <= '9') i--;
+    if (i == len || i < 2 || q[i - 1] != 'x' || q[i - 2] != '_') return 1u;
+    while (i < len - 1 && q[i] == '0') i++;
+    if (len - i > 10) return 1u;
+    unsigned long long d = 0;
+    for (; i < len; i++) d = d * 10 + (unsigned long long)(q[i] - '0');
+    return d <= 0xffffffffull ? (unsigned)d : 1u;
+}
+
+void swap_buf(DevBuf& a, DevBuf& b) { std::swap(a.p, b.p); std::swap(a.cap, b.cap); }
+
+// the hits of a batch of pass 1 that stay resident for pass 2
+struct KeptBatch {
+    DevBuf items, off, best, supp;
+    long long n_items = 0;
+    bool kept = false;
+};
+
+// mirp_align_reads (place == nullptr) and mirp_align_reads_placed.  stats[8], seconds[8]
+int align_file(mirp_ctx* c, const char* reads_path, const char* out_path, const char* pg_cl, int v, int k, int m, int filter_unmapped,
+               const MirpAlignPlaceOpts* place, long long stats[8], double sec[8]) {
     double t = mirp::now();
     std::string buf;
     if (int rc = mirp::read_whole(c, reads_path, buf)) return rc;
     std::vector<unsigned char> codes;
     std::vector<long long> roff(1, 0), qoff(1, 0);
+    std::vector<unsigned> depth;
     std::string qn;
     codes.reserve(buf.size() / 2);
     bool open = false;
@@ -162,6 +179,7 @@ extern "C" int mirp_align_reads(mirp_ctx* c, const char* reads_path, const char*
             if (name.empty()) return fail(c, -10, std::string(reads_path) + ": a read header without a name");
             qn += name;
             qoff.push_back((long long)qn.size());
+            if (place) depth.push_back(depth_of(name.data(), name.size()));
             open = true;
             return 0;
         }
@@ -180,20 +198,9 @@ extern "C" int mirp_align_reads(mirp_ctx* c, const char* reads_path, const char*
     const long long n = (long long)roff.size() - 1;
     sec[0] = mirp::now() - t;
 
-    mirp::OutFile out(out_path);
-    if (!out.open()) return fail(c, -8, std::string("cannot write ") + out_path);
-    std::string head = "@HD\tVN:1.0\tSO:unsorted\n";
-    for (size_t i = 0; i < c->a_contig_names.size(); i++)
-        head += "@SQ\tSN:" + c->a_contig_names[i] + "\tLN:" + std::to_string(c->a_contig_lens[i]) + "\n";
-    head += std::string("@PG\tID:mir_prefer_amd.align\tCL:\"") + pg_cl + "\"\n";
-    auto sink = [&](const char* p, size_t len) -> int { return out.write(p, len) ? 0 : fail(c, -8, std::string("cannot write ") + out_path); };
-    rc = sink(head.data(), head.size());
-    long long st4[4] = {0, 0, 0, 0};
-    double dsec[5] = {0, 0, 0, 0, 0};
     // batches: bounded reads, bases and seeds (with e = 1 a read has up to 2 * (2 + 4 L) seeds)
-    long long r0 = 0;
-    c->a_batches = 0;
-    while (!rc && r0 < n) {
+    std::vector<long long> cut(1, 0);
+    for (long long r0 = 0; r0 < n;) {
         long long r1 = r0, seeds = 0;
         while (r1 < n && r1 - r0 < (1ll << 22) && roff[r1] - roff[r0] < (1ll << 28)) {
             const long long L = roff[r1 + 1] - roff[r1];
@@ -202,23 +209,154 @@ extern "C" int mirp_align_reads(mirp_ctx* c, const char* reads_path, const char*
             seeds += s;
             r1++;
         }
-        std::vector<long long> rb(roff.begin() + r0, roff.begin() + r1 + 1), qb(qoff.begin() + r0, qoff.begin() + r1 + 1);
+        cut.push_back(r1);
+        r0 = r1;
+    }
+    const size_t nbatch = cut.size() - 1;
+    c->a_batches = (long long)nbatch;
+    std::vector<long long> rb, qb;
+    double dsec[5] = {0, 0, 0, 0, 0};
+    auto upload = [&](size_t b) -> int {
+        const long long r0 = cut[b], r1 = cut[b + 1];
+        rb.assign(roff.begin() + r0, roff.begin() + r1 + 1);
+        qb.assign(qoff.begin() + r0, qoff.begin() + r1 + 1);
         for (auto& x : rb) x -= roff[r0];
         for (auto& x : qb) x -= qoff[r0];
-        rc = mirp_device_align_batch(c, codes.data() + roff[r0], rb.data(), qn.data() + qoff[r0], qb.data(), r1 - r0, v, k, m, filter_unmapped, sink, st4,
-                                     dsec);
-        r0 = r1;
-        c->a_batches++;
+        return mirp_device_align_upload(c, codes.data() + roff[r0], rb.data(), qn.data() + qoff[r0], qb.data(), place ? depth.data() + r0 : nullptr, r1 - r0, dsec);
+    };
+
+    // ---- placement, pass 1: the hits of every batch, the unique reads of the whole file
+    long long st7[7] = {0, 0, 0, 0, 0, 0, 0};      // aligned, unaligned, suppressed, records, unique, by density, at random
+    std::vector<KeptBatch> kept(place ? nbatch : 0);
+    long long n_unique = 0;
+    if (place) {
+        const double t1 = mirp::now();
+        const long long cap = c->a_place_cap > 0 ? c->a_place_cap : (1ll << 28);
+        long long resident = 0;
+        c->a_place_realigned = 0;
+        for (size_t b = 0; b < nbatch; b++) {
+            const long long nb = cut[b + 1] - cut[b];
+            long long NI = 0;
+            if ((rc = upload(b)) || (rc = mirp_device_align_hits(c, nb, v, m, filter_unmapped, &NI, dsec))) return rc;
+            unsigned long long cnt[3] = {0, 0, 0};
+            HIPCHK(c, hipMemcpy(cnt, c->a_small.p, sizeof cnt, hipMemcpyDeviceToHost));
+            for (int i = 0; i < 3; i++) st7[i] += (long long)cnt[i];
+            t = mirp::now();
+            if ((rc = mirp_device_place_unique(c, nb, &n_unique))) return rc;
+            sec[6] += mirp::now() - t;
+            if (nbatch == 1) break;                     // pass 2 follows on the same resident hits
+            if (resident + NI <= cap) {
+                swap_buf(kept[b].items, c->a_items); swap_buf(kept[b].off, c->a_off); swap_buf(kept[b].best, c->a_best); swap_buf(kept[b].supp, c->a_supp);
+                kept[b].n_items = NI;
+                kept[b].kept = true;
+                resident += NI;
+            } else {
+                c->a_place_realigned++;
+            }
+        }
+        t = mirp::now();
+        unsigned long long depth_sum = 0;
+        if ((rc = mirp_device_place_prepare(c, n_unique, &depth_sum))) return rc;
+        sec[6] += mirp::now() - t;
+        sec[7] = mirp::now() - t1;
+        if (depth_sum >= ((1ull << 63) + (unsigned long long)m - 1) / (unsigned long long)m)      // m * depth_sum >= 2^63
+            return fail(c, -10, std::string(reads_path) + ": -m times the total depth of the uniquely mapped reads is 2^63 or more (placement weights would overflow)");
+    }
+
+    mirp::OutFile out(out_path);
+    if (!out.open()) return fail(c, -8, std::string("cannot write ") + out_path);
+    std::string head = "@HD\tVN:1.0\tSO:unsorted\n";
+    for (size_t i = 0; i < c->a_contig_names.size(); i++)
+        head += "@SQ\tSN:" + c->a_contig_names[i] + "\tLN:" + std::to_string(c->a_contig_lens[i]) + "\n";
+    head += std::string("@PG\tID:mir_prefer_amd.align\tCL:\"") + pg_cl + "\"\n";
+    auto sink = [&](const char* p, size_t len) -> int { return out.write(p, len) ? 0 : fail(c, -8, std::string("cannot write ") + out_path); };
+    rc = sink(head.data(), head.size());
+    for (size_t b = 0; !rc && b < nbatch; b++) {
+        const long long nb = cut[b + 1] - cut[b];
+        long long NI = 0;
+        unsigned long long cnt[8];
+        if (!place) {
+            if ((rc = upload(b)) || (rc = mirp_device_align_hits(c, nb, v, m, filter_unmapped, &NI, dsec)) ||
+                (rc = mirp_device_align_emit(c, nb, NI, v, k, m, filter_unmapped, 0, sink, cnt, dsec)))
+                break;
+            for (int i = 0; i < 4; i++) st7[i] += (long long)cnt[i];
+            continue;
+        }
+        // ---- placement, pass 2: the batch's hits again (resident, or aligned a second time), the weights, the picks, one record per read
+        if (nbatch > 1) {
+            if ((rc = upload(b))) break;
+            if (kept[b].kept) {
+                swap_buf(kept[b].items, c->a_items); swap_buf(kept[b].off, c->a_off); swap_buf(kept[b].best, c->a_best); swap_buf(kept[b].supp, c->a_supp);
+                NI = kept[b].n_items;
+            } else if ((rc = mirp_device_align_hits(c, nb, v, m, filter_unmapped, &NI, dsec))) {
+                break;
+            }
+        } else {
+            HIPCHK(c, hipMemcpy(&NI, (const long long*)c->a_off.p + nb, 8, hipMemcpyDeviceToHost));
+        }
+        t = mirp::now();
+        if ((rc = mirp_device_place_pick(c, nb, NI, place->mode, place->window, place->seed, n_unique))) break;
+        sec[6] += mirp::now() - t;
+        if ((rc = mirp_device_align_emit(c, nb, NI, v, k, m, filter_unmapped, place->mode, sink, cnt, dsec))) break;
+        st7[3] += (long long)cnt[3];
+        for (int i = 0; i < 3; i++) st7[4 + i] += (long long)cnt[5 + i];
     }
     if (rc) return rc;
     if (!out.commit()) return fail(c, -8, std::string("cannot write ") + out_path);
     for (int i = 0; i < 5; i++) sec[1 + i] = dsec[i];
-    if (stats) {
-        stats[0] = n;
-        for (int i = 0; i < 4; i++) stats[1 + i] = st4[i];
-    }
+    stats[0] = n;
+    for (int i = 0; i < 7; i++) stats[1 + i] = st7[i];
+    return 0;
+}
+
+}  // namespace
+
+// Aligns the reads of one FASTA file against the resident index and writes the SAM file (DESIGN.md §12).  stats = {reads, aligned, unaligned,
+// suppressed by -m, records written}; seconds = {read + parse, upload, seeds, verify, sort, emit + download + write}.  Refusals (a read longer than
+// 1,024 nt, more than 2^31 - 1 reads, a header without a name) happen before out_path is opened; on a later error the partial file is removed.
+extern "C" int mirp_align_reads(mirp_ctx* c, const char* reads_path, const char* out_path, const char* pg_cl, int32_t v, int32_t k, int32_t m,
+                                int32_t filter_unmapped, int64_t stats[5], double seconds[6]) {
+    if (!c) return -1;
+    if (!reads_path || !out_path || !pg_cl || v < 0 || v > 3 || k < 1 || m < 0) return fail(c, -1, "mirp_align_reads: bad argument");
+    if (!c->a_ready) return fail(c, -1, "mirp_align_reads: no index (mirp_align_index first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double sec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (int rc = align_file(c, reads_path, out_path, pg_cl, v, k, m, filter_unmapped, nullptr, st, sec)) return rc;
+    if (stats) for (int i = 0; i < 5; i++) stats[i] = st[i];
+    if (seconds) std::memcpy(seconds, sec, 6 * sizeof(double));
+    return 0;
+}
+
+// mirp_align_reads with the placement of multi-mapped reads (DESIGN.md §12 "Placement"): one record per read.  place == NULL or mode 0: exactly
+// mirp_align_reads.  stats = mirp_align_reads' five, then {unique, placed by density, placed at random}; seconds = mirp_align_reads' six, then
+// {unique list + sort + prefix + weights + picks, the whole of pass 1}.  With a mode, m must be 1..10000 and k is not consulted; a file whose
+// m * (total depth of its unique reads) is 2^63 or more is refused (-10) before out_path is opened.
+extern "C" int mirp_align_reads_placed(mirp_ctx* c, const char* reads_path, const char* out_path, const char* pg_cl, int32_t v, int32_t k, int32_t m,
+                                       int32_t filter_unmapped, const MirpAlignPlaceOpts* place, int64_t stats[8], double seconds[8]) {
+    if (!c) return -1;
+    const bool on = place && place->mode != 0;
+    if (!reads_path || !out_path || !pg_cl || v < 0 || v > 3 || k < 1 || m < 0) return fail(c, -1, "mirp_align_reads_placed: bad argument");
+    if (on && (place->mode < 1 || place->mode > 2 || place->window < 0 || place->window > 10000 || m < 1 || m > 10000))
+        return fail(c, -1, "mirp_align_reads_placed: bad placement argument (mode 0..2, window 0..10000, m 1..10000)");
+    if (!c->a_ready) return fail(c, -1, "mirp_align_reads: no index (mirp_align_index first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double sec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (int rc = align_file(c, reads_path, out_path, pg_cl, v, k, m, filter_unmapped, on ? place : nullptr, st, sec)) return rc;
+    if (stats) for (int i = 0; i < 8; i++) stats[i] = st[i];
     if (seconds) std::memcpy(seconds, sec, sizeof sec);
     return 0;
 }
 
 extern "C" int64_t mirp_align_last_batches(const mirp_ctx* c) { return c ? c->a_batches : -1; }
+
+extern "C" int mirp_set_align_place_capacity(mirp_ctx* c, int64_t items) {
+    if (!c) return -1;
+    if (items < 0) return fail(c, -1, "mirp_set_align_place_capacity: bad argument");
+    c->a_place_cap = items;
+    return 0;
+}
+
+extern "C" int64_t mirp_align_place_last_realigned(const mirp_ctx* c) { return c ? c->a_place_realigned : -1; }
+

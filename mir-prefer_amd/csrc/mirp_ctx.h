@@ -123,7 +123,12 @@ struct mirp_ctx {
     std::vector<long long> a_contig_lens;
     DevBuf a_codes, a_roff, a_qn, a_qoff, a_small, a_rcnt, a_rscan, a_seeds, a_ccnt, a_cscan, a_lvl, a_best, a_supp, a_slots, a_off, a_cursor, a_items, a_itmp,
         a_size, a_toff, a_text;
-    std::vector<char> h_text;         // one piece (<= 1 GiB) of the SAM text on its way to the file
+    // placement (mirp_align_reads_placed): the reads' depths, the unique list of the file (gpos << 32 | depth), its sorted positions and depth
+    // prefix, the weights of a batch's items and the per-read picks and tag fields
+    DevBuf a_depth, a_ulist, a_utmp, a_upos, a_ulo, a_uhi, a_uls, a_uhs, a_upre, a_w, a_pick, a_pn, a_pcls, a_pw, a_pwt;
+    long long a_place_cap = 0;        // items of pass 1 kept resident for pass 2; 0 = the default, 2^28 (mirp_set_align_place_capacity)
+    long long a_place_realigned = 0;  // batches the last mirp_align_reads_placed aligned twice (mirp_align_place_last_realigned)
+    std::vector<char> h_text;        // one piece (<= 1 GiB) of the SAM text on its way to the file
     // ---- read trimming (trim_kernels.hip, mirp_trim.cpp): the file text, its lines and the per-read arrays, reused from file to file
     DevBuf t_text, t_bcnt, t_bscan, t_starts, t_small, t_hdr, t_llen, t_lb, t_hscan, t_goff, t_first, t_gbuf, t_src, t_len, t_qual, t_nameb, t_namel,
         t_flen, t_off, t_out;
@@ -218,8 +223,15 @@ int mirp_device_collapse_reads(mirp_ctx* c, const char* text, long long n, const
 // align_kernels.hip: the alignment index and one batch of reads (mirp_align.cpp parses the files)
 int mirp_device_align_index(mirp_ctx* c, const unsigned* pk, const unsigned* amb, const unsigned* cst, long long total,
                             const std::vector<unsigned long long>& cstart, const std::string& names, const std::vector<long long>& noff, double seconds[4]);
-int mirp_device_align_batch(mirp_ctx* c, const unsigned char* codes, const long long* roff, const char* qn, const long long* qoff, long long n, int v, int k,
-                            int m, int filter, const std::function<int(const char*, size_t)>& sink, long long stats[4], double seconds[5]);
+// the three steps of a batch, and the placement of multi-mapped reads between hits and emit (mirp_align_reads_placed)
+int mirp_device_align_upload(mirp_ctx* c, const unsigned char* codes, const long long* roff, const char* qn, const long long* qoff, const unsigned* depth,
+                             long long n, double seconds[5]);
+int mirp_device_align_hits(mirp_ctx* c, long long n, int v, int m, int filter, long long* n_items, double seconds[5]);
+int mirp_device_align_emit(mirp_ctx* c, long long n, long long n_items, int v, int k, int m, int filter, int place,
+                           const std::function<int(const char*, size_t)>& sink, unsigned long long cnt[8], double seconds[5]);
+int mirp_device_place_unique(mirp_ctx* c, long long n, long long* n_unique);
+int mirp_device_place_prepare(mirp_ctx* c, long long n_unique, unsigned long long* depth_sum);
+int mirp_device_place_pick(mirp_ctx* c, long long n, long long n_items, int mode, int window, unsigned long long seed, long long n_unique);
 // reads_kernels.hip: the line split of an uploaded text shared by the collapse and the trim (starts[0 .. n_lines]); trim_kernels.hip: the trim of one FASTQ / FASTA text
 int mirp_device_split_lines(mirp_ctx* c, const unsigned char* d_text, long long n, long long max_lines, DevBuf& tile_cnt, DevBuf& tile_scan, DevBuf& starts,
                             unsigned long long* d_first_bad, long long* n_lines, long long* bad_offset);
