@@ -156,6 +156,20 @@ int mirp_limit_windows(mirp_ctx* ctx, int64_t n_keep);
  * MP:877-962 and MP:1246-1371 append to lists instead): out[k] = in[0] + .. + in[k-1] for k = 0 .. n, host arrays in and out, computed on the
  * context's device by the kernels the stage uses (one workgroup up to 16,384 elements, a single-pass look-back scan beyond).  For tests. */
 int mirp_excl_scan_i32(mirp_ctx* ctx, const int32_t* in, int64_t n, int64_t* out);
+/* The stable device sort under the ingest, the read collapse, the align index and every key pass (sort_kernels.hip): a least-significant-digit
+ * radix sort, 8 bits per pass, whole records moved; records whose sorted bits are equal keep their input order.  Three record types, each sorted
+ * on the context's device and stream by the kernels the commands use, host arrays in and out (out may be in).  For tests.
+ *   mirp_sort_alns     MirpAln by the key (uint32) tid << posbits | (uint32) pos, width posbits + tidbits; posbits and tidbits 0..32.
+ *   mirp_sort_records  16-byte records {uint64 key; uint32 a, b} (MirpSortRec) by the low `bits` bits of key; a and b are payload.
+ *   mirp_sort_u64      64-bit records by the bits [base, base + bits).
+ * The passes are whole digits: a width that is not a multiple of 8 is rounded up, so the order is by the key bits [base, base + 8 * ceil(bits / 8))
+ * (base = 0 for the first two; bits past 63 count as 0).  A caller whose width is not a multiple of 8 keeps the bits above it equal, or means
+ * them.  Bits outside that range have no influence.  Refused with -1: n < 0, a null array with n > 0, a negative base or width, base + bits > 64
+ * (posbits + tidbits > 64, posbits or tidbits > 32).  n = 0 and a width of 0 succeed and copy the input. */
+typedef struct { uint64_t key; uint32_t a, b; } MirpSortRec;
+int mirp_sort_alns(mirp_ctx* ctx, const MirpAln* in, int64_t n, int32_t posbits, int32_t tidbits, MirpAln* out);
+int mirp_sort_records(mirp_ctx* ctx, const MirpSortRec* in, int64_t n, int32_t bits, MirpSortRec* out);
+int mirp_sort_u64(mirp_ctx* ctx, const uint64_t* in, int64_t n, int32_t base, int32_t bits, uint64_t* out);
 /* Replaces gen_contig_typeA + gen_candidate_region_typeA + dump_loci_seqs_and_alignment_multiprocess
  * (MP:877-962, 1246-1371, 1065-1244). contig_order = contig indices in the order sorted(dict_contigs) visits them (MP:1309). */
 int mirp_candidate(mirp_ctx* ctx, const MirpCandidateParams* params, const int32_t* contig_order, int64_t* n_peaks, int64_t* n_loci,
@@ -525,6 +539,13 @@ int mirp_target_scan(mirp_ctx* ctx, const char* mirna_path, const char* const* t
  * split into passes by (miRNA, score) and by ranges of offsets; lowered only to test that path.  With bulge a pass holds at least 4 keys whatever
  * is set here: the most one offset can hold of one miRNA and score (t and m on both strands), so that the split always ends. */
 int mirp_set_target_capacity(mirp_ctx* ctx, int64_t keys);
+/* Bytes of text that leave the device in one piece: the lines of a pass of mirp_target_scan and mirp_mimic_scan (whole lines per piece; a longer
+ * line is a piece of its own) and the SAM / FASTA text of a batch of mirp_align_reads, mirp_align_reads_placed and mirp_trim_reads (cut at any
+ * byte).  0 = the default, 1 GiB; negative values are refused (-1).  Lowered only to test the piece path; no output depends on it.
+ * mirp_text_pieces_last: the non-empty pieces handed to the output by the last of those calls (the header lines a call writes itself are not
+ * pieces); -1 without a context. */
+int mirp_set_text_piece(mirp_ctx* ctx, int64_t bytes);
+int64_t mirp_text_pieces_last(const mirp_ctx* ctx);
 
 /* Endogenous target mimics: sites where a target pairs with a miRNA around a loop of loop_len unpaired target bases opposite the
  * gap between miRNA positions P and P + 1, P in {9, 10, 11}, so that the site cannot be sliced.  Positions 2..8 are Watson-Crick pairs, the pairs

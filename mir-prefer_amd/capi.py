@@ -115,6 +115,7 @@ HOMOLOG_STATS = ("queries", "repeat_like", "placements", "passing", "loci", "sca
 
 # MirpUnpairedRec of include/mirprefer.h: one window of mirp_unpaired_batch, kcal/mol
 UNPAIRED_DTYPE = np.dtype([("efe", "<f8"), ("efe_open", "<f8"), ("upe", "<f8")])
+SORT_REC_DTYPE = np.dtype([("key", "<u8"), ("a", "<u4"), ("b", "<u4")])      # MirpSortRec (mirp_sort_records)
 UNPAIRED_STATS = ("windows", "passes", "cells")
 
 
@@ -1326,6 +1327,45 @@ class Context:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         self._check(fn(self.h, v.ctypes.data if len(v) else None, len(v), out.ctypes.data), "mirp_excl_scan_i32")
         return out
+
+    def _sort_hook(self, name, values, dtype, *widths):
+        v = np.ascontiguousarray(values, dtype=dtype)
+        out = np.empty_like(v)
+        fn = getattr(self.lib, name)
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int32] * len(widths) + [C.c_void_p]
+        self._check(fn(self.h, v.ctypes.data if len(v) else None, len(v), *[int(w) for w in widths], out.ctypes.data if len(v) else None), name)
+        return out
+
+    def sort_alns(self, alns, posbits, tidbits):
+        """The stable device sort of MirpAln records by tid << posbits | pos (mirp_sort_alns, the sort of the ingest) -> the sorted copy.  Like the two
+        below it orders by whole 8-bit digits: the key bits [base, base + 8 * ceil(bits / 8)).  For tests."""
+        from .synth import ALN_DTYPE
+        return self._sort_hook("mirp_sort_alns", alns, ALN_DTYPE, posbits, tidbits)
+
+    def sort_records(self, recs, bits):
+        """The stable device sort of SORT_REC_DTYPE records by the low bits of `key` (mirp_sort_records, the sort of the read collapse) -> the sorted copy."""
+        return self._sort_hook("mirp_sort_records", recs, SORT_REC_DTYPE, bits)
+
+    def sort_u64(self, values, base, bits):
+        """The stable device sort of uint64 values by the bits from `base` up (mirp_sort_u64, the sort of the align index and the key passes) -> the
+        sorted copy."""
+        return self._sort_hook("mirp_sort_u64", values, np.uint64, base, bits)
+
+    def set_text_piece(self, nbytes):
+        """Bytes of text that leave the device in one piece in target_scan, mimic_scan, align_reads and trim_reads (mirp_set_text_piece); 0 = the
+        default, 1 GiB.  Lowered only to test the piece path; no output depends on it."""
+        fn = self.lib.mirp_set_text_piece
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int64]
+        self._check(fn(self.h, int(nbytes)), "mirp_set_text_piece")
+
+    def text_pieces_last(self):
+        """Non-empty pieces of text the last target_scan, mimic_scan, align_reads or trim_reads handed to its output (mirp_text_pieces_last)."""
+        fn = self.lib.mirp_text_pieces_last
+        fn.restype = C.c_int64
+        fn.argtypes = [C.c_void_p]
+        return int(fn(self.h))
 
     def limit_windows(self, n_keep):
         """Keeps the first n_keep windows of the last candidate() for the following stages (mirp_limit_windows)."""

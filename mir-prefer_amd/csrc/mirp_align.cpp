@@ -317,6 +317,7 @@ int align_file(mirp_ctx* c, const char* reads_path, const char* out_path, const 
 extern "C" int mirp_align_reads(mirp_ctx* c, const char* reads_path, const char* out_path, const char* pg_cl, int32_t v, int32_t k, int32_t m,
                                 int32_t filter_unmapped, int64_t stats[5], double seconds[6]) {
     if (!c) return -1;
+    c->text_pieces = 0;
     if (!reads_path || !out_path || !pg_cl || v < 0 || v > 3 || k < 1 || m < 0) return fail(c, -1, "mirp_align_reads: bad argument");
     if (!c->a_ready) return fail(c, -1, "mirp_align_reads: no index (mirp_align_index first)");
     HIPCHK(c, hipSetDevice(c->device));
@@ -335,6 +336,7 @@ extern "C" int mirp_align_reads(mirp_ctx* c, const char* reads_path, const char*
 extern "C" int mirp_align_reads_placed(mirp_ctx* c, const char* reads_path, const char* out_path, const char* pg_cl, int32_t v, int32_t k, int32_t m,
                                        int32_t filter_unmapped, const MirpAlignPlaceOpts* place, int64_t stats[8], double seconds[8]) {
     if (!c) return -1;
+    c->text_pieces = 0;
     const bool on = place && place->mode != 0;
     if (!reads_path || !out_path || !pg_cl || v < 0 || v > 3 || k < 1 || m < 0) return fail(c, -1, "mirp_align_reads_placed: bad argument");
     if (on && (place->mode < 1 || place->mode > 2 || place->window < 0 || place->window > 10000 || m < 1 || m > 10000))

@@ -57,6 +57,16 @@ extern "C" int mirp_create(int device, mirp_ctx** out) {
     return 0;
 }
 
+// The piece in which text leaves the device (site_finish_pass of site_lines.h, mirp_download_text of mirp_ctx.h) and the pieces of the last call
+extern "C" int mirp_set_text_piece(mirp_ctx* c, int64_t bytes) {
+    if (!c) return -1;
+    if (bytes < 0) return fail(c, -1, "mirp_set_text_piece: bad argument");
+    c->text_piece = bytes;
+    return 0;
+}
+
+extern "C" int64_t mirp_text_pieces_last(const mirp_ctx* c) { return c ? c->text_pieces : -1; }
+
 extern "C" int mirp_set_fold_model(mirp_ctx* c, int32_t model) {
     if (!c) return -1;
     if (model != MIRP_FOLD_MODEL_VIENNA_212 && model != MIRP_FOLD_MODEL_VIENNA_185) return fail(c, -1, "mirp_set_fold_model: unknown model");

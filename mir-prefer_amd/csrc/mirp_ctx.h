@@ -128,7 +128,10 @@ struct mirp_ctx {
     DevBuf a_depth, a_ulist, a_utmp, a_upos, a_ulo, a_uhi, a_uls, a_uhs, a_upre, a_w, a_pick, a_pn, a_pcls, a_pw, a_pwt;
     long long a_place_cap = 0;        // items of pass 1 kept resident for pass 2; 0 = the default, 2^28 (mirp_set_align_place_capacity)
     long long a_place_realigned = 0;  // batches the last mirp_align_reads_placed aligned twice (mirp_align_place_last_realigned)
-    std::vector<char> h_text;        // one piece (<= 1 GiB) of the SAM text on its way to the file
+    std::vector<char> h_text;        // one piece (<= text_piece_bytes()) of the SAM text on its way to the file
+    long long text_piece = 0;        // bytes of text per piece; 0 = the default, 1 GiB (mirp_set_text_piece: lowered only to test the piece path)
+    long long text_pieces = 0;       // non-empty pieces handed to a sink since the last call that emits text started (mirp_text_pieces_last)
+    long long text_piece_bytes() const { return text_piece > 0 ? text_piece : 1ll << 30; }
     // ---- read trimming (trim_kernels.hip, mirp_trim.cpp): the file text, its lines and the per-read arrays, reused from file to file
     DevBuf t_text, t_bcnt, t_bscan, t_starts, t_small, t_hdr, t_llen, t_lb, t_hscan, t_goff, t_first, t_gbuf, t_src, t_len, t_qual, t_nameb, t_namel,
         t_flen, t_off, t_out;
@@ -197,15 +200,16 @@ namespace mirp {
 inline double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 }  // namespace mirp
 
-// Copies `bytes` of device text to the host through c->h_text in pieces of at most 1 GiB and hands every piece to the sink; the seconds spent inside
-// the sink are added to *in_sink when it is given.
+// Copies `bytes` of device text to the host through c->h_text in pieces of at most c->text_piece_bytes() (1 GiB unless a test lowered it) and hands
+// every piece to the sink, counting it in c->text_pieces; the seconds spent inside the sink are added to *in_sink when it is given.
 inline int mirp_download_text(mirp_ctx* c, const char* d_text, long long bytes, const std::function<int(const char*, size_t)>& sink, double* in_sink = nullptr) {
-    const size_t piece = (size_t)1 << 30;
+    const size_t piece = (size_t)c->text_piece_bytes();
     if (bytes > 0 && c->h_text.size() < std::min((size_t)bytes, piece)) c->h_text.resize(std::min((size_t)bytes, piece));
     for (long long at = 0; at < bytes;) {
         const size_t len = (size_t)std::min<long long>(bytes - at, (long long)piece);
         HIPCHK(c, hipMemcpy(c->h_text.data(), d_text + at, len, hipMemcpyDeviceToHost));
         const double t = mirp::now();
+        c->text_pieces++;
         if (int rc = sink(c->h_text.data(), len)) return rc;
         if (in_sink) *in_sink += mirp::now() - t;
         at += (long long)len;
@@ -213,7 +217,8 @@ inline int mirp_download_text(mirp_ctx* c, const char* d_text, long long bytes, 
     return 0;
 }
 
-// sort_kernels.hip: stable device sort by (tid, pos) / keep-region filter of the resident record array
+// sort_kernels.hip: stable device sort by (tid, pos) / keep-region filter of the resident record array.  Every sort orders by whole 8-bit digits, the
+// key bits [base, base + 8 * ceil(bits / 8)): callers keep the bits above their `bits` equal or meaningful.
 int mirp_device_sort_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long n, int posbits, int tidbits);
 int mirp_device_sort_u64(mirp_ctx* c, unsigned long long* d, unsigned long long* d_tmp, long long n, int base, int bits);
 int mirp_device_sort_hashes(mirp_ctx* c, MirpHashRec* d, MirpHashRec* d_tmp, long long n, int bits);

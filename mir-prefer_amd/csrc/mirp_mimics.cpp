@@ -29,6 +29,7 @@ int seed_key(const unsigned char* cd) {
 extern "C" int mirp_mimic_scan(mirp_ctx* c, const char* mirna_path, const char* const* target_paths, int32_t n_targets, const MirpMimicOpts* o,
                                const char* out_path, int64_t stats[8], double seconds[5]) {
     if (!c) return -1;
+    c->text_pieces = 0;
     if (!mirna_path || !target_paths || n_targets < 1 || !o || !out_path) return fail(c, -1, "mirp_mimic_scan: bad argument");
     if (o->max_imperfect < 0 || o->max_imperfect > 6 || o->loop_len < 2 || o->loop_len > 6 || o->max_sites < 0 || (o->both_strands != 0 && o->both_strands != 1))
         return fail(c, -1, "mirp_mimic_scan: bad options");

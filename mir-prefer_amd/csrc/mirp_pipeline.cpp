@@ -253,6 +253,46 @@ extern "C" int mirp_excl_scan_i32(mirp_ctx* c, const int32_t* in, int64_t n, int
     return 0;
 }
 
+// The three instantiations of the device sort (sort_kernels.hip) on host arrays, for tests: the records and the sort's second buffer live in
+// scoped device allocations, the counters and the scan's state are the context's, as in every command.
+template <class Rec, class Sort>
+static int sort_host_array(mirp_ctx* c, const Rec* in, int64_t n, Rec* out, Sort sort) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n == 0) return 0;
+    TmpDevice T;
+    Rec* d = (Rec*)T.get(sizeof(Rec) * (size_t)n);
+    Rec* d_tmp = (Rec*)T.get(sizeof(Rec) * (size_t)n);
+    if (!d || !d_tmp) return fail(c, -6, "device allocation failed (sort hook)");
+    HIPCHK(c, hipMemcpyAsync(d, in, sizeof(Rec) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    if (int rc = sort(d, d_tmp)) return rc;
+    HIPCHK(c, hipMemcpyAsync(out, d, sizeof(Rec) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int mirp_sort_alns(mirp_ctx* c, const MirpAln* in, int64_t n, int32_t posbits, int32_t tidbits, MirpAln* out) {
+    if (!c) return -1;
+    if (n < 0 || (n > 0 && (!in || !out)) || posbits < 0 || tidbits < 0 || posbits > 32 || tidbits > 32 || posbits + tidbits > 64)
+        return fail(c, -1, "mirp_sort_alns: bad argument");
+    return sort_host_array(c, in, n, out, [&](MirpAln* d, MirpAln* t) { return mirp_device_sort_alns(c, d, t, n, posbits, tidbits); });
+}
+
+static_assert(sizeof(MirpSortRec) == sizeof(MirpHashRec) && sizeof(MirpSortRec) == 16, "MirpSortRec is the layout of the collapse's (hash, index) records");
+
+extern "C" int mirp_sort_records(mirp_ctx* c, const MirpSortRec* in, int64_t n, int32_t bits, MirpSortRec* out) {
+    if (!c) return -1;
+    if (n < 0 || (n > 0 && (!in || !out)) || bits < 0 || bits > 64) return fail(c, -1, "mirp_sort_records: bad argument");
+    return sort_host_array(c, (const MirpHashRec*)in, n, (MirpHashRec*)out,
+                           [&](MirpHashRec* d, MirpHashRec* t) { return mirp_device_sort_hashes(c, d, t, n, bits); });
+}
+
+extern "C" int mirp_sort_u64(mirp_ctx* c, const uint64_t* in, int64_t n, int32_t base, int32_t bits, uint64_t* out) {
+    if (!c) return -1;
+    if (n < 0 || (n > 0 && (!in || !out)) || base < 0 || bits < 0 || base > 64 || bits > 64 || base + bits > 64) return fail(c, -1, "mirp_sort_u64: bad argument");
+    return sort_host_array(c, (const unsigned long long*)in, n, (unsigned long long*)out,
+                           [&](unsigned long long* d, unsigned long long* t) { return mirp_device_sort_u64(c, d, t, n, base, bits); });
+}
+
 extern "C" int mirp_candidate(mirp_ctx* c, const MirpCandidateParams* params, const int32_t* contig_order, int64_t* n_peaks_out,
                               int64_t* n_loci_out, int64_t* n_windows_out) {
     if (!c) return -1;

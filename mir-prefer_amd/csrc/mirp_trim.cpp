@@ -12,6 +12,7 @@
 extern "C" int mirp_trim_reads(mirp_ctx* c, const char* data, int64_t n, const char* name, const MirpTrimOpts* o, const char* out_path, int64_t stats[7],
                                double seconds[6]) {
     if (!c) return -1;
+    c->text_pieces = 0;
     if ((!data && n > 0) || n < 0 || !name || !o || !out_path) return fail(c, -1, "mirp_trim_reads: bad argument");
     if (o->adapter_len < 0 || o->adapter_len > 64 || o->error_permille < 0 || o->error_permille > 999 || o->quality_cutoff < 0 || o->quality_cutoff > 93 ||
         o->min_length < 0 || o->max_length < 0 || (o->max_length > 0 && o->max_length < o->min_length) ||

@@ -5,7 +5,8 @@
 //
 //   order  mirp_device_sort_u64 by the whole key = the output order.
 //   cut    site_size_kernel: the line's length, 0 where -k cuts the key (site_kept, site_keys.h); site_emitted_kernel; launch_excl_scan.
-//   emit   site_emit_kernel writes the lines; the text goes to the sink in pieces of at most 1 GiB (text_pieces.h).
+//   emit   site_emit_kernel writes the lines; the text goes to the sink in pieces of whole lines, at most c->text_piece_bytes() each (1 GiB
+//          unless a test lowered it; text_pieces.h), counted in c->text_pieces.
 // The keys, offsets and text of a pass live in the context's tg_* buffers, which both searches size.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -89,7 +90,7 @@ int site_finish_pass(mirp_ctx* c, const LINE& line, long long n, int key_bits, l
     };
     for (long long i0 = 0, base = 0; i0 < n;) {
         long long i1 = n, end = bytes;
-        if (int rc = text_piece_end(i0, n, base, bytes, 1ll << 30, read_toff, &i1, &end)) return rc;
+        if (int rc = text_piece_end(i0, n, base, bytes, c->text_piece_bytes(), read_toff, &i1, &end)) return rc;
         const long long len = end - base;
         if (len > 0) {
             if (c->tg_text.ensure((size_t)len + 16)) return fail(c, -6, std::string("device allocation failed (") + name + ": text)");
@@ -98,6 +99,7 @@ int site_finish_pass(mirp_ctx* c, const LINE& line, long long n, int key_bits, l
             HIPCHK(c, hipGetLastError());
             if (c->h_text.size() < (size_t)len) c->h_text.resize((size_t)len);
             HIPCHK(c, hipMemcpy(c->h_text.data(), c->tg_text.p, (size_t)len, hipMemcpyDeviceToHost));
+            c->text_pieces++;
             if (int rc = sink(c->h_text.data(), (size_t)len)) return rc;
         }
         i0 = i1;

@@ -24,7 +24,7 @@ struct AlnDigit {
         return (unsigned)(key >> shift) & 255u;
     }
 };
-// 64-bit records by bits [base, base + bits): the alignment index (key32 << 32 | pos, by key) and its hits (read << 33 | gpos << 1 | strand)
+// 64-bit records by the digits from bit `base` up: the alignment index (key32 << 32 | pos, by key) and its hits (read << 33 | gpos << 1 | strand)
 struct U64Digit {
     int base;
     __device__ __forceinline__ unsigned operator()(const unsigned long long& r, int shift) const { return (unsigned)(r >> (shift + base)) & 255u; }
@@ -124,7 +124,11 @@ static inline int grid_for(long long n, int block, int cap) {
     return (int)(g < 1 ? 1 : g > cap ? cap : g);
 }
 
-// Stable LSD sort of d[0, n) over the low `bits` bits of the digit function's key into place; d_tmp: a second record buffer of the same size.
+// Stable LSD sort of d[0, n) by the digit function's key into place; d_tmp: a second record buffer of the same size.  The passes are whole 8-bit
+// digits, so the order is by the key bits [0, 8 * ceil(bits / 8)), not by the low `bits` bits alone: a caller whose `bits` is not a multiple of 8
+// keeps the key bits above `bits` equal over the records, or means them to take part (clusters_kernels.hip passes 32 + cl_bits(ntid - 1) and
+// 17 + cl_bits(n - 1) over keys that are 0 above those widths).  Records with equal digits keep their input order.  n <= 1 and bits <= 0 leave d
+// as it is.  Pinned directly, record type by record type, through the mirp_sort_* hooks (mirp_pipeline.cpp; tests/test_device_sort_gpu.py).
 template <class Rec, class Digit>
 static int device_radix_sort(mirp_ctx* c, Rec* d, Rec* d_tmp, long long n, int bits, Digit digit) {
     if (n <= 1) return 0;
@@ -151,17 +155,21 @@ static int device_radix_sort(mirp_ctx* c, Rec* d, Rec* d_tmp, long long n, int b
     return 0;
 }
 
-// Stable sort of d_alns[0, n) by (tid, pos) into place; d_tmp: a second record buffer of the same size.
+// Stable sort of d_alns[0, n) by (tid, pos) into place; d_tmp: a second record buffer of the same size.  The key is (unsigned)tid << posbits |
+// (unsigned)pos, sorted by its bits [0, 8 * ceil((posbits + tidbits) / 8)) (whole digits, see device_radix_sort): pos must fit posbits, and a tid
+// wider than tidbits takes part up to the next multiple of 8.
 int mirp_device_sort_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long n, int posbits, int tidbits) {
     return device_radix_sort(c, d_alns, d_tmp, n, posbits + tidbits, mirp::AlnDigit{posbits});
 }
 
-// Stable sort of (hash, read index) records by the low `bits` bits of the hash (the read collapse, reads_kernels.hip).
+// Stable sort of (hash, read index) records by the hash bits [0, 8 * ceil(bits / 8)) (whole digits, see device_radix_sort): the read collapse
+// (reads_kernels.hip) rounds its hash_bits up itself and masks the hash, the cluster search passes keys that are 0 above `bits`.
 int mirp_device_sort_hashes(mirp_ctx* c, MirpHashRec* d, MirpHashRec* d_tmp, long long n, int bits) {
     return device_radix_sort(c, d, d_tmp, n, bits, mirp::HashDigit{});
 }
 
-// Stable sort of 64-bit records by bits [base, base + bits) (the read alignment, align_kernels.hip).
+// Stable sort of 64-bit records by the bits [base, base + 8 * ceil(bits / 8)) (whole digits, see device_radix_sort; bits past 63 read as 0): the
+// read alignment (align_kernels.hip), the key passes of the site searches (site_lines.h).  The bits below base are payload and keep their order.
 int mirp_device_sort_u64(mirp_ctx* c, unsigned long long* d, unsigned long long* d_tmp, long long n, int base, int bits) {
     return device_radix_sort(c, d, d_tmp, n, bits, mirp::U64Digit{base});
 }

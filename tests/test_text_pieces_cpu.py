@@ -158,6 +158,26 @@ def test_a_failing_read_stops_the_walk(driver):
     assert stopped > 30 and all(rc == 0 for _, rc in whole)
 
 
+def test_abi_entries_are_declared():
+    """the piece knob and the sort hooks the GPU tests use (test_text_pieces_gpu.py, test_device_sort_gpu.py): declared, defined and bound"""
+    header = open(os.path.join(ROOT, "include", "mirprefer.h")).read()
+    csrc = os.path.join(ROOT, "mir-prefer_amd", "csrc")
+    defined = "".join(open(os.path.join(csrc, f)).read() for f in ("mirp_api.cpp", "mirp_pipeline.cpp"))
+    binding = open(os.path.join(ROOT, "mir-prefer_amd", "capi.py")).read()
+    for name in ("mirp_set_text_piece", "mirp_text_pieces_last", "mirp_sort_alns", "mirp_sort_records", "mirp_sort_u64"):
+        assert name + "(" in header and name + "(" in defined and name in binding, name
+    assert "typedef struct { uint64_t key; uint32_t a, b; } MirpSortRec;" in header
+    assert "lowered only to test the piece path; no output depends on it" in header.lower().replace("\n * ", " ")
+    assert "#define MIRP_ABI_VERSION 17 " in open(os.path.join(csrc, "mirp_api.cpp")).read()          # only entries are added
+    from mir_prefer_amd import capi
+    assert capi.ABI_VERSION == 17 and capi.SORT_REC_DTYPE.itemsize == 16 and capi.SORT_REC_DTYPE.names == ("key", "a", "b")
+    # the two literals are gone: both piece loops read the context's size
+    for f, text in (("site_lines.h", "c->text_piece_bytes()"), ("mirp_ctx.h", "c->text_piece_bytes()")):
+        src = open(os.path.join(csrc, f)).read()
+        assert text in src and "c->text_pieces++" in src, f
+    assert "1ll << 30, read_toff" not in open(os.path.join(csrc, "site_lines.h")).read()
+
+
 def test_the_driver_is_clean_under_the_host_sanitizers(tmp_path):
     run = _build(tmp_path, ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"])
     scenarios = _scenarios(20273, 100) + [(p, 3, s) for p, _, s in _scenarios(20274, 30)]
