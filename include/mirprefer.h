@@ -509,6 +509,11 @@ typedef struct {
  * summed), seconds = {upload, split, records, trim, emit + download, write}. */
 int mirp_trim_reads(mirp_ctx* ctx, const char* data, int64_t n, const char* name, const MirpTrimOpts* opts, const char* out_path, int64_t stats[7],
                     double seconds[6]);
+/* How the trim kernel of the last mirp_trim_reads of this context read its reads: out[0] = the workgroups (128 consecutive reads each) that
+ * staged their reads' text in LDS, out[1] = those whose text is over 32 KiB and was read from device memory; a workgroup without a valid read
+ * counts as neither.  Both are 0 after a call that was refused or failed.  No output depends on the path; the entry is there for tests.
+ * Returns -1 without a context or out. */
+int mirp_trim_last_paths(const mirp_ctx* ctx, int64_t out[2]);
 
 /* Plant miRNA target sites: every miRNA against every offset of every target, ungapped, scored by position-weighted mismatches
  * (mismatch 1, G:U 0.5, doubled at miRNA positions 2..13) in half-units.  max_half_score 0..16 (= 2 x the -s score); both_strands: also the minus

@@ -490,6 +490,8 @@ def load_library():
     lib.mirp_align_place_last_realigned.restype = C.c_int64
     lib.mirp_trim_reads.argtypes = [vp, C.c_char_p, C.c_int64, C.c_char_p, C.POINTER(TrimOpts), C.c_char_p, i64p, C.POINTER(C.c_double)]
     lib.mirp_trim_reads.restype = C.c_int
+    lib.mirp_trim_last_paths.argtypes = [vp, i64p]
+    lib.mirp_trim_last_paths.restype = C.c_int
     lib.mirp_target_scan.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(TargetOpts), C.c_char_p, i64p, C.POINTER(C.c_double)]
     lib.mirp_target_scan.restype = C.c_int
     lib.mirp_mimic_scan.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(MimicOpts), C.c_char_p, i64p, C.POINTER(C.c_double)]
@@ -679,6 +681,13 @@ class Context:
         sec = (C.c_double * 6)()
         self._check(self.lib.mirp_trim_reads(self.h, data, len(data), os.fsencode(name), C.byref(o), os.fsencode(out_path), st, sec), "mirp_trim_reads")
         return dict(zip(TRIM_STATS, list(st)), seconds=list(sec))
+
+    def trim_last_paths(self):
+        """(workgroups that staged their reads in LDS, workgroups that read them from device memory) of the last trim_reads (mirp_trim_last_paths);
+        (0, 0) after a refused call."""
+        out = (C.c_int64 * 2)()
+        self._check(self.lib.mirp_trim_last_paths(self.h, out), "mirp_trim_last_paths")
+        return int(out[0]), int(out[1])
 
     def target_scan(self, mirna_path, target_paths, out_path, max_half_score=8, both_strands=False, cleavage_site=False, max_sites=0, bulge=False,
                     energy=False, accessibility=False, flanks=None):

@@ -135,6 +135,7 @@ struct mirp_ctx {
     // ---- read trimming (trim_kernels.hip, mirp_trim.cpp): the file text, its lines and the per-read arrays, reused from file to file
     DevBuf t_text, t_bcnt, t_bscan, t_starts, t_small, t_hdr, t_llen, t_lb, t_hscan, t_goff, t_first, t_gbuf, t_src, t_len, t_qual, t_nameb, t_namel,
         t_flen, t_off, t_out;
+    long long t_paths[2] = {0, 0};    // workgroups of the last mirp_trim_reads that staged their reads in LDS / read them from global memory (mirp_trim_last_paths)
     // ---- target-site search (targets_kernels.hip, mirp_targets.cpp): the packed targets, the miRNAs and the key / text buffers of one call
     DevBuf tg_pk, tg_amb, tg_cst, tg_cstart, tg_names, tg_noff, tg_mcodes, tg_mnames, tg_mnoff, tg_mi, tg_emitted, tg_hist, tg_small, tg_keys, tg_ktmp,
         tg_size, tg_toff, tg_text;

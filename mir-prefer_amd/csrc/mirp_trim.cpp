@@ -13,6 +13,7 @@ extern "C" int mirp_trim_reads(mirp_ctx* c, const char* data, int64_t n, const c
                                double seconds[6]) {
     if (!c) return -1;
     c->text_pieces = 0;
+    c->t_paths[0] = c->t_paths[1] = 0;
     if ((!data && n > 0) || n < 0 || !name || !o || !out_path) return fail(c, -1, "mirp_trim_reads: bad argument");
     if (o->adapter_len < 0 || o->adapter_len > 64 || o->error_permille < 0 || o->error_permille > 999 || o->quality_cutoff < 0 || o->quality_cutoff > 93 ||
         o->min_length < 0 || o->max_length < 0 || (o->max_length > 0 && o->max_length < o->min_length) ||
@@ -29,5 +30,12 @@ extern "C" int mirp_trim_reads(mirp_ctx* c, const char* data, int64_t n, const c
     if (!out.commit()) return fail(c, -8, std::string("cannot write ") + out_path);          // nothing kept: the output is an empty file
     if (stats) for (int i = 0; i < 7; i++) stats[i] = st[i];
     if (seconds) std::memcpy(seconds, sec, sizeof sec);
+    return 0;
+}
+
+extern "C" int mirp_trim_last_paths(const mirp_ctx* c, int64_t out[2]) {
+    if (!c || !out) return -1;
+    out[0] = c->t_paths[0];
+    out[1] = c->t_paths[1];
     return 0;
 }

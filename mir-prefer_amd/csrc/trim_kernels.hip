@@ -194,6 +194,7 @@ __device__ __forceinline__ unsigned tr_one(const unsigned char* s, const unsigne
 }
 
 // one workgroup per TR_NT consecutive reads; base = the text (FASTQ, qual = quality starts) or the gathered reads (FASTA, qual = nullptr)
+// counts[0 .. 6) = the reads per flag bit 0..5; counts[6], counts[7] = the workgroups that staged their slab in LDS / read from global memory
 __global__ void __launch_bounds__(TR_NT) trim_reads_kernel(const unsigned char* __restrict__ base, const long long* __restrict__ src, const int* __restrict__ len,
                                                            const long long* __restrict__ qual, long long R, TrimArgs a, int* __restrict__ flen,
                                                            unsigned long long* __restrict__ counts, unsigned long long* __restrict__ err) {
@@ -215,6 +216,7 @@ __global__ void __launch_bounds__(TR_NT) trim_reads_kernel(const unsigned char* 
     const long long lo = (long long)(s_lo & ~15ull), span = (long long)s_hi - lo;
     unsigned fl = 0;
     int f = -1;
+    if (threadIdx.x == 0 && s_lo != ~0ull) atomicAdd(&counts[span <= TR_SLAB ? 6 : 7], 1ull);
     if (s_lo != ~0ull && span <= TR_SLAB) {
         for (long long o = threadIdx.x * 16; o < span; o += TR_NT * 16) slab[o >> 4] = *(const uint4*)(base + lo + o);
         __syncthreads();
@@ -278,15 +280,16 @@ int mirp_device_trim_reads(mirp_ctx* c, const char* text, long long n, const cha
                            const std::function<int(const char*, size_t)>& sink, long long stats[7], double seconds[6]) {
     using namespace mirp;
     for (int i = 0; i < 7; i++) stats[i] = 0;
+    c->t_paths[0] = c->t_paths[1] = 0;
     if (n == 0) return 0;
     hipStream_t st = c->stream;
     double t = mirp::now();
-    if (c->t_text.ensure((size_t)n + TR_PAD) || c->t_small.ensure(64)) return fail(c, -6, "device allocation failed (trim: text)");
+    if (c->t_text.ensure((size_t)n + TR_PAD) || c->t_small.ensure(80)) return fail(c, -6, "device allocation failed (trim: text)");
     unsigned char* d_text = (unsigned char*)c->t_text.p;
-    unsigned long long* d_small = (unsigned long long*)c->t_small.p;   // [0] first byte >= 0x80, [1] first bad record key, [2 .. 8) counts
+    unsigned long long* d_small = (unsigned long long*)c->t_small.p;   // [0] first byte >= 0x80, [1] first bad record key, [2 .. 8) counts, [8 .. 10) workgroups per path
     HIPCHK(c, hipMemcpy(d_text, text, (size_t)n, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemsetAsync(d_text + n, 0, TR_PAD, st));
-    unsigned long long init[8] = {~0ull, ~0ull, 0, 0, 0, 0, 0, 0};
+    unsigned long long init[10] = {~0ull, ~0ull, 0, 0, 0, 0, 0, 0, 0, 0};
     HIPCHK(c, hipMemcpyAsync(d_small, init, sizeof init, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipStreamSynchronize(st));
     seconds[0] += mirp::now() - t;
@@ -384,7 +387,7 @@ int mirp_device_trim_reads(mirp_ctx* c, const char* text, long long n, const cha
     if (R > 0)
         hipLaunchKernelGGL(trim_reads_kernel, dim3((unsigned)((R + TR_NT - 1) / TR_NT)), dim3(TR_NT), 0, st, d_base, (const long long*)d_src, (const int*)d_len,
                            fq ? (const long long*)c->t_qual.p : (const long long*)nullptr, R, a, d_flen, d_small + 2, d_err);
-    unsigned long long res[7];
+    unsigned long long res[9];
     HIPCHK(c, hipMemcpyAsync(res, d_small + 1, sizeof res, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
@@ -415,5 +418,7 @@ int mirp_device_trim_reads(mirp_ctx* c, const char* text, long long n, const cha
     seconds[5] += in_sink;
     stats[0] = R;
     for (int i = 0; i < 6; i++) stats[1 + i] = (long long)res[1 + i];
+    c->t_paths[0] = (long long)res[7];
+    c->t_paths[1] = (long long)res[8];
     return 0;
 }
