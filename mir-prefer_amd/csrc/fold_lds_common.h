@@ -74,6 +74,12 @@ __device__ inline void xt_fill(TAB& T, const FoldParams* __restrict__ P, int tid
 #define CSTR MIRP_RING_CSTR      // 378 (fold_params.h; the host builds FoldParams::ring_rowoff from the same constant)
 #define MIRP_CK(d) ((d) % 3)
 #define CRING_ROWS 33       // diagonal dd lives in row dd & 31; row 32 mirrors row 0, so "the row after row r" is always r + 1 (phase A1 mixes lanes of two diagonals)
+// The batched bulge / 1xn jobs (a1_b0f .. a1_i1f) take at most A1_CHUNK consecutive loop sizes at a time, i.e. that many consecutive ring rows.  The two-per-CU
+// layout mirrors the first A1_CHUNK rows behind row 31 (row 32 + r = row r), so that the rows of a chunk never wrap -- a chunk whose lowest row is r <= 31
+// ends at row r + A1_CHUNK - 1 <= 40 -- and are read at compile-time offsets from one lane base; the lanes that go ahead read one row later (<= 41).
+#define A1_CHUNK 10
+#define CRING_ROWS_WIN (32 + A1_CHUNK)
+template <bool TWO> __host__ __device__ constexpr int cring_rows() { return TWO ? CRING_ROWS_WIN : CRING_ROWS; }
 
 struct LTab {               // table accessors for the shared epilogue/backtrack
     static constexpr bool kTiled = true;   // 8 x 8 tiles over (row, diagonal): see the archive layout below
@@ -164,6 +170,7 @@ __host__ __device__ inline int arch_rowblk_off(int b, int n, int dcap) {
 
 struct LdsLayout {
     unsigned fml, aux, S, seq, pax, qb2, list, tabs, misc, total, fml_bytes, code4, spec;
+    int ring_rows;      // rows of the c ring (cring_rows: the two-per-CU layout mirrors a whole chunk of rows)
 };
 // bytes per shifted copy of a pair-code array, a multiple of 16.  The batched jobs (a1_codes4) read the codes of a whole chunk as dwords: the N <= A1_CHUNK
 // codes from index A on, rounded up to four.  In the steady state A + N - 1 <= n; on the first diagonals, which run the same code (see CSTR), a job
@@ -183,8 +190,8 @@ __host__ __device__ constexpr unsigned lds_al(unsigned x) { return (x + 15u) & ~
 // The candidate-pool pass shares its CUs with the epilogue of the chunk before it (mirp_run_fold, "fold overlap"): two of its workgroups leave room for
 // MIRP_OVERLAP_EPI_WGS epilogue workgroup of up to MIRP_OVERLAP_EPI_LDS bytes (fold_lds_epilogue_bytes is 18.4 KB at the default number of structure
 // lines; a call whose epilogue needs more takes the serial path, see fold_lds_overlap_epi_wgs).  gfx950 hands out LDS in granules of 1280 bytes, 128
-// per CU: 2 x 56 + 16.  The pool keeps 3,477 of its 5,184 entries; no benchmark window fills more than 1,328, and a window that does
-// overflow is folded by the dense pass as before.  (Two epilogue workgroups per CU would need 62,720 bytes, a pool of 1,984, and a fill kernel of
+// per CU: 2 x 56 + 16.  The pool keeps 2,343 of its 5,184 entries (3,477 before the ring's mirror rows, CRING_ROWS_WIN); no benchmark window fills more
+// than 1,328, and a window that does overflow is folded by the dense pass as before.  (Two epilogue workgroups per CU would need 62,720 bytes, a pool of 1,984, and a fill kernel of
 // 96 VGPRs, which spills.)
 #ifndef MIRP_FILL_TWO_BYTES
 #define MIRP_FILL_TWO_BYTES 71680
@@ -202,7 +209,8 @@ __host__ __device__ constexpr LdsLayout lds_layout() {
     LdsLayout L{};
     unsigned o = 0;
     if (!SPARSE) { L.fml = o; L.fml_bytes = FML_REGION_BYTES; o += L.fml_bytes; }
-    L.aux = o; o += lds_al(CRING_ROWS * CSTR * 2 + (MODEL ? 5 : 3) * LCAP * 2 + (SPARSE ? 6 : 5) * LCAP * 4);   // c ring (32 diagonals + mirror row), DML ring (3; 5 in the vienna-1.8.5 model), 3 x ckey, 2 (sparse: 3) x mdec
+    L.ring_rows = cring_rows<TWO>();
+    L.aux = o; o += lds_al(L.ring_rows * CSTR * 2 + (MODEL ? 5 : 3) * LCAP * 2 + (SPARSE ? 6 : 5) * LCAP * 4);   // c ring (32 diagonals + mirror rows), DML ring (3; 5 in the vienna-1.8.5 model), 3 x ckey, 2 (sparse: 3) x mdec
     L.S = o; o += lds_al(LCAP + 8);
     L.seq = o; o += lds_al(LCAP + 8);
     if (SPARSE) {      // 4 byte-shifted copies of the q codes, then 4 of the p codes (bytes); copy 0 of each IS the array (a1_codes4)
@@ -254,9 +262,11 @@ struct A1 {
 // every ring-row offset (rowtab[U] = k * CSTR shorts) must be a whole dword.
 static_assert(CSTR % 2 == 0, "the aligned-dword ring reads need dword-aligned ring rows");
 // Those reads cover ring entries up to U + 1 of a lane's run, at most 3 past its last candidate (U - 2).  A run starts at column i + 1 <= LCAP - 2
-// of ring row <= 32 (the mirror row, CRING_ROWS), so the farthest read lands at most a few entries into the DML ring that follows the c ring in
+// of the ring's last row at most (a mirror row, cring_rows), so the farthest read lands at most a few entries into the DML ring that follows the c ring in
 // the aux region (lds_layout: at least 3 DML rows of LCAP shorts) -- never outside the aux allocation.
-static_assert((CRING_ROWS - 1) * CSTR + (LCAP - 2) + 1 + MAXLOOP + 1 < CRING_ROWS * CSTR + 3 * LCAP, "the ring over-read stays inside the aux region");
+template <bool TWO> __host__ __device__ constexpr bool cring_overread_ok() { return (cring_rows<TWO>() - 1) * CSTR + (LCAP - 2) + 1 + MAXLOOP + 1 < cring_rows<TWO>() * CSTR + 3 * LCAP; }
+static_assert(cring_overread_ok<false>() && cring_overread_ok<true>(), "the ring over-read stays inside the aux region");
+static_assert(lds_layout<0, true, true>().ring_rows == CRING_ROWS_WIN && lds_layout<0>().ring_rows == CRING_ROWS && lds_layout<1, true>().ring_rows == CRING_ROWS, "only the two-per-CU layout mirrors a chunk of rows");
 // First diagonals on the unchecked code (d >= 6, so i <= n - 6 <= LCAP - 8): no read of a lane leaves its ring row (see CSTR).
 #ifndef MIRP_RAMP_OLD_STRIDE      // (a VARIANT build at the old stride shows that tests/test_fold_rampup_gpu.py sees the fault)
 static_assert((LCAP - 2) - 6 + 1 + MAXLOOP + 1 < CSTR, "ramp-up diagonals: a lane's ring reads stay inside their row");
@@ -573,7 +583,7 @@ __device__ __forceinline__ void a1_small_g(const A1& a, int i, int j, int type, 
 // the table reads that depend on it as a second one, then the arithmetic.  The straightforward versions interleave a volatile read (kept
 // narrow on purpose, see a1_gen_row) with the reads that depend on it, and a volatile access is an ordering point for the scheduler: they
 // compile to one LDS round trip per candidate.
-#define A1_CHUNK 10
+// (A1_CHUNK: at CRING_ROWS_WIN)
 // N consecutive pair codes starting at byte A of a code array, four per read.  A lane's A has any alignment (consecutive cells have consecutive
 // columns) and a ds_read_b32 off its alignment costs several aligned ones (profiles/tools/lds_unaligned.hip), so the array exists four times, copy c
 // shifted by c bytes: the dword at (A - c) of copy c = A & 3 holds codes A .. A + 3 and is aligned.  The byte selects fold into the adds that use
@@ -596,7 +606,10 @@ __device__ __forceinline__ void a1_gather4(unsigned tab_idx, const unsigned (&dw
         a1_gather4<N, K + 1>(tab_idx, dw, x);
     }
 }
-template <int N>
+#ifndef MIRP_A1_TABLO
+#define MIRP_A1_TABLO 1      // 0: a timing build of the WIN form that keeps the pointer cast
+#endif
+template <int N, bool WIN = false>
 __device__ __forceinline__ void a1_codes4(const A1& a, int which, int A, const unsigned char* tab, unsigned idx, int (&x)[N]) {
     typedef const volatile __attribute__((address_space(3))) unsigned* lds_vu32;
     const int c = A & 3;
@@ -604,12 +617,25 @@ __device__ __forceinline__ void a1_codes4(const A1& a, int which, int A, const u
     unsigned dw[(N + 3) / 4];
 #pragma unroll
     for (int t = 0; t < (N + 3) / 4; t++) dw[t] = p[t];
-    const unsigned tab_idx = (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)tab + idx;      // LDS address of tab[idx]
+    // LDS address of tab[idx].  The pointer cast carries a null check (s_cmp / s_cselect on both halves of the generic pointer, once per chunk); an LDS
+    // object's generic address is the shared aperture's base in the high half and its LDS address in the low half, so WIN takes the low half as it is
+    unsigned tab_idx;
+    if constexpr (WIN && MIRP_A1_TABLO) tab_idx = (unsigned)(size_t)tab + idx;
+    else tab_idx = (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)tab + idx;
     a1_gather4<N>(tab_idx, dw, x);
 }
-template <int LO, int HI>
+// WIN (the layout with the mirror rows, CRING_ROWS_WIN): the N <= A1_CHUNK ring rows of a chunk are consecutive rows from the row of its LARGEST loop size
+// UMAX upwards -- (r0 - UMAX) & 31 is at most 31, the chunk then ends in the mirror rows instead of wrapping -- so candidate k reads at the compile-time
+// offset (N - 1 - k) rows (plus its column step) from one lane base per chunk: no per-candidate address, no row-offset table.
+template <int UMAX>
+__device__ __forceinline__ int a1_win_row(const A1& a) {
+    int r0 = a.r0;
+    asm volatile("" : "+s"(r0));      // computed where the chunk stands: hoisted out of the block's job loop the offsets of all chunks live in spilled SGPRs (92 against 81)
+    return ((r0 - UMAX) & 31) * CSTR;
+}
+template <bool WIN, int LO, int HI>
 __device__ __forceinline__ void a1_b0f(const A1& a, int i, int j, unsigned& best) {
-    if constexpr (HI - LO + 1 > A1_CHUNK) { a1_b0f<LO, LO + A1_CHUNK - 1>(a, i, j, best); a1_b0f<LO + A1_CHUNK, HI>(a, i, j, best); }
+    if constexpr (HI - LO + 1 > A1_CHUNK) { a1_b0f<WIN, LO, LO + A1_CHUNK - 1>(a, i, j, best); a1_b0f<WIN, LO + A1_CHUNK, HI>(a, i, j, best); }
     else {
         constexpr int N = HI - LO + 1;
         const unsigned idxp = a.pax[i + 1];
@@ -618,11 +644,17 @@ __device__ __forceinline__ void a1_b0f(const A1& a, int i, int j, unsigned& best
         const unsigned char* xb = a.T->XB;
         unsigned code[N], g[N];
         int x[N];
+        if constexpr (WIN) {
+            const unsigned short* rw = rb + a1_win_row<HI>(a);
 #pragma unroll
-        for (int k = 0; k < N; k++) g[k] = rb[a.rowtab[LO + k]];
+            for (int k = 0; k < N; k++) g[k] = rw[(N - 1 - k) * CSTR];
+        } else {
+#pragma unroll
+            for (int k = 0; k < N; k++) g[k] = rb[a.rowtab[LO + k]];
+        }
 #pragma unroll
         for (int k = 0; k < N; k++) if (!a.code4) code[k] = ql[LO + k];
-        if (a.code4) a1_codes4<N>(a, 0, a.n + 2 - j + LO, xb, idxp, x);
+        if (a.code4) a1_codes4<N, WIN>(a, 0, a.n + 2 - j + LO, xb, idxp, x);
         else {
 #pragma unroll
             for (int k = 0; k < N; k++) x[k] = xb[idxp + code[k]];
@@ -631,9 +663,9 @@ __device__ __forceinline__ void a1_b0f(const A1& a, int i, int j, unsigned& best
         for (int k = 0; k < N; k++) { const unsigned e = ((g[k] + (unsigned)x[k]) << 10) + a.P->kb0_key[LO + k]; best = e < best ? e : best; }
     }
 }
-template <int LO, int HI>
+template <bool WIN, int LO, int HI>
 __device__ __forceinline__ void a1_b1f(const A1& a, int i, int j, unsigned& best) {
-    if constexpr (HI - LO + 1 > A1_CHUNK) { a1_b1f<LO, LO + A1_CHUNK - 1>(a, i, j, best); a1_b1f<LO + A1_CHUNK, HI>(a, i, j, best); }
+    if constexpr (HI - LO + 1 > A1_CHUNK) { a1_b1f<WIN, LO, LO + A1_CHUNK - 1>(a, i, j, best); a1_b1f<WIN, LO + A1_CHUNK, HI>(a, i, j, best); }
     else {
         constexpr int N = HI - LO + 1;
         const unsigned idxq = a.qbr[a.n + 2 - j];
@@ -642,11 +674,17 @@ __device__ __forceinline__ void a1_b1f(const A1& a, int i, int j, unsigned& best
         const unsigned char* xb = a.T->XB;
         unsigned code[N], g[N];
         int x[N];
+        if constexpr (WIN) {
+            const unsigned short* rw = rb + a1_win_row<HI>(a);
 #pragma unroll
-        for (int k = 0; k < N; k++) g[k] = rb[a.rowtab[LO + k] + (LO + k)];
+            for (int k = 0; k < N; k++) g[k] = rw[(N - 1 - k) * CSTR + (LO + k)];
+        } else {
+#pragma unroll
+            for (int k = 0; k < N; k++) g[k] = rb[a.rowtab[LO + k] + (LO + k)];
+        }
 #pragma unroll
         for (int k = 0; k < N; k++) if (!a.code4) code[k] = pl[LO + k];
-        if (a.code4) a1_codes4<N>(a, 1, i + 1 + LO, xb, idxq, x);
+        if (a.code4) a1_codes4<N, WIN>(a, 1, i + 1 + LO, xb, idxq, x);
         else {
 #pragma unroll
             for (int k = 0; k < N; k++) x[k] = xb[idxq + code[k]];
@@ -655,9 +693,9 @@ __device__ __forceinline__ void a1_b1f(const A1& a, int i, int j, unsigned& best
         for (int k = 0; k < N; k++) { const unsigned e = ((g[k] + (unsigned)x[k]) << 10) + a.P->kb1_key[LO + k]; best = e < best ? e : best; }
     }
 }
-template <int LO, int HI>
+template <bool WIN, int LO, int HI>
 __device__ __forceinline__ void a1_i0f(const A1& a, int i, int j, unsigned& best) {
-    if constexpr (HI - LO + 1 > A1_CHUNK) { a1_i0f<LO, LO + A1_CHUNK - 1>(a, i, j, best); a1_i0f<LO + A1_CHUNK, HI>(a, i, j, best); }
+    if constexpr (HI - LO + 1 > A1_CHUNK) { a1_i0f<WIN, LO, LO + A1_CHUNK - 1>(a, i, j, best); a1_i0f<WIN, LO + A1_CHUNK, HI>(a, i, j, best); }
     else {
         constexpr int N = HI - LO + 1;
         const unsigned idxp = a.pax[i + 2];
@@ -666,11 +704,17 @@ __device__ __forceinline__ void a1_i0f(const A1& a, int i, int j, unsigned& best
         const unsigned char* xb = a.T->X1;
         unsigned code[N], g[N];
         int x[N];
+        if constexpr (WIN) {
+            const unsigned short* rw = rb + a1_win_row<HI + 1>(a);
 #pragma unroll
-        for (int k = 0; k < N; k++) g[k] = rb[a.rowtab[LO + k + 1]];
+            for (int k = 0; k < N; k++) g[k] = rw[(N - 1 - k) * CSTR];
+        } else {
+#pragma unroll
+            for (int k = 0; k < N; k++) g[k] = rb[a.rowtab[LO + k + 1]];
+        }
 #pragma unroll
         for (int k = 0; k < N; k++) if (!a.code4) code[k] = ql[LO + k];
-        if (a.code4) a1_codes4<N>(a, 0, a.n + 2 - j + LO, xb, idxp, x);
+        if (a.code4) a1_codes4<N, WIN>(a, 0, a.n + 2 - j + LO, xb, idxp, x);
         else {
 #pragma unroll
             for (int k = 0; k < N; k++) x[k] = xb[idxp + code[k]];
@@ -679,9 +723,9 @@ __device__ __forceinline__ void a1_i0f(const A1& a, int i, int j, unsigned& best
         for (int k = 0; k < N; k++) { const unsigned e = ((g[k] + (unsigned)x[k]) << 10) + a.P->k1n0_key[LO + k]; best = e < best ? e : best; }
     }
 }
-template <int LO, int HI>
+template <bool WIN, int LO, int HI>
 __device__ __forceinline__ void a1_i1f(const A1& a, int i, int j, unsigned& best) {
-    if constexpr (HI - LO + 1 > A1_CHUNK) { a1_i1f<LO, LO + A1_CHUNK - 1>(a, i, j, best); a1_i1f<LO + A1_CHUNK, HI>(a, i, j, best); }
+    if constexpr (HI - LO + 1 > A1_CHUNK) { a1_i1f<WIN, LO, LO + A1_CHUNK - 1>(a, i, j, best); a1_i1f<WIN, LO + A1_CHUNK, HI>(a, i, j, best); }
     else {
         constexpr int N = HI - LO + 1;
         const unsigned idxq = a.qbr[a.n + 3 - j];
@@ -690,11 +734,17 @@ __device__ __forceinline__ void a1_i1f(const A1& a, int i, int j, unsigned& best
         const unsigned char* xb = a.T->X1;
         unsigned code[N], g[N];
         int x[N];
+        if constexpr (WIN) {
+            const unsigned short* rw = rb + a1_win_row<HI + 1>(a);
 #pragma unroll
-        for (int k = 0; k < N; k++) g[k] = rb[a.rowtab[LO + k + 1] + (LO + k)];
+            for (int k = 0; k < N; k++) g[k] = rw[(N - 1 - k) * CSTR + (LO + k)];
+        } else {
+#pragma unroll
+            for (int k = 0; k < N; k++) g[k] = rb[a.rowtab[LO + k + 1] + (LO + k)];
+        }
 #pragma unroll
         for (int k = 0; k < N; k++) if (!a.code4) code[k] = pl[LO + k];
-        if (a.code4) a1_codes4<N>(a, 1, i + 1 + LO, xb, idxq, x);
+        if (a.code4) a1_codes4<N, WIN>(a, 1, i + 1 + LO, xb, idxq, x);
         else {
 #pragma unroll
             for (int k = 0; k < N; k++) x[k] = xb[idxq + code[k]];

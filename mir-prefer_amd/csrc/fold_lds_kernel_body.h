@@ -24,8 +24,8 @@
     long long tR = 0, nR = 0, nB = 0;                   // of tB: the intervals whose interior loops are on the ramp-up (um < MAXLOOP), and the interval counts
     long long wB = 0, wA1 = 0, wA2 = 0, wW = 0, wt = 0; // per-wave: phase B, interior loops, multiloop splits, barrier wait (lane 0 of each wave)
     unsigned short* fml = (unsigned short*)(smem + LY.fml);   // biased uint16 (see FML_BIAS)
-    unsigned short* cring = (unsigned short*)(smem + LY.aux);       // [32][CSTR] G0 + 32768 as uint16, 65535 = INF
-    short* dmlring = (short*)(cring + CRING_ROWS * CSTR);           // [DMLR][LCAP] int16
+    unsigned short* cring = (unsigned short*)(smem + LY.aux);       // [32][CSTR] G0 + 32768 as uint16, 65535 = INF; then the mirror rows (LY.ring_rows in all)
+    short* dmlring = (short*)(cring + LY.ring_rows * CSTR);         // [DMLR][LCAP] int16
     int* acc = (int*)(dmlring + DMLR * LCAP);                          // ckey[3 (diagonal % 3)][LCAP], then mdec[2 (diagonal parity)][LCAP] (SPARSE: [3 (diagonal % 3)])
     constexpr int NACC = SPARSE ? 6 : 5;
     auto mdec_of = [&](int d) -> int* { return acc + (3 + (SPARSE ? d % 3 : (d & 1))) * LCAP; };
@@ -37,6 +37,12 @@
     // Two windows per CU: the first interior-loop diagonals (6 .. 35: um < MAXLOOP, not every loop size admissible yet) run the unchecked steady-state code.
     // A candidate with n1 + n2 > um reads the ring row of a diagonal < 4, which the window start has set to INF, and loses every minimum like any other
     // INF entry: no compare, no branch.  The other instantiations keep the checked forms (MIRP_RAMP_CHECKED: a timing build of this one that does, too).
+    // The same instantiation reads the ring rows of a chunk of bulge / 1xn candidates at immediate offsets (a1_win_row; MIRP_A1_WIN=0: a timing build on the row table)
+#ifndef MIRP_A1_WIN
+#define MIRP_A1_WIN 1
+#endif
+    constexpr bool A1WIN = TWO && MIRP_A1_WIN != 0;
+    static_assert(!A1WIN || LY.ring_rows == CRING_ROWS_WIN, "immediate-offset ring reads need the mirror rows");
 #ifdef MIRP_RAMP_CHECKED
     constexpr bool RAMPF = false;
 #else
@@ -157,16 +163,18 @@
             S[x] = ch == 'A' ? 1 : ch == 'C' ? 2 : ch == 'G' ? 3 : ch == 'U' ? 4 : 0;
         }
         for (int x = tid; x < DMLR * LCAP; x += NT) dmlring[x] = (short)I16_INF;
-        // RAMPF: all CRING_ROWS rows of the c ring to INF (as dwords), once per window.  During interval d < 36 the unchecked interior loops read, for a loop size
+        // RAMPF: all rows of the c ring (LY.ring_rows, the mirror rows included) to INF (as dwords), once per window.  During interval d < 36 the unchecked interior loops read, for a loop size
         // U > um = d - 6, the row (d - 2 - U) & 31 of a diagonal x = d - 2 - U in [d - 32, 3] that does not exist.  That row is the one diagonal x + 32 in
         // [d, 35] of THIS window will use, and phase B of the interval writes diagonal d - 1: the row has not been written since this initialisation, so it
-        // is INF in every column (the columns behind n included: CSTR).  Row 32 mirrors row 0 for the lanes that go ahead (not before diagonal 36), and a
+        // is INF in every column (the columns behind n included: CSTR).  The batched bulge / 1xn jobs may read that row through its mirror, row 32 + (x & 31)
+        // (a1_win_row): phase B writes a mirror row together with its primary, on the same diagonals, so it has not been written since this initialisation
+        // either.  The lanes that go ahead read one row later (not before diagonal 36), and a
         // window that ends below diagonal 35 leaves finite rows behind -- hence every row, every window.  Rows of existing diagonals (U <= um) are complete:
         // all their candidates' inner cells (p, q), q - p = x >= 4, p >= i + 1, q <= j - 1, were written by phase B of diagonal x.
         if constexpr (RAMPF) {
-            static_assert((CRING_ROWS * CSTR) % 2 == 0, "ring initialisation by dwords");
+            static_assert((LY.ring_rows * CSTR) % 2 == 0, "ring initialisation by dwords");
             unsigned* cr32 = reinterpret_cast<unsigned*>(cring);
-            for (int x = tid; x < CRING_ROWS * CSTR / 2; x += NT) cr32[x] = 0xffffffffu;
+            for (int x = tid; x < LY.ring_rows * CSTR / 2; x += NT) cr32[x] = 0xffffffffu;
         }
         for (int x = tid; x < NACC * LCAP; x += NT) acc[x] = x >= 3 * LCAP ? INF : (int)KEY_NONE;   // ckey x 3 | mdec x 2 (3)
         if (tid == 0) {
@@ -451,7 +459,7 @@
                 // Lane fill: the blocks of 64 paired cells of diagonal d are topped up with the first cells of diagonal d+1.  All candidates of
                 // a cell of d+1 except the stacked pair have their inner pair on diagonals <= d-2, which are final in this interval; the stacked
                 // pair follows one interval later (`done` cells below).  Such a lane differs only in j = i + d + 1 and in its ring rows, which
-                // are the rows after those of diagonal d (CRING_ROWS).  Only once every loop size is admissible (um = MAXLOOP for both).
+                // are the rows after those of diagonal d (hence the mirror rows, CRING_ROWS / CRING_ROWS_WIN).  Only once every loop size is admissible (um = MAXLOOP for both).
                 const bool mix = d - 2 - (TURN + 1) >= MAXLOOP && d + 1 <= D;
                 // the length of this list is known since the previous interval (a1_ncp); the first block's entries are fetched before anything
                 // else: every dependent LDS access in front of the shape code costs hundreds of cycles when the pipe is loaded
@@ -485,11 +493,12 @@
                 A1 a;
                 a.P = P; a.T = &T; a.S = S; a.cring = cring; a.pax = pax; a.qbr = qbr; a.code4 = code4; a.n = n;
                 // what a wave does once per block of 64 cells: the wave-uniform loop parameters, re-materialised per block (keeps the admissibility tests and
-                // row offsets as plain scalar compares inside the block instead of dozens of hoisted masks: SGPR spills), and the lanes' list entries
+                // row offsets as plain scalar compares inside the block instead of dozens of hoisted masks: SGPR spills), and the lanes' list entries.
+                // (A1WIN: that instantiation has no admissibility tests, and a chunk re-materialises its own row, a1_win_row: pinned here as well, 84 spilled SGPRs against 81)
 #define MIRP_A1_BLOCK()                                                                                                        \
                     {                                                                                                          \
                         int r0 = d - 2, um = d - 2 - (TURN + 1) < MAXLOOP ? d - 2 - (TURN + 1) : MAXLOOP;                      \
-                        asm volatile("" : "+s"(r0), "+s"(um));                                                                 \
+                        if (!A1WIN) asm volatile("" : "+s"(r0), "+s"(um));                                                     \
                         a.r0 = r0; a.um = um;                                                                                  \
                         a.rowtab = P->ring_rowoff[r0 & 31];                                                                    \
                     }                                                                                                          \
@@ -537,10 +546,10 @@
                     if (role < 8) {
 #define MIRP_GEN(CK)                                                                      \
     switch (role) {                                                                       \
-    case 0: res = MIRP_A1G<CK MIRP_A1WD, 30, 23>(a, i, j, mmo); if (CK) a1_i1<CK, 28, 29>(a, i, j, xi); else a1_i1f<28, 29>(a, i, j, xi); break;      \
-    case 1: res = MIRP_A1G<CK MIRP_A1WD, 29, 24>(a, i, j, mmo); if (CK) a1_i1<CK, 25, 27>(a, i, j, xi); else a1_i1f<25, 27>(a, i, j, xi); break;      \
-    case 2: res = MIRP_A1G<CK MIRP_A1WD, 28, 25>(a, i, j, mmo); if (CK) a1_i0<CK, 26, 29>(a, i, j, xi); else a1_i0f<26, 29>(a, i, j, xi); break;      \
-    case 3: res = MIRP_A1G<CK MIRP_A1WD, 27, 26>(a, i, j, mmo); if (CK) a1_b1<CK, 26, 30>(a, i, j, xb); else a1_b1f<26, 30>(a, i, j, xb); break;      \
+    case 0: res = MIRP_A1G<CK MIRP_A1WD, 30, 23>(a, i, j, mmo); if (CK) a1_i1<CK, 28, 29>(a, i, j, xi); else a1_i1f<A1WIN, 28, 29>(a, i, j, xi); break;      \
+    case 1: res = MIRP_A1G<CK MIRP_A1WD, 29, 24>(a, i, j, mmo); if (CK) a1_i1<CK, 25, 27>(a, i, j, xi); else a1_i1f<A1WIN, 25, 27>(a, i, j, xi); break;      \
+    case 2: res = MIRP_A1G<CK MIRP_A1WD, 28, 25>(a, i, j, mmo); if (CK) a1_i0<CK, 26, 29>(a, i, j, xi); else a1_i0f<A1WIN, 26, 29>(a, i, j, xi); break;      \
+    case 3: res = MIRP_A1G<CK MIRP_A1WD, 27, 26>(a, i, j, mmo); if (CK) a1_b1<CK, 26, 30>(a, i, j, xb); else a1_b1f<A1WIN, 26, 30>(a, i, j, xb); break;      \
     case 4: res = MIRP_A1G<CK MIRP_A1WD, MIRP_ROWS4>(a, i, j, mmo); break;                    \
     case 5: res = MIRP_A1G<CK MIRP_A1WD, MIRP_ROWS5>(a, i, j, mmo); break;                    \
     case 6: res = MIRP_A1G<CK MIRP_A1WD, MIRP_ROWS6>(a, i, j, mmo); break;                    \
@@ -599,12 +608,12 @@
                         unsigned bb = KEY_INF, bi = KEY_INF;
                         if (RAMPF || a.um >= MAXLOOP) {
                             switch (role) {
-                            case 8: a1_b0f<2, 18>(a, i, j, bb); break;
-                            case 9: a1_b0f<19, 30>(a, i, j, bb); a1_b1f<2, 6>(a, i, j, bb); break;
-                            case 10: a1_b1f<7, 22>(a, i, j, bb); break;
-                            case 11: a1_b1f<23, 25>(a, i, j, bb); a1_i0f<3, 15>(a, i, j, bi); break;
-                            case 12: a1_i0f<16, 25>(a, i, j, bi); a1_i1f<3, 8>(a, i, j, bi); break;
-                            default: a1_i1f<9, 24>(a, i, j, bi); break;
+                            case 8: a1_b0f<A1WIN, 2, 18>(a, i, j, bb); break;
+                            case 9: a1_b0f<A1WIN, 19, 30>(a, i, j, bb); a1_b1f<A1WIN, 2, 6>(a, i, j, bb); break;
+                            case 10: a1_b1f<A1WIN, 7, 22>(a, i, j, bb); break;
+                            case 11: a1_b1f<A1WIN, 23, 25>(a, i, j, bb); a1_i0f<A1WIN, 3, 15>(a, i, j, bi); break;
+                            case 12: a1_i0f<A1WIN, 16, 25>(a, i, j, bi); a1_i1f<A1WIN, 3, 8>(a, i, j, bi); break;
+                            default: a1_i1f<A1WIN, 9, 24>(a, i, j, bi); break;
                             }
                         } else {
                             switch (role) {
@@ -787,7 +796,12 @@
                 const unsigned short m16 = m >= INF ? (unsigned short)65535 : (unsigned short)(m + FML_BIAS);
                 const unsigned short g16 = cv < INF ? (unsigned short)(cv + mmI + 32768) : (unsigned short)65535;
                 cring[(d & 31) * CSTR + i] = g16;
+#ifdef MIRP_NO_RING_MIRROR      // (a VARIANT build without the mirror rows' store shows that tests/test_fold_ring_window_gpu.py sees the fault: wrong values only, the rows exist)
                 if ((d & 31) == 0) cring[32 * CSTR + i] = g16;
+#else
+                // the mirror rows (wave-uniform test): row 32 for the lanes that go ahead; two windows per CU: a whole chunk of rows (CRING_ROWS_WIN)
+                if ((d & 31) < LY.ring_rows - 32) cring[(32 + (d & 31)) * CSTR + i] = g16;
+#endif
                 carch[abase + 8 * d] = c16;
                 tb_out[abase + 8 * d] = (unsigned short)tb;
                 fml[od + i] = m16;
