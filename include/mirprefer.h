@@ -491,6 +491,25 @@ int mirp_align_reads_placed(mirp_ctx* ctx, const char* reads_path, const char* o
 int mirp_set_align_place_capacity(mirp_ctx* ctx, int64_t items);
 /* Batches the last mirp_align_reads_placed of this context aligned twice. */
 int64_t mirp_align_place_last_realigned(const mirp_ctx* ctx);
+/* 3' non-templated tails (DESIGN.md §12 "Tails"): a read of length L that mirp_align_reads leaves without a hit (not one suppressed by m) and with
+ * L >= min_templated + 1 is searched for hits of its 5' m bases, L - min(max_tail, L - min_templated) <= m <= L - 1, that are exact, inside one
+ * contig, free of ambiguous bases and maximal (the read base after the templated part does not continue the match).  The largest m over both
+ * strands is the read's stratum; m (the option) and k apply to its hits as they do to end-to-end hits. */
+typedef struct {
+    int32_t max_tail;                        /* 0 off, 1..8 */
+    int32_t min_templated;                   /* 12..1024 */
+    int32_t trim;                            /* 1: SEQ and QUAL of a tailed record hold the templated part only, CIGAR <m>M */
+    int32_t reserved;
+} MirpAlignTailOpts;
+/* mirp_align_reads with the tail search.  tail == NULL or max_tail 0: exactly mirp_align_reads, and tails_path is not touched.  Otherwise a tailed
+ * record reads FLAG 0|16, POS = first templated base, CIGAR <m>M<t>S on + and <t>S<m>M on -, XA:i:0 MD:Z:<m> NM:i:0 XT:Z:<the read's last t letters
+ * as sequenced>, and tails_path gets the summary of the file: a header `tail length reads depth` and one tab-separated row per tail string among the
+ * reads reported as tailed (each read once; depth = the sum of the _x<N> of their names, 1 where there is none), ordered by (length, A < C < G < T
+ * < N).  Options out of range are refused (-1) before anything is opened; on a later error both files are removed.  Out: stats =
+ * mirp_align_reads' five, where aligned includes the tailed reads and suppressed those with more than m hits in their tail stratum, then {tailed,
+ * suppressed in the tail pass}; seconds = mirp_align_reads' six, then the tail pass. */
+int mirp_align_reads_tailed(mirp_ctx* ctx, const char* reads_path, const char* out_path, const char* tails_path, const char* pg_cl, int32_t v, int32_t k,
+                            int32_t m, int32_t filter_unmapped, const MirpAlignTailOpts* tail, int64_t stats[7], double seconds[7]);
 
 /* 3' adapter and quality trimming of raw reads, the step before mirp_collapse_reads.  adapter[0 .. adapter_len) = A C G T in either
  * case (adapter_len 0..64; 0 = no adapter search); error_permille 0..999 = E in per-mille (an overlap of length l allows floor(E * l / 1000)

@@ -7,7 +7,10 @@ Every read file X (collapsed reads, ids `sample_rA_xN`) gives X.sam next to it. 
 every read file is aligned against that index in the same device context (mirp_align_reads); there is no CPU path.  What is reported is defined in
 DESIGN.md §12: only the best stratum of hits with at most -v mismatches, the first -k of them in (contig, offset, + before -) order.  With --place u|r (and --window,
 --seed) every read is reported once: a multi-mapped read goes to one of its best hits, chosen by the depth of the file's uniquely mapped reads
-around each hit or at random (§12 "Placement", ShortStack's --mmap u / r).
+around each hit or at random (§12 "Placement", ShortStack's --mmap u / r).  With --tail T (and --tail-min, --tail-trim) the reads that find no
+such hit are searched for a templated 5' part followed by 1..T non-templated 3' bases (§12 "Tails"): their records carry the clipped tail in
+XT:Z:, and X.sam.tails.tsv counts the tails of the file.  -v 0 is the natural partner of --tail: a read that aligns end to end with
+substitutions is never reported as tailed.
 
 -i cannot be served (a bowtie index cannot be read): it passes the script's checks and is then refused.  -p is accepted and ignored.  -t is
 accepted and the folder created, as the script does; no index files are written there.  Argument errors exit before a device is opened: option
@@ -42,6 +45,7 @@ READID_ERROR = ("The ID for each read in the output files has the following form
                 "use otherwise.\n")
 PLACE_M = 50            # -m where --place is given without it
 PLACE_WINDOW = 50       # --window where --place is given without it
+TAIL_MIN = 16           # --tail-min where --tail is given without it
 READID_HINT = ("Please use the provided scripts(process-reads-fasta.py, convert-mirdeep2-fasta.py, convert-readcount-file.py) to preprocess the "
                "read fasta files. Refer to the README file for more information.\n\n")
 
@@ -65,6 +69,14 @@ def make_parser():
                            "defaults to 50 (1..10000) and -k is not consulted. Default: off.")
     parser.add_option("--window", type=int, default=None, help="With --place: bases on each side of an alignment in which uniquely mapped reads count, 0..10000. Default is 50.")
     parser.add_option("--seed", type=int, default=None, help="With --place: seed of the draw, 0..2^64-1. Default is 0.")
+    parser.add_option("--tail", type=int, default=None,
+                      help="Search the reads without an alignment for a templated 5' part followed by up to <int> (1..8) non-templated 3' bases "
+                           "(uridylation, adenylation). Such a read is reported with the tail soft-clipped and named in XT:Z:, and "
+                           "<read file>.sam.tails.tsv counts the tails. Best used with -v 0. Not with --place. Default: off.")
+    parser.add_option("--tail-min", dest="tail_min", type=int, default=None,
+                      help="With --tail: the templated part has at least <int> bases, 12..1024. Default is 16.")
+    parser.add_option("--tail-trim", dest="tail_trim", action="store_true",
+                      help="With --tail: write the templated part only (SEQ, QUAL and CIGAR without the tail), for stages that take a read's length from SEQ.")
     return parser
 
 
@@ -106,6 +118,20 @@ def parse_args(argv):
             options.seed = 0
         if not 0 <= options.seed < 2 ** 64:
             parser.error("Option --seed must be between 0 and 2^64-1.")
+    if options.tail is None:
+        if options.tail_min is not None:
+            parser.error("Option --tail-min needs --tail.")
+        if options.tail_trim:
+            parser.error("Option --tail-trim needs --tail.")
+    else:
+        if options.place is not None:
+            parser.error("Options --tail and --place cannot be combined.")
+        if not 1 <= options.tail <= 8:
+            parser.error("Option --tail must be between 1 and 8.")
+        if options.tail_min is None:
+            options.tail_min = TAIL_MIN
+        if not 12 <= options.tail_min <= 1024:
+            parser.error("Option --tail-min must be between 12 and 1024.")
     if options.reference:
         for name in options.reference:
             if not os.path.exists(os.path.abspath(os.path.expanduser(name))):
@@ -183,6 +209,9 @@ def main(argv=None):
                 if options.place:
                     res = ctx.align_reads(name, outname, cl, options.allowedmismatch, options.multialignment, m, bool(options.filterunmapped),
                                           place=options.place, window=options.window, seed=options.seed)
+                elif options.tail:
+                    res = ctx.align_reads(name, outname, cl, options.allowedmismatch, options.multialignment, m, bool(options.filterunmapped),
+                                          tail=options.tail, tail_min=options.tail_min, tail_trim=bool(options.tail_trim))
                 else:
                     ctx.align_reads(name, outname, cl, options.allowedmismatch, options.multialignment, m, bool(options.filterunmapped))
             except capi.MirpError as e:
@@ -191,6 +220,9 @@ def main(argv=None):
             if options.place:
                 sys.stdout.write("Placed: %d unique, %d by density, %d at random, %d suppressed\n"
                                  % (res["unique"], res["by_density"], res["at_random"], res["suppressed"]))
+                sys.stdout.flush()
+            if options.tail:
+                sys.stdout.write("Tailed: %d reads, %d suppressed\n" % (res["tailed"], res["tail_suppressed"]))
                 sys.stdout.flush()
             outnames.append(outname)
     finally:

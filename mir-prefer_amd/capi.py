@@ -102,6 +102,11 @@ class AlignPlaceOpts(C.Structure):
     _fields_ = [("mode", C.c_int32), ("window", C.c_int32), ("seed", C.c_uint64)]
 
 
+class AlignTailOpts(C.Structure):
+    """MirpAlignTailOpts of include/mirprefer.h."""
+    _fields_ = [("max_tail", C.c_int32), ("min_templated", C.c_int32), ("trim", C.c_int32), ("reserved", C.c_int32)]
+
+
 class HomologOpts(C.Structure):
     """MirpHomologOpts of include/mirprefer.h."""
     _fields_ = [("max_mismatches", C.c_int32), ("precursor_len", C.c_int32), ("max_placements", C.c_int32), ("reserved", C.c_int32)]
@@ -484,6 +489,9 @@ def load_library():
     lib.mirp_align_reads_placed.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AlignPlaceOpts),
                                             i64p, C.POINTER(C.c_double)]
     lib.mirp_align_reads_placed.restype = C.c_int
+    lib.mirp_align_reads_tailed.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                            C.POINTER(AlignTailOpts), i64p, C.POINTER(C.c_double)]
+    lib.mirp_align_reads_tailed.restype = C.c_int
     lib.mirp_set_align_place_capacity.argtypes = [vp, C.c_int64]
     lib.mirp_set_align_place_capacity.restype = C.c_int
     lib.mirp_align_place_last_realigned.argtypes = [vp]
@@ -635,14 +643,29 @@ class Context:
         self._check(self.lib.mirp_align_index(self.h, arr, len(paths), C.byref(nc), C.byref(tot), sec), "mirp_align_index")
         return {"n_contigs": nc.value, "total": tot.value, "seconds": list(sec)}
 
-    def align_reads(self, reads_path, out_path, pg_cl="", v=0, k=20, m=0, filter_unmapped=False, place=0, window=50, seed=0):
+    def align_reads(self, reads_path, out_path, pg_cl="", v=0, k=20, m=0, filter_unmapped=False, place=0, window=50, seed=0, tail=0, tail_min=16,
+                    tail_trim=False, tails_path=None):
         """bowtie -v v --best --strata -k k [-m m] -S on one read FASTA file against the index of align_index (mirp_align_reads): writes out_path.
         m = 0: no -m.  -> {reads, aligned, unaligned, suppressed, records, seconds}; seconds = {read + parse, upload, seeds, verify, sort,
         emit + download + write}.  A large file runs in several batches on the device; align_last_batches() tells how many the last call took.
         place = "u" / "r" (or 1 / 2): one record per read, multi-mapped reads placed by the density of the file's unique reads within `window`
         bases, or at random (mirp_align_reads_placed; DESIGN.md §12 "Placement"); m must then be 1..10000 and k is not consulted.  The result has
-        unique, by_density and at_random as well, and seconds two more entries {placement, first pass}."""
+        unique, by_density and at_random as well, and seconds two more entries {placement, first pass}.
+        tail = 1..8: the reads left without a hit are searched for a templated 5' part of at least tail_min bases followed by at most `tail`
+        non-templated bases (mirp_align_reads_tailed; DESIGN.md §12 "Tails"); tail_trim: their records hold the templated part only; the
+        summary goes to tails_path (default out_path + ".tails.tsv").  The result has tailed and tail_suppressed as well, `aligned` includes
+        the tailed reads, and seconds one more entry, the tail pass.  tail = 0: exactly the call without it.  Not together with place."""
         mode = {0: 0, None: 0, "u": 1, "r": 2, 1: 1, 2: 2}[place]
+        if tail:
+            if mode:
+                raise ValueError("align_reads: tail and place cannot be combined")
+            st = (C.c_int64 * 7)()
+            sec = (C.c_double * 7)()
+            o = AlignTailOpts(int(tail), int(tail_min), int(bool(tail_trim)), 0)
+            tp = os.fsencode(out_path) + b".tails.tsv" if tails_path is None else os.fsencode(tails_path)
+            self._check(self.lib.mirp_align_reads_tailed(self.h, os.fsencode(reads_path), os.fsencode(out_path), tp, pg_cl.encode(), int(v), int(k), int(m),
+                                                         int(bool(filter_unmapped)), C.byref(o), st, sec), "mirp_align_reads_tailed")
+            return dict(zip(("reads", "aligned", "unaligned", "suppressed", "records", "tailed", "tail_suppressed"), list(st)), seconds=list(sec))
         if mode:
             st = (C.c_int64 * 8)()
             sec = (C.c_double * 8)()

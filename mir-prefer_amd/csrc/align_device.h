@@ -76,7 +76,8 @@ __device__ __forceinline__ unsigned al_oriented(const unsigned char* __restrict_
 
 struct AlSeed { long long lo; unsigned read; unsigned char strand, half, vbase, pad; int vpos; };   // vpos -1: the exact half
 
-struct AlParams { int v, e, k, m, filter, place; };   // place: 0 off, 1 by density, 2 uniform (align --place; -k is then not consulted)
+struct AlParams { int v, e, k, m, filter, place, tail_trim; };   // place: 0 off, 1 by density, 2 uniform (align --place; -k is then not consulted)
+                                                                 // tail_trim: the record of a tailed read holds its templated part only (align --tail-trim)
 
 __device__ __forceinline__ void al_half(int L, int v, int half, int* hoff, int* hlen) {
     if (v == 0) { *hoff = 0; *hlen = L; return; }

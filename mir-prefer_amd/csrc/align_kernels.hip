@@ -23,6 +23,9 @@
 //   place     (align --place) between order and emit: al_unique_kernel collects the file's unique reads over all batches; after the last batch
 //             one sort by position and two int32 scans give the 64-bit prefix of their depths; al_weight_kernel (one item per thread, two binary
 //             searches) and al_pick_kernel (one read per thread: hash, running sum) choose one item per read, which the emit step then writes.
+//   tails     (align --tail) inside the hits step, between al_status_kernel and the scan of the per-read slots: align_tail_kernels.hip searches the
+//             reads left without a hit for a templated 5' part and 1 .. T non-templated 3' bases; their items are sorted, cut and emitted with the
+//             rest, and al_record prints the tailed forms (soft clip, XT:Z:) from the per-read tail length.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstring>
@@ -180,12 +183,16 @@ struct AlText {
     const unsigned long long* cstart; int n_contigs;
     // placement (AlParams::place != 0), per read: hits in the best stratum, class 'N' / 'U' / 'R', weight of the chosen hit, sum of the weights
     const int* pn; const unsigned char* pcls; const unsigned long long* pw; const unsigned long long* pwt;
+    // tails (align --tail), per read: length of the non-templated 3' tail of its records, 0 = an end-to-end hit; null without --tail
+    const unsigned char* tt;
 };
 
 #define AL_NO_ITEM (~0ull)      // placement: a read without a record (unaligned under -f)
 
 // one SAM record: item = read << 33 | gpos << 1 | strand; best < 0: unaligned (XM:i:0, or XM:i:<M+1> when suppressed).  With P.place the record of
-// an aligned read carries NH:i:<n> XY:Z:<class> XW:Z:<w>/<Wt> after NM:i:
+// an aligned read carries NH:i:<n> XY:Z:<class> XW:Z:<w>/<Wt> after NM:i:.  A tailed read (T.tt[read] = t > 0, DESIGN.md §12 "Tails"): the item's
+// offset is that of its templated 5' part of m = L - t bases; <m>M<t>S on +, <t>S<m>M on -, MD:Z:<m>, XT:Z:<the last t letters as sequenced>; with
+// P.tail_trim SEQ and QUAL hold the templated part only and the CIGAR is <m>M
 template <bool WRITE>
 __device__ long long al_record(const AlRef& R, const AlText& T, const AlParams& P, unsigned long long item, int best, int supp, char* out) {
     TextOut<WRITE> o{out};
@@ -215,6 +222,25 @@ __device__ long long al_record(const AlRef& R, const AlText& T, const AlParams& 
     o.ch('\t');
     o.num(g - T.cstart[a] + 1);
     o.lit("\t255\t");
+    const int t = T.tt ? (int)T.tt[r] : 0;
+    if (t > 0) {
+        const int m = L - t;
+        const int first = P.tail_trim ? (strand ? t : 0) : 0, last = P.tail_trim ? first + m : L;      // the part of the oriented read in SEQ
+        if (strand && !P.tail_trim) { o.num((unsigned long long)t); o.ch('S'); }
+        o.num((unsigned long long)m);
+        o.ch('M');
+        if (!strand && !P.tail_trim) { o.num((unsigned long long)t); o.ch('S'); }
+        o.lit("\t*\t0\t0\t");
+        for (int i = first; i < last; i++) o.ch(ACGTN[al_oriented(rd, L, strand, i)]);
+        o.ch('\t');
+        for (int i = first; i < last; i++) o.ch('I');
+        o.lit("\tXA:i:0\tMD:Z:");
+        o.num((unsigned long long)m);
+        o.lit("\tNM:i:0\tXT:Z:");
+        for (int i = m; i < L; i++) o.ch(ACGTN[rd[i]]);
+        o.ch('\n');
+        return o.n;
+    }
     o.num((unsigned long long)L);
     o.lit("M\t*\t0\t0\t");
     for (int i = 0; i < L; i++) o.ch(ACGTN[al_oriented(rd, L, strand, i)]);
@@ -467,7 +493,7 @@ int mirp_device_align_index(mirp_ctx* c, const unsigned* pk, const unsigned* amb
 
 // A batch of reads runs in three steps that share the context's a_* buffers: upload, hits (seeds .. sort) and emit (size, scan, emit, download).
 // mirp_align_reads runs them back to back; the placement (mirp_align_reads_placed) runs upload + hits of every batch first, then the placing
-// and the emit.  seconds += [0] upload, [1] seeds, [2] verify, [3] sort, [4] emit.
+// and the emit.  seconds += [0] upload, [1] seeds, [2] verify, [3] sort, [4] emit, [5] the tail pass (mirp_align_reads_tailed).
 
 // Upload: codes (0..3 ACGT, 4 other) at roff[0..n], QNAMEs at qoff[0..n], depth[0..n) (placement only, or null), all on the host.
 int mirp_device_align_upload(mirp_ctx* c, const unsigned char* codes, const long long* roff, const char* qn, const long long* qoff, const unsigned* depth,
@@ -477,23 +503,26 @@ int mirp_device_align_upload(mirp_ctx* c, const unsigned char* codes, const long
     double t = mirp::now();
     const long long nb = roff[n], nq = qoff[n];
     if (c->a_codes.ensure((size_t)nb + 16) || c->a_roff.ensure(8 * (size_t)(n + 1)) || c->a_qn.ensure((size_t)nq + 16) || c->a_qoff.ensure(8 * (size_t)(n + 1)) ||
-        c->a_small.ensure(64) || (depth && c->a_depth.ensure(4 * (size_t)n)))
+        c->a_small.ensure(128) || (depth && c->a_depth.ensure(4 * (size_t)n)))
         return fail(c, -6, "device allocation failed (align: reads)");
     if (nb) HIPCHK(c, hipMemcpyAsync(c->a_codes.p, codes, (size_t)nb, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->a_roff.p, roff, 8 * (size_t)(n + 1), hipMemcpyHostToDevice, st));
     if (nq) HIPCHK(c, hipMemcpyAsync(c->a_qn.p, qn, (size_t)nq, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->a_qoff.p, qoff, 8 * (size_t)(n + 1), hipMemcpyHostToDevice, st));
     if (depth) HIPCHK(c, hipMemcpyAsync(c->a_depth.p, depth, 4 * (size_t)n, hipMemcpyHostToDevice, st));
-    // a_small: [0..2] aligned / unaligned / suppressed, [3] records, [4] overflow flag, [5..7] placed unique / by density / at random
-    HIPCHK(c, hipMemsetAsync(c->a_small.p, 0, 64, st));
+    // a_small: [0..2] aligned / unaligned / suppressed, [3] records, [4] overflow flag, [5..7] placed unique / by density / at random,
+    // [8..9] tailed / suppressed in the tail pass (both are counted in [1] as well: mirp_align.cpp moves them)
+    HIPCHK(c, hipMemsetAsync(c->a_small.p, 0, 128, st));
     HIPCHK(c, hipStreamSynchronize(st));
     seconds[0] += mirp::now() - t;
     return 0;
 }
 
 // Hits of the uploaded batch: a_items = the *n_items sorted best-stratum items (and one item per unaligned read unless filter), a_off their
-// per-read offsets, a_best / a_supp the per-read stratum and -m decision; a_small[0..2] += {aligned, unaligned, suppressed}.
-int mirp_device_align_hits(mirp_ctx* c, long long n, int v, int m, int filter, long long* n_items, double seconds[5]) {
+// per-read offsets, a_best / a_supp the per-read stratum and -m decision; a_small[0..2] += {aligned, unaligned, suppressed}.  With tail (max_tail
+// > 0) the reads left without a hit go through the tail search (align_tail_kernels.hip) between the strata and the offsets: a tailed read gets
+// best = 0, its stratum's hits as items and a_tt[read] = its tail length; seconds[5] += the tail pass.
+int mirp_device_align_hits(mirp_ctx* c, long long n, int v, int m, int filter, const MirpAlignTailOpts* tail, long long* n_items, double seconds[6]) {
     using namespace mirp;
     hipStream_t st = c->stream;
     const AlParams P{v, v / 2, 1, m, filter, 0};
@@ -547,6 +576,13 @@ int mirp_device_align_hits(mirp_ctx* c, long long n, int v, int m, int filter, l
         hipLaunchKernelGGL(al_verify_kernel<0>, dim3(gc), dim3(256), 0, st, R, d_codes, d_roff, (const AlSeed*)d_seeds, S, (const long long*)d_cscan, P, d_lvl,
                            (const int*)nullptr, (const long long*)nullptr, (unsigned*)nullptr, (unsigned long long*)nullptr);
     hipLaunchKernelGGL(al_status_kernel, dim3(g), dim3(256), 0, st, (const unsigned*)d_lvl, d_roff, n, P, d_best, d_supp, (int*)c->a_slots.p, d_small);
+    double tail_sec = 0;
+    if (tail && tail->max_tail > 0) {
+        HIPCHK(c, hipStreamSynchronize(st));             // the counts and strata above belong to the verify phase
+        const double t0 = mirp::now();
+        if (int rc = mirp_device_align_tail_strata(c, n, *tail, m)) return rc;
+        tail_sec += mirp::now() - t0;
+    }
     launch_excl_scan(st, (const int*)c->a_slots.p, d_off, n);
     long long NI = 0;
     HIPCHK(c, hipMemcpyAsync(&NI, d_off + n, 8, hipMemcpyDeviceToHost, st));
@@ -560,7 +596,13 @@ int mirp_device_align_hits(mirp_ctx* c, long long n, int v, int m, int filter, l
     hipLaunchKernelGGL(al_unaln_kernel, dim3(g), dim3(256), 0, st, (const int*)d_best, (const long long*)d_off, n, d_items);
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
-    seconds[2] += mirp::now() - t;
+    if (tail && tail->max_tail > 0) {
+        const double t0 = mirp::now();
+        if (int rc = mirp_device_align_tail_hits(c, *tail)) return rc;
+        tail_sec += mirp::now() - t0;
+        seconds[5] += tail_sec;
+    }
+    seconds[2] += mirp::now() - t - tail_sec;
 
     // ---- order: by (read, gpos, strand)
     t = mirp::now();
@@ -575,12 +617,14 @@ int mirp_device_align_hits(mirp_ctx* c, long long n, int v, int m, int filter, l
 
 // Emit + download: the records of the batch's items go to `sink` in pieces of at most 1 GiB.  place = 0: the n_items items of
 // mirp_device_align_hits, the first k of every read.  place != 0: the picks of mirp_device_place_pick, one per read, with the placement tags.
-// cnt[0..8) = a_small after the batch ({aligned, unaligned, suppressed, records, -, placed unique, by density, at random}).
-int mirp_device_align_emit(mirp_ctx* c, long long n, long long n_items, int v, int k, int m, int filter, int place,
-                           const std::function<int(const char*, size_t)>& sink, unsigned long long cnt[8], double seconds[5]) {
+// cnt[0..8) = a_small after the batch ({aligned, unaligned, suppressed, records, -, placed unique, by density, at random}).  tail: the options the
+// batch's hits were made with (null: none); the records of its tailed reads take the tailed form.
+int mirp_device_align_emit(mirp_ctx* c, long long n, long long n_items, int v, int k, int m, int filter, int place, const MirpAlignTailOpts* tail,
+                           const std::function<int(const char*, size_t)>& sink, unsigned long long cnt[8], double seconds[6]) {
     using namespace mirp;
     hipStream_t st = c->stream;
-    const AlParams P{v, v / 2, k, m, filter, place};
+    const bool tailed = tail && tail->max_tail > 0;
+    const AlParams P{v, v / 2, k, m, filter, place, tailed && tail->trim ? 1 : 0};
     const AlRef R = al_ref(c);
     unsigned long long* d_small = (unsigned long long*)c->a_small.p;
     const unsigned long long* d_items = (const unsigned long long*)(place ? c->a_pick.p : c->a_items.p);
@@ -590,7 +634,8 @@ int mirp_device_align_emit(mirp_ctx* c, long long n, long long n_items, int v, i
         return fail(c, -6, "device allocation failed (align: text offsets)");
     const AlText TX{(const unsigned char*)c->a_codes.p, (const long long*)c->a_roff.p, (const char*)c->a_qn.p, (const long long*)c->a_qoff.p,
                     (const char*)c->a_names.p, (const long long*)c->a_noff.p, (const unsigned long long*)c->a_cstart.p, c->a_n_contigs,
-                    (const int*)c->a_pn.p, (const unsigned char*)c->a_pcls.p, (const unsigned long long*)c->a_pw.p, (const unsigned long long*)c->a_pwt.p};
+                    (const int*)c->a_pn.p, (const unsigned char*)c->a_pcls.p, (const unsigned long long*)c->a_pw.p, (const unsigned long long*)c->a_pwt.p,
+                    tailed ? (const unsigned char*)c->a_tt.p : nullptr};
     const long long* d_off = (const long long*)c->a_off.p;
     const int* d_best = (const int*)c->a_best.p;
     const int* d_supp = (const int*)c->a_supp.p;

@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <unordered_set>
 #include <vector>
@@ -158,9 +159,10 @@ struct KeptBatch {
     bool kept = false;
 };
 
-// mirp_align_reads (place == nullptr) and mirp_align_reads_placed.  stats[8], seconds[8]
+// mirp_align_reads (place == nullptr, tail == nullptr), mirp_align_reads_placed and mirp_align_reads_tailed (never both).  stats[8], seconds[8];
+// with tail, stats[5..6] = {tailed, suppressed in the tail pass} and sec[6] = the tail pass
 int align_file(mirp_ctx* c, const char* reads_path, const char* out_path, const char* pg_cl, int v, int k, int m, int filter_unmapped,
-               const MirpAlignPlaceOpts* place, long long stats[8], double sec[8]) {
+               const MirpAlignPlaceOpts* place, const MirpAlignTailOpts* tail, const char* tails_path, long long stats[8], double sec[8]) {
     double t = mirp::now();
     std::string buf;
     if (int rc = mirp::read_whole(c, reads_path, buf)) return rc;
@@ -179,7 +181,7 @@ int align_file(mirp_ctx* c, const char* reads_path, const char* out_path, const 
             if (name.empty()) return fail(c, -10, std::string(reads_path) + ": a read header without a name");
             qn += name;
             qoff.push_back((long long)qn.size());
-            if (place) depth.push_back(depth_of(name.data(), name.size()));
+            if (place || tail) depth.push_back(depth_of(name.data(), name.size()));
             open = true;
             return 0;
         }
@@ -215,14 +217,14 @@ int align_file(mirp_ctx* c, const char* reads_path, const char* out_path, const 
     const size_t nbatch = cut.size() - 1;
     c->a_batches = (long long)nbatch;
     std::vector<long long> rb, qb;
-    double dsec[5] = {0, 0, 0, 0, 0};
+    double dsec[6] = {0, 0, 0, 0, 0, 0};
     auto upload = [&](size_t b) -> int {
         const long long r0 = cut[b], r1 = cut[b + 1];
         rb.assign(roff.begin() + r0, roff.begin() + r1 + 1);
         qb.assign(qoff.begin() + r0, qoff.begin() + r1 + 1);
         for (auto& x : rb) x -= roff[r0];
         for (auto& x : qb) x -= qoff[r0];
-        return mirp_device_align_upload(c, codes.data() + roff[r0], rb.data(), qn.data() + qoff[r0], qb.data(), place ? depth.data() + r0 : nullptr, r1 - r0, dsec);
+        return mirp_device_align_upload(c, codes.data() + roff[r0], rb.data(), qn.data() + qoff[r0], qb.data(), place || tail ? depth.data() + r0 : nullptr, r1 - r0, dsec);
     };
 
     // ---- placement, pass 1: the hits of every batch, the unique reads of the whole file
@@ -237,7 +239,7 @@ int align_file(mirp_ctx* c, const char* reads_path, const char* out_path, const 
         for (size_t b = 0; b < nbatch; b++) {
             const long long nb = cut[b + 1] - cut[b];
             long long NI = 0;
-            if ((rc = upload(b)) || (rc = mirp_device_align_hits(c, nb, v, m, filter_unmapped, &NI, dsec))) return rc;
+            if ((rc = upload(b)) || (rc = mirp_device_align_hits(c, nb, v, m, filter_unmapped, nullptr, &NI, dsec))) return rc;
             unsigned long long cnt[3] = {0, 0, 0};
             HIPCHK(c, hipMemcpy(cnt, c->a_small.p, sizeof cnt, hipMemcpyDeviceToHost));
             for (int i = 0; i < 3; i++) st7[i] += (long long)cnt[i];
@@ -264,7 +266,10 @@ int align_file(mirp_ctx* c, const char* reads_path, const char* out_path, const 
     }
 
     mirp::OutFile out(out_path);
+    std::unique_ptr<mirp::OutFile> tails_out(tail ? new mirp::OutFile(tails_path) : nullptr);       // both files go if either fails
     if (!out.open()) return fail(c, -8, std::string("cannot write ") + out_path);
+    if (tail && !tails_out->open()) return fail(c, -8, std::string("cannot write ") + tails_path);
+    if (tail && (rc = mirp_device_align_tail_clear(c))) return rc;
     std::string head = "@HD\tVN:1.0\tSO:unsorted\n";
     for (size_t i = 0; i < c->a_contig_names.size(); i++)
         head += "@SQ\tSN:" + c->a_contig_names[i] + "\tLN:" + std::to_string(c->a_contig_lens[i]) + "\n";
@@ -276,10 +281,19 @@ int align_file(mirp_ctx* c, const char* reads_path, const char* out_path, const 
         long long NI = 0;
         unsigned long long cnt[8];
         if (!place) {
-            if ((rc = upload(b)) || (rc = mirp_device_align_hits(c, nb, v, m, filter_unmapped, &NI, dsec)) ||
-                (rc = mirp_device_align_emit(c, nb, NI, v, k, m, filter_unmapped, 0, sink, cnt, dsec)))
+            if ((rc = upload(b)) || (rc = mirp_device_align_hits(c, nb, v, m, filter_unmapped, tail, &NI, dsec)) ||
+                (rc = mirp_device_align_emit(c, nb, NI, v, k, m, filter_unmapped, 0, tail, sink, cnt, dsec)))
                 break;
             for (int i = 0; i < 4; i++) st7[i] += (long long)cnt[i];
+            if (tail) {             // the end-to-end pass counted these reads as unaligned
+                unsigned long long tl[2] = {0, 0};
+                HIPCHK(c, hipMemcpy(tl, (const unsigned long long*)c->a_small.p + 8, sizeof tl, hipMemcpyDeviceToHost));
+                st7[0] += (long long)tl[0];
+                st7[1] -= (long long)(tl[0] + tl[1]);
+                st7[2] += (long long)tl[1];
+                st7[4] += (long long)tl[0];
+                st7[5] += (long long)tl[1];
+            }
             continue;
         }
         // ---- placement, pass 2: the batch's hits again (resident, or aligned a second time), the weights, the picks, one record per read
@@ -288,7 +302,7 @@ int align_file(mirp_ctx* c, const char* reads_path, const char* out_path, const 
             if (kept[b].kept) {
                 swap_buf(kept[b].items, c->a_items); swap_buf(kept[b].off, c->a_off); swap_buf(kept[b].best, c->a_best); swap_buf(kept[b].supp, c->a_supp);
                 NI = kept[b].n_items;
-            } else if ((rc = mirp_device_align_hits(c, nb, v, m, filter_unmapped, &NI, dsec))) {
+            } else if ((rc = mirp_device_align_hits(c, nb, v, m, filter_unmapped, nullptr, &NI, dsec))) {
                 break;
             }
         } else {
@@ -297,13 +311,23 @@ int align_file(mirp_ctx* c, const char* reads_path, const char* out_path, const 
         t = mirp::now();
         if ((rc = mirp_device_place_pick(c, nb, NI, place->mode, place->window, place->seed, n_unique))) break;
         sec[6] += mirp::now() - t;
-        if ((rc = mirp_device_align_emit(c, nb, NI, v, k, m, filter_unmapped, place->mode, sink, cnt, dsec))) break;
+        if ((rc = mirp_device_align_emit(c, nb, NI, v, k, m, filter_unmapped, place->mode, nullptr, sink, cnt, dsec))) break;
         st7[3] += (long long)cnt[3];
         for (int i = 0; i < 3; i++) st7[4 + i] += (long long)cnt[5 + i];
     }
     if (rc) return rc;
+    if (tail) {                     // the summary of the whole file: one row per tail string among its tailed reads
+        std::vector<MirpTailRow> rows;
+        if ((rc = mirp_device_align_tail_rows(c, rows))) return rc;
+        std::string text = "tail\tlength\treads\tdepth\n";
+        for (const MirpTailRow& r : rows)
+            text += r.tail + "\t" + std::to_string(r.tail.size()) + "\t" + std::to_string(r.reads) + "\t" + std::to_string(r.depth) + "\n";
+        if (!tails_out->write(text.data(), text.size())) return fail(c, -8, std::string("cannot write ") + tails_path);
+    }
     if (!out.commit()) return fail(c, -8, std::string("cannot write ") + out_path);
+    if (tail && !tails_out->commit()) { out.discard(); return fail(c, -8, std::string("cannot write ") + tails_path); }
     for (int i = 0; i < 5; i++) sec[1 + i] = dsec[i];
+    if (tail) sec[6] = dsec[5];
     stats[0] = n;
     for (int i = 0; i < 7; i++) stats[1 + i] = st7[i];
     return 0;
@@ -323,7 +347,7 @@ extern "C" int mirp_align_reads(mirp_ctx* c, const char* reads_path, const char*
     HIPCHK(c, hipSetDevice(c->device));
     long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     double sec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (int rc = align_file(c, reads_path, out_path, pg_cl, v, k, m, filter_unmapped, nullptr, st, sec)) return rc;
+    if (int rc = align_file(c, reads_path, out_path, pg_cl, v, k, m, filter_unmapped, nullptr, nullptr, nullptr, st, sec)) return rc;
     if (stats) for (int i = 0; i < 5; i++) stats[i] = st[i];
     if (seconds) std::memcpy(seconds, sec, 6 * sizeof(double));
     return 0;
@@ -345,9 +369,31 @@ extern "C" int mirp_align_reads_placed(mirp_ctx* c, const char* reads_path, cons
     HIPCHK(c, hipSetDevice(c->device));
     long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     double sec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (int rc = align_file(c, reads_path, out_path, pg_cl, v, k, m, filter_unmapped, on ? place : nullptr, st, sec)) return rc;
+    if (int rc = align_file(c, reads_path, out_path, pg_cl, v, k, m, filter_unmapped, on ? place : nullptr, nullptr, nullptr, st, sec)) return rc;
     if (stats) for (int i = 0; i < 8; i++) stats[i] = st[i];
     if (seconds) std::memcpy(seconds, sec, sizeof sec);
+    return 0;
+}
+
+// mirp_align_reads with the search for 3' non-templated tails among the reads it leaves without a hit (DESIGN.md §12 "Tails").  tail == NULL or
+// max_tail 0: exactly mirp_align_reads, and tails_path is not touched.  stats = mirp_align_reads' five (aligned includes the tailed reads, suppressed
+// those suppressed in the tail pass), then {tailed, suppressed in the tail pass}; seconds = mirp_align_reads' six, then the tail pass.
+extern "C" int mirp_align_reads_tailed(mirp_ctx* c, const char* reads_path, const char* out_path, const char* tails_path, const char* pg_cl, int32_t v,
+                                       int32_t k, int32_t m, int32_t filter_unmapped, const MirpAlignTailOpts* tail, int64_t stats[7], double seconds[7]) {
+    if (!c) return -1;
+    c->text_pieces = 0;
+    const bool on = tail && tail->max_tail != 0;
+    if (!reads_path || !out_path || !pg_cl || v < 0 || v > 3 || k < 1 || m < 0) return fail(c, -1, "mirp_align_reads_tailed: bad argument");
+    if (on && (!tails_path || tail->max_tail < 1 || tail->max_tail > 8 || tail->min_templated < 12 || tail->min_templated > 1024 || tail->trim < 0 ||
+               tail->trim > 1))
+        return fail(c, -1, "mirp_align_reads_tailed: bad tail argument (max_tail 0..8, min_templated 12..1024, trim 0..1, a path for the summary)");
+    if (!c->a_ready) return fail(c, -1, "mirp_align_reads: no index (mirp_align_index first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double sec[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (int rc = align_file(c, reads_path, out_path, pg_cl, v, k, m, filter_unmapped, nullptr, on ? tail : nullptr, tails_path, st, sec)) return rc;
+    if (stats) for (int i = 0; i < 7; i++) stats[i] = st[i];
+    if (seconds) std::memcpy(seconds, sec, 7 * sizeof(double));
     return 0;
 }
 

@@ -126,6 +126,10 @@ struct mirp_ctx {
     // placement (mirp_align_reads_placed): the reads' depths, the unique list of the file (gpos << 32 | depth), its sorted positions and depth
     // prefix, the weights of a batch's items and the per-read picks and tag fields
     DevBuf a_depth, a_ulist, a_utmp, a_upos, a_ulo, a_uhi, a_uls, a_uhs, a_upre, a_w, a_pick, a_pn, a_pcls, a_pw, a_pwt;
+    // tails (mirp_align_reads_tailed, align_tail_kernels.hip): the batch's reads without a hit, their seeds' SA ranges and candidate scan, the hit
+    // counts per tail length, the per-read tail length, and the file's summary table ((reads, depth) per tail string, resident over its batches)
+    DevBuf a_tlist, a_tslo, a_tccnt, a_tcscan, a_tlvl, a_tt, a_thist;
+    long long a_tail_nq = 0, a_tail_tc = 0;   // searched reads and candidates of the batch whose hits are being made
     long long a_place_cap = 0;        // items of pass 1 kept resident for pass 2; 0 = the default, 2^28 (mirp_set_align_place_capacity)
     long long a_place_realigned = 0;  // batches the last mirp_align_reads_placed aligned twice (mirp_align_place_last_realigned)
     std::vector<char> h_text;        // one piece (<= text_piece_bytes()) of the SAM text on its way to the file
@@ -232,9 +236,17 @@ int mirp_device_align_index(mirp_ctx* c, const unsigned* pk, const unsigned* amb
 // the three steps of a batch, and the placement of multi-mapped reads between hits and emit (mirp_align_reads_placed)
 int mirp_device_align_upload(mirp_ctx* c, const unsigned char* codes, const long long* roff, const char* qn, const long long* qoff, const unsigned* depth,
                              long long n, double seconds[5]);
-int mirp_device_align_hits(mirp_ctx* c, long long n, int v, int m, int filter, long long* n_items, double seconds[5]);
-int mirp_device_align_emit(mirp_ctx* c, long long n, long long n_items, int v, int k, int m, int filter, int place,
-                           const std::function<int(const char*, size_t)>& sink, unsigned long long cnt[8], double seconds[5]);
+int mirp_device_align_hits(mirp_ctx* c, long long n, int v, int m, int filter, const MirpAlignTailOpts* tail, long long* n_items, double seconds[6]);
+int mirp_device_align_emit(mirp_ctx* c, long long n, long long n_items, int v, int k, int m, int filter, int place, const MirpAlignTailOpts* tail,
+                           const std::function<int(const char*, size_t)>& sink, unsigned long long cnt[8], double seconds[6]);
+// align_tail_kernels.hip: the 3' tails of the reads a batch left without a hit (mirp_align_reads_tailed), called from mirp_device_align_hits after
+// the strata (counts, stratum, -m, slots, a_tt, the file's summary table) and after the items are allocated (the stratum's hits as items)
+int mirp_device_align_tail_strata(mirp_ctx* c, long long n, const MirpAlignTailOpts& o, int m);
+int mirp_device_align_tail_hits(mirp_ctx* c, const MirpAlignTailOpts& o);
+// the summary table of a file: cleared before its first batch; after its last, rows = (tail letters, reads, depth) in (length, A < C < G < T < N) order
+struct MirpTailRow { std::string tail; unsigned long long reads, depth; };
+int mirp_device_align_tail_clear(mirp_ctx* c);
+int mirp_device_align_tail_rows(mirp_ctx* c, std::vector<MirpTailRow>& rows);
 int mirp_device_place_unique(mirp_ctx* c, long long n, long long* n_unique);
 int mirp_device_place_prepare(mirp_ctx* c, long long n_unique, unsigned long long* depth_sum);
 int mirp_device_place_pick(mirp_ctx* c, long long n, long long n_items, int mode, int window, unsigned long long seed, long long n_unique);
