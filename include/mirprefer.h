@@ -763,6 +763,9 @@ int mirp_unpaired_batch(mirp_ctx* ctx, const char* blob, const int64_t* off, con
 int mirp_set_unpaired_capacity(mirp_ctx* ctx, int64_t windows);
 /* stats = {windows, passes, cells (i < j pairs of positions, summed over the windows)} of the last mirp_unpaired_batch. */
 int mirp_unpaired_last_stats(mirp_ctx* ctx, int64_t stats[3]);
+/* The longest window whose tables mirp_unpaired_batch keeps in LDS; a longer one has them in device memory.  A constant of the build, for tests
+ * of the lengths around it: no result depends on where the tables lie. */
+int mirp_unpaired_lds_longest(void);
 /* The flanks of the windows of mirp_target_scan's accessibility column: `up` bases towards the 5' end of the target strand and `down` towards
  * its 3' end (defaults 17 and 13).  Each >= 0, up + down <= 95 (a window never exceeds 33 + 95 = 128 nt); anything else is refused with -1. */
 int mirp_set_target_flanks(mirp_ctx* ctx, int32_t up, int32_t down);
@@ -834,6 +837,13 @@ int mirp_set_homolog_capacity(mirp_ctx* ctx, int64_t keys, int64_t chunk, int32_
  * passing structure whose structure of lowest normalised energy has get_maturestar_info code k = 1..12, and at 23 those whose structure list is
  * empty} of the last mirp_homolog_scan; seconds = {scan, windows, fold, evaluation + download, merge}. */
 int mirp_homolog_last_stats(mirp_ctx* ctx, int64_t stats[24], double seconds[5]);
+
+/* How many jobs a resident slot served, for the kernels whose workgroups (or waves) keep a private slab and serve several jobs in turn.  family:
+ * 0 = the two-strand fold (a wave; mirp_duplex_batch, mirp_target_scan with energy), 1 = the accessibility kernel (a workgroup;
+ * mirp_unpaired_batch, mirp_target_scan with accessibility), 2 = the scoring kernel of mirp_hairpin_align (queries per workgroup row), 3 = the
+ * evaluation kernel of mirp_homolog_scan (a workgroup).  out = {launches of that kernel, the largest ceil(jobs / slots) over them} of the last
+ * of the named calls; each of them resets its families when it starts.  A record for tests: nothing reads it.  Another family is refused (-1). */
+int mirp_last_jobs_per_slot(mirp_ctx* ctx, int32_t family, int64_t out[2]);
 
 #ifdef __cplusplus
 }

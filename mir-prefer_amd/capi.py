@@ -529,6 +529,8 @@ def load_library():
     lib.mirp_set_unpaired_capacity.restype = C.c_int
     lib.mirp_unpaired_last_stats.argtypes = [vp, i64p]
     lib.mirp_unpaired_last_stats.restype = C.c_int
+    lib.mirp_unpaired_lds_longest.argtypes = []
+    lib.mirp_unpaired_lds_longest.restype = C.c_int
     lib.mirp_hairpin_align.argtypes = [vp, C.c_char_p, i64p, C.c_int32, C.c_char_p, i64p, C.c_int32, C.POINTER(HairpinOpts), C.POINTER(vp), i64p, C.POINTER(vp),
                                        C.POINTER(vp)]
     lib.mirp_hairpin_align.restype = C.c_int
@@ -544,6 +546,8 @@ def load_library():
     lib.mirp_set_homolog_capacity.restype = C.c_int
     lib.mirp_homolog_last_stats.argtypes = [vp, i64p, C.POINTER(C.c_double)]
     lib.mirp_homolog_last_stats.restype = C.c_int
+    lib.mirp_last_jobs_per_slot.argtypes = [vp, C.c_int32, i64p]
+    lib.mirp_last_jobs_per_slot.restype = C.c_int
     lib.mirp_set_target_flanks.argtypes = [vp, C.c_int32, C.c_int32]
     lib.mirp_set_target_flanks.restype = C.c_int
     lib.mirp_set_target_capacity.argtypes = [vp, C.c_int64]
@@ -910,6 +914,10 @@ class Context:
         self._check(self.lib.mirp_unpaired_last_stats(self.h, st), "mirp_unpaired_last_stats")
         return dict(zip(UNPAIRED_STATS, list(st)))
 
+    def unpaired_lds_longest(self):
+        """The longest window whose tables unpaired_batch keeps in LDS (mirp_unpaired_lds_longest); longer ones have them in device memory."""
+        return int(self.lib.mirp_unpaired_lds_longest())
+
     def hairpin_align(self, queries, known, match=2, mismatch=3, gap_open=5, gap_extend=2, min_score=60, max_lines=0, capacity=0):
         """Gapped local alignment of every query with every known sequence (mirp_hairpin_align): queries, known (lists of str /
         bytes, 1..3000 nt, A C G U/T in either case, anything else mismatches everything).  capacity: device bytes per pass (0 = the default),
@@ -995,6 +1003,14 @@ class Context:
         sec = (C.c_double * 5)()
         self._check(self.lib.mirp_homolog_last_stats(self.h, st, sec), "mirp_homolog_last_stats")
         return dict(zip(HOMOLOG_STATS, list(st)[:9]), fail_codes=[0] + list(st)[11:23], no_structure=int(st[23]), seconds=list(sec))
+
+    def last_jobs_per_slot(self, family):
+        """(launches, the largest ceil(jobs / slots) over them) of a wave-per-job kernel family in the last call that can launch it
+        (mirp_last_jobs_per_slot): family 0 = two-strand fold (duplex_batch, target_scan), 1 = accessibility (unpaired_batch, target_scan),
+        2 = hairpin scoring (hairpin_align; the largest chunk of queries), 3 = homolog evaluation (homolog_scan)."""
+        out = (C.c_int64 * 2)()
+        self._check(self.lib.mirp_last_jobs_per_slot(self.h, int(family), out), "mirp_last_jobs_per_slot")
+        return int(out[0]), int(out[1])
 
     def phase_scan(self, length, cycles, kmin, min_phased=3, min_depth=1):
         """Phased siRNA windows on this context's resident alignments (mirp_phase_scan).  kmin: the int32 table of the smallest

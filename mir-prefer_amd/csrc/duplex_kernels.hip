@@ -220,6 +220,7 @@ int dx_launch(mirp_ctx* c, const SRC& src, long long n, int rows, int stride, in
     }
     const long long blocks = (n + DX_WAVES - 1) / DX_WAVES;
     const long long most = (long long)c->n_cu * 8 * 4;          // a few blocks per resident slot: the jobs differ in length
+    c->note_jobs_per_slot(0, n, std::min(blocks, most) * DX_WAVES);
     hipLaunchKernelGGL((duplex_kernel<SRC>), dim3((unsigned)std::min(blocks, most)), dim3(64 * DX_WAVES), lds, c->stream, src, n,
                        (const FoldParams*)c->d_params, rows, stride, d_mfe, d_ma, d_mb, d_evals);
     HIPCHK(c, hipGetLastError());

@@ -329,6 +329,7 @@ int mirp_device_hairpin(mirp_ctx* c, const HpSeqs& Q, const HpSeqs& K, const Mir
         if (c->hp_res.ensure(8 * (size_t)(m * nk)) || c->hp_carry.ensure(8 * (size_t)(gy * carry_stride)))
             return fail(c, -6, "mirp_hairpin_align: device allocation failed (a scoring pass)");
         unsigned* carry = (unsigned*)c->hp_carry.p;
+        c->note_jobs_per_slot(2, chunk, 1);          // a blockIdx.y serves `chunk` queries in turn
         hipLaunchKernelGGL(hp_score_kernel, dim3((unsigned)n_waves, (unsigned)gy), dim3(64), 0, st, (const unsigned*)c->hp_kw.p, (const HpWave*)c->hp_waves.p,
                            (const int*)c->hp_korig.p, (const unsigned char*)c->hp_q.p, (const long long*)c->hp_qat.p, (const int*)c->hp_qlen.p, qa, qa + m, chunk, S,
                            o.min_score, carry, carry + gy * carry_stride, carry_stride, nk, (unsigned long long*)c->hp_res.p, (unsigned*)c->hp_cnt.p);

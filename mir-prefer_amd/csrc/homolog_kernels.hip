@@ -587,6 +587,7 @@ int mirp_device_homolog_eval(mirp_ctx* c, const unsigned long long* keys, long l
             gtext = (unsigned*)T.get(per * (size_t)grid + 16);
             if (!gtext) return fail(c, -6, "device allocation failed (homologs: staged text)");
         }
+        c->note_jobs_per_slot(3, n_iter, grid);
         if (lds > 64 * 1024) HIPCHK(c, hipFuncSetAttribute((const void*)homolog_eval_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(homolog_eval_kernel, dim3(grid), dim3(64), lds, st, (const HmWin*)d_win, ni, (const MirpFoldLine*)c->blines.p, (const char*)c->bss.p, stride,
                            max_lines, (const int*)c->bnlines.p, 55, (HmEval*)c->hm_eval.p, (char*)c->hm_ss.p, round ? (const int*)c->hm_sel.p : (const int*)nullptr,

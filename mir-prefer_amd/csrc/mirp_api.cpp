@@ -67,6 +67,15 @@ extern "C" int mirp_set_text_piece(mirp_ctx* c, int64_t bytes) {
 
 extern "C" int64_t mirp_text_pieces_last(const mirp_ctx* c) { return c ? c->text_pieces : -1; }
 
+// Launches and the largest jobs per resident slot of a wave-per-job kernel family in the last call that launches it (mirp_ctx::jobs_per_slot)
+extern "C" int mirp_last_jobs_per_slot(mirp_ctx* c, int32_t family, int64_t out[2]) {
+    if (!c) return -1;
+    if (family < 0 || family > 3 || !out) return fail(c, -1, "mirp_last_jobs_per_slot: bad argument");
+    out[0] = c->jobs_per_slot[family][0];
+    out[1] = c->jobs_per_slot[family][1];
+    return 0;
+}
+
 extern "C" int mirp_set_fold_model(mirp_ctx* c, int32_t model) {
     if (!c) return -1;
     if (model != MIRP_FOLD_MODEL_VIENNA_212 && model != MIRP_FOLD_MODEL_VIENNA_185) return fail(c, -1, "mirp_set_fold_model: unknown model");

@@ -45,6 +45,7 @@ extern "C" int mirp_duplex_last_stats(mirp_ctx* c, int64_t stats[3]) {
 extern "C" int mirp_duplex_batch(mirp_ctx* c, const char* a_blob, const int64_t* a_off, const char* b_blob, const int64_t* b_off, int32_t n, MirpDuplexRec* recs,
                                  char* structures) {
     if (!c) return -1;
+    c->reset_jobs_per_slot(0);
     if (n < 0 || (n > 0 && (!a_blob || !a_off || !b_blob || !b_off || !recs))) return fail(c, -1, "mirp_duplex_batch: bad argument");
     char msg[160];
     for (int q = 0; q < n; q++)

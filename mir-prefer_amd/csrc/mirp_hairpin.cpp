@@ -82,6 +82,7 @@ extern "C" int mirp_hairpin_last_stats(mirp_ctx* c, int64_t stats[8], double sec
 extern "C" int mirp_hairpin_align(mirp_ctx* c, const char* q_blob, const int64_t* q_off, int32_t n_q, const char* k_blob, const int64_t* k_off, int32_t n_k,
                                   const MirpHairpinOpts* o, MirpHairpinHit** hits, int64_t* n_hits, char** ops, int64_t** ops_off) {
     if (!c) return -1;
+    c->reset_jobs_per_slot(2);
     if (n_q < 0 || n_k < 0 || !o || !hits || !n_hits || !ops || !ops_off || (n_q > 0 && (!q_blob || !q_off)) || (n_k > 0 && (!k_blob || !k_off)))
         return fail(c, -1, "mirp_hairpin_align: bad argument");
     *hits = nullptr; *n_hits = 0; *ops = nullptr; *ops_off = nullptr;

@@ -61,6 +61,7 @@ extern "C" int mirp_homolog_contigs(mirp_ctx* c, char** names, int64_t* names_by
 extern "C" int mirp_homolog_scan(mirp_ctx* c, const char* q_blob, const int64_t* q_off, int32_t n_q, const MirpHomologOpts* o, MirpHomologRec** recs,
                                  int64_t* n_recs, char** text, int32_t** also) {
     if (!c) return -1;
+    c->reset_jobs_per_slot(3);
     if (n_q < 0 || !o || !recs || !n_recs || !text || !also || (n_q > 0 && (!q_blob || !q_off))) return fail(c, -1, "mirp_homolog_scan: bad argument");
     *recs = nullptr; *n_recs = 0; *text = nullptr; *also = nullptr;
     for (int i = 0; i < 24; i++) c->hm_stats[i] = 0;          // a refused call leaves no statistics of an earlier one

@@ -127,6 +127,8 @@ extern "C" int mirp_target_scan(mirp_ctx* c, const char* mirna_path, const char*
                                 const char* out_path, int64_t stats[6], double seconds[5]) {
     if (!c) return -1;
     c->text_pieces = 0;
+    c->reset_jobs_per_slot(0);
+    c->reset_jobs_per_slot(1);
     if (!mirna_path || !target_paths || n_targets < 1 || !o || !out_path) return fail(c, -1, "mirp_target_scan: bad argument");
     if (o->max_half_score < 0 || o->max_half_score > 16 || o->max_sites < 0 || (o->energy != 0 && o->energy != 1) ||
         (o->accessibility != 0 && o->accessibility != 1))

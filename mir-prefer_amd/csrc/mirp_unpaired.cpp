@@ -50,6 +50,7 @@ extern "C" int mirp_set_target_flanks(mirp_ctx* c, int32_t up, int32_t down) {
 
 extern "C" int mirp_unpaired_batch(mirp_ctx* c, const char* blob, const int64_t* off, const int32_t* lo, const int32_t* hi, int32_t n, MirpUnpairedRec* recs) {
     if (!c) return -1;
+    c->reset_jobs_per_slot(1);
     if (n < 0 || (n > 0 && (!blob || !off || !lo || !hi || !recs))) return fail(c, -1, "mirp_unpaired_batch: bad argument");
     char msg[160];
     long long cells = 0;

@@ -261,11 +261,13 @@ int up_launch(mirp_ctx* c, const SRC& src, long long n, int n_max, MirpUnpairedR
             lds_set = fixed + slab;
         }
         const long long resident = (long long)c->n_cu * std::min<long long>(32, (160 * 1024) / (long long)(fixed + slab));
+        c->note_jobs_per_slot(1, n, std::min(n, 2 * resident));
         hipLaunchKernelGGL((unpaired_kernel<SRC, true>), dim3((unsigned)std::min(n, 2 * resident)), dim3(64), fixed + slab, c->stream, src, n,
                            (const FoldParams*)c->d_params, n_max, stride, cells, (UpCell*)nullptr, d_out, d_milli);
     } else {
         const long long blocks = std::min<long long>(n, (long long)c->n_cu * 4);          // as many wave-private slabs
         if (c->up_slab.ensure(slab * (size_t)blocks)) return fail(c, -6, "unpaired: device allocation failed (the slabs)");
+        c->note_jobs_per_slot(1, n, blocks);
         hipLaunchKernelGGL((unpaired_kernel<SRC, false>), dim3((unsigned)blocks), dim3(64), fixed, c->stream, src, n, (const FoldParams*)c->d_params, n_max,
                            stride, cells, (UpCell*)c->up_slab.p, d_out, d_milli);
     }
@@ -281,6 +283,9 @@ int mirp_unpaired_class(int n) {
     const int up8 = (n + 7) / 8 * 8;
     return n <= up_lds_longest() && up8 > up_lds_longest() ? up_lds_longest() : up8;
 }
+
+// the longest window whose slab lies in LDS (for tests of the lengths around the hand-over to device memory)
+extern "C" int mirp_unpaired_lds_longest(void) { return up_lds_longest(); }
 
 int mirp_device_unpaired_batch(mirp_ctx* c, const unsigned char* d_codes, const long long* d_offs, const int* d_lo, const int* d_hi, const int* d_order,
                                long long n, int n_max, MirpUnpairedRec* d_recs) {
