@@ -276,6 +276,22 @@ int mirp_last_fold_overlap_chunks(mirp_ctx* ctx);
  * fold's ring of three holds max(1, N / 3).  Every output, mirp_last_fold_dense and mirp_last_fold_fallbacks are identical whatever is set; lowered
  * only to test the sub-batch path and small ring slots.  A negative value returns -1. */
 int mirp_set_fold_capacity(mirp_ctx* ctx, int64_t windows);
+/* Fold dedup (mirp_fold only): a window whose bytes repeat an earlier window of the list is not folded; it gets that window's n_lines, mfe, status,
+ * structure lines and text.  The candidate stage writes the left window of a short two-strand locus twice (MP:1184-1192), and repeats of the genome
+ * give equal windows at other coordinates.  Raw bytes are compared (no case or T/U folding: a soft-masked copy is folded on its own), after a 64-bit
+ * hash picks the candidate: a hash collision can leave a duplicate unmerged, never merge different windows.  on = 1 (default) / 0: every window is
+ * folded, exactly as before.  Every output, mirp_last_fold_fallbacks, mirp_last_fold_dense and mirp_last_fold_overflow are identical either way (a
+ * duplicate counts as its representative does).  mirp_fold_batch, mirp_ensemble, mirp_randfold and mirp_homolog_scan fold every sequence they are
+ * given. */
+int mirp_set_fold_dedup(mirp_ctx* ctx, int32_t on);
+/* Duplicates the last mirp_fold skipped (0 with dedup off). */
+int64_t mirp_last_fold_duplicates(mirp_ctx* ctx);
+/* The map of the last mirp_fold: dup_of[w] = the lowest window index r < w with the same length and bytes as window w if w was skipped, else -1
+ * (all -1 with dedup off).  The same on every run.  Free with mirp_free. */
+int mirp_get_fold_duplicates(mirp_ctx* ctx, int32_t** dup_of, int64_t* n_windows);
+/* For tests: the number of low bits of the dedup hash that count (0 = the default, all 64).  With a few bits different windows collide
+ * everywhere: outputs stay identical, some duplicates are no longer found. */
+int mirp_set_fold_dedup_hash_bits(mirp_ctx* ctx, int32_t bits);
 
 /* Device time of the kernels of the last mirp_fold, HIP events: two numbers whose sum is the device time of the fold's main pass.  Serial path:
  * ms[0] = fill kernel(s) (fold_lds_kernel: the dynamic program), ms[1] = epilogue kernel(s) (exterior sweep, enumeration, backtracks), summed

@@ -446,6 +446,14 @@ def load_library():
     lib.mirp_last_fold_overlap_chunks.restype = C.c_int
     lib.mirp_last_fold_dense.argtypes = [vp]
     lib.mirp_last_fold_dense.restype = C.c_int64
+    lib.mirp_set_fold_dedup.argtypes = [vp, C.c_int32]
+    lib.mirp_set_fold_dedup.restype = C.c_int
+    lib.mirp_set_fold_dedup_hash_bits.argtypes = [vp, C.c_int32]
+    lib.mirp_set_fold_dedup_hash_bits.restype = C.c_int
+    lib.mirp_last_fold_duplicates.argtypes = [vp]
+    lib.mirp_last_fold_duplicates.restype = C.c_int64
+    lib.mirp_get_fold_duplicates.argtypes = [vp, C.POINTER(vp), i64p]
+    lib.mirp_get_fold_duplicates.restype = C.c_int
     lib.mirp_write_fold_text.argtypes = [vp, C.c_char_p, C.c_char_p]
     lib.mirp_write_fold_text.restype = C.c_int
     lib.mirp_write_fold_text_async.argtypes = [vp, C.c_char_p, C.c_char_p]
@@ -1458,6 +1466,25 @@ class Context:
 
     def last_fold_dense(self):
         return int(self.lib.mirp_last_fold_dense(self.h))
+
+    def set_fold_dedup(self, on):
+        """True (default): fold() folds each distinct window sequence once and copies the result to its duplicates; False: every window is folded.
+        Same results and counters either way."""
+        self._check(self.lib.mirp_set_fold_dedup(self.h, 1 if on else 0), "mirp_set_fold_dedup")
+
+    def set_fold_dedup_hash_bits(self, bits):
+        """For tests: low bits of the dedup hash that count (0 = all 64); with a few bits different windows collide everywhere."""
+        self._check(self.lib.mirp_set_fold_dedup_hash_bits(self.h, int(bits)), "mirp_set_fold_dedup_hash_bits")
+
+    def last_fold_duplicates(self):
+        """Windows the last fold() skipped as duplicates of an earlier window."""
+        return int(self.lib.mirp_last_fold_duplicates(self.h))
+
+    def get_fold_duplicates(self):
+        """int32 [n_windows]: the lowest earlier window with the same bytes for every window the last fold() skipped, -1 for the others."""
+        d, n = C.c_void_p(), C.c_int64()
+        self._check(self.lib.mirp_get_fold_duplicates(self.h, C.byref(d), C.byref(n)), "mirp_get_fold_duplicates")
+        return _copy_out(self.lib, d, np.int32, n.value)
 
     def set_coverage_path(self, mode):
         """-1: by record density (default), 0: atomic scatter, 1: fused scan where the input allows it."""

@@ -93,6 +93,15 @@ struct mirp_ctx {
     hipStream_t stream_fill2 = nullptr;  // the fills of the odd chunks (tail-free schedule); created on the first fold that needs it
     int last_overlap_chunks = 0;         // chunks of the last mirp_run_fold (0: serial path)
     long long fold_cap = 0;              // windows whose slabs are resident at once; 0 = the default, 8 GiB of slabs (mirp_set_fold_capacity)
+    // ---- fold dedup (mirp_fold, fold_dedup_kernels.hip): a window that repeats an earlier one byte for byte is not folded, it gets that window's results
+    int fold_dedup = 1;                  // mirp_set_fold_dedup: 0 = every window is folded
+    int fold_dedup_bits = 0;             // mirp_set_fold_dedup_hash_bits: bits of the hash that count, 0 = all 64 (lowered only to test collisions)
+    DevBuf dd;                           // FoldDedupLayout of the last mirp_fold
+    long long dd_windows = -1;           // windows of the map in `dd`, -1 = the last mirp_fold looked for no duplicates
+    long long last_duplicates = 0;       // duplicates the last mirp_fold skipped
+    // what mirp_fold hands mirp_run_fold for one call (other callers leave n_dup null: nothing is counted, nothing more is launched), and what it
+    // gets back: the duplicates of the windows that went to the generic kernel / the dense passes, and the call's duplicates (-1: no read-back took them)
+    struct FoldDupRun { const int* n_dup = nullptr; const unsigned* total = nullptr; long long fallbacks = 0, dense = 0, duplicates = -1; } dup_run;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // ---- multi-GPU (mirp_dist.cpp): RCCL communicator of this context's device, one process per GPU
     void* comm = nullptr;

@@ -97,6 +97,25 @@ int print_clocks(const FoldCall&) { return 0; }
 int dump_slab(const FoldCall&) { return 0; }
 #endif
 
+// Fold dedup (mirp_fold, fold_dedup_kernels.hip): the duplicates have length 0 and are on no hand-off list, so a list's windows count with their
+// duplicates (c->dup_run.n_dup, null for every other caller: nothing below launches then).  The sums go to words of block 0 and reach the host with it.
+int count_dense_dups(const FoldCall& f, hipStream_t st, const int* dense_list, int block, int b0) {      // behind a dense pass over the list of `block`
+    if (!f.c->dup_run.n_dup) return 0;
+    FOLD_LAUNCH(f.c, mirp::launch_fold_dedup_count(st, dense_list, f.ctl + mirp::FOLD_CTL_BLOCK * block + mirp::FOLD_CTL_DENSE_LEN, b0, f.c->dup_run.n_dup,
+                                                   f.ctl + mirp::FOLD_CTL_DUP_DENSE, true, nullptr, nullptr));
+    return 0;
+}
+int count_fallback_dups(const FoldCall& f) {      // in front of a read-back of block 0, every fill done: the whole fallback list, and the call's duplicate count
+    if (!f.c->dup_run.n_dup) return 0;
+    FOLD_LAUNCH(f.c, mirp::launch_fold_dedup_count(f.c->stream, (const int*)f.c->flist.p, f.ctl + mirp::FOLD_CTL_FALLBACKS, 0, f.c->dup_run.n_dup,
+                                                   f.ctl + mirp::FOLD_CTL_DUP_FALLBACKS, false, f.c->dup_run.total, f.ctl + mirp::FOLD_CTL_DUPLICATES));
+    return 0;
+}
+void read_dup_counts(mirp_ctx* c, const unsigned int* block0) {
+    if (!c->dup_run.n_dup) return;
+    c->dup_run.fallbacks = block0[mirp::FOLD_CTL_DUP_FALLBACKS]; c->dup_run.dense = block0[mirp::FOLD_CTL_DUP_DENSE]; c->dup_run.duplicates = block0[mirp::FOLD_CTL_DUPLICATES];
+}
+
 // Generic kernels (tables in a global workspace): every window when the LDS-resident path does not apply, else the windows it flagged.  A batch
 // of `slots` windows (fill kernel, then epilogue kernel) at a time; the device may be shared: fewer windows per batch before giving up.
 int run_generic(const FoldCall& f, const int* work_list, int n_generic) {
@@ -146,12 +165,15 @@ int run_serial(const FoldCall& f, int sub) {
         HIPCHK(c, hipEventRecord(ev.fill_done(k), c->stream));
         FOLD_LAUNCH(c, mirp::launch_fold_lds_epilogue(c->stream, model, std::min(nb, c->n_cu * 8), a));
         HIPCHK(c, hipEventRecord(ev.epilogue_done(k), c->stream));
+        if (int rc = count_dense_dups(f, c->stream, (const int*)c->dlist.p, 0, b0)) return rc;
     }
-    unsigned int h[mirp::FOLD_CTL_POOL_MAX + 1];
+    if (int rc = count_fallback_dups(f)) return rc;
+    unsigned int h[mirp::FOLD_CTL_DUPLICATES + 1];
     HIPCHK(c, hipMemcpyAsync(h, f.ctl, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->last_fallback = h[mirp::FOLD_CTL_FALLBACKS];
     c->last_dense = h[mirp::FOLD_CTL_DENSE_TOTAL];
+    read_dup_counts(c, h);
     c->fold_kernel_ms[0] = c->fold_kernel_ms[1] = 0;
     for (int k = 0; k < n_sub; k++) {
         float fill = 0, epi = 0;
@@ -178,12 +200,16 @@ int run_deferred_dense(const FoldCall& f, const std::vector<int>& plan, const mi
         HIPCHK(c, hipMemsetAsync(a.ctl + mirp::FOLD_CTL_EPILOGUE, 0, 4, c->stream));
         FOLD_LAUNCH(c, mirp::launch_fold_lds_dense(c->stream, 0, std::min(plan[k], c->n_cu), a, false));
         FOLD_LAUNCH(c, mirp::launch_fold_lds_epilogue(c->stream, 0, std::min(plan[k], c->n_cu * 8), a));
+        if (int rc = count_dense_dups(f, c->stream, a.dense_list, 1 + k, b0)) return rc;
     }
     HIPCHK(c, hipEventRecord(ev.deferred_done(), c->stream));
-    unsigned int nfb = 0;
-    HIPCHK(c, hipMemcpyAsync(&nfb, f.ctl + mirp::FOLD_CTL_FALLBACKS, 4, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = count_fallback_dups(f)) return rc;
+    unsigned int h[mirp::FOLD_CTL_DUPLICATES + 1];      // block 0 from the fallback count on
+    HIPCHK(c, hipMemcpyAsync(h + mirp::FOLD_CTL_FALLBACKS, f.ctl + mirp::FOLD_CTL_FALLBACKS, 4 * (mirp::FOLD_CTL_DUPLICATES + 1 - mirp::FOLD_CTL_FALLBACKS), hipMemcpyDeviceToHost,
+                             c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->last_fallback = nfb;
+    c->last_fallback = h[mirp::FOLD_CTL_FALLBACKS];
+    read_dup_counts(c, h);
     (void)hipEventElapsedTime(ms, ev.deferred_start(), ev.deferred_done());
     return 0;
 }
@@ -228,7 +254,10 @@ int run_chunked(const FoldCall& f, const std::vector<int>& plan, bool tailfree) 
         const int grid = std::min(plan[k], c->n_cu);
         if (k >= mirp::FOLD_RING_SLOTS) HIPCHK(c, hipStreamWaitEvent(sf, ev.epilogue_done(k - mirp::FOLD_RING_SLOTS), 0));
         FOLD_LAUNCH(c, mirp::launch_fold_lds_pool(sf, 0, grid, a));
-        if (dense_per_chunk) FOLD_LAUNCH(c, mirp::launch_fold_lds_dense(sf, 0, grid, a, false));
+        if (dense_per_chunk) {
+            FOLD_LAUNCH(c, mirp::launch_fold_lds_dense(sf, 0, grid, a, false));
+            if (int rc = count_dense_dups(f, sf, a.dense_list, 1 + k, b0)) return rc;
+        }
         HIPCHK(c, hipEventRecord(ev.fill_done(k), sf));
         HIPCHK(c, hipStreamWaitEvent(c->stream_epi, ev.fill_done(k), 0));
         // beside a fill: no more persistent epilogue workgroups than fit next to two fill workgroups on every CU; the last one has the device alone
@@ -237,6 +266,7 @@ int run_chunked(const FoldCall& f, const std::vector<int>& plan, bool tailfree) 
     }
     HIPCHK(c, hipStreamWaitEvent(c->stream, ev.epilogue_done(n_chunks - 1), 0));      // the epilogues are in order on their stream and each waits for its fill: the last one ends them all
     HIPCHK(c, hipEventRecord(ev.all_done(), c->stream));
+    if (int rc = count_fallback_dups(f)) return rc;
     std::vector<unsigned int> h(mirp::FOLD_CTL_BLOCK * (size_t)(1 + n_chunks)), n_dense(n_chunks);
     HIPCHK(c, hipMemcpyAsync(h.data(), f.ctl, 4 * h.size(), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -244,6 +274,7 @@ int run_chunked(const FoldCall& f, const std::vector<int>& plan, bool tailfree) 
     c->last_dense = 0;
     for (int k = 0; k < n_chunks; k++) c->last_dense += n_dense[k] = h[mirp::FOLD_CTL_BLOCK * (1 + k) + mirp::FOLD_CTL_DENSE_LEN];
     c->last_overlap_chunks = n_chunks;
+    read_dup_counts(c, h.data());
     float deferred_ms = 0;
     if (!dense_per_chunk && c->last_dense)
         if (int rc = run_deferred_dense(f, plan, ring, n_dense, ev, &deferred_ms)) return rc;
@@ -276,6 +307,7 @@ int mirp_run_fold(mirp_ctx* c, const unsigned char* d_seqs, const long long* d_o
     if (n_work <= 0) return 0;
     c->last_fallback = 0;
     c->last_overlap_chunks = 0;
+    c->dup_run.fallbacks = c->dup_run.dense = 0; c->dup_run.duplicates = -1;
     FoldCall f = {c, d_seqs, d_offs, d_lens, n_work, n_cap, span, max_lines, stride, d_lines, d_ss, d_nlines, d_mfe, d_status, c->fold_model == MIRP_FOLD_MODEL_VIENNA_185, 0, nullptr, FoldDiag()};
     if (!f.m185 && mirp::fold_generic_lds_bytes(n_cap, max_lines) > 160 * 1024) return fail(c, -5, "LDS budget exceeded (window or max_lines too large)");
     // the generic kernel ranks interior-loop candidates by energy * 1024 + shape in 32 bits (fold_kernel.hip, GEN_EMAX): energies below 10^6 in magnitude
@@ -305,5 +337,6 @@ int mirp_run_fold(mirp_ctx* c, const unsigned char* d_seqs, const long long* d_o
     f.ctl = (unsigned int*)c->fctl.p;
     HIPCHK(c, hipMemsetAsync(f.ctl, 0, ctl_bytes, c->stream));
     if (int rc = plan.empty() ? run_serial(f, sub) : run_chunked(f, plan, tailfree)) return rc;
+    c->last_dense += (unsigned int)c->dup_run.dense;
     return c->last_fallback ? run_generic(f, (const int*)c->flist.p, (int)c->last_fallback) : 0;
 }

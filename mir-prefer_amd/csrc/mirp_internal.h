@@ -41,6 +41,20 @@ hipError_t launch_fold185(hipStream_t stream, int grid, const FoldParams185* P, 
                           int span, int n_cap, int* ws, size_t ws_slot_ints, int max_lines, int ss_stride, MirpFoldLine* out_lines, char* out_ss,
                           int* out_nlines, int* out_mfe, int* out_status);
 
+// fold_dedup_kernels.hip: windows of one mirp_fold that repeat an earlier window byte for byte.  One device buffer holds everything at the byte
+// offsets of its layout: the duplicate count, the table (keys, vals: `table` slots, a power of two), the duplicates per representative (n_dup), the
+// hashes, the map (dup_of[w] = lowest r < w with the same length and bytes, or -1) and the lengths the fold reads (0 for a duplicate).
+struct FoldDedupLayout { unsigned table; size_t total, keys, vals, n_dup, clear_bytes, hash, dup_of, fold_lens, bytes; };
+FoldDedupLayout fold_dedup_layout(long long n_win);
+hipError_t launch_fold_dedup_find(hipStream_t st, const unsigned char* seqs, const long long* offs, const int* lens, int n_win, int hash_bits, char* buf,
+                                  const FoldDedupLayout& L);
+// after the fold: summary, structure lines and structure text of every representative into its duplicates' slots
+hipError_t launch_fold_dedup_copy(hipStream_t st, const int* dup_of, int n_win, int max_lines, int ss_stride, MirpFoldLine* lines, char* ss, int* nlines, int* mfe,
+                                  int* status);
+// *out (+)= the duplicates of the windows base + list[0 .. *list_len); with total_dst also *total_dst = *total_src.  One workgroup: the lists are short.
+hipError_t launch_fold_dedup_count(hipStream_t st, const int* list, const unsigned* list_len, int base, const int* n_dup, unsigned* out, bool accumulate,
+                                   const unsigned* total_src, unsigned* total_dst);
+
 struct PredictCaps { int p_cap, s_cap, m_cap, l_cap; };   // pieces per line, structures per window, candidate matures per window, staged lines per window (predict_kernel.hip)
 PredictCaps predict_default_caps(int max_lines, int ss_stride);
 size_t predict_lds_bytes(int max_lines, int ss_stride);

@@ -491,11 +491,42 @@ extern "C" int mirp_fold(mirp_ctx* c, int32_t span, int32_t max_lines) {
     HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
     c->n_side = 0; c->side_max_lines = 0;
     long long fallbacks = 0;
+    // Fold dedup: the candidate stage writes the left window of a short two-strand locus twice (MP:1184-1192) and repeats of the genome give equal
+    // windows at other coordinates; a fold depends on nothing but the window's bytes.  A window that repeats an earlier one is handed to the fold
+    // with length 0, which every fill kernel takes as an empty window, and gets the earlier window's results once that one is folded (generic
+    // re-fold included), before the windows over the line capacity are picked: a duplicate of one of those is flagged and served like it.
+    const bool dedup = c->fold_dedup != 0 && nw > 1;
+    const mirp::FoldDedupLayout dl = mirp::fold_dedup_layout(nw);
+    c->last_duplicates = 0; c->dd_windows = -1;
+    const int* fold_lens = c->v_wlens();
+    if (dedup) {
+        if (c->dd.ensure(dl.bytes)) return fail(c, -6, "device allocation failed (fold dedup)");
+        char* buf = (char*)c->dd.p;
+        HIPCHK(c, mirp::launch_fold_dedup_find(c->stream, (const unsigned char*)c->wseqs.p, c->v_woffs(), c->v_wlens(), (int)nw, c->fold_dedup_bits, buf, dl));
+        fold_lens = (const int*)(buf + dl.fold_lens);
+        c->dup_run.n_dup = (const int*)(buf + dl.n_dup); c->dup_run.total = (const unsigned*)(buf + dl.total);
+    }
     {
-        int rc = mirp_run_fold(c, (const unsigned char*)c->wseqs.p, c->v_woffs(), c->v_wlens(), (int)nw, n_cap, span, max_lines,
+        int rc = mirp_run_fold(c, (const unsigned char*)c->wseqs.p, c->v_woffs(), fold_lens, (int)nw, n_cap, span, max_lines,
                                stride, (MirpFoldLine*)c->lines.p, (char*)c->ss.p, (int*)c->nlines.p, (int*)c->mfe.p, (int*)c->status.p);
+        c->dup_run.n_dup = nullptr; c->dup_run.total = nullptr;
         if (rc) return rc;
         fallbacks = c->last_fallback;
+    }
+    if (dedup) {
+        const char* buf = (const char*)c->dd.p;
+        fallbacks += c->dup_run.fallbacks;
+        long long nd = c->dup_run.duplicates;
+        if (nd < 0) {      // the fold read no control block back (generic kernel for every window)
+            unsigned int t = 0;
+            HIPCHK(c, hipMemcpyAsync(&t, buf + dl.total, 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            nd = t;
+        }
+        if (nd > 0)
+            HIPCHK(c, mirp::launch_fold_dedup_copy(c->stream, (const int*)(buf + dl.dup_of), (int)nw, max_lines, stride, (MirpFoldLine*)c->lines.p, (char*)c->ss.p,
+                                                   (int*)c->nlines.p, (int*)c->mfe.p, (int*)c->status.p));
+        c->last_duplicates = nd; c->dd_windows = nw;
     }
     const double main_kernel_ms[2] = {c->fold_kernel_ms[0], c->fold_kernel_ms[1]};
     const int main_chunks = c->last_overlap_chunks;
@@ -757,6 +788,35 @@ extern "C" int mirp_set_fold_capacity(mirp_ctx* c, int64_t windows) {
 }
 extern "C" int mirp_last_fold_overlap_chunks(mirp_ctx* c) { return c ? c->last_overlap_chunks : -1; }
 extern "C" int64_t mirp_last_fold_dense(mirp_ctx* c) { return c ? (int64_t)c->last_dense : -1; }
+extern "C" int mirp_set_fold_dedup(mirp_ctx* c, int32_t on) {
+    if (!c) return -1;
+    if (on < 0 || on > 1) return fail(c, -1, "mirp_set_fold_dedup: on is 0 (fold every window) or 1 (fold each distinct window once)");
+    c->fold_dedup = on;
+    return 0;
+}
+extern "C" int mirp_set_fold_dedup_hash_bits(mirp_ctx* c, int32_t bits) {
+    if (!c) return -1;
+    if (bits < 0 || bits > 64) return fail(c, -1, "mirp_set_fold_dedup_hash_bits: bits is 0 (the default, all 64) or 1..64");
+    c->fold_dedup_bits = bits;
+    return 0;
+}
+extern "C" int64_t mirp_last_fold_duplicates(mirp_ctx* c) { return c ? (int64_t)c->last_duplicates : -1; }
+extern "C" int mirp_get_fold_duplicates(mirp_ctx* c, int32_t** dup_of, int64_t* n_windows) {
+    if (!c) return -1;
+    if (!dup_of || !n_windows) return fail(c, -1, "mirp_get_fold_duplicates: null argument");
+    if (!c->have_fold) return fail(c, -1, "mirp_get_fold_duplicates: run mirp_fold first");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nw = (size_t)c->n_windows;
+    int32_t* h = nullptr;
+    if (c->dd_windows == c->n_windows) {
+        h = host_copy<int32_t>(c, (const char*)c->dd.p + mirp::fold_dedup_layout(c->n_windows).dup_of, nw);
+    } else if ((h = (int32_t*)std::malloc(4 * std::max<size_t>(nw, 1)))) {      // the fold looked for none
+        std::fill(h, h + nw, -1);
+    }
+    if (!h) return fail(c, -2, "D2H failed");
+    *dup_of = h; *n_windows = c->n_windows;
+    return 0;
+}
 extern "C" int mirp_set_coverage_path(mirp_ctx* c, int32_t mode) {
     if (!c) return -1;
     if (mode < -1 || mode > 1) return fail(c, -1, "mirp_set_coverage_path: mode is -1 (by record density), 0 (atomic scatter) or 1 (fused scan)");
