@@ -62,7 +62,7 @@ typedef struct {
     int32_t window, tid, fold_s, fold_e, mat_s, mat_e, star_s, star_e, strand, has_star;
     int32_t line, ss_off, ss_len;
     int32_t reserved; /* imperfect-star flags (MP:2146-2162): bit0 'max_imperfect_star' key present, bits1-2 which+1, bit3 max > 0 */
-    int32_t total_depth_mature, total_depth_star;
+    int32_t total_depth_mature, total_depth_star; /* the 64-bit sums the decision used, saturated at 2^31 - 1 */
 } MirpMirna;
 
 int mirp_create(int device, mirp_ctx** out);
@@ -233,6 +233,8 @@ int mirp_predict(mirp_ctx* ctx, const MirpPredictParams* params, MirpMirna** res
  *  mature-star distance, mature depth per sample[n_samples]};  flags: 1 mature/star too close, 2 star but too few reads on the duplex,
  *  4 no star and ALLOW_NO_STAR_EXPRESSION off, 8 too many start positions, 16 mature+iso ratio < 0.8, 32 mature depth <= 100,
  *  64 not expressed in all samples, 128 passed, 256 no read on the precursor.  Record order is unspecified (sort by the first three fields).
+ * The flags follow the 64-bit depth sums; the depth fields of a record (depth on this strand .. imperfect star[3]) saturate at 2^31 - 1, as
+ * MirpMirna's two totals do, and do not wrap.
  */
 int mirp_predict_reasons(mirp_ctx* ctx, const MirpPredictParams* params, int32_t** records, int64_t* n_records, int32_t* stride);
 /* Per-stage device time of the last mirp_candidate / mirp_fold / mirp_predict calls, measured with HIP events on the
@@ -857,7 +859,8 @@ int mirp_homolog_last_stats(mirp_ctx* ctx, int64_t stats[24], double seconds[5])
 /* How many jobs a resident slot served, for the kernels whose workgroups (or waves) keep a private slab and serve several jobs in turn.  family:
  * 0 = the two-strand fold (a wave; mirp_duplex_batch, mirp_target_scan with energy), 1 = the accessibility kernel (a workgroup;
  * mirp_unpaired_batch, mirp_target_scan with accessibility), 2 = the scoring kernel of mirp_hairpin_align (queries per workgroup row), 3 = the
- * evaluation kernel of mirp_homolog_scan (a workgroup).  out = {launches of that kernel, the largest ceil(jobs / slots) over them} of the last
+ * evaluation kernel of mirp_homolog_scan (a workgroup), 4 = the filter kernel (a workgroup serves windows it, it + grid, ...; mirp_predict_batch,
+ * mirp_predict_batch_reasons, mirp_predict, mirp_predict_reasons; re-runs of windows over a capacity count as launches).  out = {launches of that kernel, the largest ceil(jobs / slots) over them} of the last
  * of the named calls; each of them resets its families when it starts.  A record for tests: nothing reads it.  Another family is refused (-1). */
 int mirp_last_jobs_per_slot(mirp_ctx* ctx, int32_t family, int64_t out[2]);
 

@@ -1015,7 +1015,8 @@ class Context:
     def last_jobs_per_slot(self, family):
         """(launches, the largest ceil(jobs / slots) over them) of a wave-per-job kernel family in the last call that can launch it
         (mirp_last_jobs_per_slot): family 0 = two-strand fold (duplex_batch, target_scan), 1 = accessibility (unpaired_batch, target_scan),
-        2 = hairpin scoring (hairpin_align; the largest chunk of queries), 3 = homolog evaluation (homolog_scan)."""
+        2 = hairpin scoring (hairpin_align; the largest chunk of queries), 3 = homolog evaluation (homolog_scan), 4 = the filter kernel (predict_batch, predict_batch_reasons, predict, predict_reasons; windows per
+        workgroup, re-runs of windows over a capacity included)."""
         out = (C.c_int64 * 2)()
         self._check(self.lib.mirp_last_jobs_per_slot(self.h, int(family), out), "mirp_last_jobs_per_slot")
         return int(out[0]), int(out[1])

@@ -70,7 +70,7 @@ extern "C" int64_t mirp_text_pieces_last(const mirp_ctx* c) { return c ? c->text
 // Launches and the largest jobs per resident slot of a wave-per-job kernel family in the last call that launches it (mirp_ctx::jobs_per_slot)
 extern "C" int mirp_last_jobs_per_slot(mirp_ctx* c, int32_t family, int64_t out[2]) {
     if (!c) return -1;
-    if (family < 0 || family > 3 || !out) return fail(c, -1, "mirp_last_jobs_per_slot: bad argument");
+    if (family < 0 || family > 4 || !out) return fail(c, -1, "mirp_last_jobs_per_slot: bad argument");
     out[0] = c->jobs_per_slot[family][0];
     out[1] = c->jobs_per_slot[family][1];
     return 0;
@@ -262,9 +262,10 @@ static int predict_batch_impl(mirp_ctx* c, const MirpWindow* windows, int32_t n_
         (void)grid;
         {
             std::string err;
+            c->reset_jobs_per_slot(4);
             if (int rc = mirp::run_predict_launch(c->stream, c->n_cu, (const MirpWindow*)d_w, n_windows, (const MirpMature*)d_m, (const MirpAln*)d_a, n_alns,
                                                   (const MirpFoldLine*)d_l, (const char*)d_s, ss_stride, max_lines, (const int*)d_n, *pp, (MirpMirna*)d_o,
-                                                  (int*)d_no, (int*)d_st, d_cnt, d_pool, rcap, rstride, nullptr, 0, nullptr, &err))
+                                                  (int*)d_no, (int*)d_st, d_cnt, d_pool, rcap, rstride, nullptr, 0, nullptr, &err, nullptr, c->jobs_per_slot[4]))
                 return bail(rc, "mirp_predict_batch: " + err);
         }
         if (reasons) {

@@ -368,8 +368,11 @@ __global__ void __launch_bounds__(64, MIRP_PRED_WPS) predict_kernel(
                                 r[0] = w; r[1] = mi; r[2] = s; r[3] = p.line; r[4] = p.off; r[5] = p.len; r[6] = ms.code; r[8] = ms.fold_s; r[9] = ms.fold_e;
                                 r[10] = ms.star_s; r[11] = ms.star_e;
                                 if (ms.code == 0) {
-                                    r[12] = (int)rx.total_this; r[13] = (int)rx.total_anti; r[14] = (int)rx.total_mature; r[15] = (int)rx.total_iso; r[16] = (int)rx.raw_star;
-                                    r[17] = (int)rx.imp[0]; r[18] = (int)rx.imp[1]; r[19] = (int)rx.imp[2]; r[20] = rx.distance;
+                                    // the depth fields saturate at 2^31 - 1 like MirpMirna's totals; the flags below follow the 64-bit sums
+                                    const long long dv[8] = {rx.total_this, rx.total_anti, rx.total_mature, rx.total_iso, rx.raw_star, rx.imp[0], rx.imp[1], rx.imp[2]};
+#pragma unroll
+                                    for (int q = 0; q < 8; q++) r[12 + q] = (int)(dv[q] > 0x7fffffffLL ? 0x7fffffffLL : dv[q]);
+                                    r[20] = rx.distance;
                                     if (rx.exception) flags |= 256;
                                     else if (rx.distance <= 4) flags |= 1;
                                     else if (rx.total_star > 0) { if (rx.ratio_total < 0.2) flags |= 2; else flags |= 128; }
@@ -525,10 +528,11 @@ __global__ void reasons_invalidate_kernel(int* __restrict__ rpool, unsigned int 
 // One launch of the filter plus, when windows exceeded a capacity, a second launch over just those windows with capacities sized from what they
 // reported (need[]) and their number of candidate matures.  scope: the launch covers the windows wsel[0..n_sel) (slots wslot or k) or, with
 // wsel == nullptr, every window except skip[w] >= 0.  Returns 0, or a negative code with *err set (LDS budget exceeded: -5).
+// jobs_rec (optional): {launches, the largest ceil(windows / workgroups)} of the caller's record (mirp_ctx::jobs_per_slot[4]), updated per launch.
 int run_predict_launch(hipStream_t stream, int n_cu, const MirpWindow* windows, int n_windows, const MirpMature* matures, const MirpAln* alns, long long n_alns,
                        const MirpFoldLine* lines, const char* ss, int ss_stride, int max_lines, const int* n_lines, MirpPredictParams pp, MirpMirna* out, int* n_out,
                        int* status, unsigned int* rcount, int* rpool, unsigned int rcap, int rstride, const int* wsel, int n_sel, const int* skip, std::string* err,
-                       int* need_buf) {
+                       int* need_buf, long long* jobs_rec) {
     const int n_iter = wsel ? n_sel : n_windows;
     if (n_iter <= 0) return 0;
     // need_buf: 12 * n_windows bytes of the caller's (the resident pipeline keeps one; an allocation and a release per call cost more than the
@@ -541,6 +545,7 @@ int run_predict_launch(hipStream_t stream, int n_cu, const MirpWindow* windows, 
 #define MIRP_PRED_GRID 64
 #endif
     const int grid = std::min(n_iter, n_cu * MIRP_PRED_GRID);
+    if (jobs_rec) { jobs_rec[0]++; jobs_rec[1] = std::max(jobs_rec[1], ((long long)n_iter + grid - 1) / grid); }
     if (launch_predict(stream, grid, windows, n_windows, matures, alns, n_alns, lines, ss, ss_stride, max_lines, n_lines, pp, out, n_out, status, rcount, rpool, rcap, rstride,
                        wsel, n_sel, skip, nullptr, nullptr, need) != hipSuccess) { *err = "predict kernel launch failed"; return -2; }
     std::vector<int> h_status((size_t)n_windows), h_sel, h_skip;
@@ -594,7 +599,9 @@ int run_predict_launch(hipStream_t stream, int n_cu, const MirpWindow* windows, 
             if (nn > 0)
                 hipLaunchKernelGGL(reasons_invalidate_kernel, dim3((nn + 255) / 256 > 4096 ? 4096 : (nn + 255) / 256), dim3(256), 0, stream, rpool, nn, rstride, (const unsigned char*)guard.f);
         }
-        if (launch_predict(stream, std::min((int)rw.size(), n_cu * 4), windows, n_windows, matures, alns, n_alns, lines, ss, ss_stride, max_lines, n_lines, pp, out, n_out, status,
+        const int grid2 = std::min((int)rw.size(), n_cu * 4);
+        if (jobs_rec) { jobs_rec[0]++; jobs_rec[1] = std::max(jobs_rec[1], ((long long)rw.size() + grid2 - 1) / grid2); }
+        if (launch_predict(stream, grid2, windows, n_windows, matures, alns, n_alns, lines, ss, ss_stride, max_lines, n_lines, pp, out, n_out, status,
                            rcount, rpool, rcap, rstride, guard.a, (int)rw.size(), nullptr, guard.b, &caps, need) != hipSuccess) { *err = "predict kernel launch failed (re-run)"; return -2; }
         if (hipMemcpyAsync(h_status.data(), status, 4 * (size_t)n_windows, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
             *err = "predict kernel execution failed (re-run)"; return -2;

@@ -95,8 +95,27 @@ typedef struct {
     double ratio_start[ORACLE_MAX_SAMPLES];
     int32_t exception;           /* reference would raise (ZeroDivisionError) */
 } OracleExpr;
+/* The same result with the depth sums per sample 64 bits wide: the reference's are Python integers, and one sample's reads can pass 2^31.
+ * oracle_expression64 is the implementation (oracle_check_loci uses it); oracle_expression keeps the narrower layout callers were built
+ * against -- its totals, ratios and flags are the 64-bit ones, its per-sample depths saturate at 2^31 - 1. */
+typedef struct {
+    int64_t reads_pre[ORACLE_MAX_SAMPLES], reads_mature[ORACLE_MAX_SAMPLES], reads_star[ORACLE_MAX_SAMPLES], reads_antisense[ORACLE_MAX_SAMPLES];
+    int64_t reads_isoform[ORACLE_MAX_SAMPLES], reads_inside[ORACLE_MAX_SAMPLES];
+    int32_t bases_with_reads_start[ORACLE_MAX_SAMPLES];
+    int64_t imperfect[ORACLE_MAX_SAMPLES][3];
+    int64_t total_this_strand, total_anti, total_mature, total_isoform, total_star /* after max with imperfect */, total_star_perfect;
+    int64_t total_imperfect[3];
+    int32_t mature_star_distance;
+    int32_t has_imperfect_key;
+    int32_t imperfect_which, imperfect_start, imperfect_end; int64_t max_imperfect;
+    double ratio_total, ratio_both, ratio_iso;
+    double ratio_start[ORACLE_MAX_SAMPLES];
+    int32_t exception;
+} OracleExpr64;
 int oracle_expression(const OracleAln *a, size_t na, int n_samples, int tid, int ws, int we, int fold_s, int fold_e, int m0, int m1,
                       int star_s, int star_e, int strand, int allow_3nt, OracleExpr *out);
+int oracle_expression64(const OracleAln *a, size_t na, int n_samples, int tid, int ws, int we, int fold_s, int fold_e, int m0, int m1,
+                        int star_s, int star_e, int strand, int allow_3nt, OracleExpr64 *out);
 
 typedef struct {
     int32_t window;              /* index of the FASTA entry that produced the record */

@@ -39,10 +39,11 @@ class MatureStar(C.Structure):
 
 
 class Expr(C.Structure):
-    _fields_ = [("reads_pre", C.c_int32 * MAX_SAMPLES), ("reads_mature", C.c_int32 * MAX_SAMPLES), ("reads_star", C.c_int32 * MAX_SAMPLES),
-                ("reads_antisense", C.c_int32 * MAX_SAMPLES), ("reads_isoform", C.c_int32 * MAX_SAMPLES),
-                ("reads_inside", C.c_int32 * MAX_SAMPLES), ("bases_with_reads_start", C.c_int32 * MAX_SAMPLES),
-                ("imperfect", (C.c_int32 * 3) * MAX_SAMPLES),
+    """oracle_expression64's result (OracleExpr64): depth sums per sample 64 bits wide"""
+    _fields_ = [("reads_pre", C.c_int64 * MAX_SAMPLES), ("reads_mature", C.c_int64 * MAX_SAMPLES), ("reads_star", C.c_int64 * MAX_SAMPLES),
+                ("reads_antisense", C.c_int64 * MAX_SAMPLES), ("reads_isoform", C.c_int64 * MAX_SAMPLES),
+                ("reads_inside", C.c_int64 * MAX_SAMPLES), ("bases_with_reads_start", C.c_int32 * MAX_SAMPLES),
+                ("imperfect", (C.c_int64 * 3) * MAX_SAMPLES),
                 ("total_this_strand", C.c_int64), ("total_anti", C.c_int64), ("total_mature", C.c_int64), ("total_isoform", C.c_int64),
                 ("total_star", C.c_int64), ("total_star_perfect", C.c_int64), ("total_imperfect", C.c_int64 * 3),
                 ("mature_star_distance", C.c_int32), ("has_imperfect_key", C.c_int32), ("imperfect_which", C.c_int32),
@@ -102,8 +103,8 @@ class Oracle:
         lib.oracle_structures.restype = C.c_int
         lib.oracle_maturestar.argtypes = [C.c_char_p] + [C.c_int] * 7 + [C.POINTER(MatureStar)]
         lib.oracle_maturestar.restype = C.c_int
-        lib.oracle_expression.argtypes = [vp, sz] + [C.c_int] * 12 + [C.POINTER(Expr)]
-        lib.oracle_expression.restype = C.c_int
+        lib.oracle_expression64.argtypes = [vp, sz] + [C.c_int] * 12 + [C.POINTER(Expr)]
+        lib.oracle_expression64.restype = C.c_int
         lib.oracle_check_loci.argtypes = [C.POINTER(Struct), C.c_int, vp, C.c_int, vp, vp, sz, C.POINTER(PredictParams), C.POINTER(Mirna), C.c_int]
         lib.oracle_check_loci.restype = C.c_int
 
@@ -171,8 +172,8 @@ class Oracle:
 
     def expression(self, alns, n_samples, tid, ws, we, fold_s, fold_e, m0, m1, star_s, star_e, strand, allow_3nt):
         o = Expr()
-        self.lib.oracle_expression(alns.ctypes.data, len(alns), n_samples, tid, ws, we, fold_s, fold_e, m0, m1, star_s, star_e, strand,
-                                   1 if allow_3nt else 0, C.byref(o))
+        self.lib.oracle_expression64(alns.ctypes.data, len(alns), n_samples, tid, ws, we, fold_s, fold_e, m0, m1, star_s, star_e, strand,
+                                     1 if allow_3nt else 0, C.byref(o))
         return o
 
     def check_loci(self, structs, matures, window, alns, params):
