@@ -647,6 +647,45 @@ typedef struct {
 int mirp_cluster_scan(mirp_ctx* ctx, const MirpClusterOpts* opts, MirpCluster** clusters, int64_t* n_clusters, int64_t** sample_counts,
                       int64_t stats[5]);
 
+/* isomiR counts: aligned reads, with or without the 3' tails of `align --tail`, joined against annotated miRNAs.
+ *
+ * The tailed tokenizer reads SAM files as mirp_tokenize_sams does (threads, no device; @SQ table of the first file, one sample per file, records
+ * with flag & 0x704 dropped, depth N of the read id `_xN`, CRLF; the same refusals and messages) but keeps the templated footprint and the tail:
+ * alns[k] = {tid, pos = POS, depth, len = m, strand, sample} and tails[k] = the tail code, in (sample, file) order.  CIGAR `<m>M`: no clip;
+ * `<m>M<t>S` on +, `<t>S<m>M` on -: a 3' clip of t >= 1 bases whose letters as sequenced are the tail (SEQ[m:], or the reverse complement of
+ * SEQ[:t]); without a clip the value of the first XT:Z: tag is the tail (`align --tail-trim`).  Letters: upper-cased, U = T, anything outside
+ * ACGT = N.  Tail code: 0 = none, else (5^t - 5) / 4 + 1 + the digits A0 C1 G2 T3 N4 as a base-5 number, first letter first (1 .. 488,280; ordered
+ * by length, then letters).  Any other CIGAR, m outside 1..65535, len(SEQ) != m + t, or a clip with SEQ `*` skips the record (skipped_cigar); a
+ * tail of more than 8 letters skips it (skipped_long_tail).  Returns 0 or -1 with a message in errbuf; release with mirp_free_tailed_sam_data. */
+typedef struct {
+    int32_t n_contigs;  char* contig_names;   /* NUL-separated, @SQ order of the first file */
+    int64_t* contig_len;
+    int32_t n_samples;  char* sample_names;   /* NUL-separated, one per file */
+    MirpAln* alns; uint32_t* tails; int64_t n_alns;
+    int64_t skipped_cigar, skipped_long_tail;
+} MirpTailedSamData;
+int mirp_tokenize_sams_tailed(const char* const* paths, int32_t n_paths, int32_t n_threads, MirpTailedSamData* out, char* errbuf, size_t errbuf_len);
+void mirp_free_tailed_sam_data(MirpTailedSamData* data);
+
+/* One annotated miRNA: contig, strand (0 '+', 1 '-'), [start, end] 1-based inclusive.  Its number is its index in the array. */
+typedef struct { int32_t tid, strand; int64_t start, end; } MirpIsoLocus;
+typedef struct { int32_t max5, max3, n_samples, reserved; } MirpIsomirOpts;      /* max5, max3 0..15; n_samples 1..255 */
+/* One isomiR: a distinct (locus, d5, d3, tail code) among the assigned records, with the 64-bit sum of their depths. */
+typedef struct { int32_t locus, d5, d3; uint32_t tail; int64_t reads; } MirpIsomir;
+/* Depth sums of one locus over its records: all, canonical (d5 = d3 = 0, no tail), d5 != 0, d3 < 0, d3 > 0, tailed, tail all T, tail all A; its
+ * distinct isomiRs; the major isomiR (largest reads, ties to the first in isomiR order) as an index into the isomiR array, -1 without reads. */
+typedef struct { int64_t reads, canonical, shift5, trim3, ext3, tailed, tail_u, tail_a, isomirs, major_reads, major; } MirpIsoLocusSum;
+/* With r5 / r3 the 5' / 3' end of a record's footprint (pos and pos + len - 1 on +, swapped on -), l5 / l3 those of a locus and sigma = +1 / -1:
+ * d5 = sigma (r5 - l5), d3 = sigma (r3 - l3), in 64-bit arithmetic.  A locus admits a record of its contig and strand with |d5| <= max5 and
+ * |d3| <= max3; a record counts in the admitting locus with the smallest (|d5|, |d3|, locus number), or nowhere.  The records and tail codes are
+ * the caller's (any order; nothing resident is read or changed), n_loci 1 .. 2^24, a counted record with sample >= n_samples is refused.
+ * Out (each released with mirp_free): *isomirs holds the *n_isomirs isomiRs ordered by (locus, d5, d3, tail), d5 and d3 signed; sums[n_loci];
+ * locus_counts[n_loci x n_samples] and isomir_counts[n_isomirs x n_samples], row-major depth sums; stats (optional) = {records, records
+ * assigned, depth assigned, isomiRs}.  Device memory is O(records + loci x samples + isomiRs x samples), allocated and released by the call. */
+int mirp_isomir_scan(mirp_ctx* ctx, const MirpAln* alns, const uint32_t* tails, int64_t n, const MirpIsoLocus* loci, int64_t n_loci,
+                     const MirpIsomirOpts* opts, MirpIsomir** isomirs, int64_t* n_isomirs, MirpIsoLocusSum** sums, int64_t** locus_counts,
+                     int64_t** isomir_counts, int64_t stats[4]);
+
 /* Degradome (PARE / GMUCT) evidence of miRNA-guided cleavage on the context's resident alignments (after any SAM ingest, or after
  * mirp_load_alignments): the degradome reads aligned to the transcripts.  A sense record (plus strand, 1 <= pos <= LN) is a read of the unit (tid,
  * pos); a unit's abundance is the sum of its records' depths; its category 0..4 follows CleaveLand's (4: one read; 0: the transcript's only maximum;

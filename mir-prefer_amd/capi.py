@@ -7,7 +7,7 @@ import os
 import numpy as np
 
 from . import early
-from .early import LIB_PATH, FastaData, SamData
+from .early import LIB_PATH, FastaData, SamData, TailedSamData
 ABI_VERSION = 17     # include/mirprefer.h as this binding was written against (mirp_abi_version of the library must match)
 
 
@@ -144,6 +144,19 @@ CLUSTER_DTYPE = np.dtype([("tid", "<i4"), ("major_strand", "<i4"), ("major_len",
                           ("reads", "<i8"), ("plus_reads", "<i8"), ("placements", "<i8"), ("major_pos", "<i8"), ("major_reads", "<i8"),
                           ("sizes", "<i8", (7,))])
 CLUSTER_STATS = ("records", "total", "islands", "clusters", "assigned")
+
+
+class IsomirOpts(C.Structure):
+    """MirpIsomirOpts of include/mirprefer.h."""
+    _fields_ = [("max5", C.c_int32), ("max3", C.c_int32), ("n_samples", C.c_int32), ("reserved", C.c_int32)]
+
+
+# MirpIsoLocus, MirpIsomir and MirpIsoLocusSum of include/mirprefer.h: an annotated miRNA, one isomiR and the sums of one locus of mirp_isomir_scan
+ISO_LOCUS_DTYPE = np.dtype([("tid", "<i4"), ("strand", "<i4"), ("start", "<i8"), ("end", "<i8")])
+ISOMIR_DTYPE = np.dtype([("locus", "<i4"), ("d5", "<i4"), ("d3", "<i4"), ("tail", "<u4"), ("reads", "<i8")])
+ISO_SUM_DTYPE = np.dtype([(f, "<i8") for f in ("reads", "canonical", "shift5", "trim3", "ext3", "tailed", "tail_u", "tail_a", "isomirs", "major_reads",
+                                               "major")])
+ISOMIR_STATS = ("records", "assigned", "depth", "isomirs")
 
 
 class DegradomeOpts(C.Structure):
@@ -329,6 +342,41 @@ def _unpack_sam_data(lib, d):
         return np.frombuffer(buf, dtype=ALN_DTYPE, count=n)
     alns, segs = recs(d.alns, d.n_alns), recs(d.segs, d.n_segs)
     return cn, lens, sn, alns, segs
+
+
+def tokenize_sams_tailed(paths, n_threads=0):
+    """The tailed SAM tokenizer of the isomiR counts (mirp_tokenize_sams_tailed; threads, no device): every kept record as its templated
+    footprint (pos = POS, len = m of `<m>M`) and the code of its 3' tail, in (sample, file) order.  Adopts the run the CLI started before its heavy
+    imports (early.start_tailed).  -> (contig names, lengths, sample names, alns, uint32 tail codes, {cigar, long_tail} skipped records)."""
+    from .synth import ALN_DTYPE
+    lib = load_library()
+    got = early.take_tailed(paths)
+    if got is not None:
+        rc, d, msg = got
+    else:
+        arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
+        d = TailedSamData()
+        err = C.create_string_buffer(512)
+        rc = lib.mirp_tokenize_sams_tailed(arr, len(paths), int(n_threads), C.byref(d), err, 512)
+        msg = err.value.decode()
+    if rc != 0:
+        raise ValueError(msg)
+    try:
+        def names(ptr, n):
+            out, off = [], 0
+            for _ in range(n):
+                b = C.string_at(ptr + off)
+                out.append(b.decode()); off += len(b) + 1
+            return out
+        cn, sn = names(d.contig_names, d.n_contigs), names(d.sample_names, d.n_samples)
+        lens = np.array([d.contig_len[k] for k in range(d.n_contigs)], dtype=np.int64)
+        n = d.n_alns
+        alns = np.frombuffer((C.c_char * (n * 16)).from_address(d.alns), dtype=ALN_DTYPE, count=n).copy() if n else np.zeros(0, dtype=ALN_DTYPE)
+        tails = np.frombuffer((C.c_char * (n * 4)).from_address(d.tails), dtype="<u4", count=n).copy() if n else np.zeros(0, dtype="<u4")
+        skipped = {"cigar": int(d.skipped_cigar), "long_tail": int(d.skipped_long_tail)}
+    finally:
+        lib.mirp_free_tailed_sam_data(C.byref(d))
+    return cn, lens, sn, alns, tails, skipped
 
 
 def ingest_sams(paths, n_threads=0, with_segments=False):
@@ -564,6 +612,13 @@ def load_library():
     lib.mirp_phase_scan.restype = C.c_int
     lib.mirp_cluster_scan.argtypes = [vp, C.POINTER(ClusterOpts), C.POINTER(vp), i64p, C.POINTER(vp), i64p]
     lib.mirp_cluster_scan.restype = C.c_int
+    lib.mirp_tokenize_sams_tailed.argtypes = [C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.POINTER(TailedSamData), C.c_char_p, C.c_size_t]
+    lib.mirp_tokenize_sams_tailed.restype = C.c_int
+    lib.mirp_free_tailed_sam_data.argtypes = [C.POINTER(TailedSamData)]
+    lib.mirp_free_tailed_sam_data.restype = None
+    lib.mirp_isomir_scan.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int64, C.POINTER(IsomirOpts), C.POINTER(vp), i64p, C.POINTER(vp), C.POINTER(vp),
+                                     C.POINTER(vp), i64p]
+    lib.mirp_isomir_scan.restype = C.c_int
     lib.mirp_degradome_scan.argtypes = [vp, C.c_char_p, C.c_char_p, C.POINTER(DegradomeOpts), C.c_char_p, i64p, C.POINTER(C.c_double)]
     lib.mirp_degradome_scan.restype = C.c_int
     lib.mirp_dist_unique_id.argtypes = [vp]
@@ -1048,6 +1103,27 @@ class Context:
         clusters = _copy_out(self.lib, ptr, CLUSTER_DTYPE, nc.value)
         counts = _copy_out(self.lib, cnt, np.dtype("<i8"), nc.value * int(n_samples)).reshape(nc.value, int(n_samples))
         return clusters, counts, dict(zip(CLUSTER_STATS, list(st)))
+
+    def isomir_scan(self, alns, tails, loci, max5, max3, n_samples):
+        """isomiR counts (mirp_isomir_scan).  alns: ALN_DTYPE records with pos = POS and len = the templated length; tails: their uint32
+        tail codes; loci: ISO_LOCUS_DTYPE in file order.  -> (ISOMIR_DTYPE array in (locus, d5, d3, tail) order, ISO_SUM_DTYPE per locus, int64
+        [loci, n_samples], int64 [isomiRs, n_samples], {records, assigned, depth, isomirs})."""
+        alns = np.ascontiguousarray(alns)
+        assert alns.dtype.itemsize == 16
+        tails = np.ascontiguousarray(tails, dtype="<u4")
+        loci = np.ascontiguousarray(loci, dtype=ISO_LOCUS_DTYPE)
+        if len(tails) != len(alns):
+            raise ValueError("isomir_scan: alns and tails differ in length")
+        o = IsomirOpts()
+        o.max5, o.max3, o.n_samples, o.reserved = int(max5), int(max3), int(n_samples), 0
+        iso, sums, lc, ic, ni = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        st = (C.c_int64 * 4)()
+        self._check(self.lib.mirp_isomir_scan(self.h, alns.ctypes.data, tails.ctypes.data, len(alns), loci.ctypes.data, len(loci), C.byref(o),
+                                              C.byref(iso), C.byref(ni), C.byref(sums), C.byref(lc), C.byref(ic), st), "mirp_isomir_scan")
+        S, nl = int(n_samples), len(loci)
+        return (_copy_out(self.lib, iso, ISOMIR_DTYPE, ni.value), _copy_out(self.lib, sums, ISO_SUM_DTYPE, nl),
+                _copy_out(self.lib, lc, np.dtype("<i8"), nl * S).reshape(nl, S), _copy_out(self.lib, ic, np.dtype("<i8"), ni.value * S).reshape(ni.value, S),
+                dict(zip(ISOMIR_STATS, list(st))))
 
     def degradome_scan(self, mirna_path, transcripts_path, out_path, contig_names, contig_lens, max_half_score=8, cleavage_site=False, max_category=4,
                        alpha=1.0):

@@ -22,10 +22,18 @@ class SamData(C.Structure):
                 ("sample_names", C.c_void_p), ("alns", C.c_void_p), ("n_alns", C.c_int64), ("segs", C.c_void_p), ("n_segs", C.c_int64)]
 
 
+class TailedSamData(C.Structure):
+    """MirpTailedSamData of include/mirprefer.h."""
+    _fields_ = [("n_contigs", C.c_int32), ("contig_names", C.c_void_p), ("contig_len", C.POINTER(C.c_int64)), ("n_samples", C.c_int32),
+                ("sample_names", C.c_void_p), ("alns", C.c_void_p), ("tails", C.c_void_p), ("n_alns", C.c_int64), ("skipped_cigar", C.c_int64),
+                ("skipped_long_tail", C.c_int64)]
+
+
 _lib = None
 _contexts = {}      # device -> (thread, handle, result box)
 _fastas = {}        # path -> (thread, FastaData, error buffer, result box)
 _ingests = {}       # tuple of SAM paths -> (thread, tokenizer handle, error buffer, result box)
+_tailed = {}        # tuple of SAM paths -> (thread, TailedSamData, error buffer, result box)
 
 
 def cdll():
@@ -116,6 +124,35 @@ def take_ingest(paths):
     """-> (return code of mirp_tokenize_sams, handle, error text) of the tokenizer run started for these paths, or None; handed out once (the caller passes the
     handle to mirp_ingest_tokenized_gpu, which releases it)."""
     ent = _ingests.pop(tuple(str(p) for p in paths), None)
+    if ent is None:
+        return None
+    th, d, err, box = ent
+    th.join()
+    return box.get("rc", -1), d, err.value.decode()
+
+
+def start_tailed(paths):
+    """The tailed tokenizer of the isomiR counts (mirp_tokenize_sams_tailed) while the device is still being opened; capi.tokenize_sams_tailed adopts it."""
+    lib = cdll()
+    key = tuple(str(p) for p in paths)
+    if lib is None or not key or key in _tailed:
+        return
+    fn = lib.mirp_tokenize_sams_tailed
+    fn.argtypes = [C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.POINTER(TailedSamData), C.c_char_p, C.c_size_t]      # as capi.load_library declares it
+    fn.restype = C.c_int
+    arr = (C.c_char_p * len(key))(*[p.encode() for p in key])
+    d, err, box = TailedSamData(), C.create_string_buffer(512), {}
+
+    def run():
+        box["rc"] = fn(arr, len(key), 0, C.byref(d), err, 512)
+    th = threading.Thread(target=run, daemon=True)
+    th.start()
+    _tailed[key] = (th, d, err, box)
+
+
+def take_tailed(paths):
+    """-> (return code of mirp_tokenize_sams_tailed, TailedSamData, error text) of the run started for these paths, or None; handed out once (the caller frees)."""
+    ent = _tailed.pop(tuple(str(p) for p in paths), None)
     if ent is None:
         return None
     th, d, err, box = ent
