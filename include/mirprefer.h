@@ -624,6 +624,34 @@ typedef struct {
  * units kept, anchors}.  Nothing resident changes. */
 int mirp_phase_scan(mirp_ctx* ctx, const MirpPhaseOpts* opts, const int32_t* kmin, MirpPhaseWindow** windows, int64_t* n_windows, int64_t stats[3]);
 
+/* miRNA triggers of PHAS loci on the context's resident alignments (after any SAM ingest, or after mirp_load_alignments).  Every
+ * target site of a miRNA (§14 on both strands, score <= max_half_score / 2, no mismatch at miRNA position 10 or 11) that lies inside a locus
+ * interval sets a cut, and the phasing test of §15 (units of `length`, `cycles`, min_depth) runs in the windows that the cut anchors: downstream
+ * and upstream of the cut in transcript sense, each at the register offsets -drift .. drift.  A window with k >= max(kmin[n], min_phased) is a
+ * trigger.  length 1..1024, cycles 1..64, min_phased >= 1, min_depth >= 1, max_half_score 0..16, drift 0..2. */
+typedef struct { int32_t length, cycles, min_phased, min_depth, max_half_score, drift; } MirpTriggerOpts;
+/* One locus interval, already widened by the flank and clipped to the contig: the tid of the resident alignments, the index of the same contig
+ * in the genome files (file order), and [start, end], 1-based. */
+typedef struct {
+    int32_t tid, contig;
+    int64_t start, end;
+} MirpTriggerLocus;
+/* One trigger: locus and miRNA (indices in the caller's order / the file), the site's half-score, strand (0 '+', 1 '-') and 0-based offset `pos` on
+ * the contig, side (0 down, 1 up), the register offset, n, k and the abundance of the window's phased units and of all its units. */
+typedef struct {
+    int32_t locus, mirna, half, strand, side, offset, n, k;
+    int64_t pos, phased_reads, window_reads;
+} MirpTrigger;
+/* Reads the miRNA FASTA and the genome FASTA files exactly as mirp_target_scan does (same letters, same refusals).  kmin[0 .. 2 * cycles * length]
+ * is the caller's table, as for mirp_phase_scan.  Out: *triggers (release with mirp_free) holds the *n_triggers triggers ordered by locus, miRNA,
+ * half-score, pos, strand, side, offset; site_counts[q] = the sites inside locus q's interval; stats (optional) = {miRNAs, interval bases, sites,
+ * windows evaluated, records of length `length`, units kept}; seconds (optional) = {parse + pack, upload, site scan + sort, units, windows +
+ * download}.  A bad argument (a null pointer, an option out of range, n_loci < 0, a locus with tid < 0, a contig that the genome files do not
+ * hold, start < 1, start > end or end past the contig) is refused with -1 before anything is allocated on the device.  Nothing resident changes. */
+int mirp_trigger_scan(mirp_ctx* ctx, const char* mirna_path, const char* const* genome_paths, int32_t n_genome, const MirpTriggerLocus* loci,
+                      int64_t n_loci, const MirpTriggerOpts* opts, const int32_t* kmin, MirpTrigger** triggers, int64_t* n_triggers,
+                      int64_t* site_counts, int64_t stats[6], double seconds[5]);
+
 /* Small-RNA clusters on the context's resident alignments (after any SAM ingest, or after mirp_load_alignments).  A record spans
  * [pos, pos + len - 1]; coverage c(p) = the sum of the depths of the records whose span holds p, for p in 1..contig_len[tid] only (64-bit).
  * Islands are the maximal runs of c(p) >= threshold; islands of one contig whose gap (next start - end - 1) is <= pad merge into a cluster.

@@ -134,6 +134,18 @@ PHASE_WINDOW_DTYPE = np.dtype([("tid", "<i4"), ("n", "<i4"), ("k", "<i4"), ("res
                                ("window_reads", "<i8")])
 
 
+class TriggerOpts(C.Structure):
+    """MirpTriggerOpts of include/mirprefer.h."""
+    _fields_ = [(f, C.c_int32) for f in ("length", "cycles", "min_phased", "min_depth", "max_half_score", "drift")]
+
+
+# MirpTriggerLocus and MirpTrigger of include/mirprefer.h: one locus interval and one trigger of mirp_trigger_scan
+TRIGGER_LOCUS_DTYPE = np.dtype([("tid", "<i4"), ("contig", "<i4"), ("start", "<i8"), ("end", "<i8")])
+TRIGGER_DTYPE = np.dtype([("locus", "<i4"), ("mirna", "<i4"), ("half", "<i4"), ("strand", "<i4"), ("side", "<i4"), ("offset", "<i4"), ("n", "<i4"),
+                          ("k", "<i4"), ("pos", "<i8"), ("phased_reads", "<i8"), ("window_reads", "<i8")])
+TRIGGER_STATS = ("mirnas", "interval_bases", "sites", "windows", "records", "units")
+
+
 class ClusterOpts(C.Structure):
     """MirpClusterOpts of include/mirprefer.h."""
     _fields_ = [("threshold", C.c_int64), ("pad", C.c_int64), ("contig_len", C.c_void_p), ("n_contigs", C.c_int32), ("n_samples", C.c_int32)]
@@ -610,6 +622,9 @@ def load_library():
     lib.mirp_set_target_capacity.restype = C.c_int
     lib.mirp_phase_scan.argtypes = [vp, C.POINTER(PhaseOpts), vp, C.POINTER(vp), i64p, i64p]
     lib.mirp_phase_scan.restype = C.c_int
+    lib.mirp_trigger_scan.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, vp, C.c_int64, C.POINTER(TriggerOpts), vp, C.POINTER(vp), i64p,
+                                      vp, i64p, C.POINTER(C.c_double)]
+    lib.mirp_trigger_scan.restype = C.c_int
     lib.mirp_cluster_scan.argtypes = [vp, C.POINTER(ClusterOpts), C.POINTER(vp), i64p, C.POINTER(vp), i64p]
     lib.mirp_cluster_scan.restype = C.c_int
     lib.mirp_tokenize_sams_tailed.argtypes = [C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.POINTER(TailedSamData), C.c_char_p, C.c_size_t]
@@ -1089,6 +1104,28 @@ class Context:
         st = (C.c_int64 * 3)()
         self._check(self.lib.mirp_phase_scan(self.h, C.byref(o), km.ctypes.data, C.byref(ptr), C.byref(nw), st), "mirp_phase_scan")
         return _copy_out(self.lib, ptr, PHASE_WINDOW_DTYPE, nw.value), dict(zip(("records", "units", "anchors"), list(st)))
+
+    def trigger_scan(self, mirna_path, genome_paths, loci, length, cycles, kmin, min_phased=3, min_depth=1, max_half_score=8, drift=0):
+        """miRNA triggers of PHAS loci on this context's resident alignments (mirp_trigger_scan).  loci: TRIGGER_LOCUS_DTYPE, the
+        intervals already widened and clipped; kmin as for phase_scan; max_half_score = 2 x the -s score.  -> (TRIGGER_DTYPE array in output order,
+        int64 sites per locus, {mirnas, interval_bases, sites, windows, records, units, seconds}); seconds = {parse + pack, upload, site scan + sort,
+        units, windows + download}."""
+        loci = np.ascontiguousarray(loci, dtype=TRIGGER_LOCUS_DTYPE)
+        o = TriggerOpts()
+        o.length, o.cycles, o.min_phased, o.min_depth, o.max_half_score, o.drift = (int(length), int(cycles), int(min_phased), int(min_depth),
+                                                                                  int(max_half_score), int(drift))
+        km = np.ascontiguousarray(kmin, dtype=np.int32)
+        if len(km) != 2 * int(cycles) * int(length) + 1:
+            raise ValueError("trigger_scan: kmin needs 2 * cycles * length + 1 entries")
+        paths = [genome_paths] if isinstance(genome_paths, (str, bytes, os.PathLike)) else list(genome_paths)
+        arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+        counts = np.zeros(max(len(loci), 1), dtype=np.int64)
+        ptr, nt = C.c_void_p(), C.c_int64()
+        st = (C.c_int64 * 6)()
+        sec = (C.c_double * 5)()
+        self._check(self.lib.mirp_trigger_scan(self.h, os.fsencode(mirna_path), arr, len(paths), loci.ctypes.data, len(loci), C.byref(o), km.ctypes.data,
+                                               C.byref(ptr), C.byref(nt), counts.ctypes.data, st, sec), "mirp_trigger_scan")
+        return _copy_out(self.lib, ptr, TRIGGER_DTYPE, nt.value), counts[:len(loci)], dict(zip(TRIGGER_STATS, list(st)), seconds=list(sec))
 
     def cluster_scan(self, threshold, pad, contig_lens, n_samples):
         """Small-RNA clusters on this context's resident alignments (mirp_cluster_scan; DESIGN.md §16).  threshold: the integer coverage T;

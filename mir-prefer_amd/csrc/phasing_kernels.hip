@@ -16,11 +16,14 @@
 //            a binary search over at most L units that starts where the previous one stopped (the keys are distinct integers).  That is O(m log L)
 //            per anchor, also when every coordinate is taken.  A window passes when k >= max(kmin[n], K); launch_excl_scan of the pass flags;
 //            ph_window_kernel<1> recomputes the passing anchors with their abundance sums and writes them in (tid, start) order.
+// split, units and -d are ph_build_units, which the trigger scan (trigger_kernels.hip, §29) calls as well; the searches and the counting of one
+// strand are in phasing_units.h.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include "mirp_ctx.h"
+#include "phasing_units.h"
 
 namespace mirp {
 
@@ -83,25 +86,6 @@ __global__ void __launch_bounds__(PH_NT) ph_compact_kernel(const unsigned long l
     }
 }
 
-// first index in [lo, hi) whose key is >= t (hi if none)
-__device__ __forceinline__ long long ph_lower(const unsigned long long* __restrict__ a, long long lo, long long hi, unsigned long long t) {
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (a[mid] < t) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-// first index in [lo, hi) whose key is > t
-__device__ __forceinline__ long long ph_upper(const unsigned long long* __restrict__ a, long long lo, long long hi, unsigned long long t) {
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (a[mid] <= t) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __global__ void __launch_bounds__(PH_NT) ph_merge_kernel(const unsigned long long* __restrict__ fkey, long long np, long long n,
                                                          unsigned long long* __restrict__ mkey, longlong2* __restrict__ mlb) {
     for (long long v = (long long)blockIdx.x * PH_NT + threadIdx.x; v < n; v += (long long)gridDim.x * PH_NT) {
@@ -119,38 +103,6 @@ __global__ void __launch_bounds__(PH_NT) ph_merge_kernel(const unsigned long lon
         }
         mkey[r] = k;
         mlb[r] = b;
-    }
-}
-
-struct PhUnits {
-    const unsigned long long* key;   // + units [0, np), - units [np, n)
-    const long long* slo;            // prefix sums of the abundance, low 30 bits / the rest (n + 1 entries)
-    const long long* shi;
-    long long np, n;
-};
-
-__device__ __forceinline__ long long ph_prefix(const PhUnits& U, long long v) { return (U.shi[v] << 30) + U.slo[v]; }
-
-// one strand of the window [x, x + mL) of anchor key x: units from b (the anchor's lower bound in this strand) to e (the strand's end)
-template <int EMIT>
-__device__ __forceinline__ void ph_strand(const PhUnits& U, long long b, long long e, unsigned long long x, int L, int m, int& n, int& k,
-                                          long long& phased, long long& reads) {
-    const long long cap = b + (long long)m * L;
-    const long long hi = ph_lower(U.key, b, cap < e ? cap : e, x + (unsigned long long)(m * L));
-    n += (int)(hi - b);
-    if (EMIT) reads += ph_prefix(U, hi) - ph_prefix(U, b);
-    long long cur = b;
-    for (int j = 0; j < m && cur < hi; j++) {
-        const unsigned long long t = x + (unsigned long long)(j * L);
-        // keys are distinct and cur's key is >= t - L: at most L keys lie in [t - L, t)
-        const long long p = j ? ph_lower(U.key, cur, cur + L < hi ? cur + L : hi, t) : cur;
-        if (p < hi && U.key[p] == t) {
-            k++;
-            if (EMIT) phased += ph_prefix(U, p + 1) - ph_prefix(U, p);
-            cur = p + 1;
-        } else {
-            cur = p;
-        }
     }
 }
 
@@ -209,24 +161,15 @@ int ph_count(mirp_ctx* c, const long long* d, long long* h) {
 
 }  // namespace
 
-extern "C" int mirp_phase_scan(mirp_ctx* c, const MirpPhaseOpts* o, const int32_t* kmin, MirpPhaseWindow** windows, int64_t* n_windows, int64_t stats[3]) {
+int mirp::ph_build_units(mirp_ctx* c, int L, int min_depth, TmpDevice& T, PhUnits* U, long long* records) {
     using namespace mirp;
-    if (!c) return -1;
-    if (!o || !kmin || !windows || !n_windows) return fail(c, -1, "mirp_phase_scan: bad argument");
-    if (o->length < 1 || o->length > 1024 || o->cycles < 1 || o->cycles > 64 || o->min_phased < 1 || o->min_depth < 1)
-        return fail(c, -1, "mirp_phase_scan: bad options");
-    *windows = nullptr;
-    *n_windows = 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    const int L = o->length, m = o->cycles, S = 2 * m * L;
     const hipStream_t st = c->stream;
     const long long n = c->n_alns;
     const MirpAln* alns = (const MirpAln*)c->alns.p;
-    long long rec_p = 0, rec_m = 0, nk = 0, nw = 0;
-    unsigned long long anchors = 0;
-    TmpDevice T;
-    MirpPhaseWindow* d_out = nullptr;
+    long long rec_p = 0, rec_m = 0, nk = 0;
     long long *sp = nullptr, *sm = nullptr;
+    *U = PhUnits{nullptr, nullptr, nullptr, 0, 0};
+    *records = 0;
     auto grab = [&](size_t bytes) { return T.get(bytes); };
     if (n > 0) {
         int* fp = (int*)grab(4 * (size_t)n);
@@ -242,66 +185,90 @@ extern "C" int mirp_phase_scan(mirp_ctx* c, const MirpPhaseOpts* o, const int32_
         if (int rc = ph_count(c, sm + n, &rec_m)) return rc;
     }
     const long long nrec = rec_p + rec_m;
-    if (nrec > 0) {
-        unsigned long long* key = (unsigned long long*)grab(8 * (size_t)nrec);
-        unsigned* dep = (unsigned*)grab(4 * (size_t)nrec);
-        int* head = (int*)grab(4 * (size_t)nrec);
-        long long* us = (long long*)grab(8 * (size_t)(nrec + 1));
-        if (!key || !dep || !head || !us) return fail(c, -6, "device allocation failed (phase scan)");
-        hipLaunchKernelGGL(ph_gather_kernel, dim3(ph_grid(n)), dim3(PH_NT), 0, st, alns, n, L, sp, sm, rec_p, key, dep);
-        hipLaunchKernelGGL(ph_head_kernel, dim3(ph_grid(nrec)), dim3(PH_NT), 0, st, key, nrec, rec_p, head);
-        launch_excl_scan(st, head, us, nrec);
+    *records = nrec;
+    if (nrec == 0) return 0;
+    unsigned long long* key = (unsigned long long*)grab(8 * (size_t)nrec);
+    unsigned* dep = (unsigned*)grab(4 * (size_t)nrec);
+    int* head = (int*)grab(4 * (size_t)nrec);
+    long long* us = (long long*)grab(8 * (size_t)(nrec + 1));
+    if (!key || !dep || !head || !us) return fail(c, -6, "device allocation failed (phase scan)");
+    hipLaunchKernelGGL(ph_gather_kernel, dim3(ph_grid(n)), dim3(PH_NT), 0, st, alns, n, L, sp, sm, rec_p, key, dep);
+    hipLaunchKernelGGL(ph_head_kernel, dim3(ph_grid(nrec)), dim3(PH_NT), 0, st, key, nrec, rec_p, head);
+    launch_excl_scan(st, head, us, nrec);
+    HIPCHK(c, hipGetLastError());
+    long long nu = 0, nu_p = 0;
+    if (int rc = ph_count(c, us + nrec, &nu)) return rc;
+    if (int rc = ph_count(c, us + rec_p, &nu_p)) return rc;
+    unsigned long long* ab = (unsigned long long*)grab(8 * (size_t)nu);
+    unsigned long long* ukey = (unsigned long long*)grab(8 * (size_t)nu);
+    int* keep = (int*)grab(4 * (size_t)nu);
+    long long* ks = (long long*)grab(8 * (size_t)(nu + 1));
+    if (!ab || !ukey || !keep || !ks) return fail(c, -6, "device allocation failed (phase scan)");
+    HIPCHK(c, hipMemsetAsync(ab, 0, 8 * (size_t)nu, st));
+    hipLaunchKernelGGL(ph_unit_kernel, dim3(ph_grid(nrec)), dim3(PH_NT), 0, st, key, dep, head, us, nrec, ab, ukey);
+    hipLaunchKernelGGL(ph_keep_kernel, dim3(ph_grid(nu)), dim3(PH_NT), 0, st, ab, nu, (unsigned long long)min_depth, keep);
+    launch_excl_scan(st, keep, ks, nu);
+    HIPCHK(c, hipGetLastError());
+    long long nk_p = 0;
+    if (int rc = ph_count(c, ks + nu, &nk)) return rc;
+    if (int rc = ph_count(c, ks + nu_p, &nk_p)) return rc;
+    if (nk == 0) return 0;
+    unsigned long long* fkey = (unsigned long long*)grab(8 * (size_t)nk);
+    int* lo = (int*)grab(4 * (size_t)nk);
+    int* hi = (int*)grab(4 * (size_t)nk);
+    long long* slo = (long long*)grab(8 * (size_t)(nk + 1));
+    long long* shi = (long long*)grab(8 * (size_t)(nk + 1));
+    if (!fkey || !lo || !hi || !slo || !shi) return fail(c, -6, "device allocation failed (phase scan)");
+    hipLaunchKernelGGL(ph_compact_kernel, dim3(ph_grid(nu)), dim3(PH_NT), 0, st, ukey, ab, keep, ks, nu, fkey, lo, hi);
+    launch_excl_scan(st, lo, slo, nk);
+    launch_excl_scan(st, hi, shi, nk);
+    HIPCHK(c, hipGetLastError());
+    *U = PhUnits{fkey, slo, shi, nk_p, nk};
+    return 0;
+}
+
+extern "C" int mirp_phase_scan(mirp_ctx* c, const MirpPhaseOpts* o, const int32_t* kmin, MirpPhaseWindow** windows, int64_t* n_windows, int64_t stats[3]) {
+    using namespace mirp;
+    if (!c) return -1;
+    if (!o || !kmin || !windows || !n_windows) return fail(c, -1, "mirp_phase_scan: bad argument");
+    if (o->length < 1 || o->length > 1024 || o->cycles < 1 || o->cycles > 64 || o->min_phased < 1 || o->min_depth < 1)
+        return fail(c, -1, "mirp_phase_scan: bad options");
+    *windows = nullptr;
+    *n_windows = 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int L = o->length, m = o->cycles, S = 2 * m * L;
+    const hipStream_t st = c->stream;
+    long long nrec = 0, nw = 0;
+    unsigned long long anchors = 0;
+    TmpDevice T;
+    MirpPhaseWindow* d_out = nullptr;
+    PhUnits U;
+    auto grab = [&](size_t bytes) { return T.get(bytes); };
+    if (int rc = ph_build_units(c, L, o->min_depth, T, &U, &nrec)) return rc;
+    const long long nk = U.n;
+    if (nk > 0) {
+        unsigned long long* mkey = (unsigned long long*)grab(8 * (size_t)nk);
+        longlong2* mlb = (longlong2*)grab(16 * (size_t)nk);
+        int* pass = (int*)grab(4 * (size_t)nk);
+        long long* pscan = (long long*)grab(8 * (size_t)(nk + 1));
+        int* d_kmin = (int*)grab(4 * (size_t)(S + 1));
+        unsigned long long* d_anchors = (unsigned long long*)grab(8);
+        if (!mkey || !mlb || !pass || !pscan || !d_kmin || !d_anchors) return fail(c, -6, "device allocation failed (phase scan)");
+        HIPCHK(c, hipMemcpyAsync(d_kmin, kmin, 4 * (size_t)(S + 1), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemsetAsync(d_anchors, 0, 8, st));
+        hipLaunchKernelGGL(ph_merge_kernel, dim3(ph_grid(nk)), dim3(PH_NT), 0, st, U.key, U.np, nk, mkey, mlb);
+        hipLaunchKernelGGL(ph_window_kernel<0>, dim3(ph_grid(nk)), dim3(PH_NT), 0, st, mkey, mlb, U, L, m, (int)o->min_phased, d_kmin, pass,
+                           (const long long*)nullptr, (MirpPhaseWindow*)nullptr, d_anchors);
+        launch_excl_scan(st, pass, pscan, nk);
         HIPCHK(c, hipGetLastError());
-        long long nu = 0, nu_p = 0;
-        if (int rc = ph_count(c, us + nrec, &nu)) return rc;
-        if (int rc = ph_count(c, us + rec_p, &nu_p)) return rc;
-        unsigned long long* ab = (unsigned long long*)grab(8 * (size_t)nu);
-        unsigned long long* ukey = (unsigned long long*)grab(8 * (size_t)nu);
-        int* keep = (int*)grab(4 * (size_t)nu);
-        long long* ks = (long long*)grab(8 * (size_t)(nu + 1));
-        if (!ab || !ukey || !keep || !ks) return fail(c, -6, "device allocation failed (phase scan)");
-        HIPCHK(c, hipMemsetAsync(ab, 0, 8 * (size_t)nu, st));
-        hipLaunchKernelGGL(ph_unit_kernel, dim3(ph_grid(nrec)), dim3(PH_NT), 0, st, key, dep, head, us, nrec, ab, ukey);
-        hipLaunchKernelGGL(ph_keep_kernel, dim3(ph_grid(nu)), dim3(PH_NT), 0, st, ab, nu, (unsigned long long)o->min_depth, keep);
-        launch_excl_scan(st, keep, ks, nu);
-        HIPCHK(c, hipGetLastError());
-        long long nk_p = 0;
-        if (int rc = ph_count(c, ks + nu, &nk)) return rc;
-        if (int rc = ph_count(c, ks + nu_p, &nk_p)) return rc;
-        if (nk > 0) {
-            unsigned long long* fkey = (unsigned long long*)grab(8 * (size_t)nk);
-            int* lo = (int*)grab(4 * (size_t)nk);
-            int* hi = (int*)grab(4 * (size_t)nk);
-            long long* slo = (long long*)grab(8 * (size_t)(nk + 1));
-            long long* shi = (long long*)grab(8 * (size_t)(nk + 1));
-            unsigned long long* mkey = (unsigned long long*)grab(8 * (size_t)nk);
-            longlong2* mlb = (longlong2*)grab(16 * (size_t)nk);
-            int* pass = (int*)grab(4 * (size_t)nk);
-            long long* pscan = (long long*)grab(8 * (size_t)(nk + 1));
-            int* d_kmin = (int*)grab(4 * (size_t)(S + 1));
-            unsigned long long* d_anchors = (unsigned long long*)grab(8);
-            if (!fkey || !lo || !hi || !slo || !shi || !mkey || !mlb || !pass || !pscan || !d_kmin || !d_anchors)
-                return fail(c, -6, "device allocation failed (phase scan)");
-            HIPCHK(c, hipMemcpyAsync(d_kmin, kmin, 4 * (size_t)(S + 1), hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipMemsetAsync(d_anchors, 0, 8, st));
-            hipLaunchKernelGGL(ph_compact_kernel, dim3(ph_grid(nu)), dim3(PH_NT), 0, st, ukey, ab, keep, ks, nu, fkey, lo, hi);
-            launch_excl_scan(st, lo, slo, nk);
-            launch_excl_scan(st, hi, shi, nk);
-            hipLaunchKernelGGL(ph_merge_kernel, dim3(ph_grid(nk)), dim3(PH_NT), 0, st, fkey, nk_p, nk, mkey, mlb);
-            const PhUnits U = {fkey, slo, shi, nk_p, nk};
-            hipLaunchKernelGGL(ph_window_kernel<0>, dim3(ph_grid(nk)), dim3(PH_NT), 0, st, mkey, mlb, U, L, m, (int)o->min_phased, d_kmin, pass,
-                               (const long long*)nullptr, (MirpPhaseWindow*)nullptr, d_anchors);
-            launch_excl_scan(st, pass, pscan, nk);
+        HIPCHK(c, hipMemcpyAsync(&anchors, d_anchors, 8, hipMemcpyDeviceToHost, st));
+        if (int rc = ph_count(c, pscan + nk, &nw)) return rc;
+        if (nw > 0) {
+            d_out = (MirpPhaseWindow*)grab(sizeof(MirpPhaseWindow) * (size_t)nw);
+            if (!d_out) return fail(c, -6, "device allocation failed (phase scan)");
+            hipLaunchKernelGGL(ph_window_kernel<1>, dim3(ph_grid(nk)), dim3(PH_NT), 0, st, mkey, mlb, U, L, m, (int)o->min_phased, d_kmin, pass,
+                               pscan, d_out, d_anchors);
             HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipMemcpyAsync(&anchors, d_anchors, 8, hipMemcpyDeviceToHost, st));
-            if (int rc = ph_count(c, pscan + nk, &nw)) return rc;
-            if (nw > 0) {
-                d_out = (MirpPhaseWindow*)grab(sizeof(MirpPhaseWindow) * (size_t)nw);
-                if (!d_out) return fail(c, -6, "device allocation failed (phase scan)");
-                hipLaunchKernelGGL(ph_window_kernel<1>, dim3(ph_grid(nk)), dim3(PH_NT), 0, st, mkey, mlb, U, L, m, (int)o->min_phased, d_kmin, pass,
-                                   pscan, d_out, d_anchors);
-                HIPCHK(c, hipGetLastError());
-            }
         }
     }
     MirpPhaseWindow* h_out = (MirpPhaseWindow*)std::malloc(sizeof(MirpPhaseWindow) * (size_t)std::max(nw, 1ll));
