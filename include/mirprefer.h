@@ -923,6 +923,40 @@ int mirp_set_homolog_capacity(mirp_ctx* ctx, int64_t keys, int64_t chunk, int32_
  * empty} of the last mirp_homolog_scan; seconds = {scan, windows, fold, evaluation + download, merge}. */
 int mirp_homolog_last_stats(mirp_ctx* ctx, int64_t stats[24], double seconds[5]);
 
+/* Inverted repeats of a genome: the banded local alignment of every contig with its own reverse complement.  Cell (i, j), i < j,
+ * pairs base i with base j (A.T and C.G only; every other letter pairs with nothing); H(i, j) = max(0, H(i+1, j-1) +match / -mismatch,
+ * H(i+1, j) - gap, H(i, j-1) - gap) over the cells with j - i + 1 <= max_span.  max_span 8..4096, min_score >= 1, match and mismatch 1..10,
+ * gap 1..50; `reserved` must be 0. */
+typedef struct { int32_t max_span, min_score, match, mismatch, gap, reserved; } MirpInvertedOpts;
+/* One repeat: the 0-based contig of the call, the score, the two arms (1-based, inclusive; left_start < left_end + 1 <= right_start <= right_end)
+ * and the counts of the alignment's columns: `=`, `X`, and `L` + `R` (a base of the left / right arm that pairs with nothing). */
+typedef struct {
+    int32_t contig, score;
+    int64_t left_start, left_end, right_start, right_end;
+    int32_t matches, mismatches, gaps, reserved;
+} MirpInvertedRec;
+/* Rows (left-arm positions) a wave of the row scan owns, rows of one strip (what its 64 lanes hold in registers at once; the rows beyond a tile
+ * that a wave recomputes are ceil((max_span - 1) / strip) strips), and the largest max_span.  For tests of the lengths around them: no result
+ * depends on where a tile or a strip ends. */
+#define MIRP_INVERTED_TILE 8192
+#define MIRP_INVERTED_STRIP 1024
+#define MIRP_INVERTED_MAX_SPAN 4096
+/* blob / off as mirp_ensemble's seqs / offsets: n_contigs contigs of any length (an empty one has no repeat).  Refusal (-10 and the 1-based contig
+ * in mirp_last_error): a byte >= 0x80.  Out (library-owned, mirp_free; NULL when there is no repeat): *recs holds the *n_recs accepted repeats
+ * ordered by (contig, left_start, right_end); *ops one byte (`=` `X` `L` `R`) per alignment column in outer-to-inner order, repeat r at
+ * (*ops)[(*ops_off)[r] .. (*ops_off)[r + 1]).  A contig's repeats are the same whatever else is in the call and however the work is split into
+ * passes.  Nothing resident changes. */
+int mirp_inverted_scan(mirp_ctx* ctx, const char* blob, const int64_t* off, int32_t n_contigs, const MirpInvertedOpts* opts, MirpInvertedRec** recs,
+                       int64_t* n_recs, char** ops, int64_t** ops_off);
+/* Device bytes one pass of mirp_inverted_scan holds: a traceback pass's direction bytes (span x span per candidate) and a scan pass's row keys
+ * (4 bytes per row, whole tiles).  0 = the default, 2^31.  A candidate or a tile that alone is larger runs in a pass of its own.  Lowered only
+ * to test the splits. */
+int mirp_set_inverted_capacity(mirp_ctx* ctx, int64_t bytes);
+/* stats = {contigs, bases, cells of the band, rows with r >= min_score, candidates, candidates traced, candidates dropped without a traceback,
+ * accepted repeats, scan passes, traceback passes, tiles, 0} of the last mirp_inverted_scan; seconds = {upload, scan, candidates + sort,
+ * traceback + selection, download}. */
+int mirp_inverted_last_stats(mirp_ctx* ctx, int64_t stats[12], double seconds[5]);
+
 /* How many jobs a resident slot served, for the kernels whose workgroups (or waves) keep a private slab and serve several jobs in turn.  family:
  * 0 = the two-strand fold (a wave; mirp_duplex_batch, mirp_target_scan with energy), 1 = the accessibility kernel (a workgroup;
  * mirp_unpaired_batch, mirp_target_scan with accessibility), 2 = the scoring kernel of mirp_hairpin_align (queries per workgroup row), 3 = the

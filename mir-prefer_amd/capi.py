@@ -97,6 +97,19 @@ HAIRPIN_DTYPE = np.dtype([(f, "<i4") for f in ("query", "known", "score", "q_sta
 HAIRPIN_STATS = ("queries", "known", "pairs", "cells", "hits", "passes", "score_passes", "trace_passes")
 HAIRPIN_STRIP = 16          # MIRP_HAIRPIN_STRIP of include/mirprefer.h: query rows a lane of the scoring kernel holds in registers
 
+class InvertedOpts(C.Structure):
+    """MirpInvertedOpts of include/mirprefer.h."""
+    _fields_ = [("max_span", C.c_int32), ("min_score", C.c_int32), ("match", C.c_int32), ("mismatch", C.c_int32), ("gap", C.c_int32), ("reserved", C.c_int32)]
+
+
+# MirpInvertedRec of include/mirprefer.h: one inverted repeat, positions 1-based and inclusive within its contig
+INVERTED_DTYPE = np.dtype([("contig", "<i4"), ("score", "<i4"), ("left_start", "<i8"), ("left_end", "<i8"), ("right_start", "<i8"), ("right_end", "<i8"),
+                           ("matches", "<i4"), ("mismatches", "<i4"), ("gaps", "<i4"), ("reserved", "<i4")])
+INVERTED_STATS = ("contigs", "bases", "cells", "rows_above", "candidates", "traced", "dropped_untraced", "accepted", "scan_passes", "trace_passes", "tiles")
+INVERTED_TILE = 8192          # MIRP_INVERTED_TILE of include/mirprefer.h: rows a wave of the row scan owns
+INVERTED_STRIP = 1024         # MIRP_INVERTED_STRIP: rows the 64 lanes of a wave hold at once
+INVERTED_MAX_SPAN = 4096      # MIRP_INVERTED_MAX_SPAN: the largest max_span
+
 class AlignPlaceOpts(C.Structure):
     """MirpAlignPlaceOpts of include/mirprefer.h."""
     _fields_ = [("mode", C.c_int32), ("window", C.c_int32), ("seed", C.c_uint64)]
@@ -606,6 +619,12 @@ def load_library():
     lib.mirp_set_hairpin_capacity.restype = C.c_int
     lib.mirp_hairpin_last_stats.argtypes = [vp, i64p, C.POINTER(C.c_double), i64p]
     lib.mirp_hairpin_last_stats.restype = C.c_int
+    lib.mirp_inverted_scan.argtypes = [vp, C.c_char_p, i64p, C.c_int32, C.POINTER(InvertedOpts), C.POINTER(vp), i64p, C.POINTER(vp), C.POINTER(vp)]
+    lib.mirp_inverted_scan.restype = C.c_int
+    lib.mirp_set_inverted_capacity.argtypes = [vp, C.c_int64]
+    lib.mirp_set_inverted_capacity.restype = C.c_int
+    lib.mirp_inverted_last_stats.argtypes = [vp, i64p, C.POINTER(C.c_double)]
+    lib.mirp_inverted_last_stats.restype = C.c_int
     lib.mirp_homolog_scan.argtypes = [vp, C.c_char_p, i64p, C.c_int32, C.POINTER(HomologOpts), C.POINTER(vp), i64p, C.POINTER(vp), C.POINTER(vp)]
     lib.mirp_homolog_scan.restype = C.c_int
     lib.mirp_homolog_contigs.argtypes = [vp, C.POINTER(vp), i64p, C.POINTER(vp), C.POINTER(C.c_int32)]
@@ -1037,6 +1056,40 @@ class Context:
         per = np.zeros(st[0] + 1, dtype=np.int64)          # (st[0] = the queries of that call: what the library writes)
         self._check(self.lib.mirp_hairpin_last_stats(self.h, st, sec, per.ctypes.data_as(C.POINTER(C.c_int64))), "mirp_hairpin_last_stats")
         return dict(zip(HAIRPIN_STATS, list(st)), seconds=list(sec), per_query=per[:st[0]].tolist())
+
+    def inverted_scan(self, contigs, max_span=2000, min_score=50, match=3, mismatch=4, gap=12, capacity=0):
+        """Inverted repeats of every contig (mirp_inverted_scan): contigs (list of str / bytes / uint8 arrays of any length; A C G
+        T/U in either case, any other byte pairs with nothing, a byte >= 0x80 is refused).  capacity: device bytes per pass (0 = the default),
+        lowered only in tests.  -> (INVERTED_DTYPE array of the accepted repeats ordered by (contig, left_start, right_end), [str] of their
+        structures: runs of = X L R from the outer end inwards)."""
+        bs = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in contigs]
+        off = np.zeros(len(bs) + 1, dtype=np.int64)
+        if bs:
+            off[1:] = np.cumsum([len(b) for b in bs])
+        o = InvertedOpts()
+        o.max_span, o.min_score, o.match, o.mismatch, o.gap, o.reserved = int(max_span), int(min_score), int(match), int(mismatch), int(gap), 0
+        recs, n_recs, ops, ops_off = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p()
+        self._check(self.lib.mirp_set_inverted_capacity(self.h, int(capacity)), "mirp_set_inverted_capacity")
+        try:
+            self._check(self.lib.mirp_inverted_scan(self.h, b"".join(bs), off.ctypes.data_as(C.POINTER(C.c_int64)), len(bs), C.byref(o), C.byref(recs),
+                                                    C.byref(n_recs), C.byref(ops), C.byref(ops_off)), "mirp_inverted_scan")
+        finally:
+            self.lib.mirp_set_inverted_capacity(self.h, 0)
+        n = n_recs.value
+        if n == 0:
+            return np.zeros(0, dtype=INVERTED_DTYPE), []
+        at = _copy_out(self.lib, ops_off, np.int64, n + 1)
+        text = _copy_out(self.lib, ops, np.uint8, int(at[-1])).tobytes()
+        r = _copy_out(self.lib, recs, INVERTED_DTYPE, n)
+        return r, [cigar_of(text[int(a):int(b)]) for a, b in zip(at[:-1], at[1:])]
+
+    def inverted_last_stats(self):
+        """{contigs, bases, cells, rows_above, candidates, traced, dropped_untraced, accepted, scan_passes, trace_passes, tiles, seconds} of the
+        last inverted_scan; seconds = {upload, scan, candidates + sort, traceback + selection, download}."""
+        st = (C.c_int64 * 12)()
+        sec = (C.c_double * 5)()
+        self._check(self.lib.mirp_inverted_last_stats(self.h, st, sec), "mirp_inverted_last_stats")
+        return dict(zip(INVERTED_STATS, list(st)), seconds=list(sec))
 
     def homolog_scan(self, queries, max_mismatches=1, precursor_len=300, max_placements=100, keys=0, chunk=0, fold_lines=0, eval_caps=(0, 0, 0)):
         """Homologs of known mature miRNAs in the genome of align_index (mirp_homolog_scan).  queries: distinct sequences (str /

@@ -195,6 +195,12 @@ struct mirp_ctx {
     // ---- target-mimic search (mimic_kernels.hip, mirp_mimics.cpp): the seed start table, the file index of every miRNA in seed order and the
     // lengths in file order; the packed targets, names, miRNA masks, keys and text use the target-site search's buffers (tg_*)
     DevBuf mm_start, mm_mid, mm_len;
+    // ---- inverted repeats (inverted_kernels.hip, mirp_inverted.cpp): the packed contigs and their padded starts and ends, the row keys, the
+    // candidate keys and the jobs, records, direction bytes and ops of one traceback pass
+    DevBuf iv_words, iv_pstart, iv_pend, iv_keys, iv_cand, iv_ctmp, iv_small, iv_jobs, iv_recs, iv_dir, iv_ops;
+    long long iv_cap = 0;             // bytes per pass of mirp_inverted_scan; 0 = the default, 2^31 (mirp_set_inverted_capacity)
+    long long iv_stats[12] = {0};     // the last mirp_inverted_scan (mirp_inverted_last_stats)
+    double iv_sec[5] = {0, 0, 0, 0, 0};
     long long n_result = 0;          // records of the last mirp_predict (p_res / p_text), what mirp_gather_loci sends
     bool have_result = false;
     // ---- jobs per resident slot (mirp_last_jobs_per_slot): per family (0 duplex_kernel, 1 unpaired_kernel, 2 hp_score_kernel, 3 homolog_eval_kernel, 4 predict_kernel)
@@ -366,6 +372,17 @@ int mirp_device_hairpin(mirp_ctx* c, const HpSeqs& Q, const HpSeqs& K, const Mir
                         std::vector<long long>& ops_off);
 // homolog_kernels.hip: the placements of coded queries (0..3 = A C G T at roff[0 .. nq]) in the resident alignment index as sorted keys
 // (query << 35 | packed position << 3 | strand << 2 | mismatches); windows, fold and evaluation of a chunk of them
+// inverted_kernels.hip: the inverted repeats of DESIGN.md §30.  G: the contigs as 4-bit codes (A C G T = 0..3, anything else and the padding 4),
+// 16 to a 64-bit word; contig k starts at row pstart[k], a multiple of 16, its last base is row pend[k] - 1, and at least one padding row follows
+// it; `rows` = pstart[n_contigs].  Out: the accepted repeats in output order with contig-local 1-based positions, their ops and the ops' offsets;
+// c->iv_stats and c->iv_sec are filled.
+struct IvGenome {
+    std::vector<unsigned long long> words;
+    std::vector<long long> pstart, pend;
+    long long rows = 0;
+};
+int mirp_device_inverted(mirp_ctx* c, const IvGenome& G, const MirpInvertedOpts& o, std::vector<MirpInvertedRec>& recs, std::vector<char>& ops,
+                         std::vector<long long>& ops_off);
 int mirp_device_homolog_scan(mirp_ctx* c, const unsigned char* codes, const long long* roff, long long nq, int v, int max_placements,
                              std::vector<unsigned long long>& keys, long long stats[3]);
 int mirp_device_homolog_eval(mirp_ctx* c, const unsigned long long* keys, long long n, int precursor_len, int max_lines, HmWin* win, HmEval* ev,
