@@ -675,6 +675,31 @@ typedef struct {
 int mirp_cluster_scan(mirp_ctx* ctx, const MirpClusterOpts* opts, MirpCluster** clusters, int64_t* n_clusters, int64_t** sample_counts,
                       int64_t stats[5]);
 
+/* Reads on given loci on the context's resident alignments (after any SAM ingest, or after mirp_load_alignments).  One locus:
+ * contig, strand (0 '+', 1 '-', 2 none), [start, end] 1-based inclusive.  Its number is its index in the array.  (MirpLocus is the candidate
+ * stage's dict_loci entry, hence the longer name.) */
+typedef struct { int32_t tid, strand; int64_t start, end; } MirpLocusSpan;
+typedef struct {
+    const int64_t* contig_len;      /* LN of contigs 0 .. n_contigs - 1, each 0 .. 2^31 - 1 */
+    int32_t n_contigs, n_samples, stranded, reserved;
+} MirpLocusOpts;
+/* Table rows (records, placements) one wave-job of the scan serves, and the most loci of a call.  For tests of the ranges around a multiple of
+ * the chunk: no result depends on where a chunk ends. */
+#define MIRP_LOCI_CHUNK 4096
+#define MIRP_LOCI_MAX 16777216
+/* A record's span is mirp_cluster_scan's, [max(pos, 1), min(pos + len - 1, LN)]; a record with an empty span or a tid >= n_contigs counts
+ * nowhere.  A record counts in every locus of its contig whose [start, end] shares a position with its span -- the loci may overlap, nest and
+ * repeat -- and, with `stranded`, only in loci of its own strand or of none.  Per locus the sums of MirpCluster over the records it counts, all
+ * 64-bit.  n_samples 1..255 (a counted record with sample >= n_samples is refused).  A bad argument (a null pointer, n_loci outside 0 .. 2^24,
+ * n_samples out of range, a contig length outside 0 .. 2^31 - 1, a locus with a tid outside the table, a strand outside 0..2, start < 1,
+ * start > end or end > LN) is refused with -1 before anything is allocated on the device.
+ * Out: *out (release with mirp_free) holds one MirpCluster per locus in input order, tid, start and end echoed, everything else zero for a
+ * locus that counts no record; *sample_counts (release with mirp_free) the depth per (locus, sample), n_loci x n_samples, row-major; stats
+ * (optional) = {records, loci, (locus, chunk of records) jobs, (record, locus) pairs counted, the longest record}.  n_loci = 0 succeeds with
+ * empty results.  Device memory is O(records + loci x samples), allocated and released by the call.  Nothing resident changes. */
+int mirp_locus_scan(mirp_ctx* ctx, const MirpLocusSpan* loci, int64_t n_loci, const MirpLocusOpts* opts, MirpCluster** out, int64_t** sample_counts,
+                    int64_t stats[5]);
+
 /* isomiR counts: aligned reads, with or without the 3' tails of `align --tail`, joined against annotated miRNAs.
  *
  * The tailed tokenizer reads SAM files as mirp_tokenize_sams does (threads, no device; @SQ table of the first file, one sample per file, records
@@ -961,7 +986,7 @@ int mirp_inverted_last_stats(mirp_ctx* ctx, int64_t stats[12], double seconds[5]
  * 0 = the two-strand fold (a wave; mirp_duplex_batch, mirp_target_scan with energy), 1 = the accessibility kernel (a workgroup;
  * mirp_unpaired_batch, mirp_target_scan with accessibility), 2 = the scoring kernel of mirp_hairpin_align (queries per workgroup row), 3 = the
  * evaluation kernel of mirp_homolog_scan (a workgroup), 4 = the filter kernel (a workgroup serves windows it, it + grid, ...; mirp_predict_batch,
- * mirp_predict_batch_reasons, mirp_predict, mirp_predict_reasons; re-runs of windows over a capacity count as launches).  out = {launches of that kernel, the largest ceil(jobs / slots) over them} of the last
+ * mirp_predict_batch_reasons, mirp_predict, mirp_predict_reasons; re-runs of windows over a capacity count as launches), 5 = the count kernel of mirp_locus_scan (a wave serves (locus, chunk) jobs w, w + waves, ...).  out = {launches of that kernel, the largest ceil(jobs / slots) over them} of the last
  * of the named calls; each of them resets its families when it starts.  A record for tests: nothing reads it.  Another family is refused (-1). */
 int mirp_last_jobs_per_slot(mirp_ctx* ctx, int32_t family, int64_t out[2]);
 

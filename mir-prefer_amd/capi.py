@@ -171,6 +171,18 @@ CLUSTER_DTYPE = np.dtype([("tid", "<i4"), ("major_strand", "<i4"), ("major_len",
 CLUSTER_STATS = ("records", "total", "islands", "clusters", "assigned")
 
 
+class LocusOpts(C.Structure):
+    """MirpLocusOpts of include/mirprefer.h."""
+    _fields_ = [("contig_len", C.c_void_p), ("n_contigs", C.c_int32), ("n_samples", C.c_int32), ("stranded", C.c_int32), ("reserved", C.c_int32)]
+
+
+# MirpLocusSpan of include/mirprefer.h: one locus of mirp_locus_scan; strand 0 '+', 1 '-', 2 none
+LOCUS_DTYPE = np.dtype([("tid", "<i4"), ("strand", "<i4"), ("start", "<i8"), ("end", "<i8")])
+LOCUS_STATS = ("records", "loci", "jobs", "pairs", "max_len")
+LOCI_CHUNK = 4096           # MIRP_LOCI_CHUNK of include/mirprefer.h: table rows (records, placements) one wave-job of the locus scan serves
+LOCI_MAX = 1 << 24          # MIRP_LOCI_MAX
+
+
 class IsomirOpts(C.Structure):
     """MirpIsomirOpts of include/mirprefer.h."""
     _fields_ = [("max5", C.c_int32), ("max3", C.c_int32), ("n_samples", C.c_int32), ("reserved", C.c_int32)]
@@ -646,6 +658,8 @@ def load_library():
     lib.mirp_trigger_scan.restype = C.c_int
     lib.mirp_cluster_scan.argtypes = [vp, C.POINTER(ClusterOpts), C.POINTER(vp), i64p, C.POINTER(vp), i64p]
     lib.mirp_cluster_scan.restype = C.c_int
+    lib.mirp_locus_scan.argtypes = [vp, vp, C.c_int64, C.POINTER(LocusOpts), C.POINTER(vp), C.POINTER(vp), i64p]
+    lib.mirp_locus_scan.restype = C.c_int
     lib.mirp_tokenize_sams_tailed.argtypes = [C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.POINTER(TailedSamData), C.c_char_p, C.c_size_t]
     lib.mirp_tokenize_sams_tailed.restype = C.c_int
     lib.mirp_free_tailed_sam_data.argtypes = [C.POINTER(TailedSamData)]
@@ -1139,7 +1153,7 @@ class Context:
         """(launches, the largest ceil(jobs / slots) over them) of a wave-per-job kernel family in the last call that can launch it
         (mirp_last_jobs_per_slot): family 0 = two-strand fold (duplex_batch, target_scan), 1 = accessibility (unpaired_batch, target_scan),
         2 = hairpin scoring (hairpin_align; the largest chunk of queries), 3 = homolog evaluation (homolog_scan), 4 = the filter kernel (predict_batch, predict_batch_reasons, predict, predict_reasons; windows per
-        workgroup, re-runs of windows over a capacity included)."""
+        workgroup, re-runs of windows over a capacity included), 5 = the count kernel of the locus scan (locus_scan; (locus, chunk) jobs per wave)."""
         out = (C.c_int64 * 2)()
         self._check(self.lib.mirp_last_jobs_per_slot(self.h, int(family), out), "mirp_last_jobs_per_slot")
         return int(out[0]), int(out[1])
@@ -1193,6 +1207,22 @@ class Context:
         clusters = _copy_out(self.lib, ptr, CLUSTER_DTYPE, nc.value)
         counts = _copy_out(self.lib, cnt, np.dtype("<i8"), nc.value * int(n_samples)).reshape(nc.value, int(n_samples))
         return clusters, counts, dict(zip(CLUSTER_STATS, list(st)))
+
+    def locus_scan(self, loci, contig_lens, n_samples, stranded=False):
+        """Reads on given loci on this context's resident alignments (mirp_locus_scan).  loci: LOCUS_DTYPE, which may overlap, nest
+        and repeat; contig_lens: LN per contig.  -> (CLUSTER_DTYPE array, one row per locus in input order, int64 [loci, n_samples] depth per
+        sample, {records, loci, jobs, pairs, max_len})."""
+        loci = np.ascontiguousarray(loci, dtype=LOCUS_DTYPE)
+        lens = np.ascontiguousarray(contig_lens, dtype=np.int64)
+        o = LocusOpts()
+        o.contig_len, o.n_contigs, o.n_samples, o.stranded, o.reserved = lens.ctypes.data, len(lens), int(n_samples), int(bool(stranded)), 0
+        ptr, cnt = C.c_void_p(), C.c_void_p()
+        st = (C.c_int64 * 5)()
+        self._check(self.lib.mirp_locus_scan(self.h, loci.ctypes.data, len(loci), C.byref(o), C.byref(ptr), C.byref(cnt), st), "mirp_locus_scan")
+        nl, S = len(loci), int(n_samples)
+        rows = _copy_out(self.lib, ptr, CLUSTER_DTYPE, nl)
+        counts = _copy_out(self.lib, cnt, np.dtype("<i8"), nl * S).reshape(nl, S)
+        return rows, counts, dict(zip(LOCUS_STATS, list(st)))
 
     def isomir_scan(self, alns, tails, loci, max5, max3, n_samples):
         """isomiR counts (mirp_isomir_scan).  alns: ALN_DTYPE records with pos = POS and len = the templated length; tails: their uint32
