@@ -700,6 +700,43 @@ typedef struct {
 int mirp_locus_scan(mirp_ctx* ctx, const MirpLocusSpan* loci, int64_t n_loci, const MirpLocusOpts* opts, MirpCluster** out, int64_t** sample_counts,
                     int64_t stats[5]);
 
+/* Differential expression between two groups of samples: the exact negative-binomial test of Anders & Huber 2010 on a feature x
+ * sample count matrix, as mirp_cluster_scan, mirp_isomir_scan and mirp_locus_scan write it.  counts: n_features x n_samples, row-major, the
+ * used samples only.  The size factors, the common dispersion, the adjustment of the p-values and all text are the host's; the moments of
+ * every feature and the whole test (one term per read of a feature) run on the device. */
+typedef struct {
+    const double* size_factor;      /* n_samples values, each finite and > 0 */
+    const uint8_t* group;           /* n_samples values: 0 = group A, 1 = group B */
+    int32_t n_samples;              /* 2 .. 255 */
+    int32_t mode;                   /* dispersion: 0 max(raw, common), 1 common, 2 max(raw, 0) per feature, 3 `phi` for every feature */
+    double phi;                     /* mode 3: the dispersion, >= 0 (0 = the Poisson case, an exact binomial test); otherwise ignored but checked */
+    double min_mean;                /* the common dispersion is the median raw dispersion of the features with base_mean >= min_mean */
+    double pseudo;                  /* log2fc = log2((mean_b + pseudo) / (mean_a + pseudo)) */
+} MirpDiffexpOpts;
+typedef struct {
+    double base_mean, mean_a, mean_b, log2fc, dispersion, p;   /* p = -1: an untested feature (no read in the used samples) */
+    uint64_t k_a, k_b;                                         /* raw counts of the two groups */
+} MirpDiffexpRow;
+/* Terms one wave-job of the test serves, the most features of a call and the bound of a count and of the terms of a call.  For tests of the
+ * sizes around a multiple of the chunk: no result depends on where a chunk ends beyond the rounding of a sum. */
+#define MIRP_DIFFEXP_CHUNK 4096
+#define MIRP_DIFFEXP_MAX_FEATURES 16777216
+#define MIRP_DIFFEXP_MAX_COUNT 1099511627776
+/* With y = count / size factor: base_mean, mean_a, mean_b = the means of y over all used samples and over either group; the raw dispersion is
+ * (v - z) / base_mean^2 (0 where base_mean = 0, or where no group has two samples), v the pooled within-group variance of y over the groups
+ * with two or more samples, z = base_mean x the mean of 1 / size factor.  The common dispersion is max(0, the median raw dispersion over the
+ * features with base_mean >= min_mean); without such a feature modes 0 and 1 fail with -10 (mode 2 reports 0).  `dispersion` is the value
+ * the test used.  p is the two-sided exact test conditioned on n = k_a + k_b: the probability of every split (a, n - a) that is at most as
+ * likely as the observed one (within the relative slack 1e-7), over that of all n + 1 splits; 0 where the latter overflows a double.
+ * A bad argument (a null pointer, n_features outside 0 .. 2^24, n_samples outside 2 .. 255, a group value above 1, an empty group, a size
+ * factor that is not finite and > 0, a negative or non-finite phi, min_mean or pseudo, a mode outside 0 .. 3, modes 0 .. 2 without a group
+ * of two or more samples, a count >= 2^40, more than 2^40 terms = the sum of n + 1 over the features) is refused with -1 before anything is
+ * allocated on the device.  Out: *rows (release with mirp_free) one MirpDiffexpRow per feature in input order; stats (optional) = {features,
+ * features tested, (feature, chunk) jobs, terms, the bits of the common dispersion as a double (mode 3: of phi)}.  n_features = 0 succeeds
+ * with an empty result.  Device memory is O(features x samples + jobs), allocated and released by the call.  Nothing resident changes.  Two
+ * calls on the same input return the same bytes: every sum is made in a fixed order, without floating-point atomics. */
+int mirp_diffexp(mirp_ctx* ctx, const uint64_t* counts, int64_t n_features, const MirpDiffexpOpts* opts, MirpDiffexpRow** rows, int64_t stats[5]);
+
 /* isomiR counts: aligned reads, with or without the 3' tails of `align --tail`, joined against annotated miRNAs.
  *
  * The tailed tokenizer reads SAM files as mirp_tokenize_sams does (threads, no device; @SQ table of the first file, one sample per file, records
@@ -986,7 +1023,7 @@ int mirp_inverted_last_stats(mirp_ctx* ctx, int64_t stats[12], double seconds[5]
  * 0 = the two-strand fold (a wave; mirp_duplex_batch, mirp_target_scan with energy), 1 = the accessibility kernel (a workgroup;
  * mirp_unpaired_batch, mirp_target_scan with accessibility), 2 = the scoring kernel of mirp_hairpin_align (queries per workgroup row), 3 = the
  * evaluation kernel of mirp_homolog_scan (a workgroup), 4 = the filter kernel (a workgroup serves windows it, it + grid, ...; mirp_predict_batch,
- * mirp_predict_batch_reasons, mirp_predict, mirp_predict_reasons; re-runs of windows over a capacity count as launches), 5 = the count kernel of mirp_locus_scan (a wave serves (locus, chunk) jobs w, w + waves, ...).  out = {launches of that kernel, the largest ceil(jobs / slots) over them} of the last
+ * mirp_predict_batch_reasons, mirp_predict, mirp_predict_reasons; re-runs of windows over a capacity count as launches), 5 = the count kernel of mirp_locus_scan (a wave serves (locus, chunk) jobs w, w + waves, ...), 6 = the sum kernel of mirp_diffexp (a wave serves (feature, chunk) jobs w, w + waves, ...).  out = {launches of that kernel, the largest ceil(jobs / slots) over them} of the last
  * of the named calls; each of them resets its families when it starts.  A record for tests: nothing reads it.  Another family is refused (-1). */
 int mirp_last_jobs_per_slot(mirp_ctx* ctx, int32_t family, int64_t out[2]);
 

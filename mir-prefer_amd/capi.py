@@ -183,6 +183,21 @@ LOCI_CHUNK = 4096           # MIRP_LOCI_CHUNK of include/mirprefer.h: table rows
 LOCI_MAX = 1 << 24          # MIRP_LOCI_MAX
 
 
+class DiffexpOpts(C.Structure):
+    """MirpDiffexpOpts of include/mirprefer.h."""
+    _fields_ = [("size_factor", C.c_void_p), ("group", C.c_void_p), ("n_samples", C.c_int32), ("mode", C.c_int32), ("phi", C.c_double),
+                ("min_mean", C.c_double), ("pseudo", C.c_double)]
+
+
+# MirpDiffexpRow of include/mirprefer.h: one feature of mirp_diffexp; p = -1 marks an untested feature
+DIFFEXP_DTYPE = np.dtype([(f, "<f8") for f in ("base_mean", "mean_a", "mean_b", "log2fc", "dispersion", "p")] + [("k_a", "<u8"), ("k_b", "<u8")])
+DIFFEXP_STATS = ("features", "tested", "jobs", "terms", "phi_c")
+DIFFEXP_MODES = ("max", "common", "feature", "fixed")      # MirpDiffexpOpts.mode 0 .. 3
+DIFFEXP_CHUNK = 4096                   # MIRP_DIFFEXP_CHUNK: terms one wave-job of the test serves
+DIFFEXP_MAX_FEATURES = 1 << 24         # MIRP_DIFFEXP_MAX_FEATURES
+DIFFEXP_MAX_COUNT = 1 << 40            # MIRP_DIFFEXP_MAX_COUNT
+
+
 class IsomirOpts(C.Structure):
     """MirpIsomirOpts of include/mirprefer.h."""
     _fields_ = [("max5", C.c_int32), ("max3", C.c_int32), ("n_samples", C.c_int32), ("reserved", C.c_int32)]
@@ -660,6 +675,8 @@ def load_library():
     lib.mirp_cluster_scan.restype = C.c_int
     lib.mirp_locus_scan.argtypes = [vp, vp, C.c_int64, C.POINTER(LocusOpts), C.POINTER(vp), C.POINTER(vp), i64p]
     lib.mirp_locus_scan.restype = C.c_int
+    lib.mirp_diffexp.argtypes = [vp, vp, C.c_int64, C.POINTER(DiffexpOpts), C.POINTER(vp), i64p]
+    lib.mirp_diffexp.restype = C.c_int
     lib.mirp_tokenize_sams_tailed.argtypes = [C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.POINTER(TailedSamData), C.c_char_p, C.c_size_t]
     lib.mirp_tokenize_sams_tailed.restype = C.c_int
     lib.mirp_free_tailed_sam_data.argtypes = [C.POINTER(TailedSamData)]
@@ -1153,7 +1170,8 @@ class Context:
         """(launches, the largest ceil(jobs / slots) over them) of a wave-per-job kernel family in the last call that can launch it
         (mirp_last_jobs_per_slot): family 0 = two-strand fold (duplex_batch, target_scan), 1 = accessibility (unpaired_batch, target_scan),
         2 = hairpin scoring (hairpin_align; the largest chunk of queries), 3 = homolog evaluation (homolog_scan), 4 = the filter kernel (predict_batch, predict_batch_reasons, predict, predict_reasons; windows per
-        workgroup, re-runs of windows over a capacity included), 5 = the count kernel of the locus scan (locus_scan; (locus, chunk) jobs per wave)."""
+        workgroup, re-runs of windows over a capacity included), 5 = the count kernel of the locus scan (locus_scan; (locus, chunk) jobs per wave), 6 = the sum kernel of the exact test (diffexp; (feature, chunk)
+        jobs per wave)."""
         out = (C.c_int64 * 2)()
         self._check(self.lib.mirp_last_jobs_per_slot(self.h, int(family), out), "mirp_last_jobs_per_slot")
         return int(out[0]), int(out[1])
@@ -1223,6 +1241,31 @@ class Context:
         rows = _copy_out(self.lib, ptr, CLUSTER_DTYPE, nl)
         counts = _copy_out(self.lib, cnt, np.dtype("<i8"), nl * S).reshape(nl, S)
         return rows, counts, dict(zip(LOCUS_STATS, list(st)))
+
+    def diffexp(self, counts, size_factors, groups, mode="max", phi=0.0, min_mean=10.0, pseudo=0.5):
+        """The exact negative-binomial test between two groups of samples (mirp_diffexp).  counts: [features, samples] whole
+        numbers, the used samples only; size_factors: one per sample; groups: 0 (A) or 1 (B) per sample; mode: one of DIFFEXP_MODES or its
+        index, `phi` the dispersion of mode "fixed".  -> (DIFFEXP_DTYPE array, one row per feature in input order, p = -1 where untested,
+        {features, tested, jobs, terms, phi_c})."""
+        counts = np.ascontiguousarray(counts, dtype=np.uint64)
+        if counts.ndim != 2:
+            raise ValueError("diffexp: counts must be [features, samples]")
+        sf = np.ascontiguousarray(size_factors, dtype=np.float64)
+        grp = np.ascontiguousarray(groups, dtype=np.uint8)
+        if len(sf) != counts.shape[1] or len(grp) != counts.shape[1]:
+            raise ValueError("diffexp: size_factors and groups need one value per sample")
+        o = DiffexpOpts()
+        o.size_factor, o.group, o.n_samples = sf.ctypes.data, grp.ctypes.data, counts.shape[1]
+        o.mode = DIFFEXP_MODES.index(mode) if isinstance(mode, str) else int(mode)
+        o.phi, o.min_mean, o.pseudo = float(phi), float(min_mean), float(pseudo)
+        ptr = C.c_void_p()
+        st = (C.c_int64 * 5)()
+        self._check(self.lib.mirp_diffexp(self.h, counts.ctypes.data if counts.size else None, counts.shape[0], C.byref(o), C.byref(ptr), st),
+                    "mirp_diffexp")
+        rows = _copy_out(self.lib, ptr, DIFFEXP_DTYPE, counts.shape[0])
+        stats = dict(zip(DIFFEXP_STATS[:4], list(st)[:4]))
+        stats["phi_c"] = float(np.array([st[4]], dtype=np.int64).view(np.float64)[0])
+        return rows, stats
 
     def isomir_scan(self, alns, tails, loci, max5, max3, n_samples):
         """isomiR counts (mirp_isomir_scan).  alns: ALN_DTYPE records with pos = POS and len = the templated length; tails: their uint32
