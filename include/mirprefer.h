@@ -700,6 +700,37 @@ typedef struct {
 int mirp_locus_scan(mirp_ctx* ctx, const MirpLocusSpan* loci, int64_t n_loci, const MirpLocusOpts* opts, MirpCluster** out, int64_t** sample_counts,
                     int64_t stats[5]);
 
+/* siRNA duplexes and the 5' overlap signature on given loci on the context's resident alignments, all samples pooled (the sample
+ * field is not looked at).  A record is kept when min_len <= len <= max_len; its 5' end is f = pos on '+' and pos + len - 1 on '-'; it belongs
+ * to every locus [start, end] of its contig with start <= f <= end (5'-end membership, not mirp_locus_scan's span overlap; the locus strand is
+ * ignored).  With U(x) / V(y) the depth sums of the kept '+' / '-' records whose 5' end is x / y, the signature of a locus is
+ * H[k] = sum over x in [start, end] with x + k - 1 <= end of min(U(x), V(x + k - 1)), k = 1 .. max_overlap.  A duplex is a '+' placement
+ * (p, L) and a '-' placement (p - overhang, L) of kept records (a placement = a distinct (pos, strand, len) with its depth sum) whose 5' ends p
+ * and p - overhang + L - 1 both lie in the locus; its paired reads are m = min of the two sums. */
+typedef struct {
+    const int64_t* contig_len;      /* LN of contigs 0 .. n_contigs - 1, each 0 .. 2^31 - 1 */
+    int32_t n_contigs, min_len, max_len, max_overlap, overhang, reserved;   /* 1 <= min_len <= max_len <= 65535; max_overlap 1 .. 64; overhang 0 .. 8, < min_len */
+    int64_t min_reads;              /* a duplex with m >= min_reads (>= 1) is listed */
+} MirpSignatureOpts;
+/* Per locus: the depth sums of its member records (all, '+'), the number of duplexes and the sum of their m, and the major duplex (largest m;
+ * ties to the smallest p, then the shorter L): p, the two depth sums and L; the five major fields are 0 for a locus without a duplex. */
+typedef struct { int64_t reads, plus_reads, duplexes, duplex_reads, major_pos, major_plus, major_minus; int32_t major_len, reserved; } MirpSignatureRow;
+/* One listed duplex: the locus (index in the call), p, the depth sums of the '+' and the '-' placement, L. */
+typedef struct { int64_t locus, pos, plus_reads, minus_reads; int32_t len, reserved; } MirpDuplexSite;
+/* Table rows (U entries, placements) one wave-job serves, and the largest max_overlap.  No result depends on where a chunk ends. */
+#define MIRP_SIGNATURE_CHUNK 4096
+#define MIRP_SIGNATURE_MAX_OVERLAP 64
+/* Out: *rows holds one MirpSignatureRow per locus in input order; *overlaps H as n_loci x max_overlap, row-major (column k - 1 = overlap k);
+ * *sites the *n_sites listed duplexes ordered by (locus, p, L), a duplex that lies in several loci once under each; each is released with
+ * mirp_free.  stats (optional) = {records, kept records, U entries, V entries, (locus, chunk of U entries) jobs of the overlap kernel, duplex
+ * sites written}; the entries of U and V are the distinct 5' ends that lie on their contig (1 .. LN), which are all a locus can hold; with
+ * n_loci = 0 nothing runs on the device and stats[1 .. 5] are 0.  A bad argument (a null pointer, n_loci outside 0 .. 2^24, an option out of
+ * its range, overhang >= min_len, a contig length outside 0 .. 2^31 - 1, a locus with a tid outside the table, start < 1, start > end or
+ * end > LN) is refused with -1 before anything is allocated on the device.  n_loci = 0 succeeds with empty results.  Device memory is
+ * O(records + loci x max_overlap + sites), allocated and released by the call.  Nothing resident changes. */
+int mirp_signature_scan(mirp_ctx* ctx, const MirpLocusSpan* loci, int64_t n_loci, const MirpSignatureOpts* opts, MirpSignatureRow** rows,
+                        int64_t** overlaps, MirpDuplexSite** sites, int64_t* n_sites, int64_t stats[6]);
+
 /* Differential expression between two groups of samples: the exact negative-binomial test of Anders & Huber 2010 on a feature x
  * sample count matrix, as mirp_cluster_scan, mirp_isomir_scan and mirp_locus_scan write it.  counts: n_features x n_samples, row-major, the
  * used samples only.  The size factors, the common dispersion, the adjustment of the p-values and all text are the host's; the moments of
@@ -1023,7 +1054,7 @@ int mirp_inverted_last_stats(mirp_ctx* ctx, int64_t stats[12], double seconds[5]
  * 0 = the two-strand fold (a wave; mirp_duplex_batch, mirp_target_scan with energy), 1 = the accessibility kernel (a workgroup;
  * mirp_unpaired_batch, mirp_target_scan with accessibility), 2 = the scoring kernel of mirp_hairpin_align (queries per workgroup row), 3 = the
  * evaluation kernel of mirp_homolog_scan (a workgroup), 4 = the filter kernel (a workgroup serves windows it, it + grid, ...; mirp_predict_batch,
- * mirp_predict_batch_reasons, mirp_predict, mirp_predict_reasons; re-runs of windows over a capacity count as launches), 5 = the count kernel of mirp_locus_scan (a wave serves (locus, chunk) jobs w, w + waves, ...), 6 = the sum kernel of mirp_diffexp (a wave serves (feature, chunk) jobs w, w + waves, ...).  out = {launches of that kernel, the largest ceil(jobs / slots) over them} of the last
+ * mirp_predict_batch_reasons, mirp_predict, mirp_predict_reasons; re-runs of windows over a capacity count as launches), 5 = the count kernel of mirp_locus_scan (a wave serves (locus, chunk) jobs w, w + waves, ...), 6 = the sum kernel of mirp_diffexp (a wave serves (feature, chunk) jobs w, w + waves, ...), 7 = the overlap kernel of mirp_signature_scan (a wave serves (locus, chunk of U entries) jobs w, w + waves, ...).  out = {launches of that kernel, the largest ceil(jobs / slots) over them} of the last
  * of the named calls; each of them resets its families when it starts.  A record for tests: nothing reads it.  Another family is refused (-1). */
 int mirp_last_jobs_per_slot(mirp_ctx* ctx, int32_t family, int64_t out[2]);
 

@@ -183,6 +183,21 @@ LOCI_CHUNK = 4096           # MIRP_LOCI_CHUNK of include/mirprefer.h: table rows
 LOCI_MAX = 1 << 24          # MIRP_LOCI_MAX
 
 
+class SignatureOpts(C.Structure):
+    """MirpSignatureOpts of include/mirprefer.h."""
+    _fields_ = [("contig_len", C.c_void_p), ("n_contigs", C.c_int32), ("min_len", C.c_int32), ("max_len", C.c_int32), ("max_overlap", C.c_int32),
+                ("overhang", C.c_int32), ("reserved", C.c_int32), ("min_reads", C.c_int64)]
+
+
+# MirpSignatureRow and MirpDuplexSite of include/mirprefer.h: one row per locus and one listed duplex of mirp_signature_scan
+SIGNATURE_ROW_DTYPE = np.dtype([("reads", "<i8"), ("plus_reads", "<i8"), ("duplexes", "<i8"), ("duplex_reads", "<i8"), ("major_pos", "<i8"),
+                                ("major_plus", "<i8"), ("major_minus", "<i8"), ("major_len", "<i4"), ("reserved", "<i4")])
+DUPLEX_SITE_DTYPE = np.dtype([("locus", "<i8"), ("pos", "<i8"), ("plus_reads", "<i8"), ("minus_reads", "<i8"), ("len", "<i4"), ("reserved", "<i4")])
+SIGNATURE_STATS = ("records", "kept", "u_entries", "v_entries", "jobs", "sites")
+SIGNATURE_CHUNK = 4096      # MIRP_SIGNATURE_CHUNK: table rows (U entries, placements) one wave-job of the signature scan serves
+SIGNATURE_MAX_OVERLAP = 64  # MIRP_SIGNATURE_MAX_OVERLAP
+
+
 class DiffexpOpts(C.Structure):
     """MirpDiffexpOpts of include/mirprefer.h."""
     _fields_ = [("size_factor", C.c_void_p), ("group", C.c_void_p), ("n_samples", C.c_int32), ("mode", C.c_int32), ("phi", C.c_double),
@@ -675,6 +690,8 @@ def load_library():
     lib.mirp_cluster_scan.restype = C.c_int
     lib.mirp_locus_scan.argtypes = [vp, vp, C.c_int64, C.POINTER(LocusOpts), C.POINTER(vp), C.POINTER(vp), i64p]
     lib.mirp_locus_scan.restype = C.c_int
+    lib.mirp_signature_scan.argtypes = [vp, vp, C.c_int64, C.POINTER(SignatureOpts), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i64p, i64p]
+    lib.mirp_signature_scan.restype = C.c_int
     lib.mirp_diffexp.argtypes = [vp, vp, C.c_int64, C.POINTER(DiffexpOpts), C.POINTER(vp), i64p]
     lib.mirp_diffexp.restype = C.c_int
     lib.mirp_tokenize_sams_tailed.argtypes = [C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.POINTER(TailedSamData), C.c_char_p, C.c_size_t]
@@ -1171,7 +1188,7 @@ class Context:
         (mirp_last_jobs_per_slot): family 0 = two-strand fold (duplex_batch, target_scan), 1 = accessibility (unpaired_batch, target_scan),
         2 = hairpin scoring (hairpin_align; the largest chunk of queries), 3 = homolog evaluation (homolog_scan), 4 = the filter kernel (predict_batch, predict_batch_reasons, predict, predict_reasons; windows per
         workgroup, re-runs of windows over a capacity included), 5 = the count kernel of the locus scan (locus_scan; (locus, chunk) jobs per wave), 6 = the sum kernel of the exact test (diffexp; (feature, chunk)
-        jobs per wave)."""
+        jobs per wave), 7 = the overlap kernel of the signature scan (signature_scan; (locus, chunk of U entries) jobs per wave)."""
         out = (C.c_int64 * 2)()
         self._check(self.lib.mirp_last_jobs_per_slot(self.h, int(family), out), "mirp_last_jobs_per_slot")
         return int(out[0]), int(out[1])
@@ -1241,6 +1258,26 @@ class Context:
         rows = _copy_out(self.lib, ptr, CLUSTER_DTYPE, nl)
         counts = _copy_out(self.lib, cnt, np.dtype("<i8"), nl * S).reshape(nl, S)
         return rows, counts, dict(zip(LOCUS_STATS, list(st)))
+
+    def signature_scan(self, loci, contig_lens, min_len=20, max_len=25, max_overlap=30, overhang=2, min_reads=5):
+        """siRNA duplexes and the 5' overlap signature on given loci, on this context's resident alignments (mirp_signature_scan).
+        loci: LOCUS_DTYPE (the strand is ignored), which may overlap, nest and repeat; contig_lens: LN per contig.  -> (SIGNATURE_ROW_DTYPE array,
+        one row per locus in input order, int64 [loci, max_overlap] H with column k - 1 = overlap k, DUPLEX_SITE_DTYPE array of the duplexes with
+        min(plus_reads, minus_reads) >= min_reads in (locus, pos, len) order, {records, kept, u_entries, v_entries, jobs, sites})."""
+        loci = np.ascontiguousarray(loci, dtype=LOCUS_DTYPE)
+        lens = np.ascontiguousarray(contig_lens, dtype=np.int64)
+        o = SignatureOpts()
+        o.contig_len, o.n_contigs, o.min_len, o.max_len, o.max_overlap, o.overhang, o.reserved, o.min_reads = (
+            lens.ctypes.data, len(lens), int(min_len), int(max_len), int(max_overlap), int(overhang), 0, int(min_reads))
+        rows, hp, sp, ns = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        st = (C.c_int64 * 6)()
+        self._check(self.lib.mirp_signature_scan(self.h, loci.ctypes.data, len(loci), C.byref(o), C.byref(rows), C.byref(hp), C.byref(sp), C.byref(ns),
+                                                 st), "mirp_signature_scan")
+        nl, K = len(loci), int(max_overlap)
+        out = _copy_out(self.lib, rows, SIGNATURE_ROW_DTYPE, nl)
+        H = _copy_out(self.lib, hp, np.dtype("<i8"), nl * K).reshape(nl, K)
+        sites = _copy_out(self.lib, sp, DUPLEX_SITE_DTYPE, ns.value)
+        return out, H, sites, dict(zip(SIGNATURE_STATS, list(st)))
 
     def diffexp(self, counts, size_factors, groups, mode="max", phi=0.0, min_mean=10.0, pseudo=0.5):
         """The exact negative-binomial test between two groups of samples (mirp_diffexp).  counts: [features, samples] whole

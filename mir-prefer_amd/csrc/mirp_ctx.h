@@ -203,9 +203,9 @@ struct mirp_ctx {
     double iv_sec[5] = {0, 0, 0, 0, 0};
     long long n_result = 0;          // records of the last mirp_predict (p_res / p_text), what mirp_gather_loci sends
     bool have_result = false;
-    // ---- jobs per resident slot (mirp_last_jobs_per_slot): per family (0 duplex_kernel, 1 unpaired_kernel, 2 hp_score_kernel, 3 homolog_eval_kernel, 4 predict_kernel, 5 lc_count_kernel, 6 de_sum_kernel)
+    // ---- jobs per resident slot (mirp_last_jobs_per_slot): per family (0 duplex_kernel, 1 unpaired_kernel, 2 hp_score_kernel, 3 homolog_eval_kernel, 4 predict_kernel, 5 lc_count_kernel, 6 de_sum_kernel, 7 sg_overlap_kernel)
     // the launches of the last C-ABI call that can launch it and the largest ceil(jobs / slots) among them; a record, read by nothing in the library
-    long long jobs_per_slot[7][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}};
+    long long jobs_per_slot[8][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}};
     void reset_jobs_per_slot(int family) { jobs_per_slot[family][0] = jobs_per_slot[family][1] = 0; }
     void note_jobs_per_slot(int family, long long jobs, long long slots) {
         jobs_per_slot[family][0]++;
