@@ -167,22 +167,22 @@ __global__ void hm_winseq_kernel(AlRef R, const HmWin* __restrict__ win, long lo
 struct HmCaps { int p_cap, s_cap, l_cap; };
 
 // mature / star duplex figures of a passing structure (the values get_maturestar_info returns beside the star, MP:1876-1999)
-__device__ void hm_duplex_stats(SS ss, int len, int l0, int l1, int* prime5, int* total_bps, int* total_dots) {
-    int a = l0, b = l1; d_clip(len, a, b);
+__device__ void hm_duplex_stats(SSW ss, int len, int l0, int l1, int* prime5, int* total_bps, int* total_dots) {
+    int a = l0, b = l1; ssw_clip(len, a, b);
     char sym = '(';
     *prime5 = 1;
-    int firstbp = d_find(ss, '(', a, b);
-    if (firstbp == -1) { firstbp = d_find(ss, ')', a, b); sym = ')'; *prime5 = 0; }
-    const int p_first = d_partner(ss, len, firstbp);
-    int ra = l0, rb = l1 - 2; d_clip(len, ra, rb);
-    const int mend = d_rfind(ss, sym, ra, rb);
-    const int p_mend = d_partner(ss, len, mend);
+    int firstbp = ssw_find(ss, '(', a, b);
+    if (firstbp == -1) { firstbp = ssw_find(ss, ')', a, b); sym = ')'; *prime5 = 0; }
+    const int p_first = ssw_partner(ss, len, firstbp);
+    int ra = l0, rb = l1 - 2; ssw_clip(len, ra, rb);
+    const int mend = ssw_rfind(ss, sym, ra, rb);
+    const int p_mend = ssw_partner(ss, len, mend);
     int md0 = l0, md1 = mend + 1, sd0 = p_mend, sd1 = p_first + 1;
-    d_clip(len, md0, md1); d_clip(len, sd0, sd1);
+    ssw_clip(len, md0, md1); ssw_clip(len, sd0, sd1);
     if (md1 < md0) md1 = md0;
     if (sd1 < sd0) sd1 = sd0;
-    const int mdots = d_count(ss, '.', md0, md1);
-    *total_dots = mdots + d_count(ss, '.', sd0, sd1);
+    const int mdots = ssw_count(ss, '.', md0, md1);
+    *total_dots = mdots + ssw_count(ss, '.', sd0, sd1);
     *total_bps = (md1 - md0) - mdots;
 }
 
@@ -193,12 +193,12 @@ __global__ void __launch_bounds__(64) homolog_eval_kernel(const HmWin* __restric
                                                           const char* __restrict__ ss, int ss_stride, int max_lines, const int* __restrict__ n_lines,
                                                           int minlen, HmEval* __restrict__ out, char* __restrict__ out_ss,
                                                           const int* __restrict__ wsel, int n_sel, HmCaps caps, int* __restrict__ need,
-                                                          unsigned* __restrict__ gtext) {
+                                                          unsigned long long* __restrict__ gtext) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const int wpl = (ss_stride + 15) >> 4;                                // packed words per line
+    const int wpl = ssw_words(ss_stride);                                 // 64-bit words per staged line (32 characters each)
     const int max_structs = caps.s_cap, P_CAP = caps.p_cap, L_CAP = caps.l_cap;
-    unsigned* textw = gtext ? gtext + (size_t)blockIdx.x * L_CAP * wpl : (unsigned*)smem;
-    PStruct* sts = (PStruct*)(smem + (gtext ? (size_t)0 : (((size_t)L_CAP * wpl * 4 + 15) & ~(size_t)15)));   // s_cap
+    unsigned long long* textw = gtext ? gtext + (size_t)blockIdx.x * L_CAP * wpl : (unsigned long long*)smem;
+    PStruct* sts = (PStruct*)(smem + (gtext ? (size_t)0 : (((size_t)L_CAP * wpl * 8 + 15) & ~(size_t)15)));   // s_cap
     PStruct* slot = sts + max_structs;                                    // 64 * p_cap
     int* cnts = (int*)(slot + 64 * P_CAP);                                // 64
     unsigned short* lslot = (unsigned short*)(cnts + 64);                 // max_lines: staged slot of a line, 0xffff = not staged
@@ -225,26 +225,13 @@ __global__ void __launch_bounds__(64) homolog_eval_kernel(const HmWin* __restric
             n_used += (int)__popcll(bal);
         }
         __syncthreads();
-        // stage their text, 2 bits per character (lane = one packed word = 16 characters)
+        // stage their text as '(' and ')' bit planes (lane = one word = 32 characters)
         {
             const char* src = ss + (size_t)w * max_lines * ss_stride;
             const int nu = n_used < L_CAP ? n_used : L_CAP;
             for (int x = lane; x < nu * wpl; x += 64) {
                 const int us = x / wpl, wi = x - us * wpl, ln = lline[us];
-                const char* p = src + (size_t)ln * ss_stride + wi * 16;
-                const int lim = ss_stride - wi * 16;       // bytes of this line left
-                unsigned v = 0;
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    unsigned four = 0;
-                    if (q * 4 + 4 <= lim) four = *reinterpret_cast<const unsigned*>(p + q * 4);
-#pragma unroll
-                    for (int b = 0; b < 4; b++) {
-                        const unsigned ch = (four >> (8 * b)) & 0xffu;
-                        v |= (ch == '(' ? 1u : (ch == ')' ? 2u : 0u)) << ((q * 4 + b) * 2);
-                    }
-                }
-                textw[x] = v;
+                textw[x] = d_stage_word(src + (size_t)ln * ss_stride, ss_stride, wi);
             }
         }
         __syncthreads();
@@ -255,26 +242,26 @@ __global__ void __launch_bounds__(64) homolog_eval_kernel(const HmWin* __restric
             if (k < nl) {
                 MirpFoldLine ln = wl[k];
                 const int us = lslot[k];
-                SS s; s.w = textw + (size_t)(us == 0xffff ? 0 : us) * wpl; s.o = 0;
+                SSW s; s.w = textw + (size_t)(us == 0xffff ? 0 : us) * wpl; s.o = 0;
                 if (ln.printed && ln.len >= minlen && us != 0xffff) {
-                    if (d_is_stem_loop(s, ln.len)) {
+                    if (ssw_is_stem_loop(s, ln.len)) {
                         PStruct p; p.line = (unsigned short)k; p.off = 0; p.len = (unsigned short)ln.len; p.type = 0;
                         slot[lane * P_CAP + cnt++] = p;
                     } else {
                         // filter_ss (MP:1685-1724): one piece per top-level stem, [previous gap start, next stem start)
                         int len = ln.len;
-                        int prefirst = d_find(s, '(', 0, len);
+                        int prefirst = ssw_find(s, '(', 0, len);
                         if (prefirst >= 0) {
-                            int prelast = d_partner(s, len, prefirst), curfirst = prefirst, curlast = prelast, pregap0 = 0;
+                            int prelast = ssw_partner(s, len, prefirst), curfirst = prefirst, curlast = prelast, pregap0 = 0;
                             while (curfirst != -1) {
-                                curfirst = d_find(s, '(', prelast < 0 ? len : prelast, len);
+                                curfirst = ssw_find(s, '(', prelast < 0 ? len : prelast, len);
                                 int after1 = len;
-                                if (curfirst != -1) { after1 = curfirst; curlast = d_partner(s, len, curfirst); }
+                                if (curfirst != -1) { after1 = curfirst; curlast = ssw_partner(s, len, curfirst); }
                                 int ps = pregap0, pl = after1 - pregap0;
                                 if (pl > 55) {
                                     int type = -1;
-                                    if (d_is_stem_loop(s + ps, pl)) type = 0;
-                                    else if (d_good_bifurcation(s + ps, pl)) type = 1;
+                                    if (ssw_is_stem_loop(s + ps, pl)) type = 0;
+                                    else if (ssw_good_bifurcation(s + ps, pl)) type = 1;
                                     if (type >= 0) {
                                         if (cnt < P_CAP) {
                                             PStruct p; p.line = (unsigned short)k; p.off = (unsigned short)ps; p.len = (unsigned short)pl; p.type = (unsigned short)type;
@@ -320,9 +307,9 @@ __global__ void __launch_bounds__(64) homolog_eval_kernel(const HmWin* __restric
                 const PStruct p = sts[s];
                 const MirpFoldLine ln = wl[p.line];
                 const double ne = ((double)ln.energy / 100.0) / (double)ln.len;
-                SS str; str.w = textw + (size_t)lslot[p.line] * wpl; str.o = p.off;
+                SSW str; str.w = textw + (size_t)lslot[p.line] * wpl; str.o = p.off;
                 MStar ms;
-                d_maturestar(str, p.len, W.m0, W.m1, ln.start + p.off, W.ws, W.we, W.strand, ms);
+                ssw_maturestar(str, p.len, W.m0, W.m1, ln.start + p.off, W.ws, W.we, W.strand, ms);
                 if (a_s < 0 || ne < a_ne) { a_ne = ne; a_s = s; a_code = ms.code; }
                 if (ms.code == 0 && (p_s < 0 || ne < p_ne)) { p_ne = ne; p_s = s; p_ms = ms; }
             }
@@ -352,7 +339,7 @@ __global__ void __launch_bounds__(64) homolog_eval_kernel(const HmWin* __restric
             if (r_s >= 0) {
                 const PStruct bp = sts[r_s];
                 const MirpFoldLine ln = wl[bp.line];
-                SS str; str.w = textw + (size_t)lslot[bp.line] * wpl; str.o = bp.off;
+                SSW str; str.w = textw + (size_t)lslot[bp.line] * wpl; str.o = bp.off;
                 const int fst = ln.start + bp.off;
                 const int l0 = W.strand == 0 ? W.m0 - W.ws - fst + 1 : W.we - W.m1 - fst + 1, l1 = l0 + (W.m1 - W.m0);
                 hm_duplex_stats(str, bp.len, l0, l1, &e.prime5, &e.total_bps, &e.total_dots);
@@ -366,7 +353,7 @@ __global__ void __launch_bounds__(64) homolog_eval_kernel(const HmWin* __restric
 }
 
 static size_t hm_eval_lds(int max_lines, int ss_stride, HmCaps caps, bool text_in_lds) {
-    size_t b = text_in_lds ? (((size_t)caps.l_cap * ((ss_stride + 15) >> 4) * 4 + 15) & ~(size_t)15) : 0;
+    size_t b = text_in_lds ? (((size_t)caps.l_cap * ssw_words(ss_stride) * 8 + 15) & ~(size_t)15) : 0;
     b += sizeof(PStruct) * ((size_t)caps.s_cap + 64 * (size_t)caps.p_cap);
     b += sizeof(int) * 64;
     b += sizeof(unsigned short) * ((size_t)max_lines + (size_t)caps.l_cap);
@@ -576,15 +563,15 @@ int mirp_device_homolog_eval(mirp_ctx* c, const unsigned long long* keys, long l
     for (int round = 0;; round++) {
         const int n_iter = round ? (int)sel.size() : ni;
         size_t lds = hm_eval_lds(max_lines, stride, caps, true);
-        unsigned* gtext = nullptr;
+        unsigned long long* gtext = nullptr;
         TmpDevice T;
         int grid = std::min(n_iter, c->n_cu * 32);
         if (lds > 160 * 1024) {          // the staged text does not fit in LDS: a scratch area per workgroup in global memory
             lds = hm_eval_lds(max_lines, stride, caps, false);
             if (lds > 160 * 1024) return fail(c, -5, "mirp_homolog_scan: a window has more structures than the evaluation kernel can hold in LDS");
-            const size_t per = (size_t)caps.l_cap * ((stride + 15) >> 4) * 4;
+            const size_t per = (size_t)caps.l_cap * ssw_words(stride) * 8;
             grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, ((size_t)1 << 30) / std::max<size_t>(per, 1)));
-            gtext = (unsigned*)T.get(per * (size_t)grid + 16);
+            gtext = (unsigned long long*)T.get(per * (size_t)grid + 16);
             if (!gtext) return fail(c, -6, "device allocation failed (homologs: staged text)");
         }
         c->note_jobs_per_slot(3, n_iter, grid);

@@ -5,10 +5,13 @@
 // and its two `samtools view` subprocesses per window.
 //
 // Phase 1 (lane per RNALfold line): structure list of the window (MP:1541-1599).
-// Phase 2 (lane per structure, loop over matures): get_maturestar_info + check_expression_new.
-// Phase 3 (lane 0): the sequential "lowest normalised energy that passes" rule (MP:2246-2343).
+// Phase 2 (lane per (in-range mature, structure) pair, passes of 64 pairs): get_maturestar_info + check_expression_new.
+// Phase 3 (per mature, over the lanes that hold its pairs): the sequential "lowest normalised energy that passes" rule (MP:2246-2343).
+// The structure rules of phases 1 and 2 work on words of the staged text (ss_words.h).
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 #include <string>
 #include <vector>
 #include "mirp_internal.h"
@@ -21,6 +24,36 @@ namespace mirp {
 // (status 2 / 3) with what it needs, and run_predict_launch re-runs just those windows with capacities sized for them: the reference has no
 // such limits (MP:1541-1599, 2241), so neither does the result.
 #define PW_MIN_STRUCTS 192
+
+// Diagnostics build (make DIAG=1): phase clocks of the filter, read by every wave at the phase edges (s_memtime is wave-uniform), summed over windows by
+// lane 0 into one of PCLK_ROWS rows (so that the sums of thousands of waves do not queue on eight addresses in front of the next window's loads) and
+// printed after the launch when MIRP_PREDICT_CLOCKS is set (profiles/tools/pred_clocks.py).  The product build carries none of this.
+#ifdef MIRP_DIAG
+#define PCLK_N 7
+#define PCLK_ROWS 4096
+__device__ unsigned long long g_pclk[PCLK_ROWS][PCLK_N + 1];
+#define PCLK_DECL long long pc_t = clock64(), pc_acc[PCLK_N] = {0, 0, 0, 0, 0, 0, 0};
+#define PCLK(i) { const long long t_ = clock64(); pc_acc[i] += t_ - pc_t; pc_t = t_; }
+#define PCLK_FLUSH if (lane == 0) { unsigned long long* row_ = g_pclk[blockIdx.x & (PCLK_ROWS - 1)]; for (int q_ = 0; q_ < PCLK_N; q_++) atomicAdd(&row_[q_], (unsigned long long)pc_acc[q_]); atomicAdd(&row_[PCLK_N], 1ull); }
+static void predict_clocks_print() {
+    static const char* const name[PCLK_N] = {"line selection + text staging", "phase 1 (classification)", "phase 1 ordered compaction", "mature ranking + wave_lower_bound x2",
+                                             "d_maturestar over all pairs", "d_expression", "arg-min, write and the rest"};
+    std::vector<unsigned long long> all((size_t)PCLK_ROWS * (PCLK_N + 1)), z(all.size(), 0ull);
+    if (hipMemcpyFromSymbol(all.data(), HIP_SYMBOL(g_pclk), 8 * all.size()) != hipSuccess || hipMemcpyToSymbol(HIP_SYMBOL(g_pclk), z.data(), 8 * z.size()) != hipSuccess) return;
+    unsigned long long h[PCLK_N + 1] = {};
+    for (size_t k = 0; k < all.size(); k++) h[k % (PCLK_N + 1)] += all[k];
+    unsigned long long tot = 0;
+    for (int q = 0; q < PCLK_N; q++) tot += h[q];
+    std::fprintf(stderr, "[mirp predict clocks] windows=%llu total=%llu ticks (sum over windows, s_memtime)\n", h[PCLK_N], tot);
+    for (int q = 0; q < PCLK_N; q++)
+        std::fprintf(stderr, "[mirp predict clocks] %-40s %14llu  %5.1f %%  %9.0f / window\n", name[q], h[q], tot ? 100.0 * (double)h[q] / (double)tot : 0.0,
+                     h[PCLK_N] ? (double)h[q] / (double)h[PCLK_N] : 0.0);
+}
+#else
+#define PCLK_DECL
+#define PCLK(i)
+#define PCLK_FLUSH
+#endif
 
 __device__ __forceinline__ long long aln_lower_bound(const MirpAln* __restrict__ a, long long n, int tid, long long pos) {
     long long lo = 0, hi = n;
@@ -177,18 +210,17 @@ __global__ void __launch_bounds__(64, MIRP_PRED_WPS) predict_kernel(
     MirpMirna* __restrict__ out /* [n_windows * MIRP_MAX_MIRNA_PER_WINDOW] */, int* __restrict__ n_out, int* __restrict__ status,
     unsigned int* __restrict__ rcount, int* __restrict__ rpool, unsigned int rcap, int rstride,
     const int* __restrict__ wsel, int n_sel, const int* __restrict__ skip, const int* __restrict__ wslot, PredictCaps caps, int* __restrict__ need,
-    unsigned* __restrict__ gtext) {
+    unsigned long long* __restrict__ gtext) {
     // wsel == nullptr: every window w in [0, n_windows) with its fold output at slot w, except those with skip[w] >= 0 (folded again at full
     // line capacity: a second launch handles them); wsel != nullptr: the windows wsel[k], k in [0, n_sel), with their fold output at slot
     // wslot[k] (wslot == nullptr: slot k).  need (optional): need[3 w] = structures, need[3 w + 1] = pieces of one line, need[3 w + 2] = staged lines the window has.
     extern __shared__ __align__(16) unsigned char smem[];
-    const int wpl = (ss_stride + 15) >> 4;                                // packed words per line
+    const int wpl = ssw_words(ss_stride);                                 // 64-bit words per staged line (32 characters each)
     const int max_structs = caps.s_cap, PW_MAX_PIECES = caps.p_cap, PW_MAX_MATURES = caps.m_cap, L_CAP = caps.l_cap;
-    unsigned* textw = GTEXT ? gtext + (size_t)blockIdx.x * L_CAP * wpl : (unsigned*)smem;      // l_cap * wpl: only the lines phase 1 looks at (printed, >= minlen) are staged
-    PStruct* sts = (PStruct*)(smem + (GTEXT ? (size_t)0 : (((size_t)L_CAP * wpl * 4 + 15) & ~(size_t)15))); // max_structs
+    unsigned long long* textw = GTEXT ? gtext + (size_t)blockIdx.x * L_CAP * wpl : (unsigned long long*)smem;      // l_cap * wpl: only the lines phase 1 looks at (printed, >= minlen) are staged
+    PStruct* sts = (PStruct*)(smem + (GTEXT ? (size_t)0 : (((size_t)L_CAP * wpl * 8 + 15) & ~(size_t)15))); // max_structs
     PStruct* slot = sts + max_structs;                                // 64 * p_cap
-    int* cnts = (int*)(slot + 64 * PW_MAX_PIECES);                       // 64
-    int* morder = cnts + 64;                                             // m_cap: mature indices in stable depth-descending order (MP:2241)
+    int* morder = (int*)(slot + 64 * PW_MAX_PIECES);                     // m_cap: mature indices in stable depth-descending order (MP:2241)
     unsigned short* lslot = (unsigned short*)(morder + PW_MAX_MATURES);  // max_lines: staged slot of a line, 0xffff = not staged
     unsigned short* lline = lslot + max_lines;                           // l_cap: line of a staged slot
     const int lane = threadIdx.x;
@@ -201,6 +233,7 @@ __global__ void __launch_bounds__(64, MIRP_PRED_WPS) predict_kernel(
         const int nl = n_lines[sl] < max_lines ? n_lines[sl] : max_lines;
         const MirpFoldLine* wl = lines + (size_t)sl * max_lines;
         int st_flag = 0, need_pieces = 0;
+        PCLK_DECL
         // which lines are staged: the printed ones of at least minlen characters (MP:1568-1570), in line order; about half of a window's lines
         // (23 of 42 on the benchmark input), which is what lets 16 instead of 11 windows be resident per CU
         int n_used = 0;
@@ -216,29 +249,17 @@ __global__ void __launch_bounds__(64, MIRP_PRED_WPS) predict_kernel(
             n_used += (int)__popcll(bal);
         }
         __syncthreads();
-        // stage their text, 2 bits per character (lane = one packed word = 16 characters)
+        // stage their text as '(' and ')' bit planes (lane = one word = 32 characters)
         {
             const char* src = ss + (size_t)sl * max_lines * ss_stride;
             const int nu = n_used < L_CAP ? n_used : L_CAP;
             for (int x = lane; x < nu * wpl; x += 64) {
                 const int us = x / wpl, wi = x - us * wpl, ln = lline[us];
-                const char* p = src + (size_t)ln * ss_stride + wi * 16;
-                const int lim = ss_stride - wi * 16;       // bytes of this line left
-                unsigned v = 0;
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    unsigned four = 0;
-                    if (q * 4 + 4 <= lim) four = *reinterpret_cast<const unsigned*>(p + q * 4);
-#pragma unroll
-                    for (int b = 0; b < 4; b++) {
-                        const unsigned ch = (four >> (8 * b)) & 0xffu;
-                        v |= (ch == '(' ? 1u : (ch == ')' ? 2u : 0u)) << ((q * 4 + b) * 2);
-                    }
-                }
-                textw[x] = v;
+                textw[x] = d_stage_word(src + (size_t)ln * ss_stride, ss_stride, wi);
             }
         }
         __syncthreads();
+        PCLK(0)
         // ---- phase 1: structures (lane per line, chunks of 64 lines)
         int nst = 0;
         for (int lb = 0; lb < nl; lb += 64) {
@@ -246,26 +267,26 @@ __global__ void __launch_bounds__(64, MIRP_PRED_WPS) predict_kernel(
             if (k < nl) {
                 MirpFoldLine ln = wl[k];
                 const int us = lslot[k];
-                SS s; s.w = textw + (size_t)(us == 0xffff ? 0 : us) * wpl; s.o = 0;
+                SSW s; s.w = textw + (size_t)(us == 0xffff ? 0 : us) * wpl; s.o = 0;
                 if (ln.printed && ln.len >= pp.minlen && us != 0xffff) {
-                    if (d_is_stem_loop(s, ln.len)) {
+                    if (ssw_is_stem_loop(s, ln.len)) {
                         PStruct p; p.line = (unsigned short)k; p.off = 0; p.len = (unsigned short)ln.len; p.type = 0;
                         slot[lane * PW_MAX_PIECES + cnt++] = p;
                     } else {
                         // filter_ss (MP:1685-1724): one piece per top-level stem, [previous gap start, next stem start)
                         int len = ln.len;
-                        int prefirst = d_find(s, '(', 0, len);
+                        int prefirst = ssw_find(s, '(', 0, len);
                         if (prefirst >= 0) {
-                            int prelast = d_partner(s, len, prefirst), curfirst = prefirst, curlast = prelast, pregap0 = 0;
+                            int prelast = ssw_partner(s, len, prefirst), curfirst = prefirst, curlast = prelast, pregap0 = 0;
                             while (curfirst != -1) {
-                                curfirst = d_find(s, '(', prelast < 0 ? len : prelast, len);
+                                curfirst = ssw_find(s, '(', prelast < 0 ? len : prelast, len);
                                 int after1 = len;
-                                if (curfirst != -1) { after1 = curfirst; curlast = d_partner(s, len, curfirst); }
+                                if (curfirst != -1) { after1 = curfirst; curlast = ssw_partner(s, len, curfirst); }
                                 int ps = pregap0, pl = after1 - pregap0;
                                 if (pl > 55) {
                                     int type = -1;
-                                    if (d_is_stem_loop(s + ps, pl)) type = 0;
-                                    else if (d_good_bifurcation(s + ps, pl)) type = 1;
+                                    if (ssw_is_stem_loop(s + ps, pl)) type = 0;
+                                    else if (ssw_good_bifurcation(s + ps, pl)) type = 1;
                                     if (type >= 0) {
                                         if (cnt < PW_MAX_PIECES) {
                                             PStruct p; p.line = (unsigned short)k; p.off = (unsigned short)ps; p.len = (unsigned short)pl; p.type = (unsigned short)type;
@@ -281,16 +302,16 @@ __global__ void __launch_bounds__(64, MIRP_PRED_WPS) predict_kernel(
                     }
                 }
             }
-            cnts[lane] = cnt;
-            __syncthreads();
-            // ordered compaction (line order, piece order)
-            int base = nst;
-            for (int l = 0; l < 64; l++) { if (l < lane) base += cnts[l]; }
+            PCLK(1)
+            // ordered compaction (line order, piece order): a wave prefix sum of the lanes' counts
+            int incl = cnt;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
+            const int base = nst + incl - cnt;
             for (int c = 0; c < cnt; c++) { if (base + c < max_structs) sts[base + c] = slot[lane * PW_MAX_PIECES + c]; else st_flag = 2; }
-            int tot = 0;
-            for (int l = 0; l < 64; l++) tot += cnts[l];
-            nst += tot;
+            nst += __shfl(incl, 63);
             __syncthreads();
+            PCLK(2)
         }
         if (need) {          // what this window needs, for the re-run of flagged windows: structures in all, pieces of its richest line
             int np = need_pieces;
@@ -301,38 +322,68 @@ __global__ void __launch_bounds__(64, MIRP_PRED_WPS) predict_kernel(
         // ---- phases 2+3 per mature, depth-descending stable order (MP:2241)
         int nm = W.n_matures < PW_MAX_MATURES ? W.n_matures : PW_MAX_MATURES;
         if (W.n_matures > PW_MAX_MATURES) st_flag = 3;
-        for (int k = lane; k < nm; k += 64) {          // rank of mature k among the first nm: lane-parallel, then the order is a table
-            const int dk = matures[W.mature_off + k].depth;
+        if (nm <= 64) {          // lane k holds mature k, read once: its rank among the nm by shuffles
+            int dk = 0;
+            if (lane < nm) dk = matures[W.mature_off + lane].depth;
             int r = 0;
-            for (int j = 0; j < nm; j++) { const int dj = matures[W.mature_off + j].depth; if (dj > dk || (dj == dk && j < k)) r++; }
-            morder[r] = k;
+            for (int j = 0; j < nm; j++) { const int dj = __shfl(dk, j); if (dj > dk || (dj == dk && j < lane)) r++; }
+            if (lane < nm) morder[r] = lane;
+        } else {
+            for (int k = lane; k < nm; k += 64) {          // rank of mature k among the first nm: lane-parallel, then the order is a table
+                const int dk = matures[W.mature_off + k].depth;
+                int r = 0;
+                for (int j = 0; j < nm; j++) { const int dj = matures[W.mature_off + j].depth; if (dj > dk || (dj == dk && j < k)) r++; }
+                morder[r] = k;
+            }
         }
         __syncthreads();
+        // keep the matures inside the length range, in rank order, in place: morder[0 .. n_in)
+        int n_in = 0;
+        for (int rb = 0; rb < nm; rb += 64) {
+            const int rank = rb + lane;
+            int mi = -1;
+            bool inr = false;
+            if (rank < nm) { mi = morder[rank]; const MirpMature mk = matures[W.mature_off + mi]; const int l = mk.end - mk.start; inr = !(l < pp.min_mature_len || l > pp.max_mature_len); }
+            const unsigned long long bal = __ballot(inr);
+            __syncthreads();          // every read of this chunk before a write into it (a write goes to an index <= its lane's rank)
+            if (inr) morder[n_in + (int)__popcll(bal & ((1ull << lane) - 1ull))] = mi;
+            n_in += (int)__popcll(bal);
+        }
+        __syncthreads();
+        const bool any_in_range = n_in > 0;
         int nout = 0;
         const long long wk0 = wave_lower_bound(alns, n_alns, W.tid, W.ws), wk1 = wave_lower_bound(alns, n_alns, W.tid, W.we);
-        bool any_in_range = false;
-        for (int k = 0; k < nm; k++) { MirpMature m = matures[W.mature_off + k]; int l = m.end - m.start; if (!(l < pp.min_mature_len || l > pp.max_mature_len)) any_in_range = true; }
+        PCLK(3)
         if (nst > 0 && any_in_range) {
-            for (int rank = 0; rank < nm; rank++) {
-                const int mi = morder[rank];          // rank-th mature in stable depth-descending order
-                MirpMature m = matures[W.mature_off + mi];
-                int ml = m.end - m.start;
-                if (ml < pp.min_mature_len || ml > pp.max_mature_len) continue;
-                // Each lane evaluates its structures and keeps its own winner of the sequential rule of MP:2246-2343
-                // ("for s in order: skip if ne > lowest; if it passes: best = s, lowest = ne", lowest starting at 0.0), which selects the
-                // passing structure with the smallest normalised energy <= 0 and, among equals, the LAST one in order.
-                double b_ne = 0.0;
-                int b_s = -1, b_has_star = 0, b_star_s = 0, b_star_e = 0, b_fold_s = 0, b_fold_e = 0, b_tm = 0, b_ts = 0, b_imp = 0;
-                for (int sb = 0; sb < nst; sb += 64) {
-                    int s = sb + lane;
-                    if (s < nst) {
+            // Phases 2+3: a lane per (in-range mature in rank order, structure) pair, in passes of 64 pairs -- one pass for nearly every window, where the
+            // loop over matures ran a pass per mature with a tenth of the lanes.  Per mature the sequential rule of MP:2246-2343 ("for s in order: skip if
+            // ne > lowest; if it passes: best = s, lowest = ne", lowest starting at 0.0) selects the passing structure with the smallest normalised
+            // energy <= 0 and, among equals, the LAST one in order: an arg-min over the lanes that hold the mature's pairs, carried (c_*) to the next
+            // pass when the mature's pairs go on there.  The winner's lane writes the row; a better one of a later pass writes over it.
+            const int npairs = n_in * nst;
+            double c_ne = 0.0;
+            int c_s = -1, c_i = -1;
+            for (int pb = 0; pb < npairs; pb += 64) {
+                const int pr = pb + lane;
+                int pi = -1, s = -1, pass = 0;
+                double ne = 0.0;
+                MirpMature m;
+                m.start = m.end = m.strand = m.depth = 0;
+                int b_has_star = 0, b_star_s = 0, b_star_e = 0, b_fold_s = 0, b_fold_e = 0, b_tm = 0, b_ts = 0, b_imp = 0;
+                {
+                    if (pr < npairs) {
+                        pi = pr / nst; s = pr - pi * nst;
+                        const int mi = morder[pi];          // the pi-th in-range mature in stable depth-descending order
+                        m = matures[W.mature_off + mi];
                         const PStruct p = sts[s];
                         const MirpFoldLine ln = wl[p.line];
-                        const double ne = ((double)ln.energy / 100.0) / (double)ln.len;
-                        SS str; str.w = textw + (size_t)lslot[p.line] * wpl; str.o = p.off;
+                        ne = ((double)ln.energy / 100.0) / (double)ln.len;
+                        SSW str; str.w = textw + (size_t)lslot[p.line] * wpl; str.o = p.off;
                         MStar ms;
-                        d_maturestar(str, p.len, m.start, m.end, ln.start + p.off, W.ws, W.we, m.strand, ms);
-                        int pass = 0, has_star = 0, star_s = ms.star_s, star_e = ms.star_e, impf = 0;
+                        PCLK(6)
+                        ssw_maturestar(str, p.len, m.start, m.end, ln.start + p.off, W.ws, W.we, m.strand, ms);
+                        PCLK(4)
+                        int has_star = 0, star_s = ms.star_s, star_e = ms.star_e, impf = 0;
                         long long tm = 0, ts = 0;
                         ExprRes rx;
                         rx.exception = true;
@@ -359,13 +410,14 @@ __global__ void __launch_bounds__(64, MIRP_PRED_WPS) predict_kernel(
                                 }
                             }
                         }
+                        PCLK(5)
                         if (REASONS) {
                             int flags = 0;
                             ExprRes* exp_ = nullptr;
                             (void)exp_;
                             if (rrec) {
                                 int* r = rrec;
-                                r[0] = w; r[1] = mi; r[2] = s; r[3] = p.line; r[4] = p.off; r[5] = p.len; r[6] = ms.code; r[8] = ms.fold_s; r[9] = ms.fold_e;
+                                r[0] = w; r[1] = morder[pi]; r[2] = s; r[3] = p.line; r[4] = p.off; r[5] = p.len; r[6] = ms.code; r[8] = ms.fold_s; r[9] = ms.fold_e;
                                 r[10] = ms.star_s; r[11] = ms.star_e;
                                 if (ms.code == 0) {
                                     // the depth fields saturate at 2^31 - 1 like MirpMirna's totals; the flags below follow the 64-bit sums
@@ -388,32 +440,41 @@ __global__ void __launch_bounds__(64, MIRP_PRED_WPS) predict_kernel(
                                 r[7] = flags;
                             }
                         }
-                        if (pass && ne <= b_ne) {   // later structures win ties (this lane's s only grows)
-                            b_ne = ne; b_s = s; b_has_star = has_star; b_star_s = star_s; b_star_e = star_e; b_fold_s = ms.fold_s; b_fold_e = ms.fold_e;
-                            b_tm = (int)(tm > 0x7fffffffLL ? 0x7fffffffLL : tm); b_ts = (int)(ts > 0x7fffffffLL ? 0x7fffffffLL : ts); b_imp = impf;
+                        pass = (pass && ne <= 0.0) ? 1 : 0;
+                        b_has_star = has_star; b_star_s = star_s; b_star_e = star_e; b_fold_s = ms.fold_s; b_fold_e = ms.fold_e;
+                        b_tm = (int)(tm > 0x7fffffffLL ? 0x7fffffffLL : tm); b_ts = (int)(ts > 0x7fffffffLL ? 0x7fffffffLL : ts); b_imp = impf;
+                    }
+                }
+                // the matures of this pass, in rank order
+                const int last_pair = (pb + 63 < npairs - 1) ? pb + 63 : npairs - 1;
+                for (int ii = pb / nst; ii <= last_pair / nst; ii++) {
+                    if (c_i != ii) { c_i = ii; c_ne = 0.0; c_s = -1; }
+                    const bool mine = pi == ii && pass;
+                    if (__ballot(mine) != 0ull) {
+                        // wave arg-min over (ne ascending, s descending) among the lanes that hold a passing pair of this mature
+                        double r_ne = ne;
+                        int r_s = mine ? s : -1;
+                        for (int o = 32; o > 0; o >>= 1) {
+                            const double t_ne = __shfl_xor(r_ne, o);
+                            const int t_s = __shfl_xor(r_s, o);
+                            const bool take = t_s >= 0 && (r_s < 0 || t_ne < r_ne || (t_ne == r_ne && t_s > r_s));
+                            if (take) { r_ne = t_ne; r_s = t_s; }
+                        }
+                        if (c_s < 0 || r_ne < c_ne || (r_ne == c_ne && r_s > c_s)) {          // against what the passes before found for it (their s is smaller)
+                            c_ne = r_ne; c_s = r_s;
+                            if (mine && s == r_s && nout < MIRP_MAX_MIRNA_PER_WINDOW) {   // exactly one lane owns the winner
+                                const PStruct bp = sts[r_s];
+                                MirpMirna r;
+                                r.window = w; r.tid = W.tid; r.fold_s = b_fold_s; r.fold_e = b_fold_e; r.mat_s = m.start; r.mat_e = m.end;
+                                r.star_s = b_star_s; r.star_e = b_star_e; r.strand = m.strand; r.has_star = b_has_star;
+                                r.line = bp.line; r.ss_off = bp.off; r.ss_len = bp.len; r.reserved = b_imp;
+                                r.total_depth_mature = b_tm; r.total_depth_star = b_ts;
+                                out[(size_t)w * MIRP_MAX_MIRNA_PER_WINDOW + nout] = r;
+                            }
                         }
                     }
-                }
-                // wave arg-min over (ne ascending, s descending) among lanes that have a candidate
-                double r_ne = b_ne;
-                int r_s = b_s;
-                for (int o = 32; o > 0; o >>= 1) {
-                    const double t_ne = __shfl_xor(r_ne, o);
-                    const int t_s = __shfl_xor(r_s, o);
-                    const bool take = t_s >= 0 && (r_s < 0 || t_ne < r_ne || (t_ne == r_ne && t_s > r_s));
-                    if (take) { r_ne = t_ne; r_s = t_s; }
-                }
-                if (r_s >= 0 && nout < MIRP_MAX_MIRNA_PER_WINDOW) {
-                    if (b_s == r_s) {   // exactly one lane owns the winner
-                        const PStruct bp = sts[r_s];
-                        MirpMirna r;
-                        r.window = w; r.tid = W.tid; r.fold_s = b_fold_s; r.fold_e = b_fold_e; r.mat_s = m.start; r.mat_e = m.end;
-                        r.star_s = b_star_s; r.star_e = b_star_e; r.strand = m.strand; r.has_star = b_has_star;
-                        r.line = bp.line; r.ss_off = bp.off; r.ss_len = bp.len; r.reserved = b_imp;
-                        r.total_depth_mature = b_tm; r.total_depth_star = b_ts;
-                        out[(size_t)w * MIRP_MAX_MIRNA_PER_WINDOW + nout] = r;
-                    }
-                    nout++;
+                    // the mature's last pair lies in this pass: its row, if it has one, is final
+                    if ((ii + 1) * nst <= pb + 64 && c_s >= 0 && nout < MIRP_MAX_MIRNA_PER_WINDOW) nout++;
                 }
             }
         }
@@ -432,6 +493,8 @@ __global__ void __launch_bounds__(64, MIRP_PRED_WPS) predict_kernel(
             for (int o = 32; o > 0; o >>= 1) { int t = __shfl_xor(f, o); f = t > f ? t : f; }
             if (lane == 0) status[w] = f;
         }
+        PCLK(6)
+        PCLK_FLUSH
         __syncthreads();
     }
 }
@@ -455,9 +518,9 @@ PredictCaps predict_default_caps(int max_lines, int ss_stride) {
 }
 
 size_t predict_lds_bytes(int max_lines, int ss_stride, PredictCaps caps, bool text_in_lds) {
-    size_t b = text_in_lds ? (((size_t)caps.l_cap * ((ss_stride + 15) >> 4) * 4 + 15) & ~(size_t)15) : 0;
+    size_t b = text_in_lds ? (((size_t)caps.l_cap * ssw_words(ss_stride) * 8 + 15) & ~(size_t)15) : 0;
     b += sizeof(PStruct) * ((size_t)caps.s_cap + 64 * (size_t)caps.p_cap);
-    b += sizeof(int) * (64 + (size_t)caps.m_cap);
+    b += sizeof(int) * (size_t)caps.m_cap;
     b += sizeof(unsigned short) * ((size_t)max_lines + (size_t)caps.l_cap);
     return (b + 15) & ~(size_t)15;
 }
@@ -471,7 +534,7 @@ template <bool REASONS, bool GTEXT>
 static hipError_t launch_predict_as(hipStream_t stream, int grid, size_t lds, const MirpWindow* windows, int n_windows, const MirpMature* matures,
                                     const MirpAln* alns, long long n_alns, const MirpFoldLine* lines, const char* ss, int ss_stride, int max_lines,
                                     const int* n_lines, MirpPredictParams pp, MirpMirna* out, int* n_out, int* status, unsigned int* rcount, int* rpool,
-                                    unsigned int rcap, int rstride, const int* wsel, int n_sel, const int* skip, const int* wslot, PredictCaps caps, int* need, unsigned* gtext) {
+                                    unsigned int rcap, int rstride, const int* wsel, int n_sel, const int* skip, const int* wslot, PredictCaps caps, int* need, unsigned long long* gtext) {
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)predict_kernel<REASONS, GTEXT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -501,9 +564,9 @@ hipError_t launch_predict(hipStream_t stream, int grid, const MirpWindow* window
     // the staged text does not fit in LDS: a scratch area per workgroup in global memory (a few workgroups: the area is l_cap lines of ss_stride / 4 bytes each),
     // allocated and released around the launch -- the path of PRECURSOR_LEN in the thousands, not of the benchmark
     lds = predict_lds_bytes(max_lines, ss_stride, caps, false);
-    const size_t per = (size_t)caps.l_cap * ((ss_stride + 15) >> 4) * 4;
+    const size_t per = (size_t)caps.l_cap * ssw_words(ss_stride) * 8;
     grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, ((size_t)2 << 30) / std::max<size_t>(per, 1)));
-    unsigned* gtext = nullptr;
+    unsigned long long* gtext = nullptr;
     hipError_t e = hipMalloc((void**)&gtext, per * (size_t)grid + 16);
     if (e != hipSuccess) return e;
     if (rpool)
@@ -554,6 +617,9 @@ int run_predict_launch(hipStream_t stream, int n_cu, const MirpWindow* windows, 
         (rcount && hipMemcpyAsync(&n1, rcount, 4, hipMemcpyDeviceToHost, stream) != hipSuccess) || hipStreamSynchronize(stream) != hipSuccess) {
         *err = "predict kernel execution failed"; return -2;
     }
+#ifdef MIRP_DIAG
+    if (std::getenv("MIRP_PREDICT_CLOCKS")) predict_clocks_print();
+#endif
     if (wsel) { h_sel.resize((size_t)n_sel); if (hipMemcpy(h_sel.data(), wsel, 4 * (size_t)n_sel, hipMemcpyDeviceToHost) != hipSuccess) { *err = "D2H failed"; return -2; } }
     else if (skip) { h_skip.resize((size_t)n_windows); if (hipMemcpy(h_skip.data(), skip, 4 * (size_t)n_windows, hipMemcpyDeviceToHost) != hipSuccess) { *err = "D2H failed"; return -2; } }
     std::vector<int> rw, rs;          // windows to run again, their slots
