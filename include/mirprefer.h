@@ -1011,9 +1011,10 @@ int mirp_homolog_contigs(mirp_ctx* ctx, char** names, int64_t* names_bytes, int6
  * to test the multi-pass, multi-chunk and re-run paths. */
 int mirp_set_homolog_capacity(mirp_ctx* ctx, int64_t keys, int64_t chunk, int32_t fold_lines, int32_t pieces, int32_t structures, int32_t staged_lines);
 /* stats = {queries, queries dropped by max_placements, placements (= windows folded), placements with a passing structure, loci, scan passes,
- * chunks, folds (a chunk is folded again when a window needs more structure lines), evaluation re-runs, 0, then at 10 + k the placements without a
- * passing structure whose structure of lowest normalised energy has get_maturestar_info code k = 1..12, and at 23 those whose structure list is
- * empty} of the last mirp_homolog_scan; seconds = {scan, windows, fold, evaluation + download, merge}. */
+ * chunks, folds (a chunk is folded again when a window needs more structure lines), evaluation re-runs, at 9 the launches of the evaluation kernel
+ * whose staged structure text lay in global memory instead of LDS, 0 at 10, then at 10 + k the placements without a passing structure whose
+ * structure of lowest normalised energy has get_maturestar_info code k = 1..12, and at 23 those whose structure list is empty} of the last
+ * mirp_homolog_scan; seconds = {scan, windows, fold, evaluation + download, merge}. */
 int mirp_homolog_last_stats(mirp_ctx* ctx, int64_t stats[24], double seconds[5]);
 
 /* Inverted repeats of a genome: the banded local alignment of every contig with its own reverse complement.  Cell (i, j), i < j,

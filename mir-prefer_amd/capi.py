@@ -129,7 +129,7 @@ class HomologOpts(C.Structure):
 HOMOLOG_DTYPE = np.dtype([(f, "<i4") for f in ("query", "contig", "strand", "mismatches", "mat_s", "mat_e", "star_s", "star_e", "fold_s", "fold_e", "win_s",
                                                "win_e", "prime5", "total_bps", "total_dots", "energy", "line_len", "ss_len", "n_also", "reserved")] +
                          [("text_off", "<i8"), ("also_off", "<i8")])
-HOMOLOG_STATS = ("queries", "repeat_like", "placements", "passing", "loci", "scan_passes", "chunks", "folds", "eval_reruns")
+HOMOLOG_STATS = ("queries", "repeat_like", "placements", "passing", "loci", "scan_passes", "chunks", "folds", "eval_reruns", "eval_global_text")
 
 # MirpUnpairedRec of include/mirprefer.h: one window of mirp_unpaired_batch, kcal/mol
 UNPAIRED_DTYPE = np.dtype([("efe", "<f8"), ("efe_open", "<f8"), ("upe", "<f8")])
@@ -1175,13 +1175,14 @@ class Context:
         return blob.split("\0")[:-1], ln
 
     def homolog_last_stats(self):
-        """{queries, repeat_like, placements, passing, loci, scan_passes, chunks, folds, eval_reruns, fail_codes, no_structure, seconds} of the
-        last homolog_scan; fail_codes[k]: placements without a passing structure whose structure of lowest normalised energy has
-        get_maturestar_info code k (index 0 unused); seconds = {scan, windows, fold, evaluation + download, merge}."""
+        """{queries, repeat_like, placements, passing, loci, scan_passes, chunks, folds, eval_reruns, eval_global_text (launches of the evaluation
+        kernel with the staged text in global memory), fail_codes, no_structure, seconds} of the last homolog_scan; fail_codes[k]:
+        placements without a passing structure whose structure of lowest normalised energy has get_maturestar_info code k (index 0 unused);
+        seconds = {scan, windows, fold, evaluation + download, merge}."""
         st = (C.c_int64 * 24)()
         sec = (C.c_double * 5)()
         self._check(self.lib.mirp_homolog_last_stats(self.h, st, sec), "mirp_homolog_last_stats")
-        return dict(zip(HOMOLOG_STATS, list(st)[:9]), fail_codes=[0] + list(st)[11:23], no_structure=int(st[23]), seconds=list(sec))
+        return dict(zip(HOMOLOG_STATS, list(st)[:10]), fail_codes=[0] + list(st)[11:23], no_structure=int(st[23]), seconds=list(sec))
 
     def last_jobs_per_slot(self, family):
         """(launches, the largest ceil(jobs / slots) over them) of a wave-per-job kernel family in the last call that can launch it

@@ -166,26 +166,6 @@ __global__ void hm_winseq_kernel(AlRef R, const HmWin* __restrict__ win, long lo
 // needs more is flagged (status 2) with what it needs and run again with capacities sized for it.
 struct HmCaps { int p_cap, s_cap, l_cap; };
 
-// mature / star duplex figures of a passing structure (the values get_maturestar_info returns beside the star, MP:1876-1999)
-__device__ void hm_duplex_stats(SSW ss, int len, int l0, int l1, int* prime5, int* total_bps, int* total_dots) {
-    int a = l0, b = l1; ssw_clip(len, a, b);
-    char sym = '(';
-    *prime5 = 1;
-    int firstbp = ssw_find(ss, '(', a, b);
-    if (firstbp == -1) { firstbp = ssw_find(ss, ')', a, b); sym = ')'; *prime5 = 0; }
-    const int p_first = ssw_partner(ss, len, firstbp);
-    int ra = l0, rb = l1 - 2; ssw_clip(len, ra, rb);
-    const int mend = ssw_rfind(ss, sym, ra, rb);
-    const int p_mend = ssw_partner(ss, len, mend);
-    int md0 = l0, md1 = mend + 1, sd0 = p_mend, sd1 = p_first + 1;
-    ssw_clip(len, md0, md1); ssw_clip(len, sd0, sd1);
-    if (md1 < md0) md1 = md0;
-    if (sd1 < sd0) sd1 = sd0;
-    const int mdots = ssw_count(ss, '.', md0, md1);
-    *total_dots = mdots + ssw_count(ss, '.', sd0, sd1);
-    *total_bps = (md1 - md0) - mdots;
-}
-
 // wsel == nullptr: the windows [0, n_windows); else the windows wsel[0 .. n_sel).  Window w's fold output is at slot w.  need[3 w] = structures,
 // need[3 w + 1] = pieces of one line, need[3 w + 2] = lines to stage that the window has.  gtext != nullptr: the staged text lives in a global
 // scratch area of the workgroup instead of LDS.
@@ -342,7 +322,7 @@ __global__ void __launch_bounds__(64) homolog_eval_kernel(const HmWin* __restric
                 SSW str; str.w = textw + (size_t)lslot[bp.line] * wpl; str.o = bp.off;
                 const int fst = ln.start + bp.off;
                 const int l0 = W.strand == 0 ? W.m0 - W.ws - fst + 1 : W.we - W.m1 - fst + 1, l1 = l0 + (W.m1 - W.m0);
-                hm_duplex_stats(str, bp.len, l0, l1, &e.prime5, &e.total_bps, &e.total_dots);
+                ssw_duplex_stats(str, bp.len, l0, l1, &e.prime5, &e.total_bps, &e.total_dots);
                 e.star_s = p_ms.star_s; e.star_e = p_ms.star_e; e.fold_s = p_ms.fold_s; e.fold_e = p_ms.fold_e;
                 e.energy = ln.energy; e.line_len = ln.len; e.ss_len = bp.len;
             }
@@ -490,9 +470,10 @@ int mirp_device_homolog_scan(mirp_ctx* c, const unsigned char* codes, const long
 
 // Windows, fold and evaluation of the n placements keys[0 .. n): win[i], ev[i] and, for a placement with a passing structure, at text[text_off[i]]
 // the we - ws letters of its window on its strand followed by the ev[i].ss_len characters of the structure.  max_lines: structure lines the fold keeps per window at first; a chunk with a window that needs more
-// is folded again with room for it.  stats += {fold chunks, evaluation re-runs, folds repeated for more lines}; seconds += {windows, fold, evaluation + download}.
+// is folded again with room for it.  stats += {fold chunks, evaluation re-runs, folds repeated for more lines, evaluation launches with the staged
+// text in global memory}; seconds += {windows, fold, evaluation + download}.
 int mirp_device_homolog_eval(mirp_ctx* c, const unsigned long long* keys, long long n, int precursor_len, int max_lines, HmWin* win, HmEval* ev,
-                             std::vector<char>& text, long long* text_off, long long stats[3], double seconds[3]) {
+                             std::vector<char>& text, long long* text_off, long long stats[4], double seconds[3]) {
     if (n <= 0) return 0;
     hipStream_t st = c->stream;
     const AlRef R = hm_ref(c);
@@ -573,6 +554,7 @@ int mirp_device_homolog_eval(mirp_ctx* c, const unsigned long long* keys, long l
             grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, ((size_t)1 << 30) / std::max<size_t>(per, 1)));
             gtext = (unsigned long long*)T.get(per * (size_t)grid + 16);
             if (!gtext) return fail(c, -6, "device allocation failed (homologs: staged text)");
+            stats[3]++;
         }
         c->note_jobs_per_slot(3, n_iter, grid);
         if (lds > 64 * 1024) HIPCHK(c, hipFuncSetAttribute((const void*)homolog_eval_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -386,7 +386,7 @@ int mirp_device_inverted(mirp_ctx* c, const IvGenome& G, const MirpInvertedOpts&
 int mirp_device_homolog_scan(mirp_ctx* c, const unsigned char* codes, const long long* roff, long long nq, int v, int max_placements,
                              std::vector<unsigned long long>& keys, long long stats[3]);
 int mirp_device_homolog_eval(mirp_ctx* c, const unsigned long long* keys, long long n, int precursor_len, int max_lines, HmWin* win, HmEval* ev,
-                             std::vector<char>& text, long long* text_off, long long stats[3], double seconds[3]);
+                             std::vector<char>& text, long long* text_off, long long stats[4], double seconds[3]);
 int mirp_device_mask_alns(mirp_ctx* c, MirpAln* d_alns, MirpAln* d_tmp, long long* n_io, MirpAln* d_segs, MirpAln* d_segtmp, const int* d_owner, const int* d_seg_span,
                           long long* nseg_io,
                           const long long* d_rfirst, const int* d_rstart, const int* d_remax);

@@ -115,14 +115,14 @@ extern "C" int mirp_homolog_scan(mirp_ctx* c, const char* q_blob, const int64_t*
     std::vector<long long> text_off(n);
     std::vector<char> wtext;
     double sec3[3] = {0, 0, 0};
-    long long est3[3] = {0, 0, 0};
+    long long est4[4] = {0, 0, 0, 0};
     for (size_t p0 = 0; p0 < n; p0 += (size_t)chunk) {
         const long long m = (long long)std::min<size_t>((size_t)chunk, n - p0);
-        if (int rc = mirp_device_homolog_eval(c, keys.data() + p0, m, o->precursor_len, lines0, win.data() + p0, ev.data() + p0, wtext, text_off.data() + p0, est3, sec3))
+        if (int rc = mirp_device_homolog_eval(c, keys.data() + p0, m, o->precursor_len, lines0, win.data() + p0, ev.data() + p0, wtext, text_off.data() + p0, est4, sec3))
             return rc;
         S[6]++;
     }
-    S[7] = est3[0]; S[8] = est3[1];
+    S[7] = est4[0]; S[8] = est4[1]; S[9] = est4[3];
     for (int i = 0; i < 3; i++) c->hm_sec[1 + i] = sec3[i];
     // ---- merge: placements at one (contig, strand, interval) are one locus, named by the fewest mismatches, then the earlier query
     t = mirp::now();

@@ -354,4 +354,26 @@ SSW_HD void ssw_maturestar(SSW ss, int len, int m0, int m1, int foldstart, int r
     else { o.star_s = re - foldstart - star_end + 1; o.star_e = re - foldstart - star_start + 1; }
 }
 
+// mature / star duplex figures of a passing structure (the values get_maturestar_info returns beside the star, MP:1876-1999): prime5 = the mature
+// [l0, l1) of the view lies in the 5' arm, total_bps = the paired characters of the mature side of the duplex, total_dots = the unpaired ones of both
+// sides.  Called on a structure that ssw_maturestar passed with the same interval, so the first bracket, mend and their partners exist.
+SSW_HD void ssw_duplex_stats(SSW ss, int len, int l0, int l1, int* prime5, int* total_bps, int* total_dots) {
+    int a = l0, b = l1; ssw_clip(len, a, b);
+    char sym = '(';
+    *prime5 = 1;
+    int firstbp = ssw_find(ss, '(', a, b);
+    if (firstbp == -1) { firstbp = ssw_find(ss, ')', a, b); sym = ')'; *prime5 = 0; }
+    const int p_first = ssw_partner(ss, len, firstbp);
+    int ra = l0, rb = l1 - 2; ssw_clip(len, ra, rb);
+    const int mend = ssw_rfind(ss, sym, ra, rb);
+    const int p_mend = ssw_partner(ss, len, mend);
+    int md0 = l0, md1 = mend + 1, sd0 = p_mend, sd1 = p_first + 1;
+    ssw_clip(len, md0, md1); ssw_clip(len, sd0, sd1);
+    if (md1 < md0) md1 = md0;
+    if (sd1 < sd0) sd1 = sd0;
+    const int mdots = ssw_count(ss, '.', md0, md1);
+    *total_dots = mdots + ssw_count(ss, '.', sd0, sd1);
+    *total_bps = (md1 - md0) - mdots;
+}
+
 }  // namespace mirp

@@ -61,11 +61,18 @@ def window_of(contig, o, L, P, strand):
 
 
 @functools.lru_cache(maxsize=None)
+def _lines(letters, span, model):
+    """[(ss, energy, start)]: the structure lines of a window's fold."""
+    from tests import oracle_binding
+    return oracle_binding.load().lfold(letters, span, model=model)["lines"]
+
+
+@functools.lru_cache(maxsize=None)
 def _structures(letters, span, model):
     """[(norm_energy, fold_start, ss, sstype, line energy, line length)] of a window: a8's list, each entry with its line's figures."""
     from tests import oracle_binding
     o = oracle_binding.load()
-    lines = o.lfold(letters, span, model=model)["lines"]
+    lines = _lines(letters, span, model)
     whole = o.structures_from_lines(lines, 55)
     per_line = []
     for ss, e, st in lines:
@@ -187,6 +194,196 @@ def mixture():
     contigs, queries, planted = planted_genome(**MIXTURE)
     loci, stats = run(queries, contigs, v=2)
     return contigs, queries, planted, loci, stats
+
+
+# ---- inputs of tests/test_homologs_large_gpu.py: windows of 600 .. 2,500 nt.  Every builder returns its input with the figures its test conditions
+# read, computed from the restatement alone; tests/test_homologs_cpu.py asserts those conditions without a GPU.
+FOLD_LINES, STAGED_LINES, MIN_LINE = 96, 48, 55          # mirp_homolog_scan's defaults: lines the fold keeps at first, lines staged at first, a8's minlen
+ORACLE_MAX_LINES, ORACLE_MAX_STRUCTS = 384, 512           # what tests/oracle_binding.py holds per window
+BOUNDARIES = (32, 64, 96, 128, 160, 192)
+_SWAP = {"A": "C", "C": "A", "G": "T", "T": "G"}
+
+
+def ssw_words(n_chars):
+    return (n_chars + 31) >> 5
+
+
+def eval_lds(max_lines, stride, caps, text_in_lds=True):
+    """hm_eval_lds of homolog_kernels.hip: the dynamic LDS bytes of homolog_eval_kernel at caps = (pieces, structures, staged lines)."""
+    p_cap, s_cap, l_cap = caps
+    b = ((l_cap * ssw_words(stride) * 8 + 15) & ~15) if text_in_lds else 0
+    b += 8 * (s_cap + 64 * p_cap) + 4 * 64 + 2 * (max_lines + l_cap)
+    return (b + 15) & ~15
+
+
+def window_shapes(queries, contigs, v, P, max_placements=100, model="vienna-2.1.2"):
+    """[{letters, lines, usable (lines of at least 55 characters), structures}] of every placement's window, in placement order."""
+    pl, _ = placements([q for q, _ in queries], contigs, v, max_placements)
+    out = []
+    for q, ci, o, strand, mm in pl:
+        _, _, letters = window_of(contigs[ci][1], o, len(queries[q][0]), P, strand)
+        lines = _lines(letters, P, model)
+        out.append({"letters": len(letters), "lines": len(lines), "usable": sum(1 for ss, _, _ in lines if len(ss) >= MIN_LINE),
+                    "structures": len(_structures(letters, P, model))})
+    return out
+
+
+def natural_launch(shapes):
+    """(max_lines, stride, caps of the last evaluation round, its LDS bytes with the text in LDS) of mirp_device_homolog_eval on one chunk of these
+    windows with nothing lowered: the fold is repeated with room for the longest line list, and the windows with more than 48 usable lines are run
+    again with capacities for the largest of them."""
+    max_lines = max([FOLD_LINES] + [w["lines"] for w in shapes])
+    stride = (max(w["letters"] for w in shapes) + 3 + 7) // 8 * 8
+    caps = (max(6, stride // 56 + 1), max(2 * max_lines, 192, *[w["structures"] for w in shapes]),
+            max([min(max_lines, STAGED_LINES)] + [min(w["usable"], max_lines) for w in shapes]))
+    return max_lines, stride, caps, eval_lds(max_lines, stride, caps)
+
+
+def within_oracle_limits(shapes):
+    return all(w["lines"] <= ORACLE_MAX_LINES and w["structures"] <= ORACLE_MAX_STRUCTS for w in shapes)
+
+
+def long_hairpin(rng, arm_len, loop_len, f5, f3, bulge_at=None, mismatch_at=None, gc=0):
+    """(5' flank, arm, loop, other arm, 3' flank): a perfect hairpin whose arm begins with `gc` letters of G and C (the whole stem is then the
+    structure of lowest normalised energy, not an inner part of it); bulge_at / mismatch_at: a 2-nt bulge and a substitution in the other arm."""
+    arm = "".join(rng.choice("GC") for _ in range(gc)) + random_seq(rng, arm_len - gc)
+    other = list(revcomp(arm))
+    if mismatch_at is not None:
+        other[mismatch_at] = _SWAP[other[mismatch_at]]
+    if bulge_at is not None:
+        other[bulge_at:bulge_at] = list("AA")
+    return random_seq(rng, f5), arm, random_seq(rng, loop_len), "".join(other), random_seq(rng, f3)
+
+
+# (arm, loop, 5' flank, 3' flank, bulge, mismatch, G/C letters): stems of 96 .. 124 nt so that either arm lies over every boundary of BOUNDARIES in some
+# structure, three of them with a bulge and a mismatch
+SWEEP = dict(seed=2, P=600, specs=((124, 8, 12, 12, None, None, 24), (120, 10, 12, 16, 40, 80), (122, 10, 12, 12, None, None, 30), (108, 9, 14, 18, 70, 30),
+                                   (96, 8, 14, 18), (96, 8, 12, 16, 30, 60)))
+
+
+def boundary_coverage(records):
+    """{(prime5, boundary, "mat" | "star", "in" | "l0" | "l1"): placements, (prime5, "far"): placements} of MatureStar records: the interval
+    straddles the boundary, starts at it, ends at it; mature and star four or more words apart."""
+    t = {}
+    for ms in records:
+        for b in BOUNDARIES:
+            for name, l0, l1 in (("mat", ms.mat_l0, ms.mat_l1), ("star", ms.star_l0, ms.star_l1)):
+                for rel, hit in (("in", l0 < b < l1), ("l0", l0 == b), ("l1", l1 == b)):
+                    if hit:
+                        t[(ms.prime5, b, name, rel)] = t.get((ms.prime5, b, name, rel), 0) + 1
+        if abs((ms.mat_l0 >> 5) - (ms.star_l0 >> 5)) >= 4:
+            t[(ms.prime5, "far")] = t.get((ms.prime5, "far"), 0) + 1
+    return t
+
+
+def coverage_gaps(t):
+    """What boundary_coverage's table lacks.  A window here is a whole contig of at most 287 nt, so a stem's 5' arm ends before character 128 of any
+    structure and its 3' arm begins after character 96: a mature in the 5' arm (prime5 = 1) meets the boundaries 32, 64, 96 and its star 128, 160,
+    192, and the other way round with the mature in the 3' arm.  Asked: at every boundary the three positions for the mature and the three for the
+    star; on either arm, at every boundary, the three positions for the interval of that arm's placements that can lie there; on either arm a
+    placement whose mature and star lie four or more words apart."""
+    gaps = []
+    for b in BOUNDARIES:
+        for name in ("mat", "star"):
+            gaps += [(b, name, rel) for rel in ("in", "l0", "l1") if not t.get((0, b, name, rel), 0) + t.get((1, b, name, rel), 0)]
+        for p in (1, 0):
+            name = "mat" if (b <= 96) == (p == 1) else "star"
+            gaps += [(p, b, name, rel) for rel in ("in", "l0", "l1") if not t.get((p, b, name, rel), 0)]
+    return gaps + [(p, "far") for p in (1, 0) if not t.get((p, "far"), 0)]
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_sweep():
+    """(contigs, queries, MatureStar of the chosen structure of every passing placement, placements): six long hairpins, each a contig short
+    enough that every placement's window at P = 600 is the whole contig (two folds per contig serve the restatement), and as queries the 21-nt
+    stretch at every offset of both arms (every 16th offset also 18 and 26 nt), none equal to another or to another's reverse complement."""
+    rng = random.Random(SWEEP["seed"])
+    P = SWEEP["P"]
+    contigs, queries, seen = [], [], set()
+    for k, spec in enumerate(SWEEP["specs"]):
+        f5, arm, loop, other, f3 = long_hairpin(rng, *spec)
+        c = f5 + arm + loop + other + f3
+        assert len(c) <= (P - 26) // 2
+        contigs.append(("hp%d" % (k + 1), c))
+        arms = ((len(f5), len(arm)), (len(f5) + len(arm) + len(loop), len(other)))
+        for off in range(len(other) - 18 + 1):
+            for start, n in (arms if off % 2 == 0 else arms[::-1]):          # the arms of a perfect stem are each other's reverse complement: take turns
+                for L in ((21,) if off % 16 else (21, 18, 26)):
+                    s = c[start + off:start + off + L]
+                    if off + L > n or s in seen or revcomp(s) in seen:
+                        continue
+                    seen.add(s)
+                    queries.append((s, ["swp-%d-%d-%d" % (k + 1, start + off, L)]))
+    pl, _ = placements([q for q, _ in queries], contigs, 0, 100)
+    records = []
+    for q, ci, o, strand, mm in pl:
+        L = len(queries[q][0])
+        ws, we, letters = window_of(contigs[ci][1], o, L, P, strand)
+        assert (ws, we) == (1, len(contigs[ci][1]) + 1)
+        best, _ = evaluate(letters, P, o + 1, o + L + 1, ws, we, strand)
+        if best is not None:
+            records.append(best[1])
+    return contigs, queries, records, len(pl)
+
+
+def spaced_genome(seed, n_planted, v, gap, repeat=None):
+    """(contigs, queries): one contig of random sequence with n_planted hairpins (planted_hairpin) on either strand, `gap` nt from each other and
+    from the contig's ends; repeat = (hairpin, unit, copies, distance): a run of `copies` x `unit` that far behind that hairpin's end."""
+    rng = random.Random(seed)
+    g = list(random_seq(rng, gap * (n_planted + 1) + 200))
+    queries = []
+    for k in range(n_planted):
+        hp, known, _ = planted_hairpin(rng, v)
+        at = gap * (k + 1)
+        g[at:at + len(hp)] = revcomp(hp) if rng.randrange(2) else hp
+        if repeat and repeat[0] == k:
+            run = repeat[1] * repeat[2]
+            g[at + len(hp) + repeat[3]:at + len(hp) + repeat[3] + len(run)] = run
+        queries.append((known, ["far-miR%d" % (k + 1)]))
+    assert len({q for q, _ in queries}) == len(queries)
+    return [("chrL", "".join(g))], queries
+
+
+THOUSAND = dict(seed=21, n_planted=4, v=1, gap=1300, repeat=(1, "GTGG", 80, 60))
+
+
+@functools.lru_cache(maxsize=None)
+def thousand():
+    """(contigs, queries, window_shapes): four planted hairpins 1,300 nt apart for windows of P = 1000 (five placements), the second with 320 nt of
+    (GTGG)n in its flank."""
+    contigs, queries = spaced_genome(**THOUSAND)
+    return contigs, queries, window_shapes(queries, contigs, THOUSAND["v"], 1000)
+
+
+def global_text_caps(shapes):
+    """(fold_lines, eval_caps) that put the staged text of these windows in global memory: the fewest lines, in steps of 64, whose words alone exceed
+    the 160 KB of LDS a workgroup can have."""
+    _, stride, _, _ = natural_launch(shapes)
+    lines = 64
+    while lines * ssw_words(stride) * 8 <= 160 * 1024:
+        lines += 64
+    return lines, (20, 2 * lines, lines)
+
+
+FIFTEEN_HUNDRED = dict(seed=41, n_planted=1, v=1, gap=800)
+
+
+@functools.lru_cache(maxsize=None)
+def fifteen_hundred():
+    """(contigs, queries, window_shapes): one planted hairpin in 1,800 nt, placed on both strands, for windows of P = 1500."""
+    contigs, queries = spaced_genome(**FIFTEEN_HUNDRED)
+    return contigs, queries, window_shapes(queries, contigs, FIFTEEN_HUNDRED["v"], 1500)
+
+
+WIDEST_P = 2600
+WIDEST = dict(seed=62, n_planted=1, v=1, gap=WIDEST_P // 2 + 60)
+
+
+@functools.lru_cache(maxsize=None)
+def widest():
+    """(contigs, queries, window_shapes): one planted hairpin placed once, for a window of P = 2600."""
+    contigs, queries = spaced_genome(**WIDEST)
+    return contigs, queries, window_shapes(queries, contigs, WIDEST["v"], WIDEST_P)
 
 
 def write_fasta(path, records):

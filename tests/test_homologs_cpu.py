@@ -97,6 +97,48 @@ def test_restatement_reports_the_mixture():
     assert stats["placements"] > stats["passing"] and sum(1 for k in stats["fail_codes"] if k) >= 3 and stats["no_structure"] > 0
 
 
+# ---- conditions of the inputs of tests/test_homologs_large_gpu.py: an input that stops exercising its path of the evaluation fails here
+def test_boundary_sweep_covers_every_word_boundary_on_either_arm():
+    """The coverage table of the sweep (hr.coverage_gaps says what is asked and why): every boundary 32 .. 192 is straddled by, begins and ends a
+    mature and a star interval of a passing placement, with the mature in either arm."""
+    contigs, queries, records, n_placements = hr.boundary_sweep()
+    assert len(contigs) == 6 and all(len(c) <= (600 - 26) // 2 for _, c in contigs)
+    seqs = [q for q, _ in queries]
+    assert len(set(seqs) | {hr.revcomp(q) for q in seqs}) == 2 * len(seqs)          # distinct, also from every reverse complement
+    assert {18, 21, 26} == {len(q) for q in seqs}
+    assert n_placements >= len(records) >= 1000
+    assert hr.coverage_gaps(hr.boundary_coverage(records)) == []
+    assert hr.coverage_gaps(hr.boundary_coverage([r for r in records if r.prime5])) != []          # the table does tell the arms apart
+    assert sum(1 for r in records if r.total_dots) >= 100 and {0, 1} == {r.prime5 for r in records}
+
+
+def test_thousand_nt_windows_need_the_refold_the_rerun_and_two_rounds_of_lines():
+    contigs, queries, shapes = hr.thousand()
+    assert 4 <= len(queries) <= 6 and len(shapes) <= 6 and all(w["letters"] == 999 for w in shapes)
+    assert max(w["lines"] for w in shapes) > hr.FOLD_LINES                  # the chunk is folded again
+    assert max(w["usable"] for w in shapes) > 64                            # more than one round of 64 lines to stage, and above the 48 staged at first
+    assert min(w["lines"] for w in shapes) <= hr.FOLD_LINES                 # beside a window the first fold holds
+    assert max(w["structures"] for w in shapes) > 64                        # the (GTGG)n window: a second round of 64 structures as well
+    assert hr.within_oracle_limits(shapes)
+    _, stride, _, lds = hr.natural_launch(shapes)
+    assert lds <= 64 * 1024                                                 # no opt-in, text in LDS
+    lines, caps = hr.global_text_caps(shapes)
+    assert lines * hr.ssw_words(stride) * 8 > 160 * 1024 >= hr.eval_lds(lines, stride, caps, text_in_lds=False) and lines >= max(w["lines"] for w in shapes)
+
+
+def test_fifteen_hundred_nt_windows_need_lds_between_64_and_160_kb():
+    contigs, queries, shapes = hr.fifteen_hundred()
+    assert 1 <= len(shapes) <= 2 and all(w["letters"] == 1499 for w in shapes) and hr.within_oracle_limits(shapes)
+    max_lines, stride, caps, lds = hr.natural_launch(shapes)
+    assert (max_lines, stride, caps, lds) == (223, 1504, (27, 446, 165), 80480) and 64 * 1024 < lds <= 160 * 1024
+
+
+def test_widest_window_stays_within_the_oracles_lines():
+    contigs, queries, shapes = hr.widest()
+    assert len(shapes) == 1 and shapes[0]["letters"] == hr.WIDEST_P - 1 and hr.within_oracle_limits(shapes)
+    assert shapes[0]["lines"] > 300 and hr.natural_launch(shapes)[3] > 160 * 1024          # its text lies in global memory on natural capacities
+
+
 # ---- the command
 @pytest.mark.parametrize("argv", [
     [], ["mature.fa"], ["-v", "4", "m.fa", "g.fa"], ["-v", "-1", "m.fa", "g.fa"], ["-P", "59", "m.fa", "g.fa"], ["-P", "3001", "m.fa", "g.fa"],

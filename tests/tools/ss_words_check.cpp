@@ -1,6 +1,6 @@
 // Check program of mir-prefer_amd/csrc/ss_words.h (tests/test_ss_words_cpu.py builds it with the host compiler under -fsanitize=address,undefined and runs it):
 // every structure rule on words against its character-by-character restatement, result by result.  The restatement is the rule set the filter kernel ran
-// before the word rules, moved here unchanged (the two attribute macros below make it host code).  Every packed row is a heap block of exactly the words its
+// and the homolog evaluation ran before the word rules, moved here unchanged (the two attribute macros below make it host code).  Every packed row is a heap block of exactly the words its
 // line needs, so a rule that reads a word beyond its view's line is a sanitizer error.
 #include <algorithm>
 #include <cstdio>
@@ -178,6 +178,26 @@ __device__ void d_maturestar(SS ss, int len, int m0, int m1, int foldstart, int 
     if (strand == 0) { o.star_s = rs + foldstart - 1 + star_start; o.star_e = rs + foldstart - 1 + star_end; }
     else { o.star_s = re - foldstart - star_end + 1; o.star_e = re - foldstart - star_start + 1; }
 }
+
+// mature / star duplex figures of a passing structure (the values get_maturestar_info returns beside the star, MP:1876-1999)
+__device__ void hm_duplex_stats(SS ss, int len, int l0, int l1, int* prime5, int* total_bps, int* total_dots) {
+    int a = l0, b = l1; d_clip(len, a, b);
+    char sym = '(';
+    *prime5 = 1;
+    int firstbp = d_find(ss, '(', a, b);
+    if (firstbp == -1) { firstbp = d_find(ss, ')', a, b); sym = ')'; *prime5 = 0; }
+    const int p_first = d_partner(ss, len, firstbp);
+    int ra = l0, rb = l1 - 2; d_clip(len, ra, rb);
+    const int mend = d_rfind(ss, sym, ra, rb);
+    const int p_mend = d_partner(ss, len, mend);
+    int md0 = l0, md1 = mend + 1, sd0 = p_mend, sd1 = p_first + 1;
+    d_clip(len, md0, md1); d_clip(len, sd0, sd1);
+    if (md1 < md0) md1 = md0;
+    if (sd1 < sd0) sd1 = sd0;
+    const int mdots = d_count(ss, '.', md0, md1);
+    *total_dots = mdots + d_count(ss, '.', sd0, sd1);
+    *total_bps = (md1 - md0) - mdots;
+}
 #undef __device__
 #undef __forceinline__
 }  // namespace ref
@@ -185,7 +205,7 @@ __device__ void d_maturestar(SS ss, int len, int m0, int m1, int foldstart, int 
 // ------------------------------------------------------------------------------------------------ harness
 using mirp::SSW;
 
-static thread_local long long g_checks = 0, g_code_hist[16] = {0};
+static thread_local long long g_checks = 0, g_code_hist[16] = {0}, g_dstats = 0, g_dstats_3p = 0;
 static thread_local std::mt19937 g_rng(20240611u);
 static int rnd(int lo, int hi) { return lo + (int)(g_rng() % (unsigned)(hi - lo + 1)); }          // inclusive
 
@@ -253,6 +273,37 @@ static void check_maturestar(const Line& L, int off, int len, int m0, int m1, in
     CHECK("maturestar fold_e", m0, m1, g.fold_e, w.fold_e);
     g_code_hist[w.code & 15]++;
 }
+// The five positions the duplex figures are made of, as the restatement finds them; false where one of them does not exist.  The kernel asks for the
+// figures only of a structure that get_maturestar_info passed, where all five exist; the restatement reads character firstbp, mend or a partner without
+// looking at its sign, so both functions are called only where these are >= 0 and the restatement's reads stay inside the line.
+struct DuplexPos { int l0, l1m2, mend, p_mend, p_first; };
+static bool duplex_positions(ref::SS R, int len, int l0, int l1, DuplexPos* out) {
+    int a = l0, b = l1; ref::d_clip(len, a, b);
+    char sym = '(';
+    int firstbp = ref::d_find(R, '(', a, b);
+    if (firstbp == -1) { firstbp = ref::d_find(R, ')', a, b); sym = ')'; }
+    if (firstbp < 0) return false;
+    const int p_first = ref::d_partner(R, len, firstbp);
+    int ra = l0, rb = l1 - 2; ref::d_clip(len, ra, rb);
+    const int mend = ref::d_rfind(R, sym, ra, rb);
+    if (mend < 0 || p_first < 0) return false;
+    const int p_mend = ref::d_partner(R, len, mend);
+    if (p_mend < 0) return false;
+    if (out) { out->l0 = l0; out->l1m2 = l1 - 2; out->mend = mend; out->p_mend = p_mend; out->p_first = p_first; }
+    return true;
+}
+static bool check_duplex_stats(const Line& L, int off, int len, int l0, int l1) {
+    if (!duplex_positions(L.r(off), len, l0, l1, nullptr)) return false;
+    int g[3] = {-7, -7, -7}, w[3] = {-7, -7, -7};
+    mirp::ssw_duplex_stats(L.v(off), len, l0, l1, &g[0], &g[1], &g[2]);
+    ref::hm_duplex_stats(L.r(off), len, l0, l1, &w[0], &w[1], &w[2]);
+    CHECK("duplex_stats prime5", l0, l1, g[0], w[0]);
+    CHECK("duplex_stats total_bps", l0, l1, g[1], w[1]);
+    CHECK("duplex_stats total_dots", l0, l1, g[2], w[2]);
+    g_dstats++;
+    g_dstats_3p += w[0] == 0;
+    return true;
+}
 // a mature of 18 .. 24 characters anywhere in the view, both strands; window coordinates chosen so that the local coordinates fall where wanted
 static void check_maturestar_at(const Line& L, int off, int len, int l0, int ml, int strand) {
     const int foldstart = rnd(1, 40), rs = rnd(100, 5000), re = rs + foldstart + len + rnd(0, 60);
@@ -316,7 +367,7 @@ static std::string hairpin(int n_pairs, int loop, int p_bulge, int t5, int t3, s
     return s;
 }
 
-struct Tally { long long views = 0, checks = 0, codes[16] = {0}; };
+struct Tally { long long views = 0, checks = 0, codes[16] = {0}, dstats = 0, dstats_3p = 0; };
 static void exhaustive_at(int off, Tally* out) {
     g_rng.seed(977u + (unsigned)off);
     long long n = 0;
@@ -330,6 +381,8 @@ static void exhaustive_at(int off, Tally* out) {
             for (int k = 0; k < len; k++) { s[(size_t)k] = ".()"[c % 3]; c /= 3; }
             const Line L(head + s + tails[code % 3]);
             n++;
+            if (s.find_first_of("()") != std::string::npos)          // the duplex figures over every interval that holds a bracket
+                for (int l0 = -2; l0 <= len + 2; l0++) for (int l1 = l0; l1 <= len + 2; l1++) check_duplex_stats(L, off, len, l0, l1);
             if (len <= 7) {
                 check_view(L, off, len, 1);
                 for (int a = 0; a <= len; a++) for (int b = a; b <= len; b++) check_range(L, off, len, a, b);
@@ -343,7 +396,7 @@ static void exhaustive_at(int off, Tally* out) {
             }
         }
     }
-    out->views = n; out->checks = g_checks;
+    out->views = n; out->checks = g_checks; out->dstats = g_dstats; out->dstats_3p = g_dstats_3p;
     for (int c = 0; c < 16; c++) out->codes[c] = g_code_hist[c];
 }
 
@@ -381,10 +434,13 @@ int main() {
                     const Line L(s);
                     check_view(L, 0, (int)s.size(), 4);
                     check_view(L, start > 3 ? start - 3 : 0, (int)s.size() - (start > 3 ? start - 3 : 0), 2);
+                    for (int l0 = start - 26; l0 <= (int)s.size(); l0++)          // the duplex figures with the interval over either arm
+                        for (const int w : {18, 21, 26}) { if (l0 >= 0) check_duplex_stats(L, 0, (int)s.size(), l0, l0 + w); }
                     // two hairpins side by side: a bifurcation whose branch point pairs straddle the boundaries
                     const std::string t = "((" + s + s.substr((size_t)start) + "))";
                     const Line T(t);
                     check_view(T, 0, (int)t.size(), 2);
+                    for (int l0 = 0; l0 <= (int)t.size(); l0 += 3) check_duplex_stats(T, 0, (int)t.size(), l0, l0 + 21);
                 }
             }
         }
@@ -420,17 +476,70 @@ int main() {
                     g_path_hit[0] - h0, g_path_hit[1] - h1);
         if (by_len[0] == 0 || by_len[1] == 0 || g_path_hit[0] == h0 || g_path_hit[1] == h1) { std::fprintf(stderr, "a side of the 64-character path was not hit\n"); return 1; }
     }
+    // 5. the duplex figures (ssw_duplex_stats) on hairpins in lines of 60 .. 3,000 characters: an interval of 18 .. 26 characters on either arm, the line
+    // shifted so that l0, l1 - 2, mend, p_mend and p_first in turn land on character 31, 32, 33, 63, 64, 65 and in the last word of the line
+    {
+        static const int kTargets[6] = {31, 32, 33, 63, 64, 65};
+        long long hit[2][5][7] = {};
+        for (int rep = 0; rep < 700; rep++) {
+            const int pairs = rep % 2 ? rnd(3, 14) : rep % 8 ? rnd(15, 120) : rnd(121, 1400);
+            const std::string core = hairpin(pairs, rnd(3, 12), rep % 3 == 0 ? 0 : rnd(2, 20), 0, rnd(0, 30));
+            const int C = (int)core.size();
+            if (C > 3000) continue;
+            const Line K(core);
+            for (int arm = 0; arm < 2; arm++) {
+                std::vector<int> br;
+                for (int i = 0; i < C; i++) if (core[(size_t)i] == (arm ? ')' : '(')) br.push_back(i);
+                for (int tries = 0; tries < 3; tries++) {
+                    const int w = rnd(18, 26), b0 = br[(size_t)rnd(0, (int)br.size() - 1)];
+                    const int l0 = std::max(0, tries == 0 ? b0 - rnd(0, 3) : tries == 1 ? br.front() - rnd(0, w - 3) : br.back() - rnd(2, w - 3)), l1 = l0 + w;
+                    DuplexPos P;
+                    if (!duplex_positions(K.r(0), C, l0, l1, &P)) continue;
+                    const int X[5] = {P.l0, P.l1m2, P.mend, P.p_mend, P.p_first};
+                    for (int q = 0; q < 5; q++) {
+                        for (int t = 0; t < 7; t++) {
+                            int shift = -1;
+                            if (t < 6) {
+                                if (X[q] <= kTargets[t] && kTargets[t] - X[q] + C <= 3000) shift = kTargets[t] - X[q];
+                                if (shift >= 0 && shift + C < 60) shift = -1;          // the line is shorter than 60 characters
+                            } else {
+                                for (int k = 0; k < 40 && shift < 0; k++) {
+                                    const int sft = rnd(std::max(0, 60 - C), 3000 - C), N = sft + C;
+                                    if (sft + X[q] >= 32 * ((N - 1) >> 5)) shift = sft;
+                                }
+                            }
+                            if (shift < 0) continue;
+                            const Line L(std::string((size_t)shift, '.') + core);
+                            const int len = shift + C, off = 0;
+                            DuplexPos Q;
+                            const bool same = duplex_positions(L.r(0), len, l0 + shift, l1 + shift, &Q);
+                            CHECK("duplex positions after the shift", l0, l1, same && Q.mend == P.mend + shift && Q.p_mend == P.p_mend + shift && Q.p_first == P.p_first + shift, 1);
+                            if (check_duplex_stats(L, 0, len, l0 + shift, l1 + shift)) hit[ref::d_find(K.r(0), '(', l0, std::min(l1, C)) < 0][q][t]++;
+                            check_duplex_stats(L, 0, len, l0 + shift - 1, l1 + shift);
+                            check_duplex_stats(L, 0, len, l0 + shift + 1, l1 + shift + 1);
+                        }
+                    }
+                }
+            }
+        }
+        for (int a = 0; a < 2; a++) for (int q = 0; q < 5; q++) for (int t = 0; t < 7; t++)
+            if (hit[a][q][t] == 0) {
+                std::fprintf(stderr, "duplex figures: arm %d, position %d (l0, l1 - 2, mend, p_mend, p_first) never landed on target %d (31 32 33 63 64 65 last word)\n", a, q, t);
+                return 1;
+            }
+    }
     {
         long long views = 0;
         for (size_t k = 0; k < workers.size(); k++) {
             workers[k].join();
-            views += tallies[k].views; g_checks += tallies[k].checks;
+            views += tallies[k].views; g_checks += tallies[k].checks; g_dstats += tallies[k].dstats; g_dstats_3p += tallies[k].dstats_3p;
             for (int c = 0; c < 16; c++) g_code_hist[c] += tallies[k].codes[c];
         }
         std::printf("exhaustive: %lld views\n", views);
     }
     std::printf("get_maturestar_info codes seen:");
     for (int c = 0; c < 13; c++) std::printf(" %d:%lld", c, g_code_hist[c]);
-    std::printf("\nOK %lld comparisons\n", g_checks);
+    std::printf("\nduplex figures: %lld comparisons, %lld with prime5 == 0\n", g_dstats, g_dstats_3p);
+    std::printf("OK %lld comparisons\n", g_checks);
     return 0;
 }
