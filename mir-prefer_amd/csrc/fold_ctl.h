@@ -20,7 +20,7 @@ enum : int {
     FOLD_CTL_DUPLICATES = 9,    // duplicates among the call's windows
     FOLD_CTL_BLOCK = 16,        // words of a block
     FOLD_CTL_CLOCKS = 16,       // diagnostics build, serial path: FOLD_CTL_CLOCKS_N 64-bit clocks from this word on (over blocks the serial path has no use for)
-    FOLD_CTL_CLOCKS_N = 4 + 64 + 8 + 3,
+    FOLD_CTL_CLOCKS_N = 4 + 64 + 8 + 3 + 16,
     FOLD_CTL_MIN_BYTES = 1024   // the driver allocates and clears at least this much
 };
 static_assert(4 * FOLD_CTL_CLOCKS % 8 == 0 && 4 * FOLD_CTL_CLOCKS + 8 * FOLD_CTL_CLOCKS_N <= FOLD_CTL_MIN_BYTES, "the diagnostics clocks lie inside what the driver clears");

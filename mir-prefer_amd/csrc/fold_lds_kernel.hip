@@ -40,6 +40,9 @@
 #ifndef MIRP_PHASEB_SKIP
 #define MIRP_PHASEB_SKIP 1    // default model, two windows per CU: waves without a cell of the diagonal branch round phase B (0: timing build, see phaseB0)
 #endif
+#ifndef MIRP_RAMP_MIX
+#define MIRP_RAMP_MIX 1       // default model, two windows per CU: lanes go ahead on the first interior-loop diagonals as well (0: timing build, see `mix` in the body)
+#endif
 
 namespace mirp {
 

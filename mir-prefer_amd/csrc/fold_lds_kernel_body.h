@@ -21,6 +21,7 @@
     const int tau_s = __builtin_amdgcn_readfirstlane(P->TerminalAU);
     constexpr int GEN_WD = 5;                // default model: |n1 - n2| from which the asymmetry term of a generic loop is saturated (checked on the host: FoldParams::gen_wing_d)
     long long tA = 0, tB = 0, tS = 0, tE = 0, t0 = 0;   // diagnostic phase clocks (thread 0 only, dbg_cycles != nullptr)
+    int g0_nb = -1;                                     // of the interval at hand: blocks of paired cells in its interior loops (thread 0; -1: it runs none)
     long long tR = 0, nR = 0, nB = 0;                   // of tB: the intervals whose interior loops are on the ramp-up (um < MAXLOOP), and the interval counts
     long long wB = 0, wA1 = 0, wA2 = 0, wW = 0, wt = 0; // per-wave: phase B, interior loops, multiloop splits, barrier wait (lane 0 of each wave)
     unsigned short* fml = (unsigned short*)(smem + LY.fml);   // biased uint16 (see FML_BIAS)
@@ -48,6 +49,7 @@
 #else
     constexpr bool RAMPF = TWO;
 #endif
+    constexpr bool RAMPMIX = RAMPF && MIRP_RAMP_MIX != 0;      // (round 16) the lane fill does not wait for the steady state: see `mix` in phase A1
     // special-hairpin energies by start position (tri-, tetra-, hexaloops): only read on diagonals 4, 5 and 7, so they borrow the ring rows
     // of diagonals 29-31, which are first written on diagonal 29 -- except where the first diagonals read those rows as INF (RAMPF): a region of their own
     short* spec = RAMPF ? (short*)(smem + LY.spec) : (short*)(cring + 29 * CSTR);
@@ -460,13 +462,25 @@
                 // a cell of d+1 except the stacked pair have their inner pair on diagonals <= d-2, which are final in this interval; the stacked
                 // pair follows one interval later (`done` cells below).  Such a lane differs only in j = i + d + 1 and in its ring rows, which
                 // are the rows after those of diagonal d (hence the mirror rows, CRING_ROWS / CRING_ROWS_WIN).  Only once every loop size is admissible (um = MAXLOOP for both).
-                const bool mix = d - 2 - (TURN + 1) >= MAXLOOP && d + 1 <= D;
+                // (round 16) RAMPMIX: from the first interior-loop diagonal on (d >= 6 here).  The instantiation has no admissibility test (RAMPF), so a lane that
+                // goes ahead runs the same code on the first diagonals as later, one ring row further on.  What it reads, in phase A of diagonal d (interval d - 1):
+                //   * loop size U >= 1 of its cell of diagonal d + 1 has its inner pairs on diagonal x = d - 1 - U, read as the row AFTER that of x - 1, i.e.
+                //     row ((x - 1) & 31) + 1 (a chunk of the bulge / 1xn jobs: up to A1_CHUNK - 1 rows further, the mirror rows).  For x >= 4 that is the finished
+                //     row of x or its mirror, as in the steady state (x <= d - 2; the stacked pair, x = d - 1, follows through the `done` cells).  For x < 4 the
+                //     diagonal does not exist: its row, primary and mirror, is next written by diagonal x + 32 = d + 31 - U >= d + 1 of this window (U <= MAXLOOP),
+                //     i.e. not before interval d + 1, so it still holds the INF of the window's initialisation, in every column a lane reaches (its cell has
+                //     i <= n - 7: the static_assert on CSTR in fold_lds_common.h covers i <= n - 6).  U >= 1 and d >= 6 give x >= -25: never two turns of the ring back.
+                //   * the list of diagonal d + 1 was built by phase B of diagonal d - 2 (the lists of 4 .. 6 by the window's prologue, so list 7 comes from
+                //     interval 4) and its length was read behind that interval's barrier; the ckey buffer of d + 1 is the one of d - 2, which phase B of
+                //     d - 2 cleared cell by cell, an interval before this one (first: diagonal 7 in the buffer of diagonal 4, cleared in interval 4, filled from interval 5).
+                const bool mix = (RAMPMIX || d - 2 - (TURN + 1) >= MAXLOOP) && d + 1 <= D;
                 // the length of this list is known since the previous interval (a1_ncp); the first block's entries are fetched before anything
                 // else: every dependent LDS access in front of the shape code costs hundreds of cycles when the pipe is loaded
                 const int ncp = a1_ncp;                    // = lcnt[d % 6], read one interval ago as ncp2: no LDS round trip in front of the first block
                 const int done = a1_done;                  // leading cells of this diagonal's list that were relaxed in the previous interval
                 const int rem = ncp - done;
                 const int nblk = (rem + 63) >> 6;
+                if (dbg_cycles && tid == 0 && !light) g0_nb = nblk < 3 ? nblk : 3;
                 int ncp2;
                 if (lc_have) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lc_pre) : : "memory"); ncp2 = __builtin_amdgcn_readfirstlane(lc_pre); }
                 else ncp2 = __builtin_amdgcn_readfirstlane(lcnt[(d + 1) % 6]);
@@ -1023,6 +1037,13 @@
                 tB += t - t0; nB++;
                 // interval d runs the interior loops of diagonal d + 1: on the ramp-up while um = d + 1 - 2 - (TURN + 1) < MAXLOOP
                 if (d + 1 >= 6 && d + 1 <= D && d + 1 - 2 - (TURN + 1) < MAXLOOP) { tR += t - t0; nR++; }
+                // thread 0's interval by the number of blocks its interior loops ran (0, 1, 2, 3+), ramp-up intervals ([4..7]) apart from the rest ([0..3])
+                if (g0_nb >= 0) {
+                    const int c = g0_nb + (d + 1 - 2 - (TURN + 1) < MAXLOOP ? 4 : 0);
+                    atomicAdd((unsigned long long*)&dbg_cycles[79 + c], (unsigned long long)(t - t0));
+                    atomicAdd((unsigned long long*)&dbg_cycles[87 + c], 1ull);
+                }
+                g0_nb = -1;
                 t0 = t;
             }
         }

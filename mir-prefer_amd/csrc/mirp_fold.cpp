@@ -82,6 +82,9 @@ int print_clocks(const FoldCall& f) {
         std::fprintf(stderr, "[mirp fold clocks] wave 9, diagonals with %d%s blocks: %lld, interior ticks %lld\n", b, b == 3 ? "+" : "", cyc[72 + b], cyc[68 + b]);
     std::fprintf(stderr, "[mirp fold clocks] ramp-up intervals (interior loops with um < MAXLOOP): %lld of %lld intervals, %lld of fillB=%lld ticks (%.1f %%)\n", cyc[77], cyc[78],
                  cyc[76], cyc[2], cyc[2] ? 100.0 * (double)cyc[76] / (double)cyc[2] : 0.0);
+    for (int b = 0; b < 8; b++)      // thread 0's barrier intervals by the blocks of paired cells their interior loops ran: the fixed part and the part per block
+        std::fprintf(stderr, "[mirp fold clocks] %s intervals with %d%s blocks: %lld, thread 0 ticks %lld\n", b < 4 ? "steady-state" : "ramp-up", b & 3, (b & 3) == 3 ? "+" : "",
+                     cyc[87 + b], cyc[79 + b]);
     mirp::fold_lds_epi_clocks_print();
     return 0;
 }
