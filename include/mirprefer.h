@@ -552,6 +552,43 @@ int mirp_trim_reads(mirp_ctx* ctx, const char* data, int64_t n, const char* name
  * Returns -1 without a context or out. */
 int mirp_trim_last_paths(const mirp_ctx* ctx, int64_t out[2]);
 
+/* Profile of a raw library, the step before mirp_trim_reads: its 3' adapter, found from the reads, and three tables.  adapter_len
+ * 0 = find the adapter; 1..64 = use adapter[0 .. adapter_len) (A C G T in either case) for the insert table, the search still runs and is reported;
+ * error_permille 0..999 as in MirpTrimOpts; min_overlap 0 = the trim's default (3), else 1..64, an overlap beyond the adapter in use counts as its
+ * length; sample 1..2^26 = the reads, from the first on, whose 12-mers are counted. */
+typedef struct {
+    char adapter[64];
+    int32_t adapter_len, error_permille, min_overlap, reserved;
+    int64_t sample;
+} MirpLibqcOpts;
+#define MIRP_LIBQC_NONE 0    /* no eligible 12-mer occurs 16 times: no adapter, adapter_len 0 and the walk's fields 0 */
+#define MIRP_LIBQC_OK 1      /* the left walk stopped where the 12-mers before the candidate are no longer one sequence: the adapter's start */
+#define MIRP_LIBQC_UNSURE 2  /* the left walk ran out of support (1) or reached its cap of 1,024 (2): the candidate may be an abundant insert */
+/* adapter[0 .. adapter_len) = the candidate in upper case (adapter_len 12..64, 0 with status NONE); seed_code = the seed 12-mer, 2 bits per base
+ * (A 0, C 1, G 2, T 3), first base most significant; seed_count = its counter; min_count = max(16, seed_count / 64), the support a step needs;
+ * left_steps = bases the left walk put before the seed; left_stop = 0 purity, 1 support, 2 the length cap. */
+typedef struct {
+    char adapter[64];
+    int32_t adapter_len, status, seed_code, left_steps, left_stop, reserved;
+    int64_t seed_count, min_count;
+} MirpLibqcFound;
+/* Profiles the reads of one FASTQ or FASTA text held in host memory (data[0 .. n), decompressed by the caller; name = what messages call the file).
+ * The input rules and refusals are those of mirp_trim_reads with quality_cutoff 0, with the same codes and messages (-9, -10); nothing is written.
+ * Every 12-mer of A C G T (after upper-casing) that lies within the first 64 bases of one of the first min(reads, sample) reads counts once in a
+ * table of 4^12 32-bit counters; the adapter is walked out of that table by integer comparisons alone, so it does not depend on
+ * the order the reads are counted in.  Out, over all reads: found; stats = {reads, sampled, with adapter, dimers}; raw_len[1025] = reads of each
+ * length; cycles[1024][6] = per cycle the reads with A, C, G, T, anything else, and the sum of quality - 33 (0 for FASTA); insert[1025][6] = per cut
+ * p of the trim's adapter step (opts' adapter, else the found one of status OK or UNSURE; error_permille and min_overlap; no quality trim, no
+ * length filter; p = the read's length without a match) the reads whose first base is A, C, G, T, anything else (a read cut at 0, a dimer, counts
+ * here), and their total; all zeros, as are with adapter and dimers, when there is no adapter to use.  with adapter = reads with a match, dimers
+ * = those matched at 0.  seconds = {upload, split, records, k-mers + adapter, trim, tables}.  Any of the out pointers may be NULL.
+ * mirp_trim_last_paths reports the trim kernel's paths of this call too. */
+int mirp_libqc_reads(mirp_ctx* ctx, const char* data, int64_t n, const char* name, const MirpLibqcOpts* opts, MirpLibqcFound* found, int64_t stats[4],
+                     int64_t raw_len[1025], int64_t cycles[1024 * 6], int64_t insert[1025 * 6], double seconds[6]);
+/* Copies the 4^12 counters of the last mirp_libqc_reads of this context to out; -1 without a context or out, and after a call that was refused or
+ * failed (or before the first call).  No output is read from it; the entry is there for tests. */
+int mirp_libqc_last_table(mirp_ctx* ctx, uint32_t out[1 << 24]);
+
 /* Plant miRNA target sites: every miRNA against every offset of every target, ungapped, scored by position-weighted mismatches
  * (mismatch 1, G:U 0.5, doubled at miRNA positions 2..13) in half-units.  max_half_score 0..16 (= 2 x the -s score); both_strands: also the minus
  * strand; cleavage_site: reject a site with a mismatch (not a G:U) at miRNA position 10 or 11; max_sites: the first N sites per miRNA in output

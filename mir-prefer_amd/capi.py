@@ -32,6 +32,23 @@ class TrimOpts(C.Structure):
 TRIM_STATS = ("reads", "quality_trimmed", "adapter", "untrimmed", "too_short", "too_long", "written")
 
 
+class LibqcOpts(C.Structure):
+    """MirpLibqcOpts of include/mirprefer.h."""
+    _fields_ = [("adapter", C.c_char * 64)] + [(f, C.c_int32) for f in ("adapter_len", "error_permille", "min_overlap", "reserved")] + [("sample", C.c_int64)]
+
+
+class LibqcFound(C.Structure):
+    """MirpLibqcFound of include/mirprefer.h."""
+    _fields_ = ([("adapter", C.c_char * 64)] + [(f, C.c_int32) for f in ("adapter_len", "status", "seed_code", "left_steps", "left_stop", "reserved")] +
+                [("seed_count", C.c_int64), ("min_count", C.c_int64)])
+
+
+LIBQC_STATS = ("reads", "sampled", "with_adapter", "dimers")
+LIBQC_STATUS = ("none", "ok", "unsure")               # MIRP_LIBQC_NONE, _OK, _UNSURE
+LIBQC_STOPS = ("purity", "support", "cap")
+LIBQC_SAMPLE = 1 << 20
+
+
 class TargetOpts(C.Structure):
     """MirpTargetOpts of include/mirprefer.h."""
     _fields_ = [("max_half_score", C.c_int32), ("both_strands", C.c_int32), ("cleavage_site", C.c_int32), ("bulge", C.c_int32), ("max_sites", C.c_int64),
@@ -623,6 +640,11 @@ def load_library():
     lib.mirp_trim_reads.restype = C.c_int
     lib.mirp_trim_last_paths.argtypes = [vp, i64p]
     lib.mirp_trim_last_paths.restype = C.c_int
+    lib.mirp_libqc_reads.argtypes = [vp, C.c_char_p, C.c_int64, C.c_char_p, C.POINTER(LibqcOpts), C.POINTER(LibqcFound), i64p, i64p, i64p, i64p,
+                                     C.POINTER(C.c_double)]
+    lib.mirp_libqc_reads.restype = C.c_int
+    lib.mirp_libqc_last_table.argtypes = [vp, C.c_void_p]
+    lib.mirp_libqc_last_table.restype = C.c_int
     lib.mirp_target_scan.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(TargetOpts), C.c_char_p, i64p, C.POINTER(C.c_double)]
     lib.mirp_target_scan.restype = C.c_int
     lib.mirp_mimic_scan.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(MimicOpts), C.c_char_p, i64p, C.POINTER(C.c_double)]
@@ -1685,6 +1707,36 @@ class Context:
         """The stable device sort of uint64 values by the bits from `base` up (mirp_sort_u64, the sort of the align index and the key passes) -> the
         sorted copy."""
         return self._sort_hook("mirp_sort_u64", values, np.uint64, base, bits)
+
+    def libqc_reads(self, data, name, adapter="", error_permille=100, overlap=None, sample=LIBQC_SAMPLE):
+        """Profile of one raw FASTQ / FASTA text (bytes, already decompressed) (mirp_libqc_reads): the 3' adapter found from the
+        first `sample` reads and three tables over all reads; name is what messages call the file.  adapter = "" uses the found adapter for the
+        insert table, otherwise the given one; overlap None = the trim's default.  -> {adapter, status ("none" / "ok" / "unsure"), seed,
+        seed_count, min_count, left_steps, left_stop ("purity" / "support" / "cap"), reads, sampled, with_adapter, dimers, raw_len [1025],
+        cycles [1024, 6] = A C G T other qsum, insert [1025, 6] = A C G T other total, seconds}; seconds = {upload, split, records, k-mers +
+        adapter, trim, tables}."""
+        o = LibqcOpts()
+        ad = adapter.encode() if isinstance(adapter, str) else bytes(adapter)
+        o.adapter = ad
+        o.adapter_len, o.error_permille, o.min_overlap, o.sample = len(ad), int(error_permille), 0 if overlap is None else int(overlap), int(sample)
+        f = LibqcFound()
+        st = (C.c_int64 * 4)()
+        sec = (C.c_double * 6)()
+        raw_len = np.zeros(1025, np.int64)
+        cycles = np.zeros((1024, 6), np.int64)
+        insert = np.zeros((1025, 6), np.int64)
+        i64p = C.POINTER(C.c_int64)
+        self._check(self.lib.mirp_libqc_reads(self.h, data, len(data), os.fsencode(name), C.byref(o), C.byref(f), st, raw_len.ctypes.data_as(i64p),
+                                              cycles.ctypes.data_as(i64p), insert.ctypes.data_as(i64p), sec), "mirp_libqc_reads")
+        code = f.seed_code
+        return dict(zip(LIBQC_STATS, list(st)), adapter=f.adapter[:f.adapter_len].decode(), status=LIBQC_STATUS[f.status],
+                    seed="".join("ACGT"[(code >> (22 - 2 * i)) & 3] for i in range(12)), seed_count=int(f.seed_count), min_count=int(f.min_count),
+                    left_steps=int(f.left_steps), left_stop=LIBQC_STOPS[f.left_stop], raw_len=raw_len, cycles=cycles, insert=insert, seconds=list(sec))
+
+    def libqc_last_table(self):
+        """The 4^12 k-mer counters (uint32) of the last libqc_reads (mirp_libqc_last_table); None after a refused call."""
+        out = np.empty(1 << 24, np.uint32)
+        return out if self.lib.mirp_libqc_last_table(self.h, out.ctypes.data) == 0 else None
 
     def set_text_piece(self, nbytes):
         """Bytes of text that leave the device in one piece in target_scan, mimic_scan, align_reads and trim_reads (mirp_set_text_piece); 0 = the

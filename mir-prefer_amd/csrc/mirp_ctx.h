@@ -149,6 +149,10 @@ struct mirp_ctx {
     DevBuf t_text, t_bcnt, t_bscan, t_starts, t_small, t_hdr, t_llen, t_lb, t_hscan, t_goff, t_first, t_gbuf, t_src, t_len, t_qual, t_nameb, t_namel,
         t_flen, t_off, t_out;
     long long t_paths[2] = {0, 0};    // workgroups of the last mirp_trim_reads that staged their reads in LDS / read them from global memory (mirp_trim_last_paths)
+    // ---- library profile (libqc_kernels.hip, mirp_libqc.cpp): the 4^12 k-mer counters, the found adapter with the walk's scratch, the three tables;
+    // the text, lines and per-read arrays are the trim's (t_*)
+    DevBuf q_table, q_found, q_hist;
+    bool q_have_table = false;        // q_table holds the counters of the last mirp_libqc_reads (mirp_libqc_last_table); false after a refused call
     // ---- target-site search (targets_kernels.hip, mirp_targets.cpp): the packed targets, the miRNAs and the key / text buffers of one call
     DevBuf tg_pk, tg_amb, tg_cst, tg_cstart, tg_names, tg_noff, tg_mcodes, tg_mnames, tg_mnoff, tg_mi, tg_emitted, tg_hist, tg_small, tg_keys, tg_ktmp,
         tg_size, tg_toff, tg_text;
@@ -276,8 +280,21 @@ int mirp_device_place_pick(mirp_ctx* c, long long n, long long n_items, int mode
 // reads_kernels.hip: the line split of an uploaded text shared by the collapse and the trim (starts[0 .. n_lines]); trim_kernels.hip: the trim of one FASTQ / FASTA text
 int mirp_device_split_lines(mirp_ctx* c, const unsigned char* d_text, long long n, long long max_lines, DevBuf& tile_cnt, DevBuf& tile_scan, DevBuf& starts,
                             unsigned long long* d_first_bad, long long* n_lines, long long* bad_offset);
+// the trim's steps, shared with the library profile: upload + split + records of a text of n > 0 bytes into the context's t_* arrays, then
+// trim_reads_kernel under o (t_flen; res = {first bad record key, reads per flag bit 0..5, workgroups per path}) with the refusals that need the reads' bytes
+struct MirpTrimParsed {
+    bool fq;                          // FASTQ: the reads lie in the text and t_qual holds the quality starts; FASTA: in the gathered buffer
+    long long R, rem, n_lines;        // reads, the lines behind the last whole FASTQ record, lines
+    const unsigned char *d_text, *d_base;   // the uploaded text; what t_src points into
+};
+int mirp_device_trim_parse(mirp_ctx* c, const char* text, long long n, const char* name, int quality_cutoff, MirpTrimParsed* p, double seconds[3]);
+int mirp_device_trim_cut(mirp_ctx* c, const MirpTrimParsed& p, const char* name, const MirpTrimOpts& o, unsigned long long res[9]);
 int mirp_device_trim_reads(mirp_ctx* c, const char* text, long long n, const char* name, const MirpTrimOpts& o,
                            const std::function<int(const char*, size_t)>& sink, long long stats[7], double seconds[6]);
+// libqc_kernels.hip: the k-mer table, the adapter walk and the three tables of one FASTQ / FASTA text (mirp_libqc.cpp checks the arguments)
+int mirp_device_libqc_reads(mirp_ctx* c, const char* text, long long n, const char* name, const MirpLibqcOpts& o, MirpLibqcFound* found, long long stats[4],
+                            long long* raw_len, long long* cycles, long long* insert, double seconds[6]);
+int mirp_device_libqc_table(mirp_ctx* c, unsigned* out);      // the 4^12 counters of the last profile, to the host
 // targets_kernels.hip: the target-site search over packed targets (mirp_targets.cpp parses the files)
 int mirp_device_target_scan(mirp_ctx* c, const unsigned long long* pk, const unsigned* amb, const unsigned* cst, long long total,
                             const std::vector<unsigned long long>& cstart, const std::string& tnames, const std::vector<long long>& tnoff,

@@ -11,6 +11,8 @@
 //   trim     trim_reads_kernel   one workgroup per TR_NT reads: their slab of text staged in LDS with 16-byte loads, then per read the quality check,
 //                                the 3' quality trim and the adapter scan, bit-parallel on 2-bit codes (one xor / or / popcount per shift)
 //   emit     trim_size_kernel, launch_excl_scan, trim_emit_kernel   record sizes, their offsets, the text; downloaded in pieces of at most 1 GiB
+// On the host the first three steps are mirp_device_trim_parse and the fourth mirp_device_trim_cut, which the library profile (libqc_kernels.hip;
+// DESIGN.md §35) calls as well; mirp_device_trim_reads calls both and emits.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstring>
@@ -274,14 +276,12 @@ static int tr_refuse_record(mirp_ctx* c, const char* name, long long r, int why)
     return fail(c, -10, std::string(name) + ": record " + std::to_string(r + 1) + ": " + kTrimReason[why]);
 }
 
-// The trim of one file held in host memory (mirp_trim.cpp checks the arguments and writes the file through sink; sink is called only once every
-// refusal has been ruled out).  stats and seconds as mirp_trim_reads; seconds[5] gains the time spent in sink.
-int mirp_device_trim_reads(mirp_ctx* c, const char* text, long long n, const char* name, const MirpTrimOpts& o,
-                           const std::function<int(const char*, size_t)>& sink, long long stats[7], double seconds[6]) {
+// Upload, line split and records of one file held in host memory (n > 0), shared by the trim and by the library profile (libqc_kernels.hip): on
+// return the per-read arrays t_src, t_len, t_qual, t_nameb, t_namel of the context are filled, and p says how to read them.  A refusal that
+// needs no look at a read's bytes is returned here; the first bad FASTQ record waits in d_small[1] for mirp_device_trim_cut.  seconds[0 .. 3) gain
+// upload, split and records.
+int mirp_device_trim_parse(mirp_ctx* c, const char* text, long long n, const char* name, int quality_cutoff, MirpTrimParsed* p, double seconds[3]) {
     using namespace mirp;
-    for (int i = 0; i < 7; i++) stats[i] = 0;
-    c->t_paths[0] = c->t_paths[1] = 0;
-    if (n == 0) return 0;
     hipStream_t st = c->stream;
     double t = mirp::now();
     if (c->t_text.ensure((size_t)n + TR_PAD) || c->t_small.ensure(80)) return fail(c, -6, "device allocation failed (trim: text)");
@@ -312,7 +312,7 @@ int mirp_device_trim_reads(mirp_ctx* c, const char* text, long long n, const cha
     t = mirp::now();
     const bool fq = text[0] == '@';
     if (!fq && text[0] != '>') return fail(c, -10, std::string(name) + ": the first byte is neither '@' (FASTQ) nor '>' (FASTA)");
-    if (!fq && o.quality_cutoff > 0) return fail(c, -10, std::string(name) + ": quality trimming needs FASTQ input, this file is FASTA");
+    if (!fq && quality_cutoff > 0) return fail(c, -10, std::string(name) + ": quality trimming needs FASTQ input, this file is FASTA");
     const long long max_reads = 0x7fffffffll;
     long long R = 0, rem = 0;
     const unsigned char* d_base = d_text;
@@ -372,9 +372,28 @@ int mirp_device_trim_reads(mirp_ctx* c, const char* text, long long n, const cha
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
     seconds[2] += mirp::now() - t;
+    p->fq = fq;
+    p->R = R;
+    p->rem = rem;
+    p->n_lines = n_lines;
+    p->d_text = d_text;
+    p->d_base = d_base;
+    return 0;
+}
 
-    // ---- trim
-    t = mirp::now();
+// trim_reads_kernel over the reads of mirp_device_trim_parse under o: t_flen of the context gains the final lengths, res = {first bad record key,
+// reads per flag bit 0..5, workgroups per path}.  The refusals that wait for the reads' bytes are returned here: the first bad record, then a file
+// that ends inside a record.
+int mirp_device_trim_cut(mirp_ctx* c, const MirpTrimParsed& p, const char* name, const MirpTrimOpts& o, unsigned long long res[9]) {
+    using namespace mirp;
+    hipStream_t st = c->stream;
+    const bool fq = p.fq;
+    const long long R = p.R, rem = p.rem;
+    const unsigned char* d_base = p.d_base;
+    unsigned long long* d_small = (unsigned long long*)c->t_small.p;
+    unsigned long long* d_err = d_small + 1;
+    const long long* d_src = (const long long*)c->t_src.p;
+    const int* d_len = (const int*)c->t_len.p;
     TrimArgs a{};
     a.m = o.adapter_len; a.e_pm = o.error_permille; a.ovl = o.min_overlap; a.q = o.quality_cutoff;
     a.min_len = o.min_length; a.max_len = o.max_length; a.discard = o.discard_untrimmed;
@@ -387,12 +406,37 @@ int mirp_device_trim_reads(mirp_ctx* c, const char* text, long long n, const cha
     if (R > 0)
         hipLaunchKernelGGL(trim_reads_kernel, dim3((unsigned)((R + TR_NT - 1) / TR_NT)), dim3(TR_NT), 0, st, d_base, (const long long*)d_src, (const int*)d_len,
                            fq ? (const long long*)c->t_qual.p : (const long long*)nullptr, R, a, d_flen, d_small + 2, d_err);
-    unsigned long long res[9];
-    HIPCHK(c, hipMemcpyAsync(res, d_small + 1, sizeof res, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(res, d_small + 1, 9 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
     if (res[0] != ~0ull) return tr_refuse_record(c, name, (long long)(res[0] >> 3), (int)(res[0] & 7));
     if (rem) return tr_refuse_record(c, name, R, 6);
+    return 0;
+}
+
+// The trim of one file held in host memory (mirp_trim.cpp checks the arguments and writes the file through sink; sink is called only once every
+// refusal has been ruled out).  stats and seconds as mirp_trim_reads; seconds[5] gains the time spent in sink.
+int mirp_device_trim_reads(mirp_ctx* c, const char* text, long long n, const char* name, const MirpTrimOpts& o,
+                           const std::function<int(const char*, size_t)>& sink, long long stats[7], double seconds[6]) {
+    using namespace mirp;
+    for (int i = 0; i < 7; i++) stats[i] = 0;
+    c->t_paths[0] = c->t_paths[1] = 0;
+    if (n == 0) return 0;
+    hipStream_t st = c->stream;
+    MirpTrimParsed p;
+    if (int rc = mirp_device_trim_parse(c, text, n, name, o.quality_cutoff, &p, seconds)) return rc;
+    const long long R = p.R;
+    const unsigned char *d_text = p.d_text, *d_base = p.d_base;
+    const long long* d_src = (const long long*)c->t_src.p;
+    int* d_len = (int*)c->t_len.p;
+    const long long* d_nameb = (const long long*)c->t_nameb.p;
+    const int* d_namel = (const int*)c->t_namel.p;
+    int* d_flen = (int*)c->t_flen.p;
+
+    // ---- trim
+    double t = mirp::now();
+    unsigned long long res[9];
+    if (int rc = mirp_device_trim_cut(c, p, name, o, res)) return rc;
     seconds[3] += mirp::now() - t;
 
     // ---- emit + download

@@ -32,4 +32,21 @@ __device__ __forceinline__ void cl_wave_atomic(unsigned long long* __restrict__ 
     }
 }
 
+// a[slot] += 1 on 32-bit counters, for every lane with slot >= 0 (libqc_kernels.hip).  Every lane of the wave must call it.  One atomic per distinct
+// slot of the wave: the lanes of a slot are counted by a ballot, so nothing is reduced.
+__device__ __forceinline__ void cl_wave_count32(unsigned* __restrict__ a, int slot) {
+    const int lane = threadIdx.x & 63;
+    bool todo = slot >= 0;
+    while (true) {
+        const unsigned long long m = __ballot(todo);
+        if (!m) break;
+        const int leader = __ffsll((long long)m) - 1;
+        const int s = __shfl(slot, leader);
+        const bool mine = todo && slot == s;
+        const unsigned long long same = __ballot(mine);
+        if (lane == leader) atomicAdd(&a[s], (unsigned)__popcll(same));
+        if (mine) todo = false;
+    }
+}
+
 }  // namespace mirp

@@ -5,6 +5,8 @@
 Every input X gives X.trimmed.fa next to it (a `.gz` suffix is dropped first: lib.fastq.gz gives lib.fastq.trimmed.fa), FASTA that
 `python -m mir_prefer_amd.reads collapse` takes as it is.  A `.gz` input is decompressed here, every gzip member in turn.  The files are trimmed in
 order, in one device context (mirp_trim_reads, trim_kernels.hip); there is no CPU path.  What is cut and kept is defined in DESIGN.md §13.
+With `-a auto` the adapter of every file is found from its reads first, as `python -m mir_prefer_amd.libqc` finds it; a file whose
+adapter is not sure (status `unsure` or `none`) is refused like any other refused input.
 
 Option errors exit with status 2 (optparse) before a device is opened; so does -q on a FASTA input.  A missing input, a refused input and "no usable
 GPU" print `Error: ...` and exit with status 255; a refused file gets no output, the files before it keep theirs and the files after it are not
@@ -28,12 +30,14 @@ HELP = """python -m mir_prefer_amd.trim [options] <reads1> ... <readsN>
     python -m mir_prefer_amd.trim -a TGGAATTCTCGGGTGCCAAGG -q 20 lib1.fastq.gz lib2.fastq.gz
 """
 ADAPTER_MAX = 64
+AUTO = "auto"          # -a auto: the adapter of every file is found from its reads first (the detection of mir_prefer_amd.libqc)
 STATS = ("reads", "quality_trimmed", "adapter", "untrimmed", "too_short", "too_long", "written")
 
 
 def make_parser():
     parser = OptionParser(HELP, prog="mir_prefer_amd.trim")
-    parser.add_option("-a", "--adapter", help="3' adapter, 1..64 characters of ACGT (either case). Without it, no adapter search.")
+    parser.add_option("-a", "--adapter", help="3' adapter, 1..64 characters of ACGT (either case), or 'auto': found from each file's reads, as "
+                      "'python -m mir_prefer_amd.libqc' finds it; a file without a sure adapter is refused. Without -a, no adapter search.")
     parser.add_option("-e", "--error-rate", default="0.1", help="Mismatches allowed per overlap base, 0 <= E < 1, at most three decimals. Default 0.1.")
     parser.add_option("-O", "--overlap", type=int, default=None, help="Minimum overlap with the adapter, 1..len(adapter). Default 3 (at most len(adapter)).")
     parser.add_option("-q", "--quality-cutoff", type=int, default=0, help="3' quality trimming cutoff (Phred+33), 0..93; 0 = off (default). FASTQ only.")
@@ -88,12 +92,12 @@ def parse_args(argv):
     if len(args) < 1:
         parser.error("incorrect number of arguments. Run with -h to see the help.")
     adapter = options.adapter
-    if adapter is not None and (not 1 <= len(adapter) <= ADAPTER_MAX or re.fullmatch(r"[ACGTacgt]+", adapter) is None):
-        parser.error("Option -a must be 1..64 characters of ACGT.")
+    if adapter is not None and adapter != AUTO and (not 1 <= len(adapter) <= ADAPTER_MAX or re.fullmatch(r"[ACGTacgt]+", adapter) is None):
+        parser.error("Option -a must be 1..64 characters of ACGT, or 'auto'.")
     pm = parse_permille(options.error_rate)
     if pm is None:
         parser.error("Option -e must be a decimal 0 <= E < 1 with at most three decimals.")
-    m = len(adapter) if adapter else 0
+    m = ADAPTER_MAX if adapter == AUTO else len(adapter) if adapter else 0          # auto: -O is checked against the found adapter per file
     if options.overlap is None:
         overlap = min(3, m) if m else 3
     else:
@@ -125,6 +129,20 @@ def _fail(msg):
     return 255
 
 
+def found_adapter(ctx, data, name, overlap):
+    """-a auto: the adapter of one file's bytes by the detection of `libqc` (capi.Context.libqc_reads, default sample).  Only status `ok` is
+    used; anything else, or an -O beyond the found adapter, raises ValueError with the status, the candidate and the advice to run libqc."""
+    res = ctx.libqc_reads(data, name)
+    if res["status"] != "ok":
+        raise ValueError("%s: -a auto found no sure adapter (status %s, candidate %s); run 'python -m mir_prefer_amd.libqc %s' to see the library, "
+                         "then give the adapter with -a" % (name, res["status"], res["adapter"] or "-", name))
+    if overlap > len(res["adapter"]):
+        raise ValueError("%s: Option -O (%d) is larger than the adapter that -a auto found (%s)" % (name, overlap, res["adapter"]))
+    sys.stderr.write("File %s: -a auto found the adapter %s\n" % (name, res["adapter"]))
+    sys.stderr.flush()
+    return res["adapter"]
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     options, files, pm, overlap = parse_args(argv)
@@ -144,7 +162,8 @@ def main(argv=None):
                 if os.path.lexists(output_name(name)):
                     os.remove(output_name(name))        # an output of an earlier run: a file that is refused must be left without one
                 data = read_input(name)
-                res = ctx.trim_reads(data, name, output_name(name), adapter=options.adapter or "", error_permille=pm, overlap=overlap,
+                adapter = found_adapter(ctx, data, name, overlap) if options.adapter == AUTO else options.adapter or ""
+                res = ctx.trim_reads(data, name, output_name(name), adapter=adapter, error_permille=pm, overlap=overlap,
                                      quality=options.quality_cutoff, min_length=options.minimum_length, max_length=options.maximum_length,
                                      discard_untrimmed=bool(options.discard_untrimmed))
             except (ValueError, OSError, capi.MirpError) as e:
