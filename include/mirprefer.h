@@ -1088,11 +1088,42 @@ int mirp_set_inverted_capacity(mirp_ctx* ctx, int64_t bytes);
  * traceback + selection, download}. */
 int mirp_inverted_last_stats(mirp_ctx* ctx, int64_t stats[12], double seconds[5]);
 
+/* Natural antisense transcripts: pairs of transcripts a < b that are complementary over a long stretch, found by seed, join and
+ * banded extension.  Cell (i, j) compares base i of A with base j of B', the reverse complement of B (Watson-Crick only; every letter but
+ * A C G T/U equals nothing).  A seed hit is an exact k-mer of A and B' without such a letter, of a k-mer value that occurs at most max_occ times
+ * in either sense; hits are binned by their shifted diagonal e = x - y + len(B) - 1 into bins of `band` diagonals, a bin with min_seeds hits is a
+ * candidate, and H(i, j) = max(0, H(i-1, j-1) +match / -mismatch, H(i-1, j) - gap, H(i, j-1) - gap) runs over the bin and its two neighbours.
+ * seed 12..24, band one of 16 32 64 128 256, max_occ 1..10000, min_seeds >= 1, match and mismatch 1..10, gap 1..50, min_score and min_length
+ * >= 1; `reserved` must be 0. */
+typedef struct { int32_t seed, band, max_occ, min_seeds, match, mismatch, gap, min_score, min_length, reserved; } MirpNatsOpts;
+/* One region: the 0-based transcripts a < b of the call, the score, the interval of A and of B (1-based, inclusive, each in its own forward
+ * coordinates) with the transcripts' lengths, the counts of the alignment's columns (`=`, `X`, and `I` + `D`: a base of A / of B without an
+ * opposite base), the seed hits of the candidate it came from and that candidate's bin. */
+typedef struct {
+    int32_t a, b, score, a_start, a_end, a_len, b_start, b_end, b_len, matches, mismatches, gaps, seeds, bin;
+} MirpNatsRec;
+/* The longest transcript that is searched; a longer one (and an empty one) is skipped and counted, and keeps its index. */
+#define MIRP_NATS_MAX_LEN 65535
+/* blob / off as mirp_inverted_scan's: n_seqs transcripts.  Refusals (-10 and the 1-based transcript in mirp_last_error): a byte >= 0x80; more
+ * than 2^25 transcripts.  Out (library-owned, mirp_free; NULL when there is no region): *recs holds the *n_recs regions ordered by (a, b,
+ * a_start, b_start); *ops one byte (`=` `X` `I` `D`) per alignment column in A's 5'->3' order, region r at (*ops)[(*ops_off)[r] ..
+ * (*ops_off)[r + 1]).  The regions are the same however the work is split into passes.  Nothing resident changes. */
+int mirp_nats_scan(mirp_ctx* ctx, const char* blob, const int64_t* off, int32_t n_seqs, const MirpNatsOpts* opts, MirpNatsRec** recs, int64_t* n_recs,
+                   char** ops, int64_t** ops_off);
+/* Device bytes one pass of mirp_nats_scan holds: a join pass's seed hits (16 bytes each: the key and the sort's second buffer; whole transcripts
+ * a) and a traceback pass's direction bytes.  0 = the default, 2^31.  A transcript or a candidate that alone is larger runs in a pass of its
+ * own.  Lowered only to test the splits. */
+int mirp_set_nats_capacity(mirp_ctx* ctx, int64_t bytes);
+/* stats = {transcripts, skipped transcripts, bases, k-mer values ignored, seed hits, candidates, kept candidates, band cells of the kept
+ * candidates, candidates with score >= min_score, candidates traced, regions, pairs, join passes, scan launches, traceback passes, 0} of the
+ * last mirp_nats_scan; seconds = {upload + keys, sort + runs, join + candidates, band scan, traceback, selection}. */
+int mirp_nats_last_stats(mirp_ctx* ctx, int64_t stats[16], double seconds[6]);
+
 /* How many jobs a resident slot served, for the kernels whose workgroups (or waves) keep a private slab and serve several jobs in turn.  family:
  * 0 = the two-strand fold (a wave; mirp_duplex_batch, mirp_target_scan with energy), 1 = the accessibility kernel (a workgroup;
  * mirp_unpaired_batch, mirp_target_scan with accessibility), 2 = the scoring kernel of mirp_hairpin_align (queries per workgroup row), 3 = the
  * evaluation kernel of mirp_homolog_scan (a workgroup), 4 = the filter kernel (a workgroup serves windows it, it + grid, ...; mirp_predict_batch,
- * mirp_predict_batch_reasons, mirp_predict, mirp_predict_reasons; re-runs of windows over a capacity count as launches), 5 = the count kernel of mirp_locus_scan (a wave serves (locus, chunk) jobs w, w + waves, ...), 6 = the sum kernel of mirp_diffexp (a wave serves (feature, chunk) jobs w, w + waves, ...), 7 = the overlap kernel of mirp_signature_scan (a wave serves (locus, chunk of U entries) jobs w, w + waves, ...).  out = {launches of that kernel, the largest ceil(jobs / slots) over them} of the last
+ * mirp_predict_batch_reasons, mirp_predict, mirp_predict_reasons; re-runs of windows over a capacity count as launches), 5 = the count kernel of mirp_locus_scan (a wave serves (locus, chunk) jobs w, w + waves, ...), 6 = the sum kernel of mirp_diffexp (a wave serves (feature, chunk) jobs w, w + waves, ...), 7 = the overlap kernel of mirp_signature_scan (a wave serves (locus, chunk of U entries) jobs w, w + waves, ...), 8 = the band scan of mirp_nats_scan (a wave serves candidates w, w + waves, ...).  out = {launches of that kernel, the largest ceil(jobs / slots) over them} of the last
  * of the named calls; each of them resets its families when it starts.  A record for tests: nothing reads it.  Another family is refused (-1). */
 int mirp_last_jobs_per_slot(mirp_ctx* ctx, int32_t family, int64_t out[2]);
 

@@ -127,6 +127,20 @@ INVERTED_TILE = 8192          # MIRP_INVERTED_TILE of include/mirprefer.h: rows 
 INVERTED_STRIP = 1024         # MIRP_INVERTED_STRIP: rows the 64 lanes of a wave hold at once
 INVERTED_MAX_SPAN = 4096      # MIRP_INVERTED_MAX_SPAN: the largest max_span
 
+
+class NatsOpts(C.Structure):
+    """MirpNatsOpts of include/mirprefer.h."""
+    _fields_ = [(f, C.c_int32) for f in ("seed", "band", "max_occ", "min_seeds", "match", "mismatch", "gap", "min_score", "min_length", "reserved")]
+
+
+# MirpNatsRec of include/mirprefer.h: one complementary region of the transcripts a < b, positions 1-based and inclusive in each transcript's own sense
+NATS_DTYPE = np.dtype([(f, "<i4") for f in ("a", "b", "score", "a_start", "a_end", "a_len", "b_start", "b_end", "b_len", "matches", "mismatches", "gaps",
+                                            "seeds", "bin")])
+NATS_STATS = ("transcripts", "skipped", "bases", "kmers_ignored", "seed_hits", "candidates", "kept_candidates", "cells", "above", "traced", "regions",
+              "pairs", "join_passes", "scan_launches", "trace_passes")
+NATS_MAX_LEN = 65535          # MIRP_NATS_MAX_LEN of include/mirprefer.h: the longest transcript that is searched
+NATS_FAMILY = 8               # the band scan's family of mirp_last_jobs_per_slot
+
 class AlignPlaceOpts(C.Structure):
     """MirpAlignPlaceOpts of include/mirprefer.h."""
     _fields_ = [("mode", C.c_int32), ("window", C.c_int32), ("seed", C.c_uint64)]
@@ -689,6 +703,12 @@ def load_library():
     lib.mirp_set_inverted_capacity.restype = C.c_int
     lib.mirp_inverted_last_stats.argtypes = [vp, i64p, C.POINTER(C.c_double)]
     lib.mirp_inverted_last_stats.restype = C.c_int
+    lib.mirp_nats_scan.argtypes = [vp, C.c_char_p, i64p, C.c_int32, C.POINTER(NatsOpts), C.POINTER(vp), i64p, C.POINTER(vp), C.POINTER(vp)]
+    lib.mirp_nats_scan.restype = C.c_int
+    lib.mirp_set_nats_capacity.argtypes = [vp, C.c_int64]
+    lib.mirp_set_nats_capacity.restype = C.c_int
+    lib.mirp_nats_last_stats.argtypes = [vp, i64p, C.POINTER(C.c_double)]
+    lib.mirp_nats_last_stats.restype = C.c_int
     lib.mirp_homolog_scan.argtypes = [vp, C.c_char_p, i64p, C.c_int32, C.POINTER(HomologOpts), C.POINTER(vp), i64p, C.POINTER(vp), C.POINTER(vp)]
     lib.mirp_homolog_scan.restype = C.c_int
     lib.mirp_homolog_contigs.argtypes = [vp, C.POINTER(vp), i64p, C.POINTER(vp), C.POINTER(C.c_int32)]
@@ -1161,6 +1181,42 @@ class Context:
         self._check(self.lib.mirp_inverted_last_stats(self.h, st, sec), "mirp_inverted_last_stats")
         return dict(zip(INVERTED_STATS, list(st)), seconds=list(sec))
 
+    def nats_scan(self, seqs, seed=16, band=64, max_occ=200, min_seeds=1, match=3, mismatch=4, gap=12, min_score=200, min_length=100, capacity=0):
+        """Complementary regions of every pair of transcripts a < b (mirp_nats_scan): seqs (list of str / bytes / uint8 arrays; A C
+        G T/U in either case, any other byte equals nothing, a byte >= 0x80 is refused; an empty transcript and one longer than NATS_MAX_LEN are
+        skipped and keep their index).  capacity: device bytes per pass (0 = the default), lowered only in tests.  -> (NATS_DTYPE array of the
+        regions ordered by (a, b, a_start, b_start), [str] of their cigars: runs of = X I D in a's 5'->3' order)."""
+        bs = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in seqs]
+        off = np.zeros(len(bs) + 1, dtype=np.int64)
+        if bs:
+            off[1:] = np.cumsum([len(b) for b in bs])
+        o = NatsOpts()
+        (o.seed, o.band, o.max_occ, o.min_seeds, o.match, o.mismatch, o.gap, o.min_score, o.min_length, o.reserved) = (
+            int(seed), int(band), int(max_occ), int(min_seeds), int(match), int(mismatch), int(gap), int(min_score), int(min_length), 0)
+        recs, n_recs, ops, ops_off = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p()
+        self._check(self.lib.mirp_set_nats_capacity(self.h, int(capacity)), "mirp_set_nats_capacity")
+        try:
+            self._check(self.lib.mirp_nats_scan(self.h, b"".join(bs), off.ctypes.data_as(C.POINTER(C.c_int64)), len(bs), C.byref(o), C.byref(recs),
+                                                C.byref(n_recs), C.byref(ops), C.byref(ops_off)), "mirp_nats_scan")
+        finally:
+            self.lib.mirp_set_nats_capacity(self.h, 0)
+        n = n_recs.value
+        if n == 0:
+            return np.zeros(0, dtype=NATS_DTYPE), []
+        at = _copy_out(self.lib, ops_off, np.int64, n + 1)
+        text = _copy_out(self.lib, ops, np.uint8, int(at[-1])).tobytes()
+        r = _copy_out(self.lib, recs, NATS_DTYPE, n)
+        return r, [cigar_of(text[int(a):int(b)]) for a, b in zip(at[:-1], at[1:])]
+
+    def nats_last_stats(self):
+        """{transcripts, skipped, bases, kmers_ignored, seed_hits, candidates, kept_candidates, cells, above, traced, regions, pairs, join_passes,
+        scan_launches, trace_passes, seconds} of the last nats_scan; seconds = {upload + keys, sort + runs, join + candidates, band scan,
+        traceback, selection}."""
+        st = (C.c_int64 * 16)()
+        sec = (C.c_double * 6)()
+        self._check(self.lib.mirp_nats_last_stats(self.h, st, sec), "mirp_nats_last_stats")
+        return dict(zip(NATS_STATS, list(st)), seconds=list(sec))
+
     def homolog_scan(self, queries, max_mismatches=1, precursor_len=300, max_placements=100, keys=0, chunk=0, fold_lines=0, eval_caps=(0, 0, 0)):
         """Homologs of known mature miRNAs in the genome of align_index (mirp_homolog_scan).  queries: distinct sequences (str /
         bytes) of 18..26 letters A C G T/U.  keys, chunk, fold_lines, eval_caps (pieces, structures, staged lines): the capacities of
@@ -1211,7 +1267,8 @@ class Context:
         (mirp_last_jobs_per_slot): family 0 = two-strand fold (duplex_batch, target_scan), 1 = accessibility (unpaired_batch, target_scan),
         2 = hairpin scoring (hairpin_align; the largest chunk of queries), 3 = homolog evaluation (homolog_scan), 4 = the filter kernel (predict_batch, predict_batch_reasons, predict, predict_reasons; windows per
         workgroup, re-runs of windows over a capacity included), 5 = the count kernel of the locus scan (locus_scan; (locus, chunk) jobs per wave), 6 = the sum kernel of the exact test (diffexp; (feature, chunk)
-        jobs per wave), 7 = the overlap kernel of the signature scan (signature_scan; (locus, chunk of U entries) jobs per wave)."""
+        jobs per wave), 7 = the overlap kernel of the signature scan (signature_scan; (locus, chunk of U entries) jobs per wave), 8 = the band scan of
+        nats_scan (candidates per wave)."""
         out = (C.c_int64 * 2)()
         self._check(self.lib.mirp_last_jobs_per_slot(self.h, int(family), out), "mirp_last_jobs_per_slot")
         return int(out[0]), int(out[1])

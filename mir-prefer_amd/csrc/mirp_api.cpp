@@ -70,7 +70,7 @@ extern "C" int64_t mirp_text_pieces_last(const mirp_ctx* c) { return c ? c->text
 // Launches and the largest jobs per resident slot of a wave-per-job kernel family in the last call that launches it (mirp_ctx::jobs_per_slot)
 extern "C" int mirp_last_jobs_per_slot(mirp_ctx* c, int32_t family, int64_t out[2]) {
     if (!c) return -1;
-    if (family < 0 || family > 7 || !out) return fail(c, -1, "mirp_last_jobs_per_slot: bad argument");
+    if (family < 0 || family > 8 || !out) return fail(c, -1, "mirp_last_jobs_per_slot: bad argument");
     out[0] = c->jobs_per_slot[family][0];
     out[1] = c->jobs_per_slot[family][1];
     return 0;

@@ -205,11 +205,20 @@ struct mirp_ctx {
     long long iv_cap = 0;             // bytes per pass of mirp_inverted_scan; 0 = the default, 2^31 (mirp_set_inverted_capacity)
     long long iv_stats[12] = {0};     // the last mirp_inverted_scan (mirp_inverted_last_stats)
     double iv_sec[5] = {0, 0, 0, 0, 0};
+    // ---- natural antisense transcripts (nats_kernels.hip, mirp_nats.cpp): the transcripts and their reverse complements as 4-bit codes, the
+    // transcript of every word and the first nibble of every transcript; the k-mer records and their sort buffer, the run heads, their scan and
+    // the runs' starts, the hits per transcript a; the hit keys of one join pass, its candidates; the jobs and results of the band scan; the
+    // jobs, records, direction bytes and ops of one traceback pass
+    DevBuf nt_a, nt_b, nt_wseq, nt_pos, nt_recs, nt_rtmp, nt_flag, nt_scan, nt_starts, nt_cnt, nt_small, nt_hits, nt_htmp, nt_cand, nt_jobs, nt_best, nt_tjobs,
+        nt_trec, nt_dir, nt_ops;
+    long long nt_cap = 0;             // bytes per pass of mirp_nats_scan; 0 = the default, 2^31 (mirp_set_nats_capacity)
+    long long nt_stats[16] = {0};     // the last mirp_nats_scan (mirp_nats_last_stats)
+    double nt_sec[6] = {0, 0, 0, 0, 0, 0};
     long long n_result = 0;          // records of the last mirp_predict (p_res / p_text), what mirp_gather_loci sends
     bool have_result = false;
-    // ---- jobs per resident slot (mirp_last_jobs_per_slot): per family (0 duplex_kernel, 1 unpaired_kernel, 2 hp_score_kernel, 3 homolog_eval_kernel, 4 predict_kernel, 5 lc_count_kernel, 6 de_sum_kernel, 7 sg_overlap_kernel)
+    // ---- jobs per resident slot (mirp_last_jobs_per_slot): per family (0 duplex_kernel, 1 unpaired_kernel, 2 hp_score_kernel, 3 homolog_eval_kernel, 4 predict_kernel, 5 lc_count_kernel, 6 de_sum_kernel, 7 sg_overlap_kernel, 8 nt_scan_kernel)
     // the launches of the last C-ABI call that can launch it and the largest ceil(jobs / slots) among them; a record, read by nothing in the library
-    long long jobs_per_slot[8][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}};
+    long long jobs_per_slot[9][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}};
     void reset_jobs_per_slot(int family) { jobs_per_slot[family][0] = jobs_per_slot[family][1] = 0; }
     void note_jobs_per_slot(int family, long long jobs, long long slots) {
         jobs_per_slot[family][0]++;
@@ -400,6 +409,17 @@ struct IvGenome {
 };
 int mirp_device_inverted(mirp_ctx* c, const IvGenome& G, const MirpInvertedOpts& o, std::vector<MirpInvertedRec>& recs, std::vector<char>& ops,
                          std::vector<long long>& ops_off);
+// nats_kernels.hip: the complementary transcript pairs of DESIGN.md §36.  T: transcript s holds len[s] bases (0: skipped) whose codes stand at
+// nibble pos[s] (a multiple of 16) of `fwd` (A C G T = 0..3, anything else and the padding 4) and, reverse-complemented, of `rc` (anything else and
+// the padding 5), 16 codes to a 64-bit word, with MIRP_NATS_GAP padding nibbles before the first transcript and after every one; wseq[w] = the
+// transcript of word w, -1 for padding.  Out: the regions in output order, their ops and the ops' offsets; c->nt_stats and c->nt_sec are filled.
+#define MIRP_NATS_GAP 1024
+struct NtSeqs {
+    std::vector<unsigned long long> fwd, rc;
+    std::vector<int> wseq, len;
+    std::vector<long long> pos;
+};
+int mirp_device_nats(mirp_ctx* c, const NtSeqs& T, const MirpNatsOpts& o, std::vector<MirpNatsRec>& recs, std::vector<char>& ops, std::vector<long long>& ops_off);
 int mirp_device_homolog_scan(mirp_ctx* c, const unsigned char* codes, const long long* roff, long long nq, int v, int max_placements,
                              std::vector<unsigned long long>& keys, long long stats[3]);
 int mirp_device_homolog_eval(mirp_ctx* c, const unsigned long long* keys, long long n, int precursor_len, int max_lines, HmWin* win, HmEval* ev,
